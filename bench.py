@@ -19,6 +19,10 @@ The JSON line also carries `roofline` (dominant kernel sequence, HIP-event timed
 `cpu_baseline` at N=1 (the reference binary oracle/_ref/shafa when present, else the oracle port, timed on
 the host cores on a bounded sample), `scatter_gather` at N>1 (X1/X2 over RCCL) and, with
 --pipeline, the F -> T -> C and D(SF+RLE) legs at -b M.
+
+`ms_per_step` is the wall time of the --steps timed steps (device synchronised, slowest rank) divided by --steps.
+--dump-outputs DIR writes the payloads and decoded bytes of the last timed step (dump_outputs), so that two builds can
+be compared output for output on the same seeded inputs.
 """
 import argparse
 import hashlib
@@ -96,7 +100,13 @@ def parse_args(argv=None):
                     help="shafa_hip_set_option(NAME, VALUE) before anything runs (A/B of kernel variants)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="test aid: allow more ranks than GPUs (ranks share devices, collectives over gloo); never a valid scaling number")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 to DIR/*.npy (float arrays, "
+                         "a seeded sample of outputs larger than 2 Mi bytes; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def free_port():
@@ -563,6 +573,53 @@ def uniform_leg(pkg, torch, dev, st):
             "decode_path": "exact (no speculation: 8/9-bit codes do not re-synchronise)"}
 
 
+DUMP_SAMPLE = 1 << 21     # bytes kept of each output: 2 outputs x 2 Mi x (4 B value + 8 B index) = 48 MiB in all
+
+
+def dump_positions(n, seed):
+    """Positions of the bytes --dump-outputs keeps of an output of n bytes: all of them when n <= DUMP_SAMPLE, else
+    DUMP_SAMPLE positions drawn from a fixed seed (sorted, repeats possible), the same in every run with the same arguments."""
+    import numpy as np
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def encoded_addresses(pos, out_off, enc_bytes):
+    """Byte positions in the concatenation of the blocks' payloads (block order, as a .shaf file holds them) -> addresses
+    in the device buffer where block b's payload starts at out_off[b]."""
+    import numpy as np
+    ends = np.cumsum(np.asarray(enc_bytes, dtype=np.int64))
+    b = np.searchsorted(ends, pos, side="right")
+    starts = ends - np.asarray(enc_bytes, dtype=np.int64)
+    return np.asarray(out_off, dtype=np.int64)[b] + (pos - starts[b])
+
+
+def dump_outputs(path, torch, dev, d_enc, out_off, enc_bytes, d_dec):
+    """What one timed step gives its caller, as .npy files in `path` (at most 51 MB in all):
+      sf_encoded_sizes   float64 [blocks]  bytes of every block's Shannon-Fano payload
+      sf_encoded         float32           payload bytes (0..255) at the positions in sf_encoded_index
+      sf_encoded_index   float64           positions in the concatenation of the payloads in block order
+      sf_decoded         float32           decoded bytes at the positions in sf_decoded_index (not with --encode-only)
+      sf_decoded_index   float64           positions in the rank's shard of the input stream
+    Outputs of more than DUMP_SAMPLE bytes are sampled at seeded positions; the inputs are seeded too, so runs with the
+    same arguments dump the same positions of the same computation."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "sf_encoded_sizes.npy"), np.asarray(enc_bytes, dtype=np.float64))
+    pos = dump_positions(int(np.sum(enc_bytes)), SEED + 2)
+    addr = encoded_addresses(pos, out_off, enc_bytes)
+    assert addr.size == 0 or (0 <= addr.min() and addr.max() < d_enc.numel())
+    got = d_enc[torch.from_numpy(addr).to(dev)].cpu().numpy()
+    np.save(os.path.join(path, "sf_encoded.npy"), got.astype(np.float32))
+    np.save(os.path.join(path, "sf_encoded_index.npy"), pos.astype(np.float64))
+    if d_dec is not None:
+        pos = dump_positions(d_dec.numel(), SEED + 3)
+        got = d_dec[torch.from_numpy(pos).to(dev)].cpu().numpy()
+        np.save(os.path.join(path, "sf_decoded.npy"), got.astype(np.float32))
+        np.save(os.path.join(path, "sf_decoded_index.npy"), pos.astype(np.float64))
+
+
 def mover_leg():
     """What a kernel that only moves the encoder's bytes reaches on THIS device right now (tools/ubench/mover, built by
     __graft_entry__.build(): 8 GiB read, 6.5 GiB written, nothing computed): the ceiling the encoder's fraction is read against.
@@ -739,6 +796,8 @@ def main():
     rc, errs = bt.finish(st, nb)
     assert rc == 0
     elapsed = comm.max(t1 - t0)
+    if args.dump_outputs and rank == 0:                # before any later leg reuses d_enc
+        dump_outputs(args.dump_outputs, torch, dev, d_enc, out_off, enc_bytes, d_dec if have_decode else None)
 
     enc_ms = [ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(args.steps)]
     dec_ms = [ev[3 * i + 1].elapsed_time(ev[3 * i + 2]) for i in range(args.steps)]

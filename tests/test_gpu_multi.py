@@ -1,6 +1,6 @@
-"""Multi-GPU path on hardware (-m gpu): X1 scatter -> HIP SF encode -> X2 gatherv over RCCL (backend "nccl") at the
-world sizes the box offers (1 GPU: world 1, so the collectives at least run through RCCL once; more GPUs: one rank
-per GPU), compared with the oracle; and bench.py's self-launching --gpus N path (c.c:392-411, multithread.c:70-87)."""
+"""Multi-GPU path on hardware (-m gpu): X1 scatter -> HIP SF encode -> X2 gatherv over RCCL (backend "nccl") with one
+rank per GPU (on a one-GPU box: two ranks sharing it, X1 / X2 over gloo), compared with the oracle; and bench.py's
+self-launching --gpus N path (c.c:392-411, multithread.c:70-87)."""
 import json
 import os
 import subprocess
@@ -15,25 +15,28 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 
 
-def _worker(rank, world, port, total, bs, q):
+def _worker(rank, world, port, total, bs, q, backend):
     sys.path.insert(0, HERE)
     import torch
     import torch.distributed as dist
     import oracle_lib
     import pkgload
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.cuda.set_device(rank)
-    dev = torch.device("cuda", rank)
-    dist.init_process_group("nccl", rank=rank, world_size=world)
+    gpu = rank % torch.cuda.device_count()
+    torch.cuda.set_device(gpu)
+    dev = torch.device("cuda", gpu)
+    mdev = dev if backend == "nccl" else torch.device("cpu")        # where X1 / X2 move the bytes (gloo: host memory)
+    dist.init_process_group(backend, rank=rank, world_size=world)
     pkg = pkgload.load()
-    pkg.lib().shafa_hip_init(rank)
+    pkg.lib().shafa_hip_init(gpu)
     sh = pkgload.load_submodule("sharding")
     orc = oracle_lib.load()
     zt = pkg.zipf_table(1.2)
     data = orc.gen_bytes(424242, total, zt)
-    src = torch.from_numpy(data).to(dev) if rank == 0 else None
+    src = torch.from_numpy(data).to(mdev) if rank == 0 else None
     stats = {}
-    local, first, sizes = sh.scatter_blocks(src, total, bs, dev, stats=stats)         # X1
+    local, first, sizes = sh.scatter_blocks(src, total, bs, mdev, stats=stats)        # X1
+    local = local.to(dev)
     nb = len(sizes)
     st = torch.cuda.Stream(device=dev)
     bt = pkg.Batch(max(nb, 1), bs)
@@ -58,10 +61,10 @@ def _worker(rank, world, port, total, bs, q):
         bt.finish(st, nb)
         assert [int(x) for x in d_enc_n.cpu().numpy()[:nb]] == enc_n
     n_blocks = (total + bs - 1) // bs
-    got = sh.gather_payloads(d_enc, eoff, enc_n, n_blocks, dev, stats=stats)           # X2
+    got = sh.gather_payloads(d_enc.to(mdev), eoff, enc_n, n_blocks, mdev, stats=stats)  # X2
     ok = True
     if rank == 0:
-        ok = len(got) == n_blocks and stats.get("p2p_ops", 0) > 0       # blocks really went over RCCL (world >= 2)
+        ok = len(got) == n_blocks and stats.get("p2p_ops", 0) > 0       # blocks really moved between the ranks
         for b in range(n_blocks):
             blk = data[b * bs:(b + 1) * bs]
             rc, enc = orc.sf_encode(blk, orc.sf_build(orc.hist256(blk)))
@@ -78,16 +81,16 @@ def _gpu_count():
 
 @pytest.mark.parametrize("total,bs", [(5 * (1 << 20) + 4096 + 16, 1 << 20), (3 * (8 << 20), 8 << 20)])
 def test_scatter_hip_encode_gather_over_rccl(total, bs):
+    """One rank per visible GPU (8 on a full node), X1 / X2 over RCCL.  With one GPU, world 1 would leave every
+    point-to-point list empty, and RCCL refuses two ranks on one device: there two ranks share the GPU for the HIP encode
+    and move the blocks over gloo through host memory (as bench.py --oversubscribe does)."""
     import torch.multiprocessing as mp
-    world = max(1, _gpu_count())                   # one rank per visible GPU (8 on a full node)
-    if world < 2:
-        # at world 1 every point-to-point list is empty: nothing of X1 / X2 would be exercised, so say so instead of passing;
-        # the movement itself is covered at world 2 and 8 over gloo (tests/test_sharding_gloo.py), the HIP kernels everywhere else
-        pytest.skip("one GPU on this box: X1 scatter / X2 gatherv over RCCL need two ranks (no send or receive happens at world 1)")
+    n = _gpu_count()
+    world, backend = (n, "nccl") if n >= 2 else (2, "gloo")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 29600 + (os.getpid() + total) % 1500
-    procs = [ctx.Process(target=_worker, args=(r, world, port, total, bs, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, port, total, bs, q, backend)) for r in range(world)]
     for p in procs:
         p.start()
     for p in procs:
@@ -123,20 +126,22 @@ def test_bench_self_launches_ranks():
         assert "scatter_gather" in j and j["scatter_gather"]["backend"] == "nccl"
 
 
-def test_bench_at_world_size_8():
-    """`bench.py --gpus 8` with tiny blocks: the rank plumbing of the node the scaling bench runs on (rendezvous of eight
-    ranks, shard offsets, barrier, max-reduce, per-rank gather, rank-0 line) is not first exercised by the driver.  On a box
-    with fewer than eight GPUs the ranks share devices (--oversubscribe: gloo for the collectives, line marked invalid)."""
+def test_bench_at_world_size_4():
+    """`bench.py --gpus 4` with tiny blocks: the rank plumbing of a multi-GPU node (rendezvous of four ranks, shard offsets,
+    barrier, max-reduce, per-rank gather, rank-0 line) is not first exercised by the driver.  On a box with fewer than four
+    GPUs the ranks share devices (--oversubscribe: gloo for the collectives, line marked invalid).  Four ranks, their
+    launcher (torch.distributed.run asks for a GPU) and this process are six processes with the GPU open, the most the
+    suite puts on one GPU at a time."""
     n = _gpu_count()
-    argv = ["--gpus", "8", "--steps", "1", "--warmup", "1", "--blocks", "2", "--block-mib", "8", "--no-cpu", "--no-pipeline",
+    argv = ["--gpus", "4", "--steps", "1", "--warmup", "1", "--blocks", "2", "--block-mib", "8", "--no-cpu", "--no-pipeline",
             "--no-host-path"]
-    if n < 8:
+    if n < 4:
         argv.append("--oversubscribe")
     j = _bench(argv, timeout=900)
-    assert j["n_gpus"] == 8 and j["value"] > 0 and j["scaling"] == "weak"
-    assert ("invalid" in j) == (n < 8)
+    assert j["n_gpus"] == 4 and j["value"] > 0 and j["scaling"] == "weak"
+    assert ("invalid" in j) == (n < 4)
     pr = j["per_rank"]
-    assert len(pr["encode_ms"]) == 8 and len(pr["decode_ms"]) == 8 and all(x > 0 for x in pr["encode_ms"] + pr["decode_ms"])
+    assert len(pr["encode_ms"]) == 4 and len(pr["decode_ms"]) == 4 and all(x > 0 for x in pr["encode_ms"] + pr["decode_ms"])
     assert j["config"]["blocks_per_gpu"] == 2
 
 
@@ -175,3 +180,36 @@ def test_bench_single_gpu_line_has_the_contract_fields():
     assert "error" not in hp and hp["pipe_3_slots"]["round_trip_identical"] and hp["cli_tmpfs"]["round_trip_identical"]
     assert hp["pipe_3_slots"]["sf_encode_GiBs"] > 1 and hp["cli_tmpfs"]["GiBs"]["c"] > 0.1
     assert len(j["per_rank"]["encode_ms"]) == 1
+
+
+def test_bench_dump_outputs_are_the_oracles(tmp_path, oracle):
+    """`bench.py --dump-outputs DIR`: the payloads and decoded bytes of the last timed step, at the positions the dump names,
+    are what the oracle computes from the same seeded input; --steps sets the number of timed steps.  4 x 1 MiB blocks:
+    both outputs are larger than the dump keeps, so the seeded sample is what is checked."""
+    import importlib.util
+    import pkgload
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    nb, bs = 4, 1 << 20
+    j = _bench(["--steps", "3", "--warmup", "1", "--blocks", str(nb), "--block-mib", "1", "--no-cpu", "--no-pipeline",
+                "--no-host-path", "--dump-outputs", str(tmp_path)])
+    assert j["steps"] == 3 and j["ms_per_step"] > 0
+    d = {k: np.load(tmp_path / (k + ".npy")) for k in ("sf_encoded_sizes", "sf_encoded", "sf_encoded_index", "sf_decoded",
+                                                        "sf_decoded_index")}
+    assert sum(a.nbytes for a in d.values()) <= 64 * 10 ** 6
+    for k, a in d.items():
+        assert a.dtype == (np.float32 if k in ("sf_encoded", "sf_decoded") else np.float64), k
+    data = oracle.gen_bytes(bench.SEED, nb * bs, pkgload.load_submodule("synth").zipf_mod256_table(1.2))
+    enc = []
+    for b in range(nb):
+        blk = data[b * bs:(b + 1) * bs]
+        rc, e = oracle.sf_encode(blk, oracle.sf_build(oracle.hist256(blk)))
+        assert rc == 0
+        enc.append(e)
+    assert d["sf_encoded_sizes"].tolist() == [float(e.size) for e in enc]
+    payload = np.concatenate(enc)
+    assert payload.size > bench.DUMP_SAMPLE and d["sf_encoded"].size == bench.DUMP_SAMPLE
+    assert (d["sf_encoded"] == payload[d["sf_encoded_index"].astype(np.int64)]).all()
+    assert d["sf_decoded"].size == bench.DUMP_SAMPLE
+    assert (d["sf_decoded"] == data[d["sf_decoded_index"].astype(np.int64)]).all()

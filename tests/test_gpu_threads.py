@@ -86,7 +86,8 @@ def test_no_entry_point_changes_the_callers_current_device(oracle, shafa):
 def test_two_processes_sharing_the_gpu_finish_without_device_errors():
     """Chained scans wait for predecessor tiles that belong to other workgroups; with a second process on the same GPU
     (or a profiler) those may be late by milliseconds.  The wait is bounded by wall-clock seconds, not by a poll count,
-    so contention shows up as a slower run, never as SHAFA_DEVICE_ERROR."""
+    so contention shows up as a slower run, never as SHAFA_DEVICE_ERROR.  --no-host-path: the host-path leg starts child
+    processes of its own on the GPU, which would make seven processes with the GPU open; the suite keeps to six."""
     import json
     import os
     import subprocess
@@ -97,7 +98,7 @@ def test_two_processes_sharing_the_gpu_finish_without_device_errors():
         env.pop(k, None)
     env["SHAFA_BENCH_ORACLE_CHECK"] = "0"
     argv = [sys.executable, os.path.join(root, "bench.py"), "--blocks", "24", "--steps", "6", "--warmup", "1", "--no-cpu",
-            "--pipeline-blocks", "8"]
+            "--pipeline-blocks", "8", "--no-host-path"]
     procs = [subprocess.Popen(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env) for _ in range(3)]
     for p in procs:
         out, err = p.communicate(timeout=600)
