@@ -162,9 +162,9 @@ int shafa_hipd_hist256(shafa_hipd_batch *b, void *stream, int nblocks, const uin
 /* Module T's core on the device (t.c:74-210, the rule set of host/sfcodes.c shafa_sf_build_codes): d_freq = nblocks x 256
  * counts (what shafa_hipd_hist256 / _rle_encode leave), d_tables = nblocks tables in DEVICE memory, bit-identical to the
  * host's for counts whose sum fits 64 bits (a block's own histogram always does; else SHAFA_OUTSIDE_MODULE for the block
- * and an empty table).  One workgroup per block.  The encoder's and decoder's entry points take their tables from the
- * HOST (their launchers choose kernels by the longest code): this is for callers that keep histograms and tables on the
- * GPU, and the device-side half of a host-free F -> T -> C. */
+ * and an empty table).  One workgroup per block.  The decoder's entry points take their tables from the HOST (its
+ * launcher prepares window tables there); shafa_hipd_sf_encode_dev encodes from these tables as they lie, which makes
+ * F -> T -> C host-free. */
 int shafa_hipd_sf_build_codes(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
                               shafa_code_table *d_tables);
 
@@ -211,6 +211,23 @@ int shafa_hipd_sf_encode_tiles(shafa_hipd_batch *b, void *stream, int nblocks, c
                                const uint64_t *h_in_off, const uint64_t *h_in_n, const shafa_code_table *h_tables,
                                const uint8_t *d_tile_hist, const uint64_t *h_tile_hist_off, uint8_t *d_out,
                                const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
+
+/* binary_coding per block as shafa_hipd_sf_encode[_tiles], with the block sizes AND the code tables in DEVICE memory: block b
+ * encodes d_in_n[b] (<= h_in_cap[b]) bytes at d_in + h_in_off[b] with d_tables[b] (what shafa_hipd_sf_build_codes leaves);
+ * d_tile_hist / h_tile_hist_off either both NULL or the blocks' tile histograms (regions sized for h_in_cap[b]).  Results —
+ * bytes, d_out_n[b], the per-block codes of shafa_hipd_finish — equal those of shafa_hipd_sf_encode[_tiles] with the same
+ * tables on the host and h_in_n = d_in_n.  d_in_n[b] > h_in_cap[b] is SHAFA_OUTSIDE_MODULE for block b (d_out_n[b] = 0).
+ * Nothing is written outside a block's output region: an output that does not fit is SHAFA_LACK_OF_MEMORY, and
+ * h_out_cap[b] = h_in_cap[b] * L / 8 + 16 always suffices for codes of at most L bits.
+ * Enqueues only: d_tables and d_in_n are never read on the host, no device-to-host copy is issued and neither the stream
+ * nor the device is synchronised — so rle_encode_tiles / hist256_tiles -> sf_build_codes -> sf_encode_dev -> one
+ * shafa_hipd_finish compresses a batch with a single synchronisation.  The one exception is the batch's growth on demand
+ * (device workspace, parameter buffers, staging), which depends on nblocks and h_in_cap only: once a call of the same
+ * shape has been made on the batch, the call never waits.  NULL b, d_in_n or d_tables: SHAFA_OUTSIDE_MODULE. */
+int shafa_hipd_sf_encode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                             const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                             const shafa_code_table *d_tables, const uint8_t *d_tile_hist, const uint64_t *h_tile_hist_off,
+                             uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
 
 /* shafa_block_decompressor per block: block b decodes h_n_symbols[b] symbols from the h_in_n[b]
  * bytes at d_in + h_in_off[b] into d_out + h_out_off[b] (which must hold h_n_symbols[b] bytes). */

@@ -112,6 +112,7 @@ def lib():
     L.shafa_hipd_hist256_tiles.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_rle_encode_tiles.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, u8p, u64p, u64p, vp, vp, u8p, u64p]
     L.shafa_hipd_sf_encode_tiles.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, tp, u8p, u64p, u8p, u64p, u64p, vp]
+    L.shafa_hipd_sf_encode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, u8p, u64p, u8p, u64p, u64p, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hipd_gen_bytes.argtypes = [vp, C.c_uint64, C.c_uint64, u8p, u8p, C.c_size_t]
     L.shafa_pipe_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -138,7 +139,7 @@ def lib():
                  "shafa_hipd_hist256", "shafa_hipd_rle_encode", "shafa_hipd_sf_encode",
                  "shafa_hipd_sf_decode", "shafa_hipd_rle_decode", "shafa_hipd_finish",
                  "shafa_hipd_gen_bytes", "shafa_hipd_hist256_tiles", "shafa_hipd_rle_encode_tiles",
-                 "shafa_hipd_sf_encode_tiles"):
+                 "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -312,6 +313,19 @@ class Batch:
         _check(lib().shafa_hipd_sf_encode_tiles(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(il),
                                                 tarr, d_thist.data_ptr(), _p64(to), d_out.data_ptr(), _p64(oo), _p64(oc),
                                                 d_out_n.data_ptr()), "hipd_sf_encode_tiles")
+
+    def sf_encode_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, d_out, out_off, out_cap, d_out_n,
+                      d_thist=None, thist_off=None):
+        """sf_encode[_tiles] with the block sizes (d_in_n: nblocks int64) and the code tables (d_tables: nblocks x
+        sizeof(CodeTable) bytes, e.g. sf_build_codes' output) in device memory; in_cap bounds each block's size.  Enqueues
+        only: nothing is read back (include/shafa_hip.h: shafa_hipd_sf_encode_dev)."""
+        io, ic, oo, oc = _u64arr(in_off), _u64arr(in_cap), _u64arr(out_off), _u64arr(out_cap)
+        to = _u64arr(thist_off) if thist_off is not None else None
+        _check(lib().shafa_hipd_sf_encode_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                              d_in_n.data_ptr(), d_tables.data_ptr(),
+                                              d_thist.data_ptr() if d_thist is not None else None,
+                                              _p64(to) if to is not None else None, d_out.data_ptr(), _p64(oo), _p64(oc),
+                                              d_out_n.data_ptr()), "hipd_sf_encode_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)

@@ -354,6 +354,17 @@ int shafa_hipd_sf_encode_tiles(shafa_hipd_batch *b, void *stream, int nblocks, c
                         h_out_off, h_out_cap, d_out_n, d_tile_hist, h_tile_hist_off);
 }
 
+int shafa_hipd_sf_encode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                             const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                             const shafa_code_table *d_tables, const uint8_t *d_tile_hist, const uint64_t *h_tile_hist_off,
+                             uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n)
+{
+    if (!b || !d_in_n || !d_tables) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return sfenc_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_tables, d_out,
+                            h_out_off, h_out_cap, d_out_n, d_tile_hist, h_tile_hist_off);
+}
+
 int shafa_hipd_rle_encode(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                           const uint64_t *h_in_off, const uint64_t *h_in_n, uint8_t *d_out,
                           const uint64_t *h_out_off, const uint64_t *h_out_cap,

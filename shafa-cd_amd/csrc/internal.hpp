@@ -137,6 +137,11 @@ int hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, cons
 int sfenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
                  const u64 *h_in_n, const shafa_code_table *h_tables, u8 *d_out, const u64 *h_out_off,
                  const u64 *h_out_cap, u64 *d_out_n, const u8 *d_thist = nullptr, const u64 *h_thist_off = nullptr);
+// sfenc_launch with the block sizes and the tables in DEVICE memory (sf_encode_dev.hip): block b encodes d_in_n[b] <= h_in_cap[b]
+// bytes with d_tables[b]; neither is read on the host
+int sfenc_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                     const u64 *d_in_n, const shafa_code_table *d_tables, u8 *d_out, const u64 *h_out_off,
+                     const u64 *h_out_cap, u64 *d_out_n, const u8 *d_thist, const u64 *h_thist_off);
 int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
                  const u64 *h_in_n, const shafa_code_table *h_tables, const u64 *h_n_symbols, u8 *d_out,
                  const u64 *h_out_off);

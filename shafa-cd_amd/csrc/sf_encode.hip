@@ -133,14 +133,10 @@ __device__ __forceinline__ u32 code_bits(const shafa_code_table *t, u32 s, u32 f
     return v;
 }
 
-__global__ __launch_bounds__(ENC_THREADS) void sf_encode_generic(const EncBlk *__restrict__ blks, int nblk,
-                                                                 u64 *desc, u32 *tickets)
+// one tile of block `blk`, the next of its tickets
+__device__ __forceinline__ void generic_tile(EncShared &sh, const EncBlk &blk, u64 *desc, u32 *tickets)
 {
-    __shared__ __attribute__((aligned(16))) EncShared sh;
     const int tid = threadIdx.x;
-    const int b = blockIdx.x % nblk;
-    const EncBlk blk = blks[b];
-    if ((u32)(blockIdx.x / nblk) >= blk.n_tiles) return;
     if (tid == 0) sh.tile = atomicAdd(tickets + blk.ticket, 1u);
     __syncthreads();
     const int k = (int)sh.tile;
@@ -200,6 +196,35 @@ __global__ __launch_bounds__(ENC_THREADS) void sf_encode_generic(const EncBlk *_
     encode_tail(sh, blk, desc, k, tile_bits, emit, lead);
 }
 
+// one workgroup per tile: grid = max tiles x nblk (sfenc_launch)
+__global__ __launch_bounds__(ENC_THREADS) void sf_encode_generic(const EncBlk *__restrict__ blks, int nblk,
+                                                                 u64 *desc, u32 *tickets)
+{
+    __shared__ __attribute__((aligned(16))) EncShared sh;
+    const int b = blockIdx.x % nblk;
+    const EncBlk blk = blks[b];
+    if ((u32)(blockIdx.x / nblk) >= blk.n_tiles) return;
+    generic_tile(sh, blk, desc, tickets);
+}
+
+// sfenc_launch_dev (sf_encode_dev.hip): the host knows neither how many generic blocks there are nor their sizes.  d_plan[1]
+// records (compacted by the plan kernel), d_plan[0] = the most tiles of any of them; a grid of any size loops over the
+// d_plan[1] x d_plan[0] slots.  A workgroup finishes the tile of its ticket before it takes another, so the chain cannot
+// deadlock whatever part of the grid is resident.
+__global__ __launch_bounds__(ENC_THREADS) void sf_encode_generic_dev(const EncBlk *__restrict__ blks, u64 *desc, u32 *tickets,
+                                                                     const u32 *__restrict__ d_plan)
+{
+    __shared__ __attribute__((aligned(16))) EncShared sh;
+    const u32 maxt = gload<u32>(d_plan), nblk = gload<u32>(d_plan + 1);
+    const u64 slots = (u64)nblk * maxt;
+    for (u64 g = blockIdx.x; g < slots; g += gridDim.x) {
+        const EncBlk blk = blks[g % nblk];
+        if (g / nblk >= blk.n_tiles) continue;
+        __syncthreads();                               // the previous tile's shared state is no longer read
+        generic_tile(sh, blk, desc, tickets);
+    }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -221,6 +246,14 @@ extern int g_sfe4_wide, g_sfe_lanes;
 // 6 blocks where the 1024-lane form runs (Lmax <= 12), 80 for the 256-lane form
 static int g_sfe4_min_blocks = 0;
 void sfenc_configure(int sfe4_min_blocks) { g_sfe4_min_blocks = sfe4_min_blocks; }
+int sfenc_min_blocks() { return g_sfe4_min_blocks; }
+
+// the generic kernel for sfenc_launch_dev (sf_encode_dev.hip): d_plan = {most tiles of a record, number of records}, written
+// on the device; `grid` workgroups loop over the slots
+void sfenc_generic_launch_dev(hipStream_t st, const EncBlk *dblk, u32 grid, u64 *d_desc, u32 *d_tickets, const u32 *d_plan)
+{
+    hipLaunchKernelGGL(sf_encode_generic_dev, dim3(grid), dim3(ENC_THREADS), 0, st, dblk, d_desc, d_tickets, d_plan);
+}
 
 // the code of symbol s (<= 32 bits: classes 1 and 2) right-aligned: its first four bytes, MSB first, shifted down.
 // (Bit by bit this loop was most of the 1.3 ms the host needed to prepare a 128-block launch: more than the kernel takes
