@@ -162,9 +162,8 @@ int shafa_hipd_hist256(shafa_hipd_batch *b, void *stream, int nblocks, const uin
 /* Module T's core on the device (t.c:74-210, the rule set of host/sfcodes.c shafa_sf_build_codes): d_freq = nblocks x 256
  * counts (what shafa_hipd_hist256 / _rle_encode leave), d_tables = nblocks tables in DEVICE memory, bit-identical to the
  * host's for counts whose sum fits 64 bits (a block's own histogram always does; else SHAFA_OUTSIDE_MODULE for the block
- * and an empty table).  One workgroup per block.  The decoder's entry points take their tables from the HOST (its
- * launcher prepares window tables there); shafa_hipd_sf_encode_dev encodes from these tables as they lie, which makes
- * F -> T -> C host-free. */
+ * and an empty table).  One workgroup per block.  shafa_hipd_sf_encode_dev and shafa_hipd_sf_decode_dev take these tables
+ * as they lie, which makes F -> T -> C -> D host-free; shafa_hipd_sf_encode / _sf_decode take HOST tables. */
 int shafa_hipd_sf_build_codes(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
                               shafa_code_table *d_tables);
 
@@ -240,6 +239,36 @@ int shafa_hipd_sf_decode(shafa_hipd_batch *b, void *stream, int nblocks, const u
 int shafa_hipd_rle_decode(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                           const uint64_t *h_in_off, const uint64_t *h_in_n, uint8_t *d_out,
                           const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
+
+/* shafa_hipd_sf_decode with the stream sizes, the symbol counts AND the code tables in DEVICE memory: block b decodes
+ * d_n_symbols[b] symbols from the d_in_n[b] (<= h_in_cap[b]) bytes at d_in + h_in_off[b] with d_tables[b] (what
+ * shafa_hipd_sf_build_codes leaves) into d_out + h_out_off[b].  Bytes and the per-block codes of shafa_hipd_finish equal
+ * those of shafa_hipd_sf_decode with the same tables on the host, h_in_n = d_in_n and h_n_symbols = d_n_symbols —
+ * malformed tables, empty streams and damaged streams included.  d_in_n[b] > h_in_cap[b] or d_n_symbols[b] > h_out_cap[b]
+ * is SHAFA_OUTSIDE_MODULE for block b and nothing is written to its region; nothing is ever written outside
+ * [h_out_off[b], h_out_off[b] + h_out_cap[b]).
+ * Memory rule: a block whose codes have at most 32 bits never fails for want of memory.  Codes of 33..64 bits have one slot
+ * per call, sized for max(h_in_cap): it goes to the first block by index with such a code, d_n_symbols > 0, d_in_n > 0
+ * and both sizes within its capacities (a malformed table counts too); later blocks with codes of 33..64 bits, and every
+ * block with a code of more than 64 bits, are SHAFA_LACK_OF_MEMORY, nothing written (malformed tables and the capacity
+ * checks report first).  The device workspace is 1.35 bytes per byte of sum(h_in_cap), plus 2.1 bytes per byte of
+ * max(h_in_cap), plus 187 KiB per block, plus 128 KiB.
+ * Enqueues only: d_tables, d_in_n and d_n_symbols are never read on the host, no device-to-host copy is issued and
+ * neither the stream nor the device is synchronised, as for shafa_hipd_sf_encode_dev (the same exception: the batch's
+ * growth, from nblocks and the capacities).  The options sf_decode_speculate and sf_decode_path act as on
+ * shafa_hipd_sf_decode.  NULL b, d_in_n, d_tables or d_n_symbols: SHAFA_OUTSIDE_MODULE. */
+int shafa_hipd_sf_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                             const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                             const shafa_code_table *d_tables, const uint64_t *d_n_symbols,
+                             uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap);
+
+/* shafa_hipd_rle_decode with the block sizes in DEVICE memory: block b decodes the d_in_n[b] (<= h_in_cap[b]) bytes at
+ * d_in + h_in_off[b].  Results equal shafa_hipd_rle_decode with h_in_n = d_in_n; d_in_n[b] > h_in_cap[b] is
+ * SHAFA_OUTSIDE_MODULE for block b (d_out_n[b] = 0).  Enqueues only, as shafa_hipd_sf_decode_dev: with it an RLE
+ * session decodes host-free (sf_decode_dev's d_n_symbols is this call's d_in_n).  NULL b or d_in_n: SHAFA_OUTSIDE_MODULE. */
+int shafa_hipd_rle_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                              const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                              uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
 
 /* Synchronise `stream`, return the first per-block error of the calls enqueued since the last
  * finish (SHAFA_SUCCESS if none).  h_block_err (nblocks ints, may be NULL) receives every block's code. */

@@ -113,6 +113,8 @@ def lib():
     L.shafa_hipd_rle_encode_tiles.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, u8p, u64p, u64p, vp, vp, u8p, u64p]
     L.shafa_hipd_sf_encode_tiles.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, tp, u8p, u64p, u8p, u64p, u64p, vp]
     L.shafa_hipd_sf_encode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, u8p, u64p, u8p, u64p, u64p, vp]
+    L.shafa_hipd_sf_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp, u8p, u64p, u64p]
+    L.shafa_hipd_rle_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hipd_gen_bytes.argtypes = [vp, C.c_uint64, C.c_uint64, u8p, u8p, C.c_size_t]
     L.shafa_pipe_create.argtypes = [C.c_int, C.POINTER(vp)]
@@ -139,7 +141,8 @@ def lib():
                  "shafa_hipd_hist256", "shafa_hipd_rle_encode", "shafa_hipd_sf_encode",
                  "shafa_hipd_sf_decode", "shafa_hipd_rle_decode", "shafa_hipd_finish",
                  "shafa_hipd_gen_bytes", "shafa_hipd_hist256_tiles", "shafa_hipd_rle_encode_tiles",
-                 "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev"):
+                 "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev", "shafa_hipd_sf_decode_dev",
+                 "shafa_hipd_rle_decode_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -326,6 +329,23 @@ class Batch:
                                               d_thist.data_ptr() if d_thist is not None else None,
                                               _p64(to) if to is not None else None, d_out.data_ptr(), _p64(oo), _p64(oc),
                                               d_out_n.data_ptr()), "hipd_sf_encode_dev")
+
+    def sf_decode_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, d_n_symbols, d_out, out_off, out_cap):
+        """sf_decode with the stream sizes (d_in_n), the symbol counts (d_n_symbols: nblocks int64 each) and the code tables
+        (d_tables: nblocks x sizeof(CodeTable) bytes, e.g. sf_build_codes' output) in device memory; in_cap / out_cap bound
+        each block's regions.  Enqueues only: nothing is read back (include/shafa_hip.h: shafa_hipd_sf_decode_dev)."""
+        io, ic, oo, oc = _u64arr(in_off), _u64arr(in_cap), _u64arr(out_off), _u64arr(out_cap)
+        _check(lib().shafa_hipd_sf_decode_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                              d_in_n.data_ptr(), d_tables.data_ptr(), d_n_symbols.data_ptr(),
+                                              d_out.data_ptr(), _p64(oo), _p64(oc)), "hipd_sf_decode_dev")
+
+    def rle_decode_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_out, out_off, out_cap, d_out_n):
+        """rle_decode with the block sizes (d_in_n: nblocks int64) in device memory; in_cap bounds each block's size.
+        Enqueues only (include/shafa_hip.h: shafa_hipd_rle_decode_dev)."""
+        io, ic, oo, oc = _u64arr(in_off), _u64arr(in_cap), _u64arr(out_off), _u64arr(out_cap)
+        _check(lib().shafa_hipd_rle_decode_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                               d_in_n.data_ptr(), d_out.data_ptr(), _p64(oo), _p64(oc),
+                                               d_out_n.data_ptr()), "hipd_rle_decode_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)

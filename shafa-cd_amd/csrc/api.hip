@@ -404,6 +404,27 @@ int shafa_hipd_rle_decode(shafa_hipd_batch *b, void *stream, int nblocks, const 
                          h_out_cap, d_out_n);
 }
 
+int shafa_hipd_sf_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                             const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                             const shafa_code_table *d_tables, const uint64_t *d_n_symbols,
+                             uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap)
+{
+    if (!b || !d_in_n || !d_tables || !d_n_symbols) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return sfdec_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_tables,
+                            d_n_symbols, d_out, h_out_off, h_out_cap);
+}
+
+int shafa_hipd_rle_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                              const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                              uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n)
+{
+    if (!b || !d_in_n) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return rledec_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out, h_out_off,
+                             h_out_cap, d_out_n);
+}
+
 }  // extern "C"
 
 // the call itself (not a block) failed: no block has a result — every block reports the call's code

@@ -148,6 +148,13 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
 int rleenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
                   const u64 *h_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n,
                   u64 *d_freq, u8 *d_thist = nullptr, const u64 *h_thist_off = nullptr);
+// sfdec_launch with the block sizes, symbol counts and tables in DEVICE memory (sfd_dev.hpp): none of them is read on the host
+int sfdec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                     const u64 *d_in_n, const shafa_code_table *d_tables, const u64 *d_n_symbols, u8 *d_out,
+                     const u64 *h_out_off, const u64 *h_out_cap);
+// rledec_launch with the block sizes in DEVICE memory (descriptors laid out from h_in_cap)
+int rledec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                      const u64 *d_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n);
 int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
                   const u64 *h_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n);
 void sfenc_configure(int sfe4_min_blocks);

@@ -474,6 +474,23 @@ __global__ __launch_bounds__(RLD_THREADS) __attribute__((amdgpu_waves_per_eu(RLD
 
 
 
+
+// rledec_launch_dev: the records were laid out from the capacities; the block sizes come from device memory
+__global__ void rld_sizes_dev(RldBlk *__restrict__ blks, int nblk, const u64 *__restrict__ d_in_n, const u64 *__restrict__ in_cap)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nblk) return;
+    const u64 n = d_in_n[b];
+    if (n > in_cap[b]) {                           // past the block's region: no tile runs, out_n stays 0
+        blks[b].n = 0;
+        blks[b].n_tiles = 0;
+        set_error(blks[b].err, SHAFA_OUTSIDE_MODULE);
+        return;
+    }
+    blks[b].n = n;
+    blks[b].n_tiles = (u32)((n + RLD_TILE - 1) / RLD_TILE);
+}
+
 }  // namespace
 
 int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
@@ -524,5 +541,62 @@ int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const 
                            (u32 *)(ws + o_tick));
         HIP_TRY(hipGetLastError());
     }
+    return SHAFA_SUCCESS;
+}
+
+int rledec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                      const u64 *d_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n)
+{
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    u64 ndesc = 0;
+    u32 max_tiles = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        if ((h_in_off[b] & 15) || (h_out_off[b] & 15)) return SHAFA_OUTSIDE_MODULE;
+        const u64 t = ceil_div_u64(h_in_cap[b], RLD_TILE);
+        ndesc += t;
+        if (t > max_tiles) max_tiles = (u32)t;
+    }
+    size_t off = 0;
+    const size_t o_state = off; off += ndesc * 8 * RLD_DSTRIDE;
+    const size_t o_sum = off; off += ndesc * 8 * RLD_DSTRIDE;
+    const size_t o_tick = off; off += (size_t)nblocks * 4 * RLD_TSTRIDE; off = (off + 15) & ~(size_t)15;
+    const size_t o_zero_end = off;
+    const size_t o_blk = off; off += (size_t)nblocks * sizeof(RldBlk); off = (off + 15) & ~(size_t)15;
+    const size_t o_cap = off; off += (size_t)nblocks * 8;
+    int rc = batch_reserve(bt, st, off);
+    if (rc) return rc;
+    u8 *ws = (u8 *)bt->d_ws;
+    const size_t rec_bytes = (size_t)nblocks * sizeof(RldBlk);
+    u8 *hs = (u8 *)batch_stage(bt, st, (o_cap - o_blk) + (size_t)nblocks * 8);
+    if (!hs) return SHAFA_LACK_OF_MEMORY;
+    RldBlk *hb = (RldBlk *)hs;
+    u32 dbase = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        RldBlk &e = hb[b];
+        e.in = d_in + h_in_off[b];
+        e.out = d_out + h_out_off[b];
+        e.n = 0;                                   // rld_sizes_dev
+        e.out_cap = h_out_cap[b];
+        e.out_n = d_out_n + b;
+        e.err = bt->d_err + b;
+        e.desc_base = dbase;
+        e.n_tiles = 0;
+        e.ticket = (u32)b;
+        e.pad = 0;
+        dbase += (u32)ceil_div_u64(h_in_cap[b], RLD_TILE);
+    }
+    memset(hs + rec_bytes, 0, (o_cap - o_blk) - rec_bytes);
+    memcpy(hs + (o_cap - o_blk), h_in_cap, (size_t)nblocks * 8);
+    HIP_TRY(hipMemsetAsync(ws, 0, o_zero_end, st));
+    HIP_TRY(hipMemsetAsync(d_out_n, 0, (size_t)nblocks * 8, st));
+    if ((rc = batch_upload(bt, st, ws + o_blk, hs, (o_cap - o_blk) + (size_t)nblocks * 8))) return rc;
+    hipLaunchKernelGGL(rld_sizes_dev, dim3((u32)(nblocks + 255) / 256), dim3(256), 0, st, (RldBlk *)(ws + o_blk), nblocks,
+                       d_in_n, (const u64 *)(ws + o_cap));
+    if (max_tiles)       // workgroups past a block's real tile count return before they take a ticket
+        hipLaunchKernelGGL(rle_decode_kernel, dim3(max_tiles * (u32)nblocks), dim3(RLD_THREADS), 0, st,
+                           (const RldBlk *)(ws + o_blk), nblocks, (u64 *)(ws + o_state), (u64 *)(ws + o_sum),
+                           (u32 *)(ws + o_tick));
+    HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

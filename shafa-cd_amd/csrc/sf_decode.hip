@@ -1727,3 +1727,5 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     HIP_TRY(hipGetLastError());
     return pscope.done();
 }
+
+#include "sfd_dev.hpp"
