@@ -22,12 +22,11 @@ seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else int(time.time())
 rng = np.random.default_rng(seed0)
 
 DEFAULTS = {"sf_encode_one_pass_min_blocks": 0, "sf_encode_lanes": 0, "sf_encode_window_bits": 0, "sf_decode_speculate": 1,
-            "sf_decode_path": 0, "rle_encode_general": 0, "rle_encode_one_pass": 0}
+            "sf_decode_path": 0, "rle_encode_general": 0}
 ALTS = [{}, {}, {}, {"sf_encode_one_pass_min_blocks": 1 << 30}, {"sf_encode_one_pass_min_blocks": 1},
         {"sf_encode_one_pass_min_blocks": 1, "sf_encode_lanes": 256}, {"sf_encode_one_pass_min_blocks": 1, "sf_encode_lanes": 512},
         {"sf_encode_one_pass_min_blocks": 1, "sf_encode_window_bits": 4}, {"sf_decode_speculate": 0}, {"sf_decode_speculate": 2},
-        {"sf_decode_speculate": 2}, {"sf_decode_path": 1}, {"sf_decode_path": 2}, {"rle_encode_general": 1},
-        {"rle_encode_one_pass": 1}, {"rle_encode_one_pass": 1, "rle_encode_general": 1}]
+        {"sf_decode_speculate": 2}, {"sf_decode_path": 1}, {"sf_decode_path": 2}, {"rle_encode_general": 1}]
 EDGES = [4096, 8192, 16384, 32768, 65536, 131072, 262144, 1 << 20]
 
 
