@@ -125,6 +125,39 @@ struct SfeRedo {
     u32 *redo;
 };
 
+// ---- Module C planning rules, shared by sfenc_launch (sf_encode.hip) and sfenc_launch_dev (sf_encode_dev.hip) --------
+// the code of symbol s (<= 32 bits: classes 1 and 2), len = t.len[s], right-aligned: its first four bytes, MSB first, shifted
+// down.  (Bit by bit this was most of the 1.3 ms the host needed to prepare a 128-block launch.)
+__host__ __device__ inline u32 sfe_code_value(const shafa_code_table &t, u32 s, u32 len)
+{
+    if (!len) return 0;
+    const u8 *b = t.bits[s];
+    const u32 be = ((u32)b[0] << 24) | ((u32)b[1] << 16) | ((u32)b[2] << 8) | (u32)b[3];
+    return len >= 32 ? be : be >> (32 - len);
+}
+// the look-up table entries of the three formats the encoder kernels read, from a symbol's code value and length
+__host__ __device__ inline u32 sfe_entry32(u32 code, u32 len)           // code | len << 16; bit 31: no code
+{
+    return len ? (code | (len << 16)) : 0x80000000u;
+}
+__host__ __device__ inline u64 sfe_entry_pair(u32 code, u32 len)        // {code, len}; a symbol without a code: len = 1 << 16
+{
+    return len ? ((u64)code | ((u64)len << 32)) : (1ull << 48);
+}
+__host__ __device__ inline u64 sfe_entry64(u32 code, u32 len)           // code | len << 32
+{
+    return (u64)code | ((u64)len << 32);
+}
+// symbol s's entry in one of those formats, for the host's staging loop: the code value only where there is a code
+// (computed first and selected after, the loop over a 128-block launch took twice as long)
+template <typename Entry> inline auto sfe_entry(Entry entry, const shafa_code_table &t, u32 s)
+{
+    const u32 len = t.len[s];
+    return len ? entry(sfe_code_value(t, s, len), len) : entry(0u, 0u);
+}
+// one-pass (chained) encoder or count / scan / pack for `count` blocks of class 1 (codes of <= 16 bits) or 2 (17..32 bits)
+bool sfenc_one_pass(int cls, int count);
+
 // ---- launchers (one per reference function) ------------------------------------------------------
 // Module T on the device (sf_tables.hip): nblocks x 256 counts -> nblocks tables, both in device memory
 int sftab_launch(Batch *bt, hipStream_t st, int nblocks, const u64 *d_freq, shafa_code_table *d_tables);

@@ -1314,11 +1314,7 @@ static bool spec_worthwhile(const shafa_code_table &t, const HostTab &h, bool fo
 {
     if (!h.ok || !(h.complete || h.complete16 || h.complete32) || h.lmax > 32 || h.lmax < 2) return false;
     if (force) return true;
-    u64 key = 1469598103934665603ull;
-    for (int s2 = 0; s2 < 256; ++s2) {
-        key = (key ^ t.len[s2]) * 1099511628211ull;
-        for (int q = 0; q < (t.len[s2] + 7) / 8; ++q) key = (key ^ t.bits[s2][q]) * 1099511628211ull;
-    }
+    const u64 key = spec_key(t.len, t.bits);
     static u64 ckey[1024];
     static signed char cval[1024];                      // 0 = empty, 1 = no, 2 = yes
     static std::mutex cmu;                              // decodes run on several host threads (pipes, layer 1 callers)
@@ -1327,36 +1323,112 @@ static bool spec_worthwhile(const shafa_code_table &t, const HostTab &h, bool fo
         std::lock_guard<std::mutex> lk(cmu);
         if (cval[slot] && ckey[slot] == key) return cval[slot] == 2;
     }
-    const u32 K1 = h.K1;
     u64 rs = key | 1ull;
-    auto rnd = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
     int fails = 0;
-    for (int trial = 0; trial < 32 && fails <= 6; ++trial) {
-        u64 w[6];                                       // 384 random bits, bit i = bit (63 - i % 64) of w[i / 64]
-        for (u64 &x : w) x = rnd();
-        auto window = [&](u32 pos) -> u32 {             // the K1 bits at pos, MSB first
-            const u32 wi = pos >> 6, r = pos & 63;
-            u64 v = w[wi] << r;
-            if (r && wi + 1 < 6) v |= w[wi + 1] >> (64 - r);
-            return (u32)(v >> (64 - K1));
-        };
-        u64 starts[5] = {0, 0, 0, 0, 0};                // code starts of the true parse, bits 0..319
-        // (a window that starts a code of more than K1 bits — one random window in 2^K1 — counts as K1 + 1 bits)
-        auto len_at = [&](u32 pos) -> u32 { const u32 l = h.lenlut[window(pos)]; return l ? l : K1 + 1; };
-        for (u32 pos = 0; pos < 300;) { starts[pos >> 6] |= 1ull << (pos & 63); pos += len_at(pos); }
-        u32 pos = 1 + (u32)(rnd() % 15);
-        bool merged = false;
-        while (pos <= 256) {
-            if ((starts[pos >> 6] >> (pos & 63)) & 1ull) { merged = true; break; }
-            pos += len_at(pos);
-        }
-        if (!merged) ++fails;
+    for (int trial = 0; trial < SPEC_TRIALS && fails <= SPEC_MAX_FAILS; ++trial) {
+        u64 w[SPEC_WORDS];
+        for (u64 &x : w) x = spec_rand(rs);
+        if (!spec_trial(w, h.lenlut.data(), h.K1)) ++fails;
     }
-    const bool yes = fails <= 6;
+    const bool yes = fails <= SPEC_MAX_FAILS;
     std::lock_guard<std::mutex> lk(cmu);
     ckey[slot] = key;
     cval[slot] = yes ? 2 : 1;
     return yes;
+}
+
+// Per-tile arrays of one decode chain.  The two entries lay their workspaces out differently: each passes its own.
+struct SfdArrays {
+    u8 *cfn, *tfn;         // chunk and tile functions of the sync pass
+    u8 *tent, *cent;       // entry state per tile, per chunk
+    u16 *ccnt;             // symbols per chunk
+    u32 *tcnt;             // symbols per tile
+    u64 *toff;             // output offset per tile
+    u8 *tguess, *texit;    // speculative entries: guess and exit per tile (packed chain)
+};
+
+// the exact kernels of the packed chain: mid32 (sfd_sync32 ...) or sfd_sync16 (long_all, or by the launch's common K1)
+enum SfdForm { SFD_MID32, SFD_LONG_ALL, SFD_PACKED12, SFD_PACKED13, SFD_PACKED };
+
+// tiles per workgroup: `most`, halved while the grid would have fewer than 2048 workgroups (keep the chip full)
+static u32 sfd_tpw(u32 most, u32 max_tiles, int nblocks)
+{
+    u32 tpw = most;
+    while (tpw > 1 && (u64)ceil_div_u64(max_tiles, tpw) * nblocks < 2048) tpw >>= 1;
+    return tpw;
+}
+
+// The chain of complete codes: sfd_tables; when `spec`, the speculative entries (sfd_scan: the guesses of every unit; sfd_ends:
+// the units the streams end in, the links between all units and the verdict per block) with counting tables of tabb bytes;
+// the exact kernels of `form`; sfd_offsets; the symbol pass sfd_wstage (with escapes when `esc`).  long_used: bytes of the
+// table of long codes the blocks fill (long_all, mid32), else 0.  all_spec: every block speculates, so the exact kernels are
+// fall-backs that normally return at once: fat workgroups (256 tiles each) make that a launch of a few thousand workgroups
+// instead of a few hundred thousand.  ws_tab, ws_cap: sfd_wstage's three-codes table and symbol image, bytes.
+static void sfd_launch_packed(hipStream_t st, const DecBlk *dblk, int nblocks, u32 max_tiles, SfdForm form, bool esc, bool spec,
+                              u32 tabb, u32 long_used, bool all_spec, u32 ws_tab, u32 ws_cap, const SfdArrays &a)
+{
+    // the kernels of each form in the order of SfdForm, which is also the order the code object holds them in
+    static decltype(&sfd_scan<0>) const scans[3] = {sfd_scan<2>, sfd_scan<1>, sfd_scan<0>};
+    static decltype(&sfd_ends<0>) const ends[3] = {sfd_ends<2>, sfd_ends<1>, sfd_ends<0>};
+    static decltype(&sfd_sync16<true, false>) const syncs[4] = {sfd_sync16<false, true>, sfd_sync16<true, false, 12>,
+                                                                sfd_sync16<true, false, 13>, sfd_sync16<true, false>};
+    const int f = form < SFD_PACKED12 ? form : 2;                           // LONG = 2 - f of sfd_scan / sfd_ends / sfd_wstage
+    const dim3 grid_b((u32)nblocks), wg(DEC_THREADS);
+    hipLaunchKernelGGL(sfd_tables, dim3((u32)nblocks, 8), wg, 0, st, dblk);
+    if (spec) {
+        const size_t lds_scan = (size_t)SC_LDS_ROWS + tabb + SC_MISC + long_used;
+        const size_t lds_ends = (size_t)SL_LDS_DATA + tabb + SL_MISC + long_used;
+        hipLaunchKernelGGL(scans[f], dim3((u32)ceil_div_u64(max_tiles, SC_TILES), (u32)nblocks), wg, lds_scan, st, dblk, a.cent, a.ccnt,
+                           a.tcnt, a.tguess, a.texit, tabb, long_used);
+        hipLaunchKernelGGL(ends[f], dim3(1u + (u32)ceil_div_u64(max_tiles, SF_LINKS), (u32)nblocks), wg, lds_ends, st, dblk, a.cent,
+                           a.ccnt, a.tcnt, a.tguess, a.texit, tabb, long_used);
+    }
+    const u32 tpw = all_spec ? 256u : sfd_tpw(4, max_tiles, nblocks);        // tiles per workgroup of the exact kernels
+    const dim3 grid_f((u32)ceil_div_u64(max_tiles, tpw), (u32)nblocks);
+    if (form == SFD_MID32) {
+        hipLaunchKernelGGL(sfd_sync32, grid_f, wg, 0, st, dblk, a.cfn, a.tfn, tpw);
+        hipLaunchKernelGGL(sfd_tiles, grid_b, wg, (size_t)32 * DEC_THREADS + DEC_THREADS, st, dblk, 32u, (const u8 *)a.tfn, a.tent);
+        hipLaunchKernelGGL(sfd_countfsm32, grid_f, wg, 0, st, dblk, (const u8 *)a.cfn, (const u8 *)a.tent, a.cent, a.ccnt, a.tcnt, tpw);
+    } else {
+        constexpr int CSUBS = 4;                       // 256-lane groups per workgroup of sfd_countfsm
+        hipLaunchKernelGGL(syncs[form - SFD_LONG_ALL], grid_f, wg, 0, st, dblk, (u64 *)a.cfn, (u64 *)a.tfn, tpw);
+        hipLaunchKernelGGL(sfd_tiles16, grid_b, wg, 0, st, dblk, (const u64 *)a.tfn, a.tent);
+        hipLaunchKernelGGL((sfd_countfsm<CSUBS>), dim3((u32)ceil_div_u64(max_tiles, tpw * CSUBS), (u32)nblocks), dim3(DEC_THREADS * CSUBS),
+                           0, st, dblk, (const u64 *)a.cfn, (const u8 *)a.tent, a.cent, a.ccnt, a.tcnt, tpw);
+    }
+    hipLaunchKernelGGL(sfd_offsets, grid_b, wg, 0, st, dblk, (const u32 *)a.tcnt, a.toff);
+    // the staged symbol pass takes 16 tiles per workgroup (table fill, image zeroing and the prefetch pipeline's start are
+    // paid once per workgroup: 7.8 -> 7.7 ms on the headline data against 4; 32: the same)
+    static decltype(&sfd_wstage<0, false>) const wstages[4] = {sfd_wstage<2, true>, sfd_wstage<1, true>, sfd_wstage<0, true>,
+                                                               sfd_wstage<0, false>};
+    const u32 tpw_ws = sfd_tpw(16, max_tiles, nblocks);
+    const size_t lds_ws = (size_t)ws_rows_bytes(esc) + ws_tab + ws_cap + WS_MISC + long_used;
+    hipLaunchKernelGGL(wstages[f == 2 && !esc ? 3 : f], dim3((u32)ceil_div_u64(max_tiles, tpw_ws), (u32)nblocks), wg, lds_ws, st,
+                       dblk, (const u8 *)a.cent, (const u16 *)a.ccnt, (const u64 *)a.toff, tpw_ws, ws_tab, ws_cap, long_used);
+}
+
+// The byte-map chain (any code of up to R bits): sfd_sync, sfd_tiles, sfd_count, sfd_offsets, sfd_write over nb blocks of at
+// most max_tiles tiles.  l2cap: level-2 look-up entries reserved in LDS after level 1.
+static int sfd_launch_bytemap(hipStream_t st, const DecBlk *dblk, u32 nb, u32 max_tiles, u32 R, u32 l2cap, const SfdArrays &a)
+{
+    const size_t lds_lut = (size_t)(1u << LUT_MAXK) * 2 + (size_t)l2cap * 2;
+    const size_t lds_sync = (size_t)LDS_DATA + (size_t)R * DEC_THREADS + lds_lut + 4 * R + 64;
+    const size_t lds_count = lds_sync + DEC_THREADS;
+    const size_t lds_write = (size_t)LDS_DATA + lds_lut + 64;
+    const size_t lds_tiles = (size_t)R * DEC_THREADS + DEC_THREADS;
+    if (lds_tiles > 65536 || lds_sync > 65536) {     // long codes (R = 256): more than the default 64 KiB
+        HIP_TRY(hipFuncSetAttribute((const void *)sfd_sync, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sync));
+        HIP_TRY(hipFuncSetAttribute((const void *)sfd_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
+        HIP_TRY(hipFuncSetAttribute((const void *)sfd_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tiles));
+    }
+    const dim3 grid_t(max_tiles, nb), grid_b(nb), wg(DEC_THREADS);
+    hipLaunchKernelGGL(sfd_sync, grid_t, wg, lds_sync, st, dblk, R, l2cap, a.cfn, a.tfn);
+    hipLaunchKernelGGL(sfd_tiles, grid_b, wg, lds_tiles, st, dblk, R, (const u8 *)a.tfn, a.tent);
+    hipLaunchKernelGGL(sfd_count, grid_t, wg, lds_count, st, dblk, R, l2cap, (const u8 *)a.cfn, (const u8 *)a.tent, a.cent, a.ccnt,
+                       a.tcnt);
+    hipLaunchKernelGGL(sfd_offsets, grid_b, wg, 0, st, dblk, (const u32 *)a.tcnt, a.toff);
+    hipLaunchKernelGGL(sfd_write, grid_t, wg, lds_write, st, dblk, l2cap, (const u8 *)a.cent, (const u16 *)a.ccnt, (const u64 *)a.toff);
+    return SHAFA_SUCCESS;
 }
 
 int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
@@ -1445,21 +1517,13 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     // speculative entries (complete codes, Lmax <= 32, tables that re-synchronise): per-tile guess / exit / redo flag
     // (long_all and mid32 launches too: a code of more than 13 bits is an escape inside the walk)
     const bool spec_path = (packed || mid32) && g_sfd_speculate != 0;
-    const int spec_long = mid32 ? 2 : long_all ? 1 : 0;
-    // window of sfd_scan's counting tables.  A 13-bit table in a launch with the table of long codes (which holds every code
-    // of more than 12 bits, by 12-bit prefix) may count with 12-bit windows: the 13-bit codes become escapes like the 14..16-
-    // bit ones, 8 KB of tables instead of 16 fit six workgroups on a CU instead of four (LABNOTES.md §3.2).  Worth it while the
-    // 13-bit codes are few (an escape is a binary search that the whole wave waits for): at most eight of them, 0.1 % of the
-    // symbols of a block coded near its entropy.
-    std::vector<u32> hblk_kw(nblocks, 0);
+    std::vector<u32> hblk_kw(nblocks, 0);             // window of sfd_scan's counting tables
     for (int b = 0; b < nblocks; ++b) {
         if (!ntiles[b]) continue;
-        hblk_kw[b] = spec_window(tabs[b].K1);
-        if (spec_long && tabs[b].K1 == 13) {
-            u32 n13 = 0;
+        u32 n13 = 0;
+        if (tabs[b].K1 == 13)
             for (int sy = 0; sy < 256; ++sy) n13 += h_tables[b].len[sy] == 13;
-            if (n13 <= 8) hblk_kw[b] = 12;
-        }
+        hblk_kw[b] = scan_window(tabs[b].K1, long_all || mid32, n13);
     }
     u32 long_used = 0;                                 // bytes of the 13..16-bit codes' table that the launch's blocks fill
     if (long_all) {
@@ -1567,104 +1631,23 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     if ((rc = batch_params_commit(bt, st, hs, stage_bytes))) return rc;
 
     const DecBlk *dblk = (const DecBlk *)(dpar + o_blk);
-    const size_t lds_data = (size_t)(DATA_WORDS + DATA_WORDS / 8 + 8) * 4;
-    const size_t lds_lut = (size_t)(1u << LUT_MAXK) * 2 + (size_t)((max_l2 + 8) & ~7u) * 2;
-    const size_t lds_sync = lds_data + (size_t)R * DEC_THREADS + lds_lut + 4 * R + 64;
-    const size_t lds_count = lds_data + (size_t)R * DEC_THREADS + lds_lut + 4 * R + DEC_THREADS + 64;
-    const size_t lds_write = lds_data + lds_lut + 64;
-    const size_t lds_tiles = (size_t)R * DEC_THREADS + DEC_THREADS;
-    if (lds_tiles > 65536 || lds_sync > 65536) {     // long codes (R = 256): more than the default 64 KiB
-        HIP_TRY(hipFuncSetAttribute((const void *)sfd_sync, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sync));
-        HIP_TRY(hipFuncSetAttribute((const void *)sfd_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
-        HIP_TRY(hipFuncSetAttribute((const void *)sfd_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tiles));
+    const SfdArrays arr = {ws + o_cfn, ws + o_tilefn, ws + o_tent, ws + o_cent, (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt),
+                           (u64 *)(ws + o_toff), ws + o_tguess, ws + o_texit};
+    if (!packed && !mid32) {
+        if ((rc = sfd_launch_bytemap(st, dblk, (u32)nblocks, max_tiles, R, (max_l2 + 8) & ~7u, arr))) return rc;
+        HIP_TRY(hipGetLastError());
+        return pscope.done();
     }
-    const u32 l2cap = (max_l2 + 8) & ~7u;             // level-2 LDS entries reserved after level 1
-    const dim3 grid_t(max_tiles, (u32)nblocks), grid_b((u32)nblocks);
-    u32 tpw = 4;                                       // tiles per workgroup of the fast kernels (one table load)
-    while (tpw > 1 && (u64)ceil_div_u64(max_tiles, tpw) * nblocks < 2048) tpw >>= 1;     // keep the chip full
-    const dim3 grid_f((u32)ceil_div_u64(max_tiles, tpw), (u32)nblocks);
-    constexpr int CSUBS = 4;                           // 256-lane groups per workgroup of sfd_countfsm
-    const dim3 grid_c((u32)ceil_div_u64(max_tiles, tpw * CSUBS), (u32)nblocks);
-    // speculative entries: the guesses of every unit (sfd_scan), then the units the streams end in, the links between all units and
-    // the verdict per block (sfd_ends)
-    auto launch_spec = [&]() {
-        u8 *tg = ws + o_tguess, *tx = ws + o_texit;
-        u32 k1_max = 1;
-        for (int b = 0; b < nblocks; ++b) if (spec_blk[b] && hblk_kw[b] > k1_max) k1_max = hblk_kw[b];
-        const u32 tabb = 2u << k1_max;
-        const size_t lds_scan = (size_t)SC_LDS_ROWS + tabb + SC_MISC + (spec_long ? (size_t)long_used : 0);
-        const dim3 grid_c((u32)ceil_div_u64(max_tiles, SC_TILES), (u32)nblocks);
-        if (spec_long == 2)
-            hipLaunchKernelGGL((sfd_scan<2>), grid_c, dim3(DEC_THREADS), lds_scan, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                               (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-        else if (spec_long == 1)
-            hipLaunchKernelGGL((sfd_scan<1>), grid_c, dim3(DEC_THREADS), lds_scan, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                               (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-        else
-            hipLaunchKernelGGL((sfd_scan<0>), grid_c, dim3(DEC_THREADS), lds_scan, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                               (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-        {   // the units the streams end in and the links between all units: checked, repaired, the blocks' verdicts
-            const size_t lds_ends = (size_t)SL_LDS_DATA + tabb + SL_MISC + (spec_long ? (size_t)long_used : 0);
-            const dim3 grid_e(1u + (u32)ceil_div_u64(max_tiles, SF_LINKS), (u32)nblocks);
-            if (spec_long == 2)
-                hipLaunchKernelGGL((sfd_ends<2>), grid_e, dim3(DEC_THREADS), lds_ends, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                                   (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-            else if (spec_long == 1)
-                hipLaunchKernelGGL((sfd_ends<1>), grid_e, dim3(DEC_THREADS), lds_ends, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                                   (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-            else
-                hipLaunchKernelGGL((sfd_ends<0>), grid_e, dim3(DEC_THREADS), lds_ends, st, dblk, ws + o_cent, (u16 *)(ws + o_ccnt),
-                                   (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-        }
-    };
-    // when every block of the launch speculates, the exact kernels are fall-backs that normally return at once:
-    // fat workgroups (256 tiles each) make that a launch of a few thousand workgroups instead of a few hundred thousand
+    u32 k1_max = 1, k1_all = 0;                        // widest sfd_scan window; common K1 of the running blocks, 0 when they differ
     bool all_spec = any_spec;
-    for (int b = 0; b < nblocks; ++b) if (ntiles[b] && !spec_blk[b]) all_spec = false;
-    const u32 tpw_dp = all_spec ? 256u : tpw;
-    const dim3 grid_fd((u32)ceil_div_u64(max_tiles, tpw_dp), (u32)nblocks);
-    if (packed) {
-        hipLaunchKernelGGL(sfd_tables, dim3((u32)nblocks, 8), dim3(DEC_THREADS), 0, st, dblk);
-        if (any_spec) launch_spec();
-        const dim3 grid_cd((u32)ceil_div_u64(max_tiles, tpw_dp * CSUBS), (u32)nblocks);
-        u32 k1_all = 0;                                // common K1 of the running blocks, 0 when they differ
-        for (int b = 0; b < nblocks; ++b)
-            if (ntiles[b]) k1_all = (k1_all == 0 || k1_all == tabs[b].K1) ? tabs[b].K1 : 0xFFFFFFFFu;
-        if (long_all)
-            hipLaunchKernelGGL((sfd_sync16<false, true>), grid_fd, dim3(DEC_THREADS), 0, st, dblk,
-                               (u64 *)(ws + o_cfn), (u64 *)(ws + o_tilefn), tpw_dp);
-        else if (k1_all == 12)
-            hipLaunchKernelGGL((sfd_sync16<true, false, 12>), grid_fd, dim3(DEC_THREADS), 0, st, dblk,
-                               (u64 *)(ws + o_cfn), (u64 *)(ws + o_tilefn), tpw_dp);
-        else if (k1_all == 13)
-            hipLaunchKernelGGL((sfd_sync16<true, false, 13>), grid_fd, dim3(DEC_THREADS), 0, st, dblk,
-                               (u64 *)(ws + o_cfn), (u64 *)(ws + o_tilefn), tpw_dp);
-        else
-            hipLaunchKernelGGL((sfd_sync16<true, false>), grid_fd, dim3(DEC_THREADS), 0, st, dblk,
-                               (u64 *)(ws + o_cfn), (u64 *)(ws + o_tilefn), tpw_dp);
-        hipLaunchKernelGGL(sfd_tiles16, grid_b, dim3(DEC_THREADS), 0, st, dblk, (const u64 *)(ws + o_tilefn),
-                           ws + o_tent);
-        hipLaunchKernelGGL((sfd_countfsm<CSUBS>), grid_cd, dim3(DEC_THREADS * CSUBS), 0, st, dblk,
-                           (const u64 *)(ws + o_cfn), (const u8 *)(ws + o_tent), ws + o_cent, (u16 *)(ws + o_ccnt),
-                           (u32 *)(ws + o_tcnt), tpw_dp);
-    } else if (mid32) {
-        hipLaunchKernelGGL(sfd_tables, dim3((u32)nblocks, 8), dim3(DEC_THREADS), 0, st, dblk);
-        if (any_spec) launch_spec();
-        hipLaunchKernelGGL(sfd_sync32, grid_fd, dim3(DEC_THREADS), 0, st, dblk, ws + o_cfn, ws + o_tilefn, tpw_dp);
-        hipLaunchKernelGGL(sfd_tiles, grid_b, dim3(DEC_THREADS), lds_tiles, st, dblk, R, (const u8 *)(ws + o_tilefn),
-                           ws + o_tent);
-        hipLaunchKernelGGL(sfd_countfsm32, grid_fd, dim3(DEC_THREADS), 0, st, dblk, (const u8 *)(ws + o_cfn),
-                           (const u8 *)(ws + o_tent), ws + o_cent, (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tpw_dp);
-    } else {
-        hipLaunchKernelGGL(sfd_sync, grid_t, dim3(DEC_THREADS), lds_sync, st, dblk, R, l2cap, ws + o_cfn, ws + o_tilefn);
-        hipLaunchKernelGGL(sfd_tiles, grid_b, dim3(DEC_THREADS), lds_tiles, st, dblk, R, (const u8 *)(ws + o_tilefn),
-                           ws + o_tent);
-        hipLaunchKernelGGL(sfd_count, grid_t, dim3(DEC_THREADS), lds_count, st, dblk, R, l2cap,
-                           (const u8 *)(ws + o_cfn), (const u8 *)(ws + o_tent), ws + o_cent, (u16 *)(ws + o_ccnt),
-                           (u32 *)(ws + o_tcnt));
+    for (int b = 0; b < nblocks; ++b) {
+        if (!ntiles[b]) continue;
+        if (spec_blk[b] && hblk_kw[b] > k1_max) k1_max = hblk_kw[b];
+        k1_all = (k1_all == 0 || k1_all == tabs[b].K1) ? tabs[b].K1 : 0xFFFFFFFFu;
+        if (!spec_blk[b]) all_spec = false;
     }
-    hipLaunchKernelGGL(sfd_offsets, grid_b, dim3(DEC_THREADS), 0, st, dblk, (const u32 *)(ws + o_tcnt),
-                       (u64 *)(ws + o_toff));
+    const SfdForm form = mid32 ? SFD_MID32 : long_all ? SFD_LONG_ALL : k1_all == 12 ? SFD_PACKED12 : k1_all == 13 ? SFD_PACKED13
+                                                                                                          : SFD_PACKED;
     u32 ws_tab = 16;                                   // sym3 bytes of the widest table of the launch
     for (int b = 0; b < nblocks; ++b) {
         const u32 k3 = sym3_window(tabs[b].K1);
@@ -1675,8 +1658,7 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     // almost in proportion to the waves it loses, and a CU's LDS is handed out as two halves of 80 KiB (8 workgroups up to
     // 20 KiB each, 6 up to 26.25, 4 up to 40, 2 above: DESIGN.md §3.2).  Codes of up to 12 bits on run-heavy data: 41.7 KB
     // with the wide margin = 2 workgroups per CU, 40 KB with the narrow one = 4.
-    const bool ws_esc = mid32 || (packed && (long_all || lmax_all > (u32)SYM3_MAXK));       // the form launched below
-    const u32 ws_rows = (u32)ws_rows_bytes(ws_esc);
+    const bool ws_esc = mid32 || long_all || lmax_all > (u32)SYM3_MAXK;                   // sfd_wstage with escapes
     u32 ws_cap = 4096, ws_tight = 4096;
     for (int b = 0; b < nblocks; ++b) {
         if (!ntiles[b]) continue;
@@ -1686,8 +1668,7 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
         if (t > ws_tight) ws_tight = (u32)(t > 40960 ? 40960 : t);
     }
     {
-        const u32 longb = long_used;
-        const u32 base = ws_rows + ws_tab + longb + (u32)WS_MISC;
+        const u32 base = (u32)ws_rows_bytes(ws_esc) + ws_tab + long_used + (u32)WS_MISC;
         const u32 most = 65536u - base;                                           // 64 KiB of dynamic LDS
         if (ws_cap > most) ws_cap = most;
         constexpr u32 steps[3] = {20480u, 26880u, 40960u};                        // 8, 6, 4 workgroups per CU as launches show them
@@ -1701,29 +1682,7 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
         }
     }
     ws_cap &= ~15u;
-    const size_t lds_ws = (size_t)ws_rows + ws_tab + ws_cap + WS_MISC;
-    // the staged symbol pass takes 16 tiles per workgroup (table fill, image zeroing and the prefetch pipeline's start are
-    // paid once per workgroup: 7.8 -> 7.7 ms on the headline data against 4; 32: the same), the chip kept full as above
-    u32 tpw_ws = 16;
-    while (tpw_ws > 1 && (u64)ceil_div_u64(max_tiles, tpw_ws) * nblocks < 2048) tpw_ws >>= 1;
-    const dim3 grid_ws((u32)ceil_div_u64(max_tiles, tpw_ws), (u32)nblocks);
-    if (mid32) {
-        hipLaunchKernelGGL((sfd_wstage<2, true>), grid_ws, dim3(DEC_THREADS), lds_ws + long_used, st, dblk,
-                           (const u8 *)(ws + o_cent), (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab, ws_cap, long_used);
-    } else if (packed) {
-        if (long_all)
-            hipLaunchKernelGGL((sfd_wstage<1, true>), grid_ws, dim3(DEC_THREADS), lds_ws + long_used, st, dblk,
-                               (const u8 *)(ws + o_cent), (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab, ws_cap, long_used);
-        else if (lmax_all > (u32)SYM3_MAXK)
-            hipLaunchKernelGGL((sfd_wstage<0, true>), grid_ws, dim3(DEC_THREADS), lds_ws, st, dblk,
-                               (const u8 *)(ws + o_cent), (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab, ws_cap, 0u);
-        else
-            hipLaunchKernelGGL((sfd_wstage<0, false>), grid_ws, dim3(DEC_THREADS), lds_ws, st, dblk,
-                               (const u8 *)(ws + o_cent), (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab, ws_cap, 0u);
-    } else {
-        hipLaunchKernelGGL(sfd_write, grid_t, dim3(DEC_THREADS), lds_write, st, dblk, l2cap, (const u8 *)(ws + o_cent),
-                           (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff));
-    }
+    sfd_launch_packed(st, dblk, nblocks, max_tiles, form, ws_esc, any_spec, 2u << k1_max, long_used, all_spec, ws_tab, ws_cap, arr);
     HIP_TRY(hipGetLastError());
     return pscope.done();
 }

@@ -236,7 +236,7 @@ bool sfenc4_needs_redo(u32 lmax);
 bool sfenc4_long_ok();
 int sfenc4_launch_long(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
 int sfenc6_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 lmax, bool any_ragged, u32 *d_tbits, u64 *d_toff);
-extern int g_sfe4_wide, g_sfe_lanes;
+extern int g_sfe_lanes;
 
 // A launch with at least this many class-1 blocks takes the one-pass encoder: every block is its own chain, and with this
 // many chains (<= ~10 workgroups per block) a tile's look-back stays inside one 64-entry descriptor window.  Measured
@@ -246,25 +246,21 @@ extern int g_sfe4_wide, g_sfe_lanes;
 // 6 blocks where the 1024-lane form runs (Lmax <= 12), 80 for the 256-lane form
 static int g_sfe4_min_blocks = 0;
 void sfenc_configure(int sfe4_min_blocks) { g_sfe4_min_blocks = sfe4_min_blocks; }
-int sfenc_min_blocks() { return g_sfe4_min_blocks; }
+
+// The one-pass encoder pays from 6 blocks per launch in its 1024-lane form (every Lmax <= 16 since the windows of 13..16-bit
+// codes are sized for 12 bits per symbol with an encode-again fall-back), from 80 in the 256-lane form.  Codes of 17..32 bits
+// take the quad form of the one-pass encoder from 6 blocks per launch, else count / scan / pack with 64-bit groups.
+bool sfenc_one_pass(int cls, int count)
+{
+    if (cls == 2) return count >= (g_sfe4_min_blocks > 0 ? g_sfe4_min_blocks : 6) && sfenc4_long_ok();
+    return count >= (g_sfe4_min_blocks > 0 ? g_sfe4_min_blocks : (g_sfe_lanes == 0 ? 6 : 80));
+}
 
 // the generic kernel for sfenc_launch_dev (sf_encode_dev.hip): d_plan = {most tiles of a record, number of records}, written
 // on the device; `grid` workgroups loop over the slots
 void sfenc_generic_launch_dev(hipStream_t st, const EncBlk *dblk, u32 grid, u64 *d_desc, u32 *d_tickets, const u32 *d_plan)
 {
     hipLaunchKernelGGL(sf_encode_generic_dev, dim3(grid), dim3(ENC_THREADS), 0, st, dblk, d_desc, d_tickets, d_plan);
-}
-
-// the code of symbol s (<= 32 bits: classes 1 and 2) right-aligned: its first four bytes, MSB first, shifted down.
-// (Bit by bit this loop was most of the 1.3 ms the host needed to prepare a 128-block launch: more than the kernel takes
-// on 1 GiB in 8 MiB blocks.)
-static u32 code_value(const shafa_code_table &t, int s)
-{
-    const u32 len = t.len[s];
-    if (!len) return 0;
-    const u8 *b = t.bits[s];
-    const u32 be = ((u32)b[0] << 24) | ((u32)b[1] << 16) | ((u32)b[2] << 8) | (u32)b[3];
-    return len >= 32 ? be : be >> (32 - len);
 }
 
 int sfenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
@@ -291,13 +287,7 @@ int sfenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
         if (c == 1 && (u32)lmax > lmax1) lmax1 = (u32)lmax;
         if (c == 2 && (u32)lmax > lmax2) lmax2 = (u32)lmax;
     }
-    // the one-pass encoder pays from 6 blocks per launch in its 1024-lane form (every Lmax <= 16 since the windows of
-    // 13..16-bit codes are sized for 12 bits per symbol with an encode-again fall-back), from 80 in the 256-lane form
-    const bool wide_form = g_sfe4_wide && g_sfe_lanes == 0 && (lmax1 <= 12 || sfenc4_needs_redo(lmax1));
-    const bool one_pass = tiles || cls_count[1] >= (g_sfe4_min_blocks > 0 ? g_sfe4_min_blocks : (wide_form ? 6 : 80));
-    // codes of 17..32 bits: the quad form of the one-pass encoder from 6 blocks per launch, else count / scan / pack with
-    // 64-bit groups
-    const bool one_pass2 = cls_count[2] >= (g_sfe4_min_blocks > 0 ? g_sfe4_min_blocks : 6) && sfenc4_long_ok();
+    const bool one_pass = tiles || sfenc_one_pass(1, cls_count[1]), one_pass2 = sfenc_one_pass(2, cls_count[2]);
     const bool redo = (one_pass && !tiles && cls_count[1] && sfenc4_needs_redo(lmax1)) || one_pass2;
     // class 1 with tile histograms: 32 KiB tiles, and one entry more per block (the block's total behind its tile offsets)
     const u64 tile_syms[4] = {1, tiles ? 32768u : 256 * 16 * 2, 256 * 16 * 2, GEN_TILE};
@@ -369,21 +359,17 @@ int sfenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
             dbase += e.n_tiles + (c == 1 && tiles ? 1 : 0);
             e.lut = dpar + (o_tab - o_blk) + tpos;
             const shafa_code_table &t = h_tables[b];
-            if (c == 1 && one_pass) {                 // {code, len}; a symbol without a code: len = 1 << 16
-                u64 *l = (u64 *)(htab + tpos);
-                for (int s = 0; s < 256; ++s) l[s] = t.len[s] ? ((u64)code_value(t, s) | ((u64)t.len[s] << 32)) : (1ull << 48);
-                tpos += 2048;
-            } else if (c == 1) {                      // code | len << 16; bit 31: no code
+            if (c == 1 && !one_pass) {
                 u32 *l = (u32 *)(htab + tpos);
-                for (int s = 0; s < 256; ++s) l[s] = t.len[s] ? (code_value(t, s) | ((u32)t.len[s] << 16)) : 0x80000000u;
+                for (u32 s = 0; s < 256; ++s) l[s] = sfe_entry(sfe_entry32, t, s);
                 tpos += 1024;
-            } else if (c == 2 && one_pass2) {         // {code, len}; a symbol without a code: len = 1 << 16
+            } else if (c == 2 && !one_pass2) {
                 u64 *l = (u64 *)(htab + tpos);
-                for (int s = 0; s < 256; ++s) l[s] = t.len[s] ? ((u64)code_value(t, s) | ((u64)t.len[s] << 32)) : (1ull << 48);
+                for (u32 s = 0; s < 256; ++s) l[s] = sfe_entry(sfe_entry64, t, s);
                 tpos += 2048;
-            } else if (c == 2) {                      // code | len << 32
+            } else if (c != 3) {                      // the one-pass forms
                 u64 *l = (u64 *)(htab + tpos);
-                for (int s = 0; s < 256; ++s) l[s] = (u64)code_value(t, s) | ((u64)t.len[s] << 32);
+                for (u32 s = 0; s < 256; ++s) l[s] = sfe_entry(sfe_entry_pair, t, s);
                 tpos += 2048;
             } else {
                 memcpy(htab + tpos, &t, sizeof(t));

@@ -31,7 +31,6 @@
 
 #include <mutex>
 
-int g_sfe4_wide = 1;                                   // 0: always the 256-lane form (A/B and tests)
 int g_sfe_window_bits = 0;                             // test knob: bits per symbol of the wide form's windows (0: min(Lmax, 12))
 int g_sfe_lanes = 0;                                   // 0: widest form that fits; 256 / 512: that workgroup width (A/B and tests)
 
@@ -334,7 +333,7 @@ int e4_launch_t(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 
     const bool ragged8 = ragged & 1u, ragged16 = ragged & 2u, ragged32 = ragged & 4u;
     if (g_sfe_lanes == 512)
         return e4_launch_nt<NW, L16, 512>(st, dblk, count, d_desc, d_tickets, lmax, lmax, ragged16, nullptr, 0);
-    if (g_sfe_lanes == 256 || !g_sfe4_wide)
+    if (g_sfe_lanes == 256)
         return e4_launch_nt<NW, L16, 256>(st, dblk, count, d_desc, d_tickets, lmax, lmax, ragged8, nullptr, 0);
     const u32 wbits = e5_window_bits(lmax);
     if (wbits == lmax) return e4_launch_nt<NW, L16, 1024>(st, dblk, count, d_desc, d_tickets, lmax, lmax, ragged32, nullptr, 0);
@@ -353,12 +352,12 @@ int e4_launch_t(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 
 // does a launch with this longest code run the wide form with windows smaller than its worst case (then it needs `x`)?
 bool sfenc4_needs_redo(u32 lmax)
 {
-    return g_sfe4_wide && g_sfe_lanes == 0 && e5_window_bits(lmax) < lmax;
+    return g_sfe_lanes == 0 && e5_window_bits(lmax) < lmax;
 }
 
 // can launches of codes of 17..32 bits take the one-pass encoder (quad form)?  It always runs with windows smaller than
 // its worst case, so it needs the second chain.
-bool sfenc4_long_ok() { return g_sfe4_wide && g_sfe_lanes == 0; }
+bool sfenc4_long_ok() { return g_sfe_lanes == 0; }
 
 // blocks whose codes are 17..32 bits (tables 256 x u64 {code, len}, len = 1 << 16 for a symbol without a code)
 int sfenc4_launch_long(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x)

@@ -9,8 +9,9 @@
 // list is compacted instead).  So a block is encoded by the kernels sfenc_launch would give it, and the bytes are the same.
 //
 // What the host still decides, from host arguments only: the workspace layout (descriptor bases sized for h_in_cap[b] over
-// every form), grid sizes (nblocks, ceil(max h_in_cap / tile)), and the one-pass / count-scan-pack choice (from nblocks and
-// the knobs instead of the per-class count: the output bytes do not depend on it).  Nothing is read back: no device-to-host
+// every form), grid sizes (nblocks, ceil(max h_in_cap / tile)), and the one-pass / count-scan-pack choice (sfenc_one_pass on
+// nblocks instead of the per-class count: the output bytes do not depend on it).  The look-up table entries and the code
+// values come from the helpers of internal.hpp that sfenc_launch uses.  Nothing is read back: no device-to-host
 // copy, no synchronisation (batch_reserve and the parameter ring aside, which depend on nblocks and h_in_cap only).
 #include "common.hpp"
 #include "internal.hpp"
@@ -58,15 +59,6 @@ struct PlanOut {
     u32 scratch_desc;      // descriptor index of the empty records (sfe6_scan writes one entry)
 };
 
-// a code of <= 32 bits right-aligned: its first four bytes, MSB first, shifted down (sf_encode.hip: code_value)
-__device__ __forceinline__ u32 dev_code_value(const shafa_code_table *t, u32 s, u32 len)
-{
-    if (!len) return 0;
-    const u8 *b = t->bits[s];
-    const u32 be = ((u32)b[0] << 24) | ((u32)b[1] << 16) | ((u32)b[2] << 8) | (u32)b[3];
-    return len >= 32 ? be : be >> (32 - len);
-}
-
 __global__ __launch_bounds__(256) void sfe_plan_kernel(const PlanBlk *__restrict__ pb, int nblocks, const u64 *__restrict__ d_in_n,
                                                        const shafa_code_table *__restrict__ d_tables, u64 *d_out_n, int *d_err,
                                                        PlanOut po, int c1mode, int one_pass2)
@@ -96,13 +88,10 @@ __global__ __launch_bounds__(256) void sfe_plan_kernel(const PlanBlk *__restrict
     // the look-up table, in the format sfenc_launch packs for this block's form
     u8 *lut = po.luts + (size_t)b * LUT_BYTES;
     if (cls == 1 || cls == 2) {
-        const u32 cv = dev_code_value(t, (u32)s, len);
-        if (cls == 1 && c1mode == C1_SFE3)             // code | len << 16; bit 31: no code
-            ((u32 *)lut)[s] = len ? (cv | (len << 16)) : 0x80000000u;
-        else if (cls == 2 && !one_pass2)               // code | len << 32
-            ((u64 *)lut)[s] = (u64)cv | ((u64)len << 32);
-        else                                           // {code, len}; a symbol without a code: len = 1 << 16
-            ((u64 *)lut)[s] = len ? ((u64)cv | ((u64)len << 32)) : (1ull << 48);
+        const u32 cv = sfe_code_value(*t, (u32)s, len);
+        if (cls == 1 && c1mode == C1_SFE3) ((u32 *)lut)[s] = sfe_entry32(cv, len);
+        else if (cls == 2 && !one_pass2) ((u64 *)lut)[s] = sfe_entry64(cv, len);
+        else ((u64 *)lut)[s] = sfe_entry_pair(cv, len);
     }
     const u32 tsyms = cls == 3 ? TILE_GEN : (cls == 1 && c1mode == C1_TILES ? TILE_E6 : TILE_E3);
     const u32 n_tiles = cls ? (u32)((n + tsyms - 1) / tsyms) : 0u;
@@ -157,12 +146,9 @@ __global__ __launch_bounds__(256) void sfe_plan_kernel(const PlanBlk *__restrict
 
 void sfenc3_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 *d_tile_bits, u64 *d_tile_off, bool lut64);
 int sfenc4_launch(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
-bool sfenc4_long_ok();
 int sfenc4_launch_long(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
 int sfenc6_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 lmax, bool any_ragged, u32 *d_tbits, u64 *d_toff);
-int sfenc_min_blocks();
 void sfenc_generic_launch_dev(hipStream_t st, const EncBlk *dblk, u32 grid, u64 *d_desc, u32 *d_tickets, const u32 *d_plan);
-extern int g_sfe4_wide, g_sfe_lanes;
 
 int sfenc_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                      const u64 *d_in_n, const shafa_code_table *d_tables, u8 *d_out, const u64 *h_out_off,
@@ -181,11 +167,8 @@ int sfenc_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, con
     const u32 scratch_desc = (u32)ndesc;
     if (++ndesc >= 0xFFFFFFFFull) return SHAFA_LACK_OF_MEMORY;
 
-    // the forms, from host arguments only (sfenc_launch decides the same from its per-class counts)
-    const bool wide = g_sfe4_wide && g_sfe_lanes == 0;
-    const int min_blocks = sfenc_min_blocks();
-    const bool one_pass = nblocks >= (min_blocks > 0 ? min_blocks : (wide ? 6 : 80));
-    const bool one_pass2 = nblocks >= (min_blocks > 0 ? min_blocks : 6) && sfenc4_long_ok();
+    // the forms, from host arguments only: sfenc_launch's rule on nblocks instead of its per-class counts
+    const bool one_pass = sfenc_one_pass(1, nblocks), one_pass2 = sfenc_one_pass(2, nblocks);
     const int c1mode = tiles ? C1_TILES : one_pass ? C1_ONE_PASS : C1_SFE3;
 
     // device workspace: [header: generic plan, scratch error, scratch size][desc][desc2][tile bits][tickets][tickets2]

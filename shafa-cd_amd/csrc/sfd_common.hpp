@@ -68,6 +68,54 @@ __host__ __device__ __forceinline__ u32 sym3_window(u32 K1)
     const u32 k = K1 < (u32)SYM3_MINW ? (u32)SYM3_MINW : K1;
     return k < (u32)SYM3_MAXK ? k : (u32)SYM3_MAXK;
 }
+// window of sfd_scan's counting tables for one block.  A 13-bit table in a launch with the table of long codes (which holds
+// every code of more than 12 bits, by 12-bit prefix) may count with 12-bit windows: the 13-bit codes become escapes like the
+// 14..16-bit ones, 8 KB of tables instead of 16 fit six workgroups on a CU instead of four (LABNOTES.md §3.2).  Worth it while
+// the 13-bit codes are few (an escape is a binary search that the whole wave waits for): at most eight of them, 0.1 % of the
+// symbols of a block coded near its entropy.
+__host__ __device__ __forceinline__ u32 scan_window(u32 K1, bool long_table, u32 n13)
+{
+    return long_table && K1 == 13 && n13 <= 8 ? 12u : spec_window(K1);
+}
+
+// The speculation verdict (spec_worthwhile on the host, sfd_plan_dev on the device): SPEC_TRIALS trials on random bits seeded
+// by the table's key; a table whose parses fail to merge in more than SPEC_MAX_FAILS of them does not speculate.
+constexpr int SPEC_TRIALS = 32, SPEC_MAX_FAILS = 6, SPEC_WORDS = 7;      // random words per trial
+// FNV-1a over the code lengths and the bytes of the codes (len[s], bits[s][0 .. (len[s] + 7) / 8))
+template <typename LenT, int NB>
+__host__ __device__ __forceinline__ u64 spec_key(const LenT *len, const u8 (*bits)[NB])
+{
+    u64 key = 1469598103934665603ull;
+    for (int s = 0; s < 256; ++s) {
+        key = (key ^ len[s]) * 1099511628211ull;
+        for (u32 q = 0; q < (len[s] + 7) / 8; ++q) key = (key ^ bits[s][q]) * 1099511628211ull;
+    }
+    return key;
+}
+// the next word of the trials' xorshift generator (seeded with key | 1)
+__host__ __device__ __forceinline__ u64 spec_rand(u64 &rs)
+{
+    rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17;
+    return rs;
+}
+// One trial: w[0..5] are 384 random bits (bit i = bit 63 - i % 64 of w[i / 64]), w[6] picks the offset.  The true parser starts at
+// bit 0, a second one at 1 + w[6] % 15; they merge when the second lands on a start of the first within 256 bits.  A window
+// that starts a code of more than K1 bits (lenlut entry 0) counts as K1 + 1 bits.
+__host__ __device__ __forceinline__ bool spec_trial(const u64 *w, const u8 *lenlut, u32 K1)
+{
+    auto window = [&](u32 pos) -> u32 {                 // the K1 bits at pos, MSB first
+        const u32 wi = pos >> 6, r = pos & 63;
+        u64 v = w[wi] << r;
+        if (r && wi + 1 < 6) v |= w[wi + 1] >> (64 - r);
+        return (u32)(v >> (64 - K1));
+    };
+    auto len_at = [&](u32 pos) -> u32 { const u32 l = lenlut[window(pos)]; return l ? l : K1 + 1; };
+    u64 starts[5] = {0, 0, 0, 0, 0};                    // code starts of the true parse, bits 0..319
+    for (u32 pos = 0; pos < 300;) { starts[pos >> 6] |= 1ull << (pos & 63); pos += len_at(pos); }
+    for (u32 pos = 1 + (u32)(w[6] % 15); pos <= 256; pos += len_at(pos))
+        if ((starts[pos >> 6] >> (pos & 63)) & 1ull) return true;
+    return false;
+}
 
 // the exact kernels of a launch that also runs the speculative ones: skip the blocks that verified
 __device__ __forceinline__ bool dp_skipped(const DecBlk &blk)

@@ -3,13 +3,14 @@
 //
 // sfd_plan_dev (one workgroup per block) does on the device what sfdec_launch + build_host_tab + spec_worthwhile do on the
 // host: it validates the table, builds the look-up tables and the trie into the block's workspace slot, runs the
-// speculation verdict and writes the block's DecBlk into one of three lists (empty records, n_tiles = 0, in the others):
+// speculation verdict (spec_trial) and writes the block's DecBlk into one of four lists (empty records, n_tiles = 0, in the others):
 //   p12      complete codes of <= 12 bits                   sfdec_launch's packed form (sfd_sync16<true, false> ...)
 //   packed   complete codes of 13..16 bits                  the long_all form of sfdec_launch (sfd_sync16<false, true> ...)
 //   bytemap  everything else of <= 32 bits                  the byte-map kernels at R = 32
 //   big      codes of 33..64 bits (one block a launch)       the byte-map kernels at R = 64, one slot of max h_in_cap
-// The host launches every list over all its slots with grids from nblocks and the capacities; tile_base comes from the
-// capacities, so no launch parameter depends on what the tables hold.
+// The host launches every list over all its slots with sfdec_launch's chain launchers (sfd_launch_packed, sfd_launch_bytemap),
+// grids from nblocks and the capacities; tile_base comes from the capacities, so no launch parameter depends on what the
+// tables hold.
 #pragma once
 
 namespace {
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void sfd_plan_dev(const SdvHost *__restrict__ 
     __shared__ __attribute__((aligned(16))) u8 lenlut[(1u << LEN_MAXK) + 16];
     __shared__ __attribute__((aligned(16))) u8 symlut[1u << LEN_MAXK];
     __shared__ __attribute__((aligned(16))) u16 longtab[LONG_BYTES / 2];
-    __shared__ u64 rnd[32 * 7];
+    __shared__ u64 rnd[SPEC_TRIALS * SPEC_WORDS];
     __shared__ u32 s_lmax, s_n, s_bad, s_kraft, s_fails, s_n13, s_nl2, s_ngrp, s_nodes, s_big_taken;
 
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -273,42 +274,19 @@ __global__ __launch_bounds__(256) void sfd_plan_dev(const SdvHost *__restrict__ 
         for (u32 i = 0, lo = sub << (K + nb - L); i < (1u << (K + nb - L)); ++i) lut2[base + lo + i] = (u16)(tid | (L << 8));
     }
 
-    // ---- the speculation verdict (spec_worthwhile: the same key, random bits and rule) --------------------------------
+    // ---- the speculation verdict (spec_worthwhile's key, random bits and rule: sfd_common.hpp) ------------------------
     bool spec = false;
     if (packed && po.run_dp && lmax >= 2) {
         if (po.speculate == 2) spec = true;
         else {
-            if (tid == 0) {
-                u64 key = 1469598103934665603ull;
-                for (int s2 = 0; s2 < 256; ++s2) {
-                    key = (key ^ len[s2]) * 1099511628211ull;
-                    for (u32 q = 0; q < (len[s2] + 7) / 8; ++q) key = (key ^ raw[s2][q]) * 1099511628211ull;
-                }
-                u64 rs = key | 1ull;
-                for (int i = 0; i < 32 * 7; ++i) { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; rnd[i] = rs; }
+            if (tid == 0) {                             // raw holds every byte of a code of <= 16 bits
+                u64 rs = spec_key(len, raw) | 1ull;
+                for (int i = 0; i < SPEC_TRIALS * SPEC_WORDS; ++i) rnd[i] = spec_rand(rs);
             }
             __syncthreads();
-            if (tid < 32) {
-                const u64 *w = rnd + 7 * tid;
-                auto window = [&](u32 pos) -> u32 {
-                    const u32 wi = pos >> 6, r = pos & 63;
-                    u64 v = w[wi] << r;
-                    if (r && wi + 1 < 6) v |= w[wi + 1] >> (64 - r);
-                    return (u32)(v >> (64 - K1));
-                };
-                auto len_at = [&](u32 pos) -> u32 { const u32 l = lenlut[window(pos)]; return l ? l : K1 + 1; };
-                u64 starts[5] = {0, 0, 0, 0, 0};
-                for (u32 pos = 0; pos < 300;) { starts[pos >> 6] |= 1ull << (pos & 63); pos += len_at(pos); }
-                u32 pos = 1 + (u32)(w[6] % 15);
-                bool merged = false;
-                while (pos <= 256) {
-                    if ((starts[pos >> 6] >> (pos & 63)) & 1ull) { merged = true; break; }
-                    pos += len_at(pos);
-                }
-                if (!merged) atomicAdd(&s_fails, 1u);
-            }
+            if (tid < SPEC_TRIALS && !spec_trial(rnd + SPEC_WORDS * tid, lenlut, K1)) atomicAdd(&s_fails, 1u);
             __syncthreads();
-            spec = s_fails <= 6;
+            spec = s_fails <= (u32)SPEC_MAX_FAILS;
         }
     }
     __syncthreads();
@@ -352,7 +330,7 @@ __global__ __launch_bounds__(256) void sfd_plan_dev(const SdvHost *__restrict__ 
             e.KW = spec_window(K1);
             po.p12[b] = e;
         } else {
-            e.KW = (K1 == 13 && s_n13 <= 8) ? 12u : spec_window(K1);  // sfd_scan's window (sfdec_launch: long_all form)
+            e.KW = scan_window(K1, true, s_n13);          // with the table of long codes, as sfdec_launch's long_all form
             po.packed[b] = e;
         }
     } else if (big) {
@@ -433,95 +411,27 @@ int sfdec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, con
                        d_n_symbols, bt->d_err, po);
     if (!max_tiles) { HIP_TRY(hipGetLastError()); return pscope.done(); }
 
-    const dim3 grid_b((u32)nblocks);
     // ---- packed lists: <= 12 bits in sfdec_launch's packed form (pair table, no escapes), 13..16 bits in its long_all form
-    // (the whole table of long codes in LDS).  Both share the per-tile arrays: a block is in one list only.
-    auto packed_list = [&](const DecBlk *dblk, bool lng) {
-        u32 tpw = 4;
-        while (tpw > 1 && (u64)ceil_div_u64(max_tiles, tpw) * nblocks < 2048) tpw >>= 1;
-        constexpr int CSUBS = 4;
-        const dim3 grid_f((u32)ceil_div_u64(max_tiles, tpw), (u32)nblocks);
-        const dim3 grid_c((u32)ceil_div_u64(max_tiles, tpw * CSUBS), (u32)nblocks);
+    // (the whole table of long codes in LDS).  Both share the per-tile arrays: a block is in one list only.  The symbol image
+    // is fixed, for four workgroups per CU (a tile that exceeds it goes in rounds); sfdec_launch gives 12-bit tables on Zipf
+    // data the same 40 KiB.
+    const SfdArrays pa = {ws + o_pcfn, ws + o_ptfn, ws + o_tent, ws + o_cent, (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt),
+                          (u64 *)(ws + o_toff), ws + o_tguess, ws + o_texit};
+    for (const bool lng : {false, true}) {
         const u32 long_used = lng ? (u32)LONG_BYTES : 0u;   // the table of any block (header, prefixes, 128 groups)
-        hipLaunchKernelGGL(sfd_tables, dim3((u32)nblocks, 8), dim3(DEC_THREADS), 0, st, dblk);
-        if (spec) {
-            u8 *tg = ws + o_tguess, *tx = ws + o_texit;
-            const u32 tabb = 2u << (lng ? LEN_MAXK : SYM3_MAXK);
-            const size_t lds_scan = (size_t)SC_LDS_ROWS + tabb + SC_MISC + long_used;
-            const dim3 grid_s((u32)ceil_div_u64(max_tiles, SC_TILES), (u32)nblocks);
-            const dim3 grid_e(1u + (u32)ceil_div_u64(max_tiles, SF_LINKS), (u32)nblocks);
-            const size_t lds_ends = (size_t)SL_LDS_DATA + tabb + SL_MISC + long_used;
-            if (lng) {
-                hipLaunchKernelGGL((sfd_scan<1>), grid_s, dim3(DEC_THREADS), lds_scan, st, dblk, ws + o_cent,
-                                   (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-                hipLaunchKernelGGL((sfd_ends<1>), grid_e, dim3(DEC_THREADS), lds_ends, st, dblk, ws + o_cent,
-                                   (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-            } else {
-                hipLaunchKernelGGL((sfd_scan<0>), grid_s, dim3(DEC_THREADS), lds_scan, st, dblk, ws + o_cent,
-                                   (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-                hipLaunchKernelGGL((sfd_ends<0>), grid_e, dim3(DEC_THREADS), lds_ends, st, dblk, ws + o_cent,
-                                   (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tg, tx, tabb, long_used);
-            }
-        }
-        if (lng)
-            hipLaunchKernelGGL((sfd_sync16<false, true>), grid_f, dim3(DEC_THREADS), 0, st, dblk, (u64 *)(ws + o_pcfn),
-                               (u64 *)(ws + o_ptfn), tpw);
-        else
-            hipLaunchKernelGGL((sfd_sync16<true, false>), grid_f, dim3(DEC_THREADS), 0, st, dblk, (u64 *)(ws + o_pcfn),
-                               (u64 *)(ws + o_ptfn), tpw);
-        hipLaunchKernelGGL(sfd_tiles16, grid_b, dim3(DEC_THREADS), 0, st, dblk, (const u64 *)(ws + o_ptfn), ws + o_tent);
-        hipLaunchKernelGGL((sfd_countfsm<CSUBS>), grid_c, dim3(DEC_THREADS * CSUBS), 0, st, dblk, (const u64 *)(ws + o_pcfn),
-                           (const u8 *)(ws + o_tent), ws + o_cent, (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt), tpw);
-        hipLaunchKernelGGL(sfd_offsets, grid_b, dim3(DEC_THREADS), 0, st, dblk, (const u32 *)(ws + o_tcnt), (u64 *)(ws + o_toff));
-        // the symbol image: fixed, for four workgroups per CU (a tile that exceeds it goes in rounds); sfdec_launch gives
-        // 12-bit tables on Zipf data the same 40 KiB
-        const u32 ws_tab = 4u << SYM3_MAXK, ws_rows = (u32)ws_rows_bytes(lng);
-        const u32 ws_cap = (40960u - ws_rows - ws_tab - long_used - (u32)WS_MISC) & ~15u;
-        const size_t lds_ws = (size_t)ws_rows + ws_tab + ws_cap + WS_MISC;
-        u32 tpw_ws = 16;
-        while (tpw_ws > 1 && (u64)ceil_div_u64(max_tiles, tpw_ws) * nblocks < 2048) tpw_ws >>= 1;
-        const dim3 grid_ws((u32)ceil_div_u64(max_tiles, tpw_ws), (u32)nblocks);
-        if (lng)
-            hipLaunchKernelGGL((sfd_wstage<1, true>), grid_ws, dim3(DEC_THREADS), lds_ws + long_used, st, dblk,
-                               (const u8 *)(ws + o_cent), (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab,
-                               ws_cap, long_used);
-        else
-            hipLaunchKernelGGL((sfd_wstage<0, false>), grid_ws, dim3(DEC_THREADS), lds_ws, st, dblk, (const u8 *)(ws + o_cent),
-                               (const u16 *)(ws + o_ccnt), (const u64 *)(ws + o_toff), tpw_ws, ws_tab, ws_cap, 0u);
-    };
-    packed_list(po.p12, false);
-    packed_list(po.packed, true);
+        const u32 ws_tab = 4u << SYM3_MAXK;
+        const u32 ws_cap = (40960u - (u32)ws_rows_bytes(lng) - ws_tab - long_used - (u32)WS_MISC) & ~15u;
+        sfd_launch_packed(st, lng ? po.packed : po.p12, nblocks, max_tiles, lng ? SFD_LONG_ALL : SFD_PACKED, lng, spec,
+                          2u << (lng ? LEN_MAXK : SYM3_MAXK), long_used, false, ws_tab, ws_cap, pa);
+    }
     // ---- byte-map lists: R = 32 over every slot, R = 64 over the one big slot ---------------------------------------
     const u32 l2cap = (u32)LUT2_MAX + 8;
-    const size_t lds_data = (size_t)(DATA_WORDS + DATA_WORDS / 8 + 8) * 4;
-    const size_t lds_lut = (size_t)(1u << LUT_MAXK) * 2 + (size_t)l2cap * 2;
-    auto bytemap = [&](const DecBlk *dblk, u32 r, u32 nb, u8 *cfn, u8 *tfn, u8 *tent, u32 *tcnt, u64 *toff, u8 *cent,
-                       u16 *ccnt) -> int {
-        const size_t lds_sync = lds_data + (size_t)r * DEC_THREADS + lds_lut + 4 * r + 64;
-        const size_t lds_count = lds_sync + DEC_THREADS;
-        const size_t lds_write = lds_data + lds_lut + 64;
-        const size_t lds_tiles = (size_t)r * DEC_THREADS + DEC_THREADS;
-        if (lds_tiles > 65536 || lds_sync > 65536) {
-            HIP_TRY(hipFuncSetAttribute((const void *)sfd_sync, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sync));
-            HIP_TRY(hipFuncSetAttribute((const void *)sfd_count, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
-            HIP_TRY(hipFuncSetAttribute((const void *)sfd_tiles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tiles));
-        }
-        const dim3 grid_t(max_tiles, nb), grid_n(nb);
-        hipLaunchKernelGGL(sfd_sync, grid_t, dim3(DEC_THREADS), lds_sync, st, dblk, r, l2cap, cfn, tfn);
-        hipLaunchKernelGGL(sfd_tiles, grid_n, dim3(DEC_THREADS), lds_tiles, st, dblk, r, (const u8 *)tfn, tent);
-        hipLaunchKernelGGL(sfd_count, grid_t, dim3(DEC_THREADS), lds_count, st, dblk, r, l2cap, (const u8 *)cfn,
-                           (const u8 *)tent, cent, ccnt, tcnt);
-        hipLaunchKernelGGL(sfd_offsets, grid_n, dim3(DEC_THREADS), 0, st, dblk, (const u32 *)tcnt, toff);
-        hipLaunchKernelGGL(sfd_write, grid_t, dim3(DEC_THREADS), lds_write, st, dblk, l2cap, (const u8 *)cent,
-                           (const u16 *)ccnt, (const u64 *)toff);
-        return SHAFA_SUCCESS;
-    };
-    if ((rc = bytemap(po.bytemap, R, (u32)nblocks, ws + o_bcfn, ws + o_btfn, ws + o_tent, (u32 *)(ws + o_tcnt),
-                      (u64 *)(ws + o_toff), ws + o_cent, (u16 *)(ws + o_ccnt))))
-        return rc;
-    if ((rc = bytemap(po.big, SDV_R_BIG, 1u, ws + o_gcfn, ws + o_gtfn, ws + o_gtent, (u32 *)(ws + o_gtcnt),
-                      (u64 *)(ws + o_gtoff), ws + o_gcent, (u16 *)(ws + o_gccnt))))
-        return rc;
+    const SfdArrays ba = {ws + o_bcfn, ws + o_btfn, ws + o_tent, ws + o_cent, (u16 *)(ws + o_ccnt), (u32 *)(ws + o_tcnt),
+                          (u64 *)(ws + o_toff), nullptr, nullptr};
+    const SfdArrays ga = {ws + o_gcfn, ws + o_gtfn, ws + o_gtent, ws + o_gcent, (u16 *)(ws + o_gccnt), (u32 *)(ws + o_gtcnt),
+                          (u64 *)(ws + o_gtoff), nullptr, nullptr};
+    if ((rc = sfd_launch_bytemap(st, po.bytemap, (u32)nblocks, max_tiles, R, l2cap, ba))) return rc;
+    if ((rc = sfd_launch_bytemap(st, po.big, 1u, max_tiles, SDV_R_BIG, l2cap, ga))) return rc;
     HIP_TRY(hipGetLastError());
     return pscope.done();
 }
