@@ -268,6 +268,46 @@ int shafa_hipd_rle_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, co
                               const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                               uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
 
+/* ---- Files in device memory: .rle, .shaf, .cod and .freq assembled from what the entries above leave -------------------
+ * Each call writes ONE contiguous file at d_dst: every byte equals what the C host writes for the same sizes, tables and
+ * counts (host/modules.c's framing around host/formats.c's shafa_cod_format / shafa_freq_format) — empty codes, 255-bit
+ * codes, all-empty tables, counts of 0 and of 2^64 - 1, runs of equal counts (repeat = empty field), payloads of 0 bytes
+ * ("@0@") and a single block included.  *d_dst_n (device) = the file's length.
+ * Enqueues only, as shafa_hipd_sf_encode_dev: device sizes, tables and counts are never read on the host, no device-to-host
+ * copy is issued and nothing is synchronised; the one exception is the batch's growth, from nblocks and the host capacities.
+ * Errors, reported by shafa_hipd_finish (the first error per block is kept, as for every entry):
+ *   d_src_n[b] > h_src_cap[b]              SHAFA_OUTSIDE_MODULE on block b, *d_dst_n = 0;
+ *   a file longer than dst_cap             SHAFA_LACK_OF_MEMORY on block 0, *d_dst_n = the length the file needs.
+ * In both cases nothing at all is written to d_dst: the sizes are checked before any byte moves.  Nothing is ever written
+ * outside [d_dst, d_dst + min(dst_cap, *d_dst_n)).
+ * Argument errors return SHAFA_OUTSIDE_MODULE from the call with nothing enqueued (checked before HIP is touched): a NULL
+ * batch or device array, nblocks < 1, a mode other than 'R' / 'N', an unknown framing, d_src + h_src_off[b] not a multiple
+ * of 16.  nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY.
+ * The packs look at sizes only, not at the error words of earlier calls: a file is meaningful when shafa_hipd_finish reports
+ * success for the whole chain (F -> T -> C -> packs).  d_dst needs no alignment. */
+#define SHAFA_FRAME_RAW 0     /* .rle: payloads back to back (f.c:307)                                   */
+#define SHAFA_FRAME_SHAF 1    /* .shaf: "@<n>", then "@<size>@" + payload per block (c.c:351,256-258)   */
+
+/* Host-only upper bounds of a file, for sizing d_dst (no GPU needed; 0 for nblocks < 1 or an unknown framing).
+ *   payloads: RAW sum(cap_b); SHAF 1 + digits(nblocks) + sum(2 + digits(cap_b) + cap_b)
+ *   .cod:     3 + digits(nblocks) + nblocks * (22 + 256 * 255 + 255) + 2    (any table: <= 65 535 code characters)
+ *   .freq:    3 + digits(nblocks) + nblocks * (22 + 256 * 20 + 255) + 2     (256 fields of <= 20 digits)        */
+size_t shafa_hip_pack_payloads_max(int nblocks, const uint64_t *h_src_cap, int framing);
+size_t shafa_hip_pack_cod_max(int nblocks);
+size_t shafa_hip_pack_freq_max(int nblocks);
+
+/* Block b's d_src_n[b] (<= h_src_cap[b]) bytes at d_src + h_src_off[b] -> one file at d_dst, framed by `framing`. */
+int shafa_hipd_pack_payloads(shafa_hipd_batch *b, void *stream, int nblocks, int framing, const uint8_t *d_src,
+                             const uint64_t *h_src_off, const uint64_t *h_src_cap, const uint64_t *d_src_n, uint8_t *d_dst,
+                             uint64_t dst_cap, uint64_t *d_dst_n);
+/* "@<mode>@<n>", then "@<d_sizes[b]>@" + the table's "c0;c1;...;c255" per block, then "@0" (t.c:302,353-361,395-396).
+ * d_tables: nblocks tables in device memory (what shafa_hipd_sf_build_codes leaves). */
+int shafa_hipd_pack_cod(shafa_hipd_batch *b, void *stream, int nblocks, char mode, const uint64_t *d_sizes,
+                        const shafa_code_table *d_tables, uint8_t *d_dst, uint64_t dst_cap, uint64_t *d_dst_n);
+/* "@<mode>@<n>", then "@<d_sizes[b]>@" + make_freq's text of d_freq[b*256 ..] per block, then "@0" (f.c:89-119). */
+int shafa_hipd_pack_freq(shafa_hipd_batch *b, void *stream, int nblocks, char mode, const uint64_t *d_sizes,
+                         const uint64_t *d_freq, uint8_t *d_dst, uint64_t dst_cap, uint64_t *d_dst_n);
+
 /* Synchronise `stream`, return the first per-block error of the calls enqueued since the last
  * finish (SHAFA_SUCCESS if none).  h_block_err (nblocks ints, may be NULL) receives every block's code. */
 int shafa_hipd_finish(shafa_hipd_batch *b, void *stream, int nblocks, int *h_block_err);

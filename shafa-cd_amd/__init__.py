@@ -116,6 +116,15 @@ def lib():
     L.shafa_hipd_sf_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp, u8p, u64p, u64p]
     L.shafa_hipd_rle_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
+    L.shafa_hip_pack_payloads_max.restype = C.c_size_t
+    L.shafa_hip_pack_cod_max.argtypes = [C.c_int]
+    L.shafa_hip_pack_cod_max.restype = C.c_size_t
+    L.shafa_hip_pack_freq_max.argtypes = [C.c_int]
+    L.shafa_hip_pack_freq_max.restype = C.c_size_t
+    L.shafa_hipd_pack_payloads.argtypes = [vp, vp, C.c_int, C.c_int, u8p, u64p, u64p, vp, u8p, C.c_uint64, vp]
+    L.shafa_hipd_pack_cod.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
+    L.shafa_hipd_pack_freq.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
     L.shafa_hipd_gen_bytes.argtypes = [vp, C.c_uint64, C.c_uint64, u8p, u8p, C.c_size_t]
     L.shafa_pipe_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.shafa_pipe_destroy.argtypes = [vp]
@@ -142,7 +151,7 @@ def lib():
                  "shafa_hipd_sf_decode", "shafa_hipd_rle_decode", "shafa_hipd_finish",
                  "shafa_hipd_gen_bytes", "shafa_hipd_hist256_tiles", "shafa_hipd_rle_encode_tiles",
                  "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev", "shafa_hipd_sf_decode_dev",
-                 "shafa_hipd_rle_decode_dev"):
+                 "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -358,6 +367,27 @@ class Batch:
         _check(lib().shafa_hipd_rle_decode(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(il),
                                            d_out.data_ptr(), _p64(oo), _p64(oc), d_out_n.data_ptr()), "hipd_rle_decode")
 
+    # ---- files in device memory (include/shafa_hip.h: "Files in device memory"); enqueue only, d_dst_n: 1 int64 ----
+    def pack_payloads(self, stream, framing, d_src, src_off, src_cap, d_src_n, d_dst, dst_cap, d_dst_n):
+        """block b's d_src_n[b] (<= src_cap[b]) bytes at d_src + src_off[b] -> one .rle (FRAME_RAW) or .shaf (FRAME_SHAF)
+        file at d_dst; its length to d_dst_n[0]."""
+        so, sc = _u64arr(src_off), _u64arr(src_cap)
+        _check(lib().shafa_hipd_pack_payloads(self.h, self._st(stream), len(so), framing, d_src.data_ptr(), _p64(so),
+                                              _p64(sc), d_src_n.data_ptr(), d_dst.data_ptr(), int(dst_cap),
+                                              d_dst_n.data_ptr()), "hipd_pack_payloads")
+
+    def pack_cod(self, stream, nblocks, mode, d_sizes, d_tables, d_dst, dst_cap, d_dst_n):
+        """.cod file of nblocks device tables (d_tables: nblocks x sizeof(CodeTable) bytes) headed by d_sizes (int64)."""
+        _check(lib().shafa_hipd_pack_cod(self.h, self._st(stream), nblocks, _mode(mode), d_sizes.data_ptr(),
+                                         d_tables.data_ptr(), d_dst.data_ptr(), int(dst_cap), d_dst_n.data_ptr()),
+               "hipd_pack_cod")
+
+    def pack_freq(self, stream, nblocks, mode, d_sizes, d_freq, d_dst, dst_cap, d_dst_n):
+        """.freq file of nblocks x 256 device counts (d_freq, int64) headed by d_sizes (int64)."""
+        _check(lib().shafa_hipd_pack_freq(self.h, self._st(stream), nblocks, _mode(mode), d_sizes.data_ptr(),
+                                          d_freq.data_ptr(), d_dst.data_ptr(), int(dst_cap), d_dst_n.data_ptr()),
+               "hipd_pack_freq")
+
     def finish(self, stream, nblocks, raise_on_error=True):
         errs = (C.c_int * max(nblocks, 1))()
         rc = lib().shafa_hipd_finish(self.h, self._st(stream), nblocks, errs)
@@ -438,6 +468,27 @@ class Pipe:
         rc = lib().shafa_pipe_wait_group(self._h, slot, n, res, brc)
         outs = [C.string_at(res[i].out, res[i].out_n) if rc == 0 and brc[i] == 0 and res[i].out_n else b"" for i in range(n)]
         return rc, list(brc), outs, res
+
+
+FRAME_RAW, FRAME_SHAF = 0, 1   # SHAFA_FRAME_*: .rle (payloads back to back), .shaf ("@n", then "@size@" + payload)
+
+
+def _mode(mode):
+    return C.c_char(mode if isinstance(mode, bytes) else str(mode).encode())
+
+
+def pack_payloads_max(src_cap, framing):
+    """bytes that Batch.pack_payloads may need for blocks of these capacities (shafa_hip_pack_payloads_max)."""
+    sc = _u64arr(src_cap)
+    return int(lib().shafa_hip_pack_payloads_max(len(sc), _p64(sc), framing))
+
+
+def pack_cod_max(nblocks):
+    return int(lib().shafa_hip_pack_cod_max(nblocks))
+
+
+def pack_freq_max(nblocks):
+    return int(lib().shafa_hip_pack_freq_max(nblocks))
 
 
 TILE_BYTES = 32768            # SHAFA_TILE_BYTES: the tile of the tile histograms
@@ -541,3 +592,110 @@ def cod_parse(text):
     t = CodeTable()
     rc = host().shafa_cod_parse(text, C.byref(t))
     return rc, t
+
+
+# ------------------------------------------------------------------ F -> T -> C into files, in device memory
+def _al16(x):
+    return (x + 15) // 16 * 16
+
+
+def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=None):
+    """The files the CLI's default run `shafa <file> -b <size> [-c r|f]` writes for the bytes of `d_in` (a contiguous uint8
+    CUDA tensor), made on the device: {".rle", ".rle.freq", ".freq", ".rle.cod", ".rle.shaf"} with RLE (".freq" only with
+    force_freq), {".freq", ".cod", ".shaf"} without.  Each value is a uint8 CUDA tensor holding exactly the file (a view of a
+    buffer sized by the pack bounds).
+
+    Block split and RLE rule of the C host (shafa_block_count; shafa_rle_worthwhile on block 0, f.c:250-258).  rle_encode_tiles
+    (and hist256_tiles where the input's histogram is needed) -> one synchronisation to read block 0's RLE size (none with
+    force_rle) -> sf_build_codes -> sf_encode_dev -> the packs -> one finish.  Raises ShafaError(FILE_TOO_SMALL) below 1 KiB
+    (f.c:220,366) and on any block's error."""
+    import torch
+    dev = d_in.device
+    total = int(d_in.numel())
+    bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
+    nb = int(host().shafa_block_count(total, C.byref(bs), C.byref(last)))
+    if total < 1024:
+        raise ShafaError(FILE_TOO_SMALL, "compress_files: fewer than 1024 bytes")
+    bs, last = bs.value, last.value
+    sizes = [bs] * (nb - 1) + [last]
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    # inputs at 16-byte aligned offsets (the device entries' rule): in place when the blocks already are
+    off = [b * bs for b in range(nb)]
+    src_in = d_in
+    if bs % 16 or d_in.data_ptr() % 16:
+        off = [b * _al16(bs) for b in range(nb)]
+        src_in = torch.zeros(off[-1] + _al16(last) + 16, dtype=torch.uint8, device=dev)
+        for b in range(nb):
+            src_in[off[b]:off[b] + sizes[b]].copy_(d_in[b * bs:b * bs + sizes[b]])
+    d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
+    bt = Batch(nb, 2 * max(sizes) + 64)
+    try:
+        # ---- Module F: RLE of every block with its histogram and tile histograms; the input's where it may be needed
+        rcap = [2 * n + 3 for n in sizes]                                   # f.c:244
+        roff, pos = [], 0
+        for c in rcap:
+            roff.append(pos)
+            pos += _al16(c)
+        d_rle = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+        rthb = [_al16(tile_hist_bytes(c)) for c in rcap]
+        rtoff = [sum(rthb[:b]) for b in range(nb)]
+        d_rth = torch.empty(sum(rthb) + 16, dtype=torch.uint8, device=dev)
+        bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff)
+        need_in = force_freq or not force_rle
+        if need_in:
+            d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+            ithb = [_al16(tile_hist_bytes(n)) for n in sizes]
+            itoff = [sum(ithb[:b]) for b in range(nb)]
+            d_ith = torch.empty(sum(ithb) + 16, dtype=torch.uint8, device=dev)
+            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_ith, itoff)
+        if force_rle:
+            use_rle = True
+        else:                                                               # the reference's decision: block 0's RLE size
+            bt.finish(st, nb)
+            use_rle = bool(host().shafa_rle_worthwhile(sizes[0], int(d_rle_n[0].item()), False))
+        mode = b"R" if use_rle else b"N"
+        # ---- Module T and Module C from what F left on the device
+        if use_rle:
+            e_src, e_off, e_cap, e_n, e_freq, e_th, e_toff = d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff
+        else:
+            e_src, e_off, e_cap, e_n, e_freq, e_th, e_toff = src_in, off, sizes, d_n_in, d_freq_in, d_ith, itoff
+        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.sf_build_codes(st, nb, e_freq, d_tab)
+        # Fano codes average under H + 1 <= 9 bits a symbol: 12 bits leave room (a block that does not fit is an error)
+        ocap = [c + c // 2 + 64 for c in e_cap]
+        ooff, pos = [], 0
+        for c in ocap:
+            ooff.append(pos)
+            pos += _al16(c)
+        d_enc = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        bt.sf_encode_dev(st, e_src, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, e_th, e_toff)
+        # ---- the files
+        jobs = []
+        lens = torch.zeros(8, dtype=torch.int64, device=dev)
+
+        def out(key, cap):
+            buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            jobs.append((key, buf))
+            return buf, lens[len(jobs) - 1:len(jobs)]
+
+        if use_rle:
+            buf, n = out(".rle", pack_payloads_max(rcap, FRAME_RAW))
+            bt.pack_payloads(st, FRAME_RAW, d_rle, roff, rcap, d_rle_n, buf, buf.numel(), n)
+            buf, n = out(".rle.freq", pack_freq_max(nb))
+            bt.pack_freq(st, nb, b"R", d_rle_n, d_freq_rle, buf, buf.numel(), n)
+        if not use_rle or force_freq:
+            buf, n = out(".freq", pack_freq_max(nb))
+            bt.pack_freq(st, nb, b"N", d_n_in, d_freq_in, buf, buf.numel(), n)
+        stem = ".rle" if use_rle else ""
+        buf, n = out(stem + ".cod", pack_cod_max(nb))
+        bt.pack_cod(st, nb, mode, e_n, d_tab, buf, buf.numel(), n)
+        buf, n = out(stem + ".shaf", pack_payloads_max(ocap, FRAME_SHAF))
+        bt.pack_payloads(st, FRAME_SHAF, d_enc, ooff, ocap, d_enc_n, buf, buf.numel(), n)
+        bt.finish(st, nb)
+        got = lens.cpu().tolist()
+        return {key: buf[:got[i]] for i, (key, buf) in enumerate(jobs)}
+    finally:
+        bt.close()
