@@ -15,10 +15,17 @@ Workload (config.workload): BASELINE config[3] weak-scaled to one GPU — the su
 the reference's .cod file) followed by Module D over every block (SF decode back to the bytes).
 value = uncompressed GiB of all ranks / step time.  Inputs are resident in HBM when the timed region starts.
 
-The JSON line also carries `roofline` (dominant kernel sequence, HIP-event timed on the launch stream),
-`cpu_baseline` at N=1 (the reference binary oracle/_ref/shafa when present, else the oracle port, timed on
-the host cores on a bounded sample), `scatter_gather` at N>1 (X1/X2 over RCCL) and, with
---pipeline, the F -> T -> C and D(SF+RLE) legs at -b M.
+A plain run does what the headline needs and nothing else: it sets up the resident inputs and the tables, encodes
+and decodes them once (sizes and round trip checked on the device), warms up, times the steps, dumps with
+--dump-outputs, and prints the line.  The line carries `roofline` (dominant kernel sequence, from the HIP events of
+the timed steps) next to the headline figures.
+--full adds every leg that takes runs of its own: the other encoder on the same blocks (`encode_f_fed`, or
+`encode_chained` with --tiles), the oracle spot check of block 0, the F -> T -> C and D(SF+RLE) legs at -b M
+(`pipeline`, `pipeline_mixed`, `pipeline_small_launches`, `uniform_stream`), `host_path`, the mover ceiling
+(`roofline_encode.mover_frac`), `cpu_baseline` at N=1 (the reference binary oracle/_ref/shafa when present, else
+the oracle port, timed on the host cores on a bounded sample) and `scatter_gather` at N>1 (X1/X2 over RCCL,
+SURVEY.md §8(e)).  Each --no-* option leaves its leg out of --full; --pipeline and --scatter-gather ask for
+their leg without it.
 
 `ms_per_step` is the wall time of the --steps timed steps (device synchronised, slowest rank) divided by --steps.
 --dump-outputs DIR writes the payloads and decoded bytes of the last timed step (dump_outputs), so that two builds can
@@ -73,7 +80,10 @@ def parse_args(argv=None):
     ap.add_argument("--dist", default="zipfmod", choices=["zipfmod", "zipf", "uniform"],
                     help="zipfmod = Zipf(s) over the integers mod 256 (surveyed cfg-4 stream); zipf = Zipf(s) truncated to 256 ranks")
     ap.add_argument("--zipf-s", type=float, default=1.2)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (see the module docstring): comparisons, the oracle spot "
+                         "check, the pipeline, host-path and mover legs, cpu_baseline at N=1, X1/X2 at N>1")
+    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg of --full")
     ap.add_argument("--cpu-sample-blocks", type=int, default=16)
     ap.add_argument("--encode-only", action="store_true")
     ap.add_argument("--tiles", action="store_true",
@@ -83,18 +93,18 @@ def parse_args(argv=None):
     ap.add_argument("--no-tiles", action="store_true", help="(kept for old command lines: the chained encoder is the default)")
     ap.add_argument("--scatter-gather", action="store_true",
                     help="time X1 (root scatters whole blocks) + encode + X2 (root gathers the payloads) also at N=1")
-    ap.add_argument("--no-scatter-gather", action="store_true", help="skip the X1/X2 leg at N>1")
-    ap.add_argument("--pipeline", action="store_true",
-                    help="(kept for old command lines: the pipeline leg runs by default)")
+    ap.add_argument("--no-scatter-gather", action="store_true", help="skip the X1/X2 leg of --full at N>1")
+    ap.add_argument("--pipeline", action="store_true", help="run the pipeline legs also without --full")
     ap.add_argument("--pipeline-blocks", type=int, default=32,
                     help="blocks of the pipeline leg (`pipeline` object: per-family times and roofline fractions of K1, K2, K5 "
                          "on run-heavy data at this block size; bounded, a fraction of a second of GPU time)")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the pipeline legs")
+    ap.add_argument("--no-pipeline", action="store_true", help="skip the pipeline legs of --full")
     ap.add_argument("--pipeline-only", action="store_true",
                     help="run one pipeline leg and nothing else (for profiles of the leg alone: tools/gpu_prof.sh <tag> --pipeline-only --pipeline-kind K)")
     ap.add_argument("--pipeline-kind", default=None, choices=["runs", "mixed"], help="the leg's data (default: both legs)")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the `host_path` object (layer-3 pipe PCIe-inclusive rates and the CLI end to end on a tmpfs file)")
+                    help="skip the `host_path` object of --full (layer-3 pipe PCIe-inclusive rates and the CLI end to end on a "
+                         "tmpfs file)")
     ap.add_argument("--host-path-blocks", type=int, default=32)
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="shafa_hip_set_option(NAME, VALUE) before anything runs (A/B of kernel variants)")
@@ -684,7 +694,7 @@ def main():
     # F-fed encoder only (`encode_f_fed`, or the headline with --tiles), the histogram of every 32 KiB tile (include/shafa_hip.h
     # "Tile histograms").  The headline times Module C as the reference defines it: the input and the .cod tables, nothing else.
     use_tiles = args.tiles and not args.no_tiles
-    side_tiles = not use_tiles and nb <= 256          # (a second copy of the encoded blocks: not at cfg[3]'s full 1024)
+    side_tiles = args.full and not use_tiles and nb <= 256    # (a second copy of the encoded blocks: not at cfg[3]'s full 1024)
     thb = pkg.tile_hist_bytes(bs)
     th_off = np.arange(nb, dtype=np.uint64) * np.uint64(thb)
     d_th = torch.zeros(nb * thb if (use_tiles or side_tiles) else 16, dtype=torch.uint8, device=dev)
@@ -734,7 +744,7 @@ def main():
         decode()
         bt.finish(st, nb)
         assert ablation or torch.equal(d_dec, d_in), "decode(encode(x)) != x"
-    if rank == 0 and os.environ.get("SHAFA_BENCH_ORACLE_CHECK", "1") == "1" and not ablation:
+    if args.full and rank == 0 and os.environ.get("SHAFA_BENCH_ORACLE_CHECK", "1") == "1" and not ablation:
         import ctypes as C
         orc = load_oracle().load()
         blk = d_in[:min(bs, 4 << 20)].cpu().numpy()           # bounded oracle spot check of block 0's head
@@ -744,10 +754,10 @@ def main():
         C.memmove(C.byref(t), C.byref(otab), C.sizeof(t))
         assert pkg.sf_encode(blk, t).tobytes() == want.tobytes(), "HIP encode differs from oracle"
 
-    # the other encoder on the same blocks: same bytes (and its time, for the line)
+    # the other encoder on the same blocks (--full): same bytes (and its time, for the line)
     other_t = None
     other = encode_chained if use_tiles else encode_tiles
-    if (use_tiles or side_tiles) and not ablation and nb <= 256:
+    if args.full and (use_tiles or side_tiles) and not ablation and nb <= 256:
         ref_enc = d_enc.clone()
         d_enc.zero_()
         other()
@@ -837,9 +847,9 @@ def main():
             "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic[dominant], "traffic_source": tsrc}
     roof["frac"] = roof["achieved"] / HBM_PEAK_GBS
 
-    # ---- root-scatter-included encode: always at N>1, never part of `value` --------
+    # ---- root-scatter-included encode: at N>1 with --full, never part of `value` --------
     sg = None
-    if ((world > 1 and not args.no_scatter_gather) or args.scatter_gather) and not comm.oversubscribed:
+    if ((world > 1 and args.full and not args.no_scatter_gather) or args.scatter_gather) and not comm.oversubscribed:
         def scatter_gather_leg():
             shd = load_pkg("sharding")
             sg_nb = min(nb, 16)                               # bounded: the root holds world * sg_nb blocks
@@ -880,7 +890,8 @@ def main():
         bt.finish(st, nb)
 
     pipe, pipe_mixed = None, None
-    if not args.no_pipeline and rank == 0:
+    run_pipeline = (args.full or args.pipeline) and not args.no_pipeline
+    if run_pipeline and rank == 0:
         pnb = max(1, min(args.blocks, args.pipeline_blocks))
         legs = {}
         for kind in ([args.pipeline_kind] if args.pipeline_kind else ["runs", "mixed"]):
@@ -892,7 +903,7 @@ def main():
                 legs[kind] = {"error": f"{type(e).__name__}: {e}"[:300]}
         pipe, pipe_mixed = legs.get("runs"), legs.get("mixed")
     small_rows, uni = None, None
-    if not args.no_pipeline and rank == 0 and args.block_mib == 64:
+    if run_pipeline and rank == 0 and args.block_mib == 64:
         for name, fn in (("small", lambda: small_launch_rows(args, pkg, torch, dev, st)), ("uniform", lambda: uniform_leg(pkg, torch, dev, st))):
             try:
                 r = fn()
@@ -907,7 +918,7 @@ def main():
 
     host_path = None
     profiled = any(k.startswith(("ROCP", "ROCPROF")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if (world == 1 and rank == 0 and not args.no_host_path and not profiled      # no child processes under a profiler
+    if (args.full and world == 1 and rank == 0 and not args.no_host_path and not profiled   # no child processes under a profiler
             and args.dist != "uniform" and args.block_mib in (8, 64)):
         try:
             host_path = host_path_leg(args, pkg, torch, dev, d_in)
@@ -970,7 +981,8 @@ def main():
             out["pipeline_small_launches"] = small_rows
         if uni:
             out["uniform_stream"] = uni
-        if world == 1 and not profiled and args.block_mib == 64 and args.dist == "zipfmod" and not args.no_host_path:
+        if (args.full and world == 1 and not profiled and args.block_mib == 64 and args.dist == "zipfmod"
+                and not args.no_host_path):
             try:
                 mv = mover_leg()                       # a child process: after everything that is timed in this one
             except Exception:
@@ -983,7 +995,7 @@ def main():
                                                     "workgroups / as a persistent grid; the chained encoder is a persistent kernel")
         if host_path:
             out["host_path"] = host_path
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(args, pkg, zt)
         print(json.dumps(out), flush=True)
     comm.close()

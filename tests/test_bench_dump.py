@@ -44,3 +44,9 @@ def test_steps_must_be_positive():
             assert e.code == 2
         else:
             raise AssertionError(f"{argv} accepted")
+
+
+def test_full_is_off_by_default():
+    b = _bench()
+    assert b.parse_args([]).full is False
+    assert b.parse_args(["--full"]).full is True

@@ -116,7 +116,7 @@ def test_bench_self_launches_ranks():
     the ranks share it (--oversubscribe, gloo for the barrier / max-reduce): the launch, rendezvous, per-rank shard
     generation, barrier and rank-0 JSON are what is under test, the number is marked invalid."""
     n = _gpu_count()
-    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4", "--block-mib", "8", "--no-cpu"]
+    argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--blocks", "4", "--block-mib", "8", "--no-cpu", "--full"]
     if n < 2:
         argv.append("--oversubscribe")
     j = _bench(argv)
@@ -134,7 +134,7 @@ def test_bench_at_world_size_4():
     suite puts on one GPU at a time."""
     n = _gpu_count()
     argv = ["--gpus", "4", "--steps", "1", "--warmup", "1", "--blocks", "2", "--block-mib", "8", "--no-cpu", "--no-pipeline",
-            "--no-host-path"]
+            "--no-host-path", "--full"]
     if n < 4:
         argv.append("--oversubscribe")
     j = _bench(argv, timeout=900)
@@ -150,7 +150,7 @@ def test_bench_on_every_visible_gpu_over_rccl():
     backend nccl, and per-rank encode/decode times in the line so that a straggler is visible.  On a one-GPU box this is
     the N=1 line with --scatter-gather (the collectives still run through RCCL)."""
     n = max(1, _gpu_count())
-    argv = ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--blocks", "8", "--block-mib", "8", "--no-cpu"]
+    argv = ["--gpus", str(n), "--steps", "2", "--warmup", "1", "--blocks", "8", "--block-mib", "8", "--no-cpu", "--full"]
     if n == 1:
         argv.append("--scatter-gather")
     j = _bench(argv, timeout=600)
@@ -163,7 +163,7 @@ def test_bench_on_every_visible_gpu_over_rccl():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields():
-    j = _bench(["--steps", "2", "--warmup", "1", "--blocks", "8", "--cpu-sample-blocks", "1", "--scatter-gather", "--pipeline"])
+    j = _bench(["--steps", "2", "--warmup", "1", "--blocks", "8", "--cpu-sample-blocks", "1", "--scatter-gather", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in j, k
@@ -213,3 +213,24 @@ def test_bench_dump_outputs_are_the_oracles(tmp_path, oracle):
     assert (d["sf_encoded"] == payload[d["sf_encoded_index"].astype(np.int64)]).all()
     assert d["sf_decoded"].size == bench.DUMP_SAMPLE
     assert (d["sf_decoded"] == data[d["sf_decoded_index"].astype(np.int64)]).all()
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """A plain run (no --full) prints the headline line without the legs that take runs of their own, and its headline
+    fields and --dump-outputs arrays are those of a --full run on the same seeded inputs."""
+    argv = ["--steps", "2", "--warmup", "1", "--blocks", "4", "--block-mib", "1"]
+    plain = _bench(argv + ["--dump-outputs", str(tmp_path / "plain")])
+    full = _bench(argv + ["--full", "--no-cpu", "--no-pipeline", "--no-host-path", "--dump-outputs", str(tmp_path / "full")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config",
+              "roofline", "per_rank"):
+        assert k in plain, k
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and "invalid" not in plain
+    for k in ("cpu_baseline", "pipeline", "pipeline_mixed", "pipeline_small_launches", "uniform_stream", "host_path",
+              "scatter_gather", "encode_f_fed", "encode_chained"):
+        assert k not in plain, k
+    assert "encode_f_fed" in full and "mover_frac" not in plain["roofline_encode"]
+    for k in ("sf_encoded_sizes", "sf_encoded", "sf_encoded_index", "sf_decoded", "sf_decoded_index"):
+        a, b = np.load(tmp_path / "plain" / (k + ".npy")), np.load(tmp_path / "full" / (k + ".npy"))
+        assert a.dtype == b.dtype and np.array_equal(a, b), k

@@ -98,7 +98,7 @@ def test_two_processes_sharing_the_gpu_finish_without_device_errors():
         env.pop(k, None)
     env["SHAFA_BENCH_ORACLE_CHECK"] = "0"
     argv = [sys.executable, os.path.join(root, "bench.py"), "--blocks", "24", "--steps", "6", "--warmup", "1", "--no-cpu",
-            "--pipeline-blocks", "8", "--no-host-path"]
+            "--pipeline-blocks", "8", "--no-host-path", "--full"]
     procs = [subprocess.Popen(argv, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env) for _ in range(3)]
     for p in procs:
         out, err = p.communicate(timeout=600)

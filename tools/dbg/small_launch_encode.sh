@@ -5,7 +5,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 export SHAFA_BENCH_ORACLE_CHECK=0
 for nb in 1 2 4 8; do
-  python bench.py --no-cpu --no-host-path --no-pipeline --encode-only --blocks $nb --steps 20 2>/dev/null | tail -1 | python3 -c "
+  python bench.py --full --tiles --no-cpu --no-host-path --no-pipeline --encode-only --blocks $nb --steps 20 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d.get('encode_chained') or {}
 print('$nb blocks: tiles %.1f us (%.3f)   without %.1f us (%.3f)' % (d['encode_ms']*1e3, d['roofline_encode']['frac'], c.get('ms',0)*1e3, c.get('frac',0)))"
