@@ -308,6 +308,63 @@ int shafa_hipd_pack_cod(shafa_hipd_batch *b, void *stream, int nblocks, char mod
 int shafa_hipd_pack_freq(shafa_hipd_batch *b, void *stream, int nblocks, char mode, const uint64_t *d_sizes,
                          const uint64_t *d_freq, uint8_t *d_dst, uint64_t dst_cap, uint64_t *d_dst_n);
 
+/* ---- Files in device memory, parsed: the inverse of the packs -----------------------------------------------------------
+ * .cod / .rle.freq / .shaf files at d_* (any alignment, lengths known on the host) -> the sizes, tables and payload
+ * positions that shafa_hipd_sf_decode_dev / _rle_decode_dev take, by the C host's rules (host/modules.c read_header,
+ * read_block, shaf_read_u64; host/formats.c shafa_cod_parse).  Enqueue only, as the packs: device sizes are never read on
+ * the host, no device-to-host copy is issued and nothing is synchronised (the one exception: the batch's growth, from
+ * max_blocks / nblocks, the file lengths and the host capacities).  Nothing is ever written outside the caller's arrays of
+ * max_blocks (nblocks) entries, d_info's SHAFA_UNPACK_INFO_WORDS words and the destination regions.
+ * Errors, reported by shafa_hipd_finish (first error per block kept):
+ *   a bad header ("@<mode>@<digits>" with a count <= remaining bytes / 3; "@" + digits for .shaf)   SHAFA_FILE_STREAM_FAILED
+ *                                                                                                  on block 0;
+ *   block b's frame fails read_block (a size of >= 1 digit between two '@', then 1 .. max field bytes and a following '@';
+ *   max field = 33 151 for .cod, 5 375 for .freq), its .shaf header fails shaf_read_u64 ('@', 1 .. 20 digits, '@'), or its
+ *   payload runs past the end of its file (.shaf; .rle of rle_n bytes)                              SHAFA_FILE_STREAM_FAILED
+ *                                                                                                  on block b;
+ *   block b's .cod text fails shafa_cod_parse (only '0', '1', ';' up to a NUL byte; exactly 256 fields of <= 255 bits)
+ *                                                                 SHAFA_FILE_UNRECOGNIZABLE on block b, all-empty table.
+ * A .shaf failure on block b replaces a table error on the same block, whichever call was enqueued first (the host reads
+ * the .shaf header and payload before the .cod text).  Blocks after the first framing failure get size 0, offset 0 and an
+ * all-empty table, and report nothing.  The mode character
+ * is recorded, not judged: the caller applies d.c:678 (R, or N without RLE decoding) or 'R' for .freq.  The .shaf count is
+ * read but the .cod's count wins (d.c:676); bytes after the last payload and the .cod's "@0" tail are not looked at.
+ * Several faults: the C host's answer depends on how far its pipeline reads ahead (a framing error up to `depth` blocks on
+ * pre-empts an earlier block's table or decode error); these calls report every block's own first fault, so a caller that
+ * takes the first error in block order (shafa.decompress_files) matches the host on files with a single fault.
+ * Argument errors return SHAFA_OUTSIDE_MODULE with nothing enqueued (checked before HIP is touched): a NULL batch or array,
+ * max_blocks / nblocks < 1, a NULL file with a length > 0, d_dst + h_dst_off[b] not a multiple of 16.  max_blocks / nblocks
+ * > the batch's max_blocks: SHAFA_LACK_OF_MEMORY. */
+#define SHAFA_UNPACK_INFO_WORDS 8
+#define SHAFA_UNPACK_INFO_STATUS 0     /* SHAFA_SUCCESS, or SHAFA_FILE_STREAM_FAILED for a bad header            */
+#define SHAFA_UNPACK_INFO_MODE 1       /* the header's mode character (0 when the file has none)                 */
+#define SHAFA_UNPACK_INFO_COUNT 2      /* the header's block count (read_u64: unbounded digits, wrapping)         */
+#define SHAFA_UNPACK_INFO_INDEXED 3    /* min(count, max_blocks): the blocks looked at                            */
+#define SHAFA_UNPACK_INFO_FRAMED 4     /* the blocks before the first framing failure                             */
+#define SHAFA_UNPACK_INFO_MAX_SIZE 5   /* the largest size among them                                             */
+
+/* .cod of cod_n bytes -> d_info, d_sizes[b] (the "@<size>@" number: the block's symbol count) and d_tables[b] (the layout of
+ * shafa_hipd_sf_build_codes, which shafa_hipd_sf_decode_dev takes as it lies), for b < max_blocks.  A text with more blocks
+ * than max_blocks is indexed up to max_blocks: with max_blocks = cod_n / 258 + 1 (a parsable block takes >= 258 bytes) a
+ * longer count always leaves a failing block among those indexed. */
+int shafa_hipd_unpack_cod(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_cod, uint64_t cod_n,
+                          uint64_t *d_info, uint64_t *d_sizes, shafa_code_table *d_tables);
+/* .rle.freq of freq_n bytes (framing only, as rle_decompress reads it) -> d_info, and block b's .rle payload
+ * [d_off[b], d_off[b] + d_n[b]) in a .rle file of rle_n bytes.  max_blocks = freq_n / 4 + 1 covers any count likewise. */
+int shafa_hipd_unpack_rle_freq(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_freq, uint64_t freq_n,
+                               uint64_t rle_n, uint64_t *d_info, uint64_t *d_off, uint64_t *d_n);
+/* .shaf of shaf_n bytes -> block b's payload [d_off[b], d_off[b] + d_n[b]) for the first min(*d_count, max_blocks) blocks
+ * (d_count: the .cod's count, e.g. d_info + SHAFA_UNPACK_INFO_INDEXED of shafa_hipd_unpack_cod).  The headers form a
+ * dependent chain: one wave walks them, about one memory latency per block. */
+int shafa_hipd_unpack_shaf(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_shaf, uint64_t shaf_n,
+                           const uint64_t *d_count, uint64_t *d_off, uint64_t *d_n);
+/* Block b's payload [d_file + d_off[b], + d_n[b]) -> d_dst + h_dst_off[b] (16-aligned regions of h_dst_cap[b] bytes, what the
+ * decoders take).  d_n[b] > h_dst_cap[b], or a payload outside [0, file_n): SHAFA_OUTSIDE_MODULE on block b, nothing written
+ * for it.  Moved by the packs' kernels (whole aligned 16-byte destination words, bytes at the ends). */
+int shafa_hipd_unpack_payloads(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_file, uint64_t file_n,
+                               const uint64_t *d_off, const uint64_t *d_n, uint8_t *d_dst, const uint64_t *h_dst_off,
+                               const uint64_t *h_dst_cap);
+
 /* Synchronise `stream`, return the first per-block error of the calls enqueued since the last
  * finish (SHAFA_SUCCESS if none).  h_block_err (nblocks ints, may be NULL) receives every block's code. */
 int shafa_hipd_finish(shafa_hipd_batch *b, void *stream, int nblocks, int *h_block_err);

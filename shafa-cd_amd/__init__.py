@@ -125,6 +125,10 @@ def lib():
     L.shafa_hipd_pack_payloads.argtypes = [vp, vp, C.c_int, C.c_int, u8p, u64p, u64p, vp, u8p, C.c_uint64, vp]
     L.shafa_hipd_pack_cod.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
     L.shafa_hipd_pack_freq.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
+    L.shafa_hipd_unpack_cod.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
+    L.shafa_hipd_unpack_rle_freq.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, C.c_uint64, vp, vp, vp]
+    L.shafa_hipd_unpack_shaf.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
+    L.shafa_hipd_unpack_payloads.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, u8p, u64p, u64p]
     L.shafa_hipd_gen_bytes.argtypes = [vp, C.c_uint64, C.c_uint64, u8p, u8p, C.c_size_t]
     L.shafa_pipe_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.shafa_pipe_destroy.argtypes = [vp]
@@ -151,7 +155,8 @@ def lib():
                  "shafa_hipd_sf_decode", "shafa_hipd_rle_decode", "shafa_hipd_finish",
                  "shafa_hipd_gen_bytes", "shafa_hipd_hist256_tiles", "shafa_hipd_rle_encode_tiles",
                  "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev", "shafa_hipd_sf_decode_dev",
-                 "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq"):
+                 "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq",
+                 "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -242,6 +247,11 @@ def _u64arr(v):
 
 def _p64(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _ptr(t):
+    """a tensor's address, None for an empty one (a file of 0 bytes may have no storage)"""
+    return t.data_ptr() if t.numel() else None
 
 
 class Batch:
@@ -387,6 +397,30 @@ class Batch:
         _check(lib().shafa_hipd_pack_freq(self.h, self._st(stream), nblocks, _mode(mode), d_sizes.data_ptr(),
                                           d_freq.data_ptr(), d_dst.data_ptr(), int(dst_cap), d_dst_n.data_ptr()),
                "hipd_pack_freq")
+
+    # ---- files in device memory, parsed (include/shafa_hip.h: "Files in device memory, parsed"); enqueue only ----
+    # d_info: UNPACK_INFO_WORDS int64; d_sizes / d_off / d_n: max_blocks int64; d_tables: max_blocks x sizeof(CodeTable) bytes
+    def unpack_cod(self, stream, max_blocks, d_cod, d_info, d_sizes, d_tables):
+        """.cod file (uint8 tensor, any alignment) -> header info, symbol counts and code tables of its first max_blocks blocks."""
+        _check(lib().shafa_hipd_unpack_cod(self.h, self._st(stream), max_blocks, _ptr(d_cod), d_cod.numel(), d_info.data_ptr(),
+                                           d_sizes.data_ptr(), d_tables.data_ptr()), "hipd_unpack_cod")
+
+    def unpack_rle_freq(self, stream, max_blocks, d_freq, rle_n, d_info, d_off, d_n):
+        """.rle.freq file -> header info and block b's payload [d_off[b], d_off[b] + d_n[b]) in a .rle file of rle_n bytes."""
+        _check(lib().shafa_hipd_unpack_rle_freq(self.h, self._st(stream), max_blocks, _ptr(d_freq), d_freq.numel(), int(rle_n),
+                                                d_info.data_ptr(), d_off.data_ptr(), d_n.data_ptr()), "hipd_unpack_rle_freq")
+
+    def unpack_shaf(self, stream, max_blocks, d_shaf, d_count, d_off, d_n):
+        """.shaf file -> block b's payload [d_off[b], d_off[b] + d_n[b]) for min(d_count[0], max_blocks) blocks."""
+        _check(lib().shafa_hipd_unpack_shaf(self.h, self._st(stream), max_blocks, _ptr(d_shaf), d_shaf.numel(),
+                                            d_count.data_ptr(), d_off.data_ptr(), d_n.data_ptr()), "hipd_unpack_shaf")
+
+    def unpack_payloads(self, stream, d_file, d_off, d_n, d_dst, dst_off, dst_cap):
+        """block b's payload (d_off / d_n: device int64) -> d_dst + dst_off[b] (16-aligned regions of dst_cap[b] bytes)."""
+        do, dc = _u64arr(dst_off), _u64arr(dst_cap)
+        _check(lib().shafa_hipd_unpack_payloads(self.h, self._st(stream), len(do), _ptr(d_file), d_file.numel(),
+                                                d_off.data_ptr(), d_n.data_ptr(), d_dst.data_ptr(), _p64(do), _p64(dc)),
+               "hipd_unpack_payloads")
 
     def finish(self, stream, nblocks, raise_on_error=True):
         errs = (C.c_int * max(nblocks, 1))()
@@ -697,5 +731,185 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
         bt.finish(st, nb)
         got = lens.cpu().tolist()
         return {key: buf[:got[i]] for i, (key, buf) in enumerate(jobs)}
+    finally:
+        bt.close()
+
+
+# ------------------------------------------------------------------ files in device memory -> the decoded bytes
+UNPACK_INFO_WORDS = 8           # SHAFA_UNPACK_INFO_*: status, mode, count, indexed, framed, largest size
+INFO_STATUS, INFO_MODE, INFO_COUNT, INFO_INDEXED, INFO_FRAMED, INFO_MAX_SIZE = range(6)
+
+
+def unpack_max_blocks(text_n, kind):
+    """max_blocks for Batch.unpack_cod ("cod": a parsable block takes >= 258 bytes, "@d@" and 255 ';') or unpack_rle_freq
+    ("freq": >= 4 bytes, "@d@x"): a header that announces more blocks leaves a failing block among those indexed."""
+    return int(text_n) // (258 if kind == "cod" else 4) + 1
+
+
+def _layout(caps):
+    """16-aligned regions of these capacities: (offsets, total bytes)"""
+    off, pos = [], 0
+    for c in caps:
+        off.append(pos)
+        pos += _al16(c)
+    return off, pos
+
+
+def _u64_host(t):
+    return t.cpu().numpy().view(np.uint64).astype(object).tolist()
+
+
+def _first_error(errs):
+    return next(((i, e) for i, e in enumerate(errs) if e), (len(errs), SUCCESS))
+
+
+def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, max_bytes):
+    """rle_decode_dev of blocks [0, len(in_n)) in groups whose output capacities (min(RLE_DECODE_MAX, 85 n + 2): a 3-byte
+    triple yields at most 255 bytes) fit max_bytes; each group synchronised, read back and packed into a tensor of exactly
+    its bytes.  -> (outputs, first error: (block, code) or None)"""
+    import torch
+    dev = d_in.device
+    nb = len(in_n)
+    caps = [min(RLE_DECODE_MAX, 85 * n + 2) for n in in_n]
+    groups, g0, acc = [], 0, 0
+    for b in range(nb):
+        if b > g0 and acc + _al16(caps[b]) > max_bytes:
+            groups.append((g0, b))
+            g0, acc = b, 0
+        acc += _al16(caps[b])
+    groups.append((g0, nb))
+    biggest = max(_layout(caps[a:z])[1] for a, z in groups)
+    d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
+    d_out_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+    outs = []
+    for a, z in groups:
+        off, _ = _layout(caps[a:z])
+        bt.rle_decode_dev(st, d_in, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, caps[a:z], d_out_n[a:z])
+        _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+        b, e = _first_error(errs[:z - a])
+        if e:
+            return outs, (a + b, e)
+        total = sum(_u64_host(d_out_n[a:z]))
+        o = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        bt.pack_payloads(st, FRAME_RAW, d_out, off, caps[a:z], d_out_n[a:z], o, total, d_len)
+        outs.append(o[:total])
+    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+    b, e = _first_error(errs)
+    return outs, ((b, e) if e else None)
+
+
+def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
+    """The file the CLI's Module D writes, decoded from files held in device memory (contiguous uint8 CUDA tensors, any
+    alignment — e.g. compress_files' values):
+      shaf + cod, decode_rle=False   `shafa X.shaf -m d`, or `X.rle.shaf -m d -d s` (the .rle bytes)
+      shaf + cod, decode_rle=True    `shafa X.rle.shaf` (a mode-N .cod is SHAFA_FILE_UNRECOGNIZABLE, d.c:678)
+      rle + freq                     `shafa X.rle -m d` (the .freq's mode must be R)
+    Returns a uint8 CUDA tensor holding exactly the decoded file.  Errors raise ShafaError(code): the first error in block
+    order, which is the C host's on files with one fault (include/shafa_hip.h: "Files in device memory, parsed").
+
+    Chain: unpack_cod + unpack_shaf (or unpack_rle_freq) -> one synchronisation, 16 bytes a block read back -> exact
+    aligned regions -> unpack_payloads -> sf_decode_dev -> pack_payloads -> finish: two synchronisations without RLE
+    decoding.  RLE decoding runs in groups whose worst-case outputs fit max_bytes (default: a quarter of the free device
+    memory), one synchronisation each.  A symbol count above 8 x the payload's bytes is SHAFA_FILE_UNRECOGNIZABLE without
+    decoding (every code of a table the decoder accepts has >= 1 bit, so the host's decoder runs out of input).  A block whose
+    codes take the decoder's single slot for 33..64-bit codes from another is decoded again on its own."""
+    import torch
+    sf = shaf is not None or cod is not None
+    if sf and (shaf is None or cod is None or rle is not None or freq is not None):
+        raise ValueError("decompress_files: shaf and cod go together, without rle / freq")
+    if not sf and (rle is None or freq is None):
+        raise ValueError("decompress_files: give shaf and cod, or rle and freq")
+    files = [t.reshape(-1) for t in ((shaf, cod) if sf else (rle, freq))]
+    for t in files:
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("decompress_files: files are contiguous uint8 CUDA tensors")
+    dev = files[0].device
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    if max_bytes is None:
+        max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+    text = files[1]
+    mb = unpack_max_blocks(text.numel(), "cod" if sf else "freq")
+    if mb > 0x7FFFFFFF:
+        raise ShafaError(LACK_OF_MEMORY, "decompress_files: text too long")
+    bt = Batch(mb, 1 << 20)
+    try:
+        d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+        d_off = torch.zeros(mb, dtype=torch.int64, device=dev)
+        d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
+        tsz = C.sizeof(CodeTable)
+        if sf:
+            d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
+            d_tab = torch.empty(mb * tsz, dtype=torch.uint8, device=dev)
+            bt.unpack_cod(st, mb, files[1], d_info, d_nsym, d_tab)
+            bt.unpack_shaf(st, mb, files[0], d_info[INFO_INDEXED:INFO_INDEXED + 1], d_off, d_n)
+        else:
+            bt.unpack_rle_freq(st, mb, files[1], files[0].numel(), d_info, d_off, d_n)
+        _, errs = bt.finish(st, mb, raise_on_error=False)                    # the parse's one synchronisation
+        info = _u64_host(d_info)
+        if info[INFO_STATUS]:
+            raise ShafaError(FILE_STREAM_FAILED, "decompress_files: bad header")
+        mode = chr(info[INFO_MODE])
+        if not (mode == "R" or (sf and mode == "N" and not decode_rle)):
+            raise ShafaError(FILE_UNRECOGNIZABLE, f"decompress_files: mode {mode!r}")
+        nidx = info[INFO_INDEXED]
+        pn = _u64_host(d_n)[:nidx]
+        errs = errs[:nidx]
+        if sf:
+            nsym = _u64_host(d_nsym)[:nidx]
+            errs = [e if e or nsym[b] <= 8 * pn[b] else FILE_UNRECOGNIZABLE for b, e in enumerate(errs)]
+        fb, parse_err = _first_error(errs)
+        if not parse_err and info[INFO_COUNT] > nidx:                        # cannot happen: max_blocks covers any count
+            parse_err = FILE_STREAM_FAILED
+        if fb == 0:
+            if parse_err:
+                raise ShafaError(parse_err, "decompress_files: block 0")
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        # ---- the payloads of blocks [0, fb), in exact aligned regions
+        pn = pn[:fb]
+        poff, ptot = _layout(pn)
+        d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=dev)
+        bt.unpack_payloads(st, files[0], d_off, d_n, d_pay, poff, pn)
+        if sf:
+            nsym = nsym[:fb]
+            ooff, otot = _layout(nsym)
+            d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+            bt.sf_decode_dev(st, d_pay, poff, pn, d_n, d_tab, d_nsym, d_sfo, ooff, nsym)
+            rle_after = mode == "R" and decode_rle
+            if not rle_after:
+                total = sum(nsym)
+                out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+                d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+                if not parse_err:
+                    bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+            _, errs = bt.finish(st, mb, raise_on_error=False)
+            errs = errs[:fb]
+            again = set()
+            b, e = _first_error(errs)
+            while e == LACK_OF_MEMORY and b not in again:                    # the one slot for 33..64-bit codes was taken
+                bt.sf_decode_dev(st, d_pay, poff[b:b + 1], pn[b:b + 1], d_n[b:b + 1], d_tab[b * tsz:(b + 1) * tsz],
+                                 d_nsym[b:b + 1], d_sfo, ooff[b:b + 1], nsym[b:b + 1])
+                _, one = bt.finish(st, mb, raise_on_error=False)
+                errs[b] = one[0]
+                again.add(b)
+                b, e = _first_error(errs)
+            if e:
+                raise ShafaError(e, f"decompress_files: block {b}")
+            if not rle_after:
+                if parse_err:
+                    raise ShafaError(parse_err, f"decompress_files: block {fb}")
+                if again:
+                    bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+                    bt.finish(st, mb)
+                return out[:total]
+            d_in, in_off, in_n, d_in_n = d_sfo, ooff, nsym, d_nsym
+        else:
+            d_in, in_off, in_n, d_in_n = d_pay, poff, pn, d_n
+        outs, err = _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, max_bytes)
+        if err:
+            raise ShafaError(err[1], f"decompress_files: block {err[0]}")
+        if parse_err:
+            raise ShafaError(parse_err, f"decompress_files: block {fb}")
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
     finally:
         bt.close()

@@ -190,6 +190,20 @@ int rledec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, co
                       const u64 *d_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n);
 int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
                   const u64 *h_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n);
+// pack.hip's payload movers (pack_bulk, pack_seams) on records laid out elsewhere (unpack.hip): block b moves n bytes from src
+// to dst, no header.  pack_bulk writes the 16-byte destination words inside [dst, dst + n) and needs src 16-aligned whenever
+// (src - dst) is not a multiple of 16 — read the record of d_bulk; pack_seams writes every other byte — from d_seam.  Both
+// return at once when *d_verdict is 0.  max_n bounds every record's n + 15 (the bulk grid).
+struct MoveDesc {
+    const u8 *src;
+    u8 *dst;
+    u64 n;
+    u64 hdr_val;    // 0
+    u32 hdr_len;    // 0
+    u32 pad;
+};
+int pack_move_launch(hipStream_t st, int nblocks, const MoveDesc *d_bulk, const MoveDesc *d_seam, const u32 *d_verdict,
+                     u64 max_n);
 void sfenc_configure(int sfe4_min_blocks);
 void sfdec_configure(int speculate);
 void sfdec_configure_path(int path);

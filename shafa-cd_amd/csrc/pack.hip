@@ -428,6 +428,23 @@ int payload_launch(Batch *bt, hipStream_t st, int nblocks, int framing, const u8
 
 }  // namespace
 
+static_assert(sizeof(MoveDesc) == sizeof(PackDesc) && offsetof(MoveDesc, src) == offsetof(PackDesc, src) &&
+                  offsetof(MoveDesc, dst) == offsetof(PackDesc, dst) && offsetof(MoveDesc, n) == offsetof(PackDesc, n) &&
+                  offsetof(MoveDesc, hdr_len) == offsetof(PackDesc, hdr_len),
+              "MoveDesc (internal.hpp) is PackDesc's layout");
+
+int pack_move_launch(hipStream_t st, int nblocks, const MoveDesc *d_bulk, const MoveDesc *d_seam, const u32 *d_verdict,
+                     u64 max_n)
+{
+    const u64 chunks = ceil_div_u64(max_n / 16 + 2, BULK_CHUNK_WORDS);
+    if (chunks > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    hipLaunchKernelGGL(pack_bulk, dim3((u32)chunks, (u32)nblocks), dim3(BULK_THREADS), 0, st, (const PackDesc *)d_bulk, d_verdict);
+    hipLaunchKernelGGL(pack_seams, dim3((u32)ceil_div_u64((u64)nblocks, 64)), dim3(64), 0, st, (const PackDesc *)d_seam, nblocks,
+                       d_verdict, (u8 *)nullptr, (u64)0, (u32)0);
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
 extern "C" {
 
 size_t shafa_hip_pack_payloads_max(int nblocks, const uint64_t *h_src_cap, int framing)
