@@ -308,6 +308,31 @@ int shafa_hipd_pack_cod(shafa_hipd_batch *b, void *stream, int nblocks, char mod
 int shafa_hipd_pack_freq(shafa_hipd_batch *b, void *stream, int nblocks, char mode, const uint64_t *d_sizes,
                          const uint64_t *d_freq, uint8_t *d_dst, uint64_t dst_cap, uint64_t *d_dst_n);
 
+/* ---- Many files per call: the packs above, segmented ------------------------------------------------------------------
+ * File f is blocks h_first[f] .. h_first[f] + h_count[f] - 1 of the call's block arrays (files may list any blocks, the
+ * same block in several files included); it is written at d_dst + h_dst_off[f] with room for h_dst_cap[f] bytes, its length
+ * goes to d_dst_n[f] (device).  Each file's bytes equal what the single-file pack writes for that file's blocks alone, its
+ * head carrying the file's block count (and for .cod / .freq its own mode h_modes[f]).  Enqueue only, as the packs.
+ * Errors, per file (reported by shafa_hipd_finish):
+ *   d_src_n[b] > h_src_cap[b]              SHAFA_OUTSIDE_MODULE on block b, d_dst_n[f] = 0 for every file that lists b;
+ *   file f longer than h_dst_cap[f]        SHAFA_LACK_OF_MEMORY on block h_first[f], d_dst_n[f] = the length it needs.
+ * A refused file has no byte of its region written; every other file of the call is written normally.  Overlapping
+ * destination regions are the caller's error; destinations need no alignment.
+ * Argument errors return SHAFA_OUTSIDE_MODULE with nothing enqueued (checked before HIP is touched): a NULL batch or array,
+ * nfiles < 1, h_count[f] < 1, a block range outside [0, the batch's max_blocks), a mode other than 'R' / 'N', an unknown
+ * framing, d_src + h_src_off[b] not a multiple of 16 for a listed block.  More than 2^31 - 1 blocks over all files:
+ * SHAFA_LACK_OF_MEMORY.  The host arrays indexed by block hold max(h_first[f] + h_count[f]) entries. */
+int shafa_hipd_pack_payloads_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                                   int framing, const uint8_t *d_src, const uint64_t *h_src_off, const uint64_t *h_src_cap,
+                                   const uint64_t *d_src_n, uint8_t *d_dst, const uint64_t *h_dst_off,
+                                   const uint64_t *h_dst_cap, uint64_t *d_dst_n);
+int shafa_hipd_pack_cod_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                              const char *h_modes, const uint64_t *d_sizes, const shafa_code_table *d_tables,
+                              uint8_t *d_dst, const uint64_t *h_dst_off, const uint64_t *h_dst_cap, uint64_t *d_dst_n);
+int shafa_hipd_pack_freq_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                               const char *h_modes, const uint64_t *d_sizes, const uint64_t *d_freq,
+                               uint8_t *d_dst, const uint64_t *h_dst_off, const uint64_t *h_dst_cap, uint64_t *d_dst_n);
+
 /* ---- Files in device memory, parsed: the inverse of the packs -----------------------------------------------------------
  * .cod / .rle.freq / .shaf files at d_* (any alignment, lengths known on the host) -> the sizes, tables and payload
  * positions that shafa_hipd_sf_decode_dev / _rle_decode_dev take, by the C host's rules (host/modules.c read_header,

@@ -125,6 +125,11 @@ def lib():
     L.shafa_hipd_pack_payloads.argtypes = [vp, vp, C.c_int, C.c_int, u8p, u64p, u64p, vp, u8p, C.c_uint64, vp]
     L.shafa_hipd_pack_cod.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
     L.shafa_hipd_pack_freq.argtypes = [vp, vp, C.c_int, C.c_char, vp, vp, u8p, C.c_uint64, vp]
+    i32p = C.POINTER(C.c_int)
+    L.shafa_hipd_pack_payloads_files.argtypes = [vp, vp, C.c_int, i32p, i32p, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p,
+                                                 vp]
+    L.shafa_hipd_pack_cod_files.argtypes = [vp, vp, C.c_int, i32p, i32p, C.c_char_p, vp, vp, u8p, u64p, u64p, vp]
+    L.shafa_hipd_pack_freq_files.argtypes = [vp, vp, C.c_int, i32p, i32p, C.c_char_p, vp, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_unpack_cod.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_rle_freq.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_shaf.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
@@ -156,6 +161,7 @@ def lib():
                  "shafa_hipd_gen_bytes", "shafa_hipd_hist256_tiles", "shafa_hipd_rle_encode_tiles",
                  "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev", "shafa_hipd_sf_decode_dev",
                  "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq",
+                 "shafa_hipd_pack_payloads_files", "shafa_hipd_pack_cod_files", "shafa_hipd_pack_freq_files",
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -247,6 +253,14 @@ def _u64arr(v):
 
 def _p64(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _i32arr(v):
+    return np.ascontiguousarray(v, dtype=np.int32)
+
+
+def _p32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
 def _ptr(t):
@@ -398,6 +412,33 @@ class Batch:
                                           d_freq.data_ptr(), d_dst.data_ptr(), int(dst_cap), d_dst_n.data_ptr()),
                "hipd_pack_freq")
 
+    # ---- many files per call (include/shafa_hip.h: "Many files per call"); enqueue only, d_dst_n: nfiles int64 ----
+    # file f is blocks first[f] .. first[f] + count[f] - 1, written at d_dst + dst_off[f] in dst_cap[f] bytes
+    def pack_payloads_files(self, stream, first, count, framing, d_src, src_off, src_cap, d_src_n, d_dst, dst_off, dst_cap,
+                            d_dst_n):
+        """pack_payloads per file: .rle (FRAME_RAW) or .shaf (FRAME_SHAF) files of the blocks' d_src_n[b] bytes at
+        d_src + src_off[b]."""
+        fi, co, so, sc, do, dc = _i32arr(first), _i32arr(count), _u64arr(src_off), _u64arr(src_cap), _u64arr(dst_off), \
+            _u64arr(dst_cap)
+        _check(lib().shafa_hipd_pack_payloads_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), framing,
+                                                    d_src.data_ptr(), _p64(so), _p64(sc), d_src_n.data_ptr(),
+                                                    d_dst.data_ptr(), _p64(do), _p64(dc), d_dst_n.data_ptr()),
+               "hipd_pack_payloads_files")
+
+    def pack_cod_files(self, stream, first, count, modes, d_sizes, d_tables, d_dst, dst_off, dst_cap, d_dst_n):
+        """pack_cod per file, file f in mode modes[f] (b"R" / b"N")."""
+        fi, co, do, dc = _i32arr(first), _i32arr(count), _u64arr(dst_off), _u64arr(dst_cap)
+        _check(lib().shafa_hipd_pack_cod_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), _modes(modes),
+                                               d_sizes.data_ptr(), d_tables.data_ptr(), d_dst.data_ptr(), _p64(do),
+                                               _p64(dc), d_dst_n.data_ptr()), "hipd_pack_cod_files")
+
+    def pack_freq_files(self, stream, first, count, modes, d_sizes, d_freq, d_dst, dst_off, dst_cap, d_dst_n):
+        """pack_freq per file, file f in mode modes[f] (b"R" / b"N")."""
+        fi, co, do, dc = _i32arr(first), _i32arr(count), _u64arr(dst_off), _u64arr(dst_cap)
+        _check(lib().shafa_hipd_pack_freq_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), _modes(modes),
+                                                d_sizes.data_ptr(), d_freq.data_ptr(), d_dst.data_ptr(), _p64(do),
+                                                _p64(dc), d_dst_n.data_ptr()), "hipd_pack_freq_files")
+
     # ---- files in device memory, parsed (include/shafa_hip.h: "Files in device memory, parsed"); enqueue only ----
     # d_info: UNPACK_INFO_WORDS int64; d_sizes / d_off / d_n: max_blocks int64; d_tables: max_blocks x sizeof(CodeTable) bytes
     def unpack_cod(self, stream, max_blocks, d_cod, d_info, d_sizes, d_tables):
@@ -509,6 +550,13 @@ FRAME_RAW, FRAME_SHAF = 0, 1   # SHAFA_FRAME_*: .rle (payloads back to back), .s
 
 def _mode(mode):
     return C.c_char(mode if isinstance(mode, bytes) else str(mode).encode())
+
+
+def _modes(modes):
+    """per-file modes (b"RN..", or a sequence of b"R" / "N") as a C string"""
+    if isinstance(modes, bytes):
+        return modes
+    return b"".join(m if isinstance(m, bytes) else str(m).encode() for m in modes)
 
 
 def pack_payloads_max(src_cap, framing):
@@ -731,6 +779,181 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
         bt.finish(st, nb)
         got = lens.cpu().tolist()
         return {key: buf[:got[i]] for i, (key, buf) in enumerate(jobs)}
+    finally:
+        bt.close()
+
+
+MANY_GROUP_BLOCKS = 16384      # compress_many: blocks per device batch (the F / T / C launches put blocks on the grid's y)
+
+
+def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_freq=False, stream=None):
+    """compress_files for many files in one device batch.  `d_in` holds the files back to back (a contiguous uint8 CUDA tensor;
+    a list of such tensors is concatenated), `sizes` their lengths (for a list: None = the tensors' lengths).  Returns one entry
+    per file: the dict compress_files returns for that file alone, byte for byte, or a ShafaError instance (not raised) for a
+    file that failed — FILE_TOO_SMALL below 1 KiB, else the first error in the file's block order.  Other files are unaffected.
+
+    Chain per batch of files, its length independent of the file count: block split (shafa_block_count) -> one unpack_payloads
+    gather into 16-aligned regions when some block start is not aligned -> rle_encode_tiles + hist256_tiles over all blocks ->
+    one synchronisation reading every file's block-0 RLE size (none with force_rle) -> sf_build_codes + sf_encode_dev over all
+    blocks, RLE and plain files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena, sizes and
+    counts selected per block on the device) -> the segmented packs, one call per kind of file -> one finish.  Two
+    synchronisations per batch (one with force_rle); files are batched by MANY_GROUP_BLOCKS blocks."""
+    import torch
+    if isinstance(d_in, (list, tuple)):
+        if sizes is None:
+            sizes = [int(t.numel()) for t in d_in]
+        d_in = torch.cat([t.reshape(-1) for t in d_in]) if d_in else None
+    sizes = [int(n) for n in (sizes or [])]
+    if not sizes:
+        raise ValueError("compress_many: no files")
+    if d_in is None or d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+        raise ValueError("compress_many: d_in is a contiguous uint8 CUDA tensor")
+    if sum(sizes) > d_in.numel() or min(sizes) < 0:
+        raise ValueError("compress_many: sizes exceed d_in")
+    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
+    results = [None] * len(sizes)
+    start, pos = [], 0
+    for n in sizes:
+        start.append(pos)
+        pos += n
+    # the C host's block split per file; a file under 1 KiB is refused before any device work (f.c:220,366)
+    split = {}
+    for f, n in enumerate(sizes):
+        bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
+        nb = int(host().shafa_block_count(n, C.byref(bs), C.byref(last)))
+        if n < 1024:
+            results[f] = ShafaError(FILE_TOO_SMALL, "compress_many: fewer than 1024 bytes")
+        else:
+            split[f] = [bs.value] * (nb - 1) + [last.value]
+    group, acc = [], 0
+    for f in split:
+        if group and acc + len(split[f]) > MANY_GROUP_BLOCKS:
+            _compress_group(d_in, start, split, group, force_rle, force_freq, st, results)
+            group, acc = [], 0
+        group.append(f)
+        acc += len(split[f])
+    if group:
+        _compress_group(d_in, start, split, group, force_rle, force_freq, st, results)
+    return results
+
+
+def _compress_group(d_in, start, split, files, force_rle, force_freq, st, results):
+    import torch
+    dev = d_in.device
+    nf = len(files)
+    sizes, first, count, src = [], [], [], []                   # per block; per file; per block: start in d_in
+    for f in files:
+        first.append(len(sizes))
+        count.append(len(split[f]))
+        o = start[f]
+        for n in split[f]:
+            src.append(o)
+            sizes.append(n)
+            o += n
+    nb = len(sizes)
+    base = d_in.data_ptr()
+    d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
+    rcap = [2 * n + 3 for n in sizes]                                       # f.c:244
+    need_in = force_freq or not force_rle
+    # tile histograms: the RLE outputs' then the inputs', in one arena
+    rthb = [_al16(tile_hist_bytes(c)) for c in rcap]
+    ithb = [_al16(tile_hist_bytes(n)) for n in sizes] if need_in else []
+    th_off, th_tot = _layout(rthb + ithb)
+    rtoff, itoff = th_off[:nb], th_off[nb:]
+    bt = Batch(nb, 2 * max(sizes) + 64)
+    try:
+        # ---- inputs at 16-byte aligned addresses: in place, or gathered by one unpack_payloads
+        if base % 16 or any(o % 16 for o in src):
+            d_so = torch.tensor(src, dtype=torch.int64, device=dev)
+            off, tot = _layout(sizes)
+            src_in = torch.empty(tot + 16, dtype=torch.uint8, device=dev)
+            bt.unpack_payloads(st, d_in, d_so, d_n_in, src_in, off, sizes)
+        else:
+            src_in, off = d_in, src
+        # ---- Module F over every block of every file
+        roff, rtot = _layout(rcap)
+        d_rle = torch.empty(rtot + 16, dtype=torch.uint8, device=dev)
+        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+        d_th = torch.empty(th_tot + 16, dtype=torch.uint8, device=dev)
+        bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_th, rtoff)
+        d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+        if need_in:
+            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_th, itoff)
+        errs0 = [SUCCESS] * nb
+        if force_rle:
+            use = [True] * nf
+        else:                                                               # the reference's decision: block 0's RLE size
+            _, errs0 = bt.finish(st, nb, raise_on_error=False)
+            r0 = d_rle_n.cpu().tolist()
+            use = [bool(host().shafa_rle_worthwhile(sizes[first[i]], r0[first[i]], False)) for i in range(nf)]
+        blk_rle = [u for u, c in zip(use, count) for _ in range(c)]
+        # ---- Module T and Module C once over all blocks: each block's sizes, counts, source and tile histograms by its file
+        if all(use):                                                        # always so with force_rle: no upload, no wait
+            e_n, e_freq = d_rle_n, d_freq_rle
+        elif not any(use):
+            e_n, e_freq = d_n_in, d_freq_in
+        else:
+            with torch.cuda.stream(st):                                     # st has drained: the mask's upload waits for nothing
+                mask = torch.tensor(blk_rle, dtype=torch.bool, device=dev)
+                e_n = torch.where(mask, d_rle_n, d_n_in)
+                e_freq = torch.where(mask[:, None], d_freq_rle.view(nb, 256), d_freq_in.view(nb, 256)).reshape(-1)
+        lo = d_rle if d_rle.data_ptr() < src_in.data_ptr() else src_in      # one base for inputs and RLE outputs
+        a_in, a_rle = src_in.data_ptr() - lo.data_ptr(), d_rle.data_ptr() - lo.data_ptr()
+        e_off = [a_rle + roff[b] if blk_rle[b] else a_in + off[b] for b in range(nb)]
+        e_cap = [rcap[b] if blk_rle[b] else sizes[b] for b in range(nb)]
+        e_toff = [rtoff[b] if blk_rle[b] else itoff[b] for b in range(nb)]
+        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.sf_build_codes(st, nb, e_freq, d_tab)
+        ocap = [c + c // 2 + 64 for c in e_cap]                             # compress_files' bound
+        ooff, otot = _layout(ocap)
+        d_enc = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        bt.sf_encode_dev(st, lo, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, d_th, e_toff)
+        # ---- the files: one segmented pack per kind, each file's region sized by the single-file bound
+        lens = torch.zeros(5 * nf, dtype=torch.int64, device=dev)
+        kinds = []                                                          # per pack call: (its files, their keys, buffer, offsets)
+
+        def pack(call, sel, keys, caps, args):
+            fs = [i for i in range(nf) if sel[i]]
+            if not fs:
+                return
+            doff, dtot = _layout([caps(i) for i in fs])
+            buf = torch.empty(dtot + 16, dtype=torch.uint8, device=dev)
+            n = lens[len(kinds) * nf:(len(kinds) + 1) * nf]
+            call(st, [first[i] for i in fs], [count[i] for i in fs], *args(fs), buf, doff, [caps(i) for i in fs], n)
+            kinds.append((fs, [keys(i) for i in fs], buf, doff))
+
+        def blocks(i):
+            return range(first[i], first[i] + count[i])
+
+        modes = [b"R" if u else b"N" for u in use]
+        pack(bt.pack_payloads_files, use, lambda i: ".rle", lambda i: pack_payloads_max([rcap[b] for b in blocks(i)],
+                                                                                        FRAME_RAW),
+             lambda fs: (FRAME_RAW, d_rle, roff, rcap, d_rle_n))
+        pack(bt.pack_freq_files, [True] * nf, lambda i: ".rle.freq" if use[i] else ".freq", lambda i: pack_freq_max(count[i]),
+             lambda fs: ([modes[i] for i in fs], e_n, e_freq))
+        if force_freq:
+            pack(bt.pack_freq_files, use, lambda i: ".freq", lambda i: pack_freq_max(count[i]),
+                 lambda fs: ([b"N"] * len(fs), d_n_in, d_freq_in))
+        stem = lambda i: ".rle" if use[i] else ""                           # noqa: E731
+        pack(bt.pack_cod_files, [True] * nf, lambda i: stem(i) + ".cod", lambda i: pack_cod_max(count[i]),
+             lambda fs: ([modes[i] for i in fs], e_n, d_tab))
+        pack(bt.pack_payloads_files, [True] * nf, lambda i: stem(i) + ".shaf",
+             lambda i: pack_payloads_max([ocap[b] for b in blocks(i)], FRAME_SHAF),
+             lambda fs: (FRAME_SHAF, d_enc, ooff, ocap, d_enc_n))
+        _, errs = bt.finish(st, nb, raise_on_error=False)
+        got = lens.cpu().tolist()
+        out = [{} for _ in range(nf)]
+        for k, (fs, keys, buf, doff) in enumerate(kinds):
+            for j, i in enumerate(fs):
+                n = got[k * nf + j]
+                out[i][keys[j]] = buf[doff[j]:doff[j] + n]
+        for i, f in enumerate(files):                                       # compress_files raises at its first finish
+            b, e = _first_error(errs0[first[i]:first[i] + count[i]])
+            if not e:
+                b, e = _first_error(errs[first[i]:first[i] + count[i]])
+            results[f] = ShafaError(e, f"compress_many: block {b}") if e else out[i]
     finally:
         bt.close()
 

@@ -16,6 +16,12 @@
 //   pack_seams                             a lane per block: "@n", "@size@" and the partial words at both ends of a payload
 //   pack_text<CodText | FreqText>          one workgroup per block, a lane per symbol: header and fields
 // Every later kernel reads the verdict word first and returns when the plan refused the file: then no byte of d_dst is written.
+// Segmented packs (shafa_hipd_pack_*_files: many files in one launch sequence) add
+//   pack_file_plan                         one workgroup per file: pack_plan's scan and checks over the file's blocks, its
+//                                          length and its verdict; a refused file's descriptors get n = 0, hdr_len = 0
+//   pack_file_text<CodText | FreqText>     pack_text without the file's head and tail, per descriptor slot
+//   pack_file_ends                         a lane per file: its "@<n>" / "@<mode>@<n>" head and its "@0" tail
+// and run pack_measure, pack_bulk and pack_seams as they are.
 //
 // Byte ownership (payloads).  With P = a payload's first destination byte and n its size, the words [ceil(P/16), floor((P+n)/16))
 // lie entirely inside the payload: pack_bulk writes them, whole, with aligned 16-byte stores (an unaligned store is serialised
@@ -426,8 +432,320 @@ int payload_launch(Batch *bt, hipStream_t st, int nblocks, int framing, const u8
     return pscope.done();
 }
 
+// ---- segmented packs: many files in one launch sequence ----------------------------------------------------------------
+// File f is blocks first .. first + count - 1 of the call's block arrays; its frames take the descriptor slots slot ..
+// slot + count - 1 (a block listed by two files has a slot in each).  Per file: a verdict word (1: write it) and its length.
+// The movers' global verdict word stays 1: a refused file's descriptors are rewritten to n = 0, hdr_len = 0, for which the
+// unchanged pack_bulk / pack_seams write nothing (unpack.hip's rule for a refused block).
+struct FileRec {
+    u8 *dst;
+    u64 cap;
+    int first, count;
+    u32 slot;
+    u32 mode;                // text: 'R' / 'N'
+};
+
+struct FilesPlanArgs {
+    const FileRec *files;
+    u32 hdr;                 // 1: every block's frame starts with "@<size>@"
+    u32 head;                // the file's prefix: 0 none, 1 "@<n>", 2 "@<mode>@<n>"
+    u64 tail_len;            // "@0": 2, else 0
+    const PackSrc *srcs;     // payloads: sources and capacities per block; text: nullptr
+    const u64 *n;            // body sizes per block
+    const u64 *hdr_vals;     // the numbers of the block headers per block: nullptr = the body sizes
+    u64 *dst_n;              // per file
+    PackDesc *desc;          // per slot
+    u32 *slot_file;          // per slot: its file
+    u32 *fverdict;           // per file
+    u32 *verdict;            // the movers' word: 1
+    int *err;                // per block
+};
+
+__device__ inline u64 file_head_len(u32 head, int count)
+{
+    return head == 0 ? 0 : (head == 1 ? 1u : 3u) + dec_digits((u64)count);
+}
+
+// one workgroup per file: pack_plan's scan and checks over the file's blocks
+__global__ __launch_bounds__(PLAN_THREADS) void pack_file_plan(FilesPlanArgs a)
+{
+    __shared__ u64 wsum[PLAN_THREADS / 64];
+    __shared__ u32 bad_sh, go_sh;
+    const u32 tid = threadIdx.x, f = blockIdx.x;
+    const FileRec fr = a.files[f];
+    if (tid == 0) bad_sh = 0;
+    __syncthreads();
+    u64 pos = file_head_len(a.head, fr.count);
+    for (int i0 = 0; i0 < fr.count; i0 += PLAN_THREADS) {
+        const int i = i0 + (int)tid;
+        u64 frame = 0;
+        PackDesc d = {};
+        if (i < fr.count) {
+            const int b = fr.first + i;
+            const u64 n = a.n[b];
+            if (a.srcs) {
+                const PackSrc s = a.srcs[b];
+                if (n > s.cap) {
+                    set_error(a.err + b, SHAFA_OUTSIDE_MODULE);
+                    atomicOr(&bad_sh, 1u);
+                }
+                d.src = s.src;
+            }
+            d.n = n;
+            d.hdr_val = a.hdr_vals ? a.hdr_vals[b] : n;
+            d.hdr_len = a.hdr ? 2u + dec_digits(d.hdr_val) : 0u;
+            frame = d.hdr_len + n;
+        }
+        u64 sum;
+        const u64 off = pos + wg_excl_scan(frame, wsum, &sum);
+        if (i < fr.count) {
+            d.dst = fr.dst + off;
+            a.desc[fr.slot + i] = d;
+            a.slot_file[fr.slot + i] = f;
+        }
+        pos += sum;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const u64 total = pos + a.tail_len;
+        u32 go = 1;
+        if (bad_sh) {
+            go = 0;
+            a.dst_n[f] = 0;
+        } else {
+            a.dst_n[f] = total;
+            if (total > fr.cap) {
+                set_error(a.err + fr.first, SHAFA_LACK_OF_MEMORY);
+                go = 0;
+            }
+        }
+        go_sh = go;
+        a.fverdict[f] = go;
+        if (f == 0) *a.verdict = 1;
+    }
+    __syncthreads();
+    if (!go_sh)                                      // each lane rewrites the slots it wrote above
+        for (int i = (int)tid; i < fr.count; i += PLAN_THREADS) {
+            a.desc[fr.slot + i].n = 0;
+            a.desc[fr.slot + i].hdr_len = 0;
+        }
+}
+
+// a lane per file: its prefix ("@<n>" / "@<mode>@<n>") and, for text, its "@0"
+__global__ __launch_bounds__(64) void pack_file_ends(const FileRec *__restrict__ files, int nfiles, const u32 *__restrict__ fverdict,
+                                                     const u64 *__restrict__ dst_n, u32 head, u32 tail)
+{
+    const int f = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (f >= nfiles || fverdict[f] == 0) return;
+    const FileRec fr = files[f];
+    u8 *o = fr.dst;
+    if (head) {
+        *o++ = '@';
+        if (head == 2) {
+            *o++ = (u8)fr.mode;
+            *o++ = '@';
+        }
+        put_dec(o, (u64)fr.count);
+    }
+    if (tail) {
+        u8 *e = fr.dst + dst_n[f] - 2;
+        e[0] = '@';
+        e[1] = '0';
+    }
+}
+
+// pack_text without the file's head and tail: slot i's "@<size>@" + fields, when its file was not refused
+template <typename Text>
+__global__ __launch_bounds__(256) void pack_file_text(Text tx, const PackDesc *__restrict__ desc, const FileRec *__restrict__ files,
+                                                      const u32 *__restrict__ slot_file, const u32 *__restrict__ fverdict)
+{
+    __shared__ u32 wsum32[4];
+    const u32 i = blockIdx.x, f = slot_file[i];
+    if (fverdict[f] == 0) return;
+    const FileRec fr = files[f];
+    const int b = fr.first + (int)(i - fr.slot), s = (int)threadIdx.x;
+    const PackDesc d = desc[i];
+    u32 total;
+    const u32 off = field_scan(tx.len(b, s), wsum32, &total);
+    u8 *body = d.dst + d.hdr_len;
+    tx.put(b, s, body + off);
+    if (s != 255) body[off + tx.len(b, s)] = ';';
+    if (s == 0) {
+        u8 *o = d.dst;
+        *o++ = '@';
+        o = put_dec(o, d.hdr_val);
+        *o = '@';
+    }
+}
+
+// the host's view of a segmented call: the blocks it reads ([0, nb)) and its descriptor slots
+struct FilesShape {
+    int nb;
+    u32 slots;
+};
+
+// argument checks shared by the three entries (no HIP call)
+int files_check(const Batch *bt, int nfiles, const int *h_first, const int *h_count, const u64 *h_dst_off,
+                const u64 *h_dst_cap, const char *h_modes, FilesShape &sh)
+{
+    if (!bt || nfiles < 1 || !h_first || !h_count || !h_dst_off || !h_dst_cap) return SHAFA_OUTSIDE_MODULE;
+    long long slots = 0, nb = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        const long long first = h_first[f], count = h_count[f];
+        if (count < 1 || first < 0 || first + count > bt->max_blocks) return SHAFA_OUTSIDE_MODULE;
+        if (h_modes && h_modes[f] != 'R' && h_modes[f] != 'N') return SHAFA_OUTSIDE_MODULE;
+        slots += count;
+        if (first + count > nb) nb = first + count;
+    }
+    if (slots > 0x7FFFFFFFll) return SHAFA_LACK_OF_MEMORY;
+    sh.nb = (int)nb;
+    sh.slots = (u32)slots;
+    return SHAFA_SUCCESS;
+}
+
+// workspace: [verdict: 256 B][file verdicts][descriptors][text lengths][slot files]
+struct FilesWs {
+    u32 *verdict, *fverdict;
+    PackDesc *desc;
+    u64 *body;
+    u32 *slot_file;
+};
+
+size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int files_ws(Batch *bt, hipStream_t st, int nfiles, const FilesShape &sh, FilesWs &w)
+{
+    const size_t o_desc = 256 + al16((size_t)nfiles * 4), o_body = o_desc + (size_t)sh.slots * sizeof(PackDesc);
+    const size_t o_slot = o_body + al16((size_t)sh.nb * 8);
+    if (int rc = batch_reserve(bt, st, o_slot + (size_t)sh.slots * 4)) return rc;
+    u8 *ws = (u8 *)bt->d_ws;
+    w.verdict = (u32 *)ws;
+    w.fverdict = (u32 *)(ws + 256);
+    w.desc = (PackDesc *)(ws + o_desc);
+    w.body = (u64 *)(ws + o_body);
+    w.slot_file = (u32 *)(ws + o_slot);
+    return SHAFA_SUCCESS;
+}
+
+// the file records (and, for payloads, the blocks' sources after them) in the staging of the launch's parameters
+void files_records(FileRec *hp, int nfiles, const int *h_first, const int *h_count, const char *h_modes, u8 *d_dst,
+                   const u64 *h_dst_off, const u64 *h_dst_cap)
+{
+    u32 slot = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        hp[f].dst = d_dst + h_dst_off[f];
+        hp[f].cap = h_dst_cap[f];
+        hp[f].first = h_first[f];
+        hp[f].count = h_count[f];
+        hp[f].slot = slot;
+        hp[f].mode = h_modes ? (u32)(u8)h_modes[f] : 0u;
+        slot += (u32)h_count[f];
+    }
+}
+
+template <typename Text>
+int text_files_launch(Batch *bt, hipStream_t st, int nfiles, const FilesShape &sh, const int *h_first, const int *h_count,
+                      const char *h_modes, const u64 *d_sizes, Text tx, u8 *d_dst, const u64 *h_dst_off, const u64 *h_dst_cap,
+                      u64 *d_dst_n)
+{
+    FilesWs w;
+    if (int rc = files_ws(bt, st, nfiles, sh, w)) return rc;
+    const size_t par_bytes = (size_t)nfiles * sizeof(FileRec);
+    u8 *dpar = batch_params_begin(bt, par_bytes);
+    if (!dpar) return SHAFA_LACK_OF_MEMORY;
+    ParamsScope pscope(bt, st);
+    FileRec *hp = (FileRec *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
+    if (!hp) return SHAFA_LACK_OF_MEMORY;
+    files_records(hp, nfiles, h_first, h_count, h_modes, d_dst, h_dst_off, h_dst_cap);
+    if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
+    const FileRec *d_files = (const FileRec *)dpar;
+    hipLaunchKernelGGL(pack_measure<Text>, dim3((u32)sh.nb), dim3(256), 0, st, tx, w.body);
+    FilesPlanArgs a = {};
+    a.files = d_files;
+    a.hdr = 1;
+    a.head = 2;                                      // "@<mode>@<n>"
+    a.tail_len = 2;                                  // "@0"
+    a.srcs = nullptr;
+    a.n = w.body;
+    a.hdr_vals = d_sizes;
+    a.dst_n = d_dst_n;
+    a.desc = w.desc;
+    a.slot_file = w.slot_file;
+    a.fverdict = w.fverdict;
+    a.verdict = w.verdict;
+    a.err = bt->d_err;
+    hipLaunchKernelGGL(pack_file_plan, dim3((u32)nfiles), dim3(PLAN_THREADS), 0, st, a);
+    hipLaunchKernelGGL(pack_file_text<Text>, dim3(sh.slots), dim3(256), 0, st, tx, (const PackDesc *)w.desc, d_files,
+                       (const u32 *)w.slot_file, (const u32 *)w.fverdict);
+    hipLaunchKernelGGL(pack_file_ends, dim3((u32)ceil_div_u64((u64)nfiles, 64)), dim3(64), 0, st, d_files, nfiles,
+                       (const u32 *)w.fverdict, (const u64 *)d_dst_n, 2u, 1u);
+    HIP_TRY(hipGetLastError());
+    return pscope.done();
+}
+
+int payload_files_launch(Batch *bt, hipStream_t st, int nfiles, const FilesShape &sh, const int *h_first, const int *h_count,
+                         int framing, const u8 *d_src, const u64 *h_src_off, const u64 *h_src_cap, const u64 *d_src_n, u8 *d_dst,
+                         const u64 *h_dst_off, const u64 *h_dst_cap, u64 *d_dst_n)
+{
+    u64 max_chunks = 1;
+    for (int b = 0; b < sh.nb; ++b) {
+        const u64 c = ceil_div_u64(h_src_cap[b] / 16 + 1, BULK_CHUNK_WORDS);
+        if (c > max_chunks) max_chunks = c;
+    }
+    if (max_chunks > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    int max_y = 0;
+    HIP_TRY(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, bt->device));
+    if (max_y < 1) max_y = 1;
+    FilesWs w;
+    if (int rc = files_ws(bt, st, nfiles, sh, w)) return rc;
+    const size_t o_src = (size_t)nfiles * sizeof(FileRec), par_bytes = o_src + (size_t)sh.nb * sizeof(PackSrc);
+    u8 *dpar = batch_params_begin(bt, par_bytes);
+    if (!dpar) return SHAFA_LACK_OF_MEMORY;
+    ParamsScope pscope(bt, st);
+    FileRec *hp = (FileRec *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
+    if (!hp) return SHAFA_LACK_OF_MEMORY;
+    files_records(hp, nfiles, h_first, h_count, nullptr, d_dst, h_dst_off, h_dst_cap);
+    PackSrc *hs = (PackSrc *)((u8 *)hp + o_src);
+    for (int b = 0; b < sh.nb; ++b) {
+        hs[b].src = d_src + h_src_off[b];
+        hs[b].cap = h_src_cap[b];
+    }
+    if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
+    const FileRec *d_files = (const FileRec *)dpar;
+    const bool shaf = framing == SHAFA_FRAME_SHAF;
+    FilesPlanArgs a = {};
+    a.files = d_files;
+    a.hdr = shaf ? 1u : 0u;
+    a.head = shaf ? 1u : 0u;                         // "@<n>"
+    a.tail_len = 0;
+    a.srcs = (const PackSrc *)(dpar + o_src);
+    a.n = d_src_n;
+    a.hdr_vals = nullptr;
+    a.dst_n = d_dst_n;
+    a.desc = w.desc;
+    a.slot_file = w.slot_file;
+    a.fverdict = w.fverdict;
+    a.verdict = w.verdict;
+    a.err = bt->d_err;
+    hipLaunchKernelGGL(pack_file_plan, dim3((u32)nfiles), dim3(PLAN_THREADS), 0, st, a);
+    // the bulk grid puts slots on y: in slices of at most the device's grid height
+    for (u32 s0 = 0; s0 < sh.slots; s0 += (u32)max_y) {
+        const u32 ns = sh.slots - s0 < (u32)max_y ? sh.slots - s0 : (u32)max_y;
+        hipLaunchKernelGGL(pack_bulk, dim3((u32)max_chunks, ns), dim3(BULK_THREADS), 0, st, (const PackDesc *)(w.desc + s0),
+                           (const u32 *)w.verdict);
+    }
+    hipLaunchKernelGGL(pack_seams, dim3((u32)ceil_div_u64((u64)sh.slots, 64)), dim3(64), 0, st, (const PackDesc *)w.desc,
+                       (int)sh.slots, (const u32 *)w.verdict, (u8 *)nullptr, (u64)0, (u32)0);
+    if (shaf)
+        hipLaunchKernelGGL(pack_file_ends, dim3((u32)ceil_div_u64((u64)nfiles, 64)), dim3(64), 0, st, d_files, nfiles,
+                           (const u32 *)w.fverdict, (const u64 *)d_dst_n, 1u, 0u);
+    HIP_TRY(hipGetLastError());
+    return pscope.done();
+}
+
 }  // namespace
 
+static_assert(sizeof(FileRec) == 32, "file records keep the blocks' PackSrc records after them 16-aligned");
 static_assert(sizeof(MoveDesc) == sizeof(PackDesc) && offsetof(MoveDesc, src) == offsetof(PackDesc, src) &&
                   offsetof(MoveDesc, dst) == offsetof(PackDesc, dst) && offsetof(MoveDesc, n) == offsetof(PackDesc, n) &&
                   offsetof(MoveDesc, hdr_len) == offsetof(PackDesc, hdr_len),
@@ -497,6 +815,50 @@ int shafa_hipd_pack_freq(shafa_hipd_batch *b, void *stream, int nblocks, char mo
         return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
     return text_launch((Batch *)b, (hipStream_t)stream, nblocks, mode, d_sizes, FreqText{d_freq}, d_dst, dst_cap, d_dst_n);
+}
+
+int shafa_hipd_pack_payloads_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                                   int framing, const uint8_t *d_src, const uint64_t *h_src_off, const uint64_t *h_src_cap,
+                                   const uint64_t *d_src_n, uint8_t *d_dst, const uint64_t *h_dst_off,
+                                   const uint64_t *h_dst_cap, uint64_t *d_dst_n)
+{
+    if (!d_src || !h_src_off || !h_src_cap || !d_src_n || !d_dst || !d_dst_n) return SHAFA_OUTSIDE_MODULE;
+    if (framing != SHAFA_FRAME_RAW && framing != SHAFA_FRAME_SHAF) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    FilesShape sh;
+    if (int rc = files_check(bt, nfiles, h_first, h_count, h_dst_off, h_dst_cap, nullptr, sh)) return rc;
+    for (int f = 0; f < nfiles; ++f)
+        for (int i = h_first[f]; i < h_first[f] + h_count[f]; ++i)
+            if ((uintptr_t)(d_src + h_src_off[i]) & 15) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return payload_files_launch(bt, (hipStream_t)stream, nfiles, sh, h_first, h_count, framing, d_src, h_src_off, h_src_cap,
+                                d_src_n, d_dst, h_dst_off, h_dst_cap, d_dst_n);
+}
+
+int shafa_hipd_pack_cod_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                              const char *h_modes, const uint64_t *d_sizes, const shafa_code_table *d_tables,
+                              uint8_t *d_dst, const uint64_t *h_dst_off, const uint64_t *h_dst_cap, uint64_t *d_dst_n)
+{
+    if (!h_modes || !d_sizes || !d_tables || !d_dst || !d_dst_n) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    FilesShape sh;
+    if (int rc = files_check(bt, nfiles, h_first, h_count, h_dst_off, h_dst_cap, h_modes, sh)) return rc;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return text_files_launch(bt, (hipStream_t)stream, nfiles, sh, h_first, h_count, h_modes, d_sizes, CodText{d_tables}, d_dst,
+                             h_dst_off, h_dst_cap, d_dst_n);
+}
+
+int shafa_hipd_pack_freq_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                               const char *h_modes, const uint64_t *d_sizes, const uint64_t *d_freq,
+                               uint8_t *d_dst, const uint64_t *h_dst_off, const uint64_t *h_dst_cap, uint64_t *d_dst_n)
+{
+    if (!h_modes || !d_sizes || !d_freq || !d_dst || !d_dst_n) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    FilesShape sh;
+    if (int rc = files_check(bt, nfiles, h_first, h_count, h_dst_off, h_dst_cap, h_modes, sh)) return rc;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return text_files_launch(bt, (hipStream_t)stream, nfiles, sh, h_first, h_count, h_modes, d_sizes, FreqText{d_freq}, d_dst,
+                             h_dst_off, h_dst_cap, d_dst_n);
 }
 
 }  // extern "C"
