@@ -390,6 +390,30 @@ int shafa_hipd_unpack_payloads(shafa_hipd_batch *b, void *stream, int nblocks, c
                                const uint64_t *d_off, const uint64_t *d_n, uint8_t *d_dst, const uint64_t *h_dst_off,
                                const uint64_t *h_dst_cap);
 
+/* ---- Many files per call, parsed: the parses above, segmented -----------------------------------------------------------
+ * File f's bytes are at base + h_*_off[f], h_*_n[f] of them (any alignment); its blocks take slots h_first[f] ..
+ * h_first[f] + h_max_blocks[f] - 1 of the call's per-slot arrays and of the batch's error words, and its record goes to
+ * d_info + f * SHAFA_UNPACK_INFO_WORDS.  Every slot's outputs and error word, and every file's record, equal what the
+ * single-file entry writes for that file alone with max_blocks = h_max_blocks[f] (header rules, first framing failure, the
+ * .shaf failure over a table error, zeroed slots after it), except that payload offsets are relative to the call's base:
+ * d_shaf, or the .rle base that h_rle_off[f] is measured from.  So shafa_hipd_unpack_payloads gathers every file's payloads
+ * in one call (d_file = that base, file_n = the end of the last file).  A fault in one file changes nothing in another's
+ * slots or record.  unpack_shaf_files reads file f's block count at d_count[f * SHAFA_UNPACK_INFO_WORDS]: pass
+ * d_info + SHAFA_UNPACK_INFO_INDEXED of unpack_cod_files.  Enqueue only, with the same exception as the entries above.
+ * Argument errors return SHAFA_OUTSIDE_MODULE with nothing enqueued (checked before HIP is touched): a NULL batch or array,
+ * nfiles < 1, h_max_blocks[f] < 1, a slot range outside [0, the batch's max_blocks), two files' slot ranges that overlap,
+ * a NULL base with a length > 0.  More than 2^31 - 1 slots or 4 KiB text chunks: SHAFA_LACK_OF_MEMORY. */
+int shafa_hipd_unpack_cod_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_max_blocks,
+                                const uint8_t *d_text, const uint64_t *h_text_off, const uint64_t *h_text_n,
+                                uint64_t *d_info, uint64_t *d_sizes, shafa_code_table *d_tables);
+int shafa_hipd_unpack_rle_freq_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first,
+                                     const int *h_max_blocks, const uint8_t *d_text, const uint64_t *h_text_off,
+                                     const uint64_t *h_text_n, const uint64_t *h_rle_off, const uint64_t *h_rle_n,
+                                     uint64_t *d_info, uint64_t *d_off, uint64_t *d_n);
+int shafa_hipd_unpack_shaf_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_max_blocks,
+                                 const uint8_t *d_shaf, const uint64_t *h_shaf_off, const uint64_t *h_shaf_n,
+                                 const uint64_t *d_count, uint64_t *d_off, uint64_t *d_n);
+
 /* Synchronise `stream`, return the first per-block error of the calls enqueued since the last
  * finish (SHAFA_SUCCESS if none).  h_block_err (nblocks ints, may be NULL) receives every block's code. */
 int shafa_hipd_finish(shafa_hipd_batch *b, void *stream, int nblocks, int *h_block_err);

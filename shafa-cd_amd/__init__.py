@@ -134,6 +134,9 @@ def lib():
     L.shafa_hipd_unpack_rle_freq.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_shaf.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_payloads.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, u8p, u64p, u64p]
+    L.shafa_hipd_unpack_cod_files.argtypes = [vp, vp, C.c_int, i32p, i32p, u8p, u64p, u64p, vp, vp, vp]
+    L.shafa_hipd_unpack_rle_freq_files.argtypes = [vp, vp, C.c_int, i32p, i32p, u8p, u64p, u64p, u64p, u64p, vp, vp, vp]
+    L.shafa_hipd_unpack_shaf_files.argtypes = [vp, vp, C.c_int, i32p, i32p, u8p, u64p, u64p, vp, vp, vp]
     L.shafa_hipd_gen_bytes.argtypes = [vp, C.c_uint64, C.c_uint64, u8p, u8p, C.c_size_t]
     L.shafa_pipe_create.argtypes = [C.c_int, C.POINTER(vp)]
     L.shafa_pipe_destroy.argtypes = [vp]
@@ -162,7 +165,8 @@ def lib():
                  "shafa_hipd_sf_encode_tiles", "shafa_hipd_sf_encode_dev", "shafa_hipd_sf_decode_dev",
                  "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq",
                  "shafa_hipd_pack_payloads_files", "shafa_hipd_pack_cod_files", "shafa_hipd_pack_freq_files",
-                 "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads"):
+                 "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
+                 "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -462,6 +466,41 @@ class Batch:
         _check(lib().shafa_hipd_unpack_payloads(self.h, self._st(stream), len(do), _ptr(d_file), d_file.numel(),
                                                 d_off.data_ptr(), d_n.data_ptr(), d_dst.data_ptr(), _p64(do), _p64(dc)),
                "hipd_unpack_payloads")
+
+    def unpack_payloads_at(self, stream, file_addr, file_n, d_off, d_n, d_dst, dst_off, dst_cap):
+        """unpack_payloads from the file [file_addr, file_addr + file_n) given by its device address (int): the base the
+        segmented parses measure offsets from, which spans many tensors."""
+        do, dc = _u64arr(dst_off), _u64arr(dst_cap)
+        _check(lib().shafa_hipd_unpack_payloads(self.h, self._st(stream), len(do), file_addr or None, int(file_n),
+                                                d_off.data_ptr(), d_n.data_ptr(), d_dst.data_ptr(), _p64(do), _p64(dc)),
+               "hipd_unpack_payloads")
+
+    # ---- many files per call, parsed (include/shafa_hip.h: "Many files per call, parsed"); enqueue only ----
+    # file f: n[f] bytes at base + off[f] (base: a device address, int); its blocks take slots first[f] .. first[f] +
+    # max_blocks[f] - 1 of the per-slot arrays; its record: d_info[f * UNPACK_INFO_WORDS:]
+    def unpack_cod_files(self, stream, first, max_blocks, base, off, n, d_info, d_sizes, d_tables):
+        """unpack_cod per file: header records, symbol counts and code tables per slot."""
+        fi, mb, o, nn = _i32arr(first), _i32arr(max_blocks), _u64arr(off), _u64arr(n)
+        _check(lib().shafa_hipd_unpack_cod_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(mb), base or None, _p64(o),
+                                                 _p64(nn), d_info.data_ptr(), d_sizes.data_ptr(), d_tables.data_ptr()),
+               "hipd_unpack_cod_files")
+
+    def unpack_rle_freq_files(self, stream, first, max_blocks, base, off, n, rle_off, rle_n, d_info, d_off, d_n):
+        """unpack_rle_freq per file: file f's .rle is rle_n[f] bytes at rle_off[f] from the call's .rle base, which d_off
+        is measured from."""
+        fi, mb, o, nn, ro, rn = _i32arr(first), _i32arr(max_blocks), _u64arr(off), _u64arr(n), _u64arr(rle_off), \
+            _u64arr(rle_n)
+        _check(lib().shafa_hipd_unpack_rle_freq_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(mb), base or None,
+                                                      _p64(o), _p64(nn), _p64(ro), _p64(rn), d_info.data_ptr(),
+                                                      d_off.data_ptr(), d_n.data_ptr()), "hipd_unpack_rle_freq_files")
+
+    def unpack_shaf_files(self, stream, first, max_blocks, base, off, n, d_count, d_off, d_n):
+        """unpack_shaf per file, its block count at d_count[f * UNPACK_INFO_WORDS] (d_info[INFO_INDEXED:] of
+        unpack_cod_files); d_off is measured from base."""
+        fi, mb, o, nn = _i32arr(first), _i32arr(max_blocks), _u64arr(off), _u64arr(n)
+        _check(lib().shafa_hipd_unpack_shaf_files(self.h, self._st(stream), len(fi), _p32(fi), _p32(mb), base or None,
+                                                  _p64(o), _p64(nn), d_count.data_ptr(), d_off.data_ptr(), d_n.data_ptr()),
+               "hipd_unpack_shaf_files")
 
     def finish(self, stream, nblocks, raise_on_error=True):
         errs = (C.c_int * max(nblocks, 1))()
@@ -1022,6 +1061,21 @@ def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, max_bytes):
     return outs, ((b, e) if e else None)
 
 
+def _decode_args(shaf, cod, rle, freq, what):
+    """decompress_files' argument checks -> (sf, [payload file, text file])"""
+    import torch
+    sf = shaf is not None or cod is not None
+    if sf and (shaf is None or cod is None or rle is not None or freq is not None):
+        raise ValueError(f"{what}: shaf and cod go together, without rle / freq")
+    if not sf and (rle is None or freq is None):
+        raise ValueError(f"{what}: give shaf and cod, or rle and freq")
+    files = [t.reshape(-1) for t in ((shaf, cod) if sf else (rle, freq))]
+    for t in files:
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what}: files are contiguous uint8 CUDA tensors")
+    return sf, files
+
+
 def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
     """The file the CLI's Module D writes, decoded from files held in device memory (contiguous uint8 CUDA tensors, any
     alignment — e.g. compress_files' values):
@@ -1038,15 +1092,7 @@ def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, 
     decoding (every code of a table the decoder accepts has >= 1 bit, so the host's decoder runs out of input).  A block whose
     codes take the decoder's single slot for 33..64-bit codes from another is decoded again on its own."""
     import torch
-    sf = shaf is not None or cod is not None
-    if sf and (shaf is None or cod is None or rle is not None or freq is not None):
-        raise ValueError("decompress_files: shaf and cod go together, without rle / freq")
-    if not sf and (rle is None or freq is None):
-        raise ValueError("decompress_files: give shaf and cod, or rle and freq")
-    files = [t.reshape(-1) for t in ((shaf, cod) if sf else (rle, freq))]
-    for t in files:
-        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("decompress_files: files are contiguous uint8 CUDA tensors")
+    sf, files = _decode_args(shaf, cod, rle, freq, "decompress_files")
     dev = files[0].device
     st = stream if stream is not None else torch.cuda.Stream(device=dev)
     if max_bytes is None:
@@ -1136,3 +1182,298 @@ def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, 
         return outs[0] if len(outs) == 1 else torch.cat(outs)
     finally:
         bt.close()
+
+
+MANY_GROUP_SLOTS = 1 << 18      # decompress_many: parse slots per device batch (error words, workspace and tables grow with them)
+RLE_GRID_TILES = 1 << 22        # decompress_many: rle_decode_dev workgroups per call (x 256 lanes: below 2^32)
+
+
+def _many_entry(e):
+    """an entry of decompress_many -> (sf, [payload file, text file], decode_rle), with decompress_files' checks"""
+    import torch
+    if not isinstance(e, dict) or not set(e) <= {"shaf", "cod", "rle", "freq", "decode_rle"}:
+        raise ValueError("decompress_many: an entry is a dict of shaf + cod or rle + freq, and decode_rle")
+    if any(e.get(k) is not None and not isinstance(e[k], torch.Tensor) for k in ("shaf", "cod", "rle", "freq")):
+        raise ValueError("decompress_many: files are contiguous uint8 CUDA tensors")
+    sf, files = _decode_args(e.get("shaf"), e.get("cod"), e.get("rle"), e.get("freq"), "decompress_many")
+    return sf, files, bool(e.get("decode_rle", True))
+
+
+def decompress_many(entries, stream=None, max_bytes=None):
+    """decompress_files for many file sets in one device batch.  entries[i] is a dict of decompress_files' file arguments:
+    shaf + cod or rle + freq (contiguous uint8 CUDA tensors of any alignment on one device, e.g. compress_many's values) and
+    an optional decode_rle.  Element i of the result equals decompress_files(**entries[i]) byte for byte, or is the ShafaError
+    instance (not raised) that call would raise, with the same code; other files are unaffected.  Malformed entries, or no
+    entries, raise ValueError before any device work.
+
+    Chain per group of files (at most MANY_GROUP_SLOTS parse slots; its length does not depend on the file count): slots per
+    file by unpack_max_blocks -> one base per kind of file (the lowest address, offsets are pointer differences, no file is
+    copied) -> unpack_cod_files + unpack_shaf_files, unpack_rle_freq_files -> synchronisation 1 (every record and size) ->
+    the framed blocks of all files gathered onto consecutive indices (index_select) -> one unpack_payloads -> one sf_decode_dev
+    over the blocks of every .shaf file -> pack_payloads_files(RAW) for files without RLE decoding -> synchronisation 2 ->
+    each block that lost sf_decode_dev's single 33..64-bit slot decoded again alone (one synchronisation each, one more to pack
+    its file again) -> rle_decode_dev in groups bounded by max_bytes (default: a quarter of the free device memory), one
+    synchronisation each, each followed by pack_payloads_files(RAW) into exact per-file regions -> one last synchronisation.
+    Synchronisations per group: 2 without RLE decoding; with it, 3 + the RLE groups with .shaf files and 2 + the RLE groups
+    for .rle + .freq only (4 and 3 in one RLE group).  Decoded blocks are taken MANY_GROUP_BLOCKS at a time (sf_decode_dev puts
+    blocks on the grid's y): a group with more repeats the chain after synchronisation 1.  Per file the error is decompress_files':
+    a bad header, the mode rule, a parse fault on block 0, SF errors before the first parse fault, RLE errors there, then the
+    parse fault."""
+    import torch
+    if not isinstance(entries, (list, tuple)) or not entries:
+        raise ValueError("decompress_many: no entries")
+    parsed = [_many_entry(e) for e in entries]
+    dev = parsed[0][1][0].device
+    if any(t.device != dev for _, fs, _ in parsed for t in fs):
+        raise ValueError("decompress_many: files on more than one device")
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    if max_bytes is None:
+        max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+    results = [None] * len(parsed)
+    slots = {}
+    for i, (sf, fs, _) in enumerate(parsed):
+        mb = unpack_max_blocks(fs[1].numel(), "cod" if sf else "freq")
+        if mb > 0x7FFFFFFF:
+            results[i] = ShafaError(LACK_OF_MEMORY, "decompress_many: text too long")
+        else:
+            slots[i] = mb
+    group, acc = [], 0
+    for i in slots:
+        if group and acc + slots[i] > MANY_GROUP_SLOTS:
+            _decompress_group(parsed, group, slots, dev, st, max_bytes, results)
+            group, acc = [], 0
+        group.append(i)
+        acc += slots[i]
+    if group:
+        _decompress_group(parsed, group, slots, dev, st, max_bytes, results)
+    return results
+
+
+def _base(ts):
+    """the lowest address of the non-empty tensors (0: none) and each tensor's offset from it"""
+    ps = [t.data_ptr() for t in ts if t.numel()]
+    b = min(ps) if ps else 0
+    return b, [t.data_ptr() - b if t.numel() else 0 for t in ts]
+
+
+class _Many:
+    """one file of a decompress_many group after the parse: its slots, its blocks to decode and its parse fault"""
+
+    def __init__(self, i, sf, rle_after, slot0, fb, perr):
+        self.i, self.sf, self.rle_after, self.slot0, self.fb, self.perr = i, sf, rle_after, slot0, fb, perr
+
+
+def _decompress_group(parsed, files, slots, dev, st, max_bytes, results):
+    import torch
+    tsz = C.sizeof(CodeTable)
+    sfs = [i for i in files if parsed[i][0]]
+    rfs = [i for i in files if not parsed[i][0]]
+    order = sfs + rfs                                                   # .shaf files' slots first: the tables cover theirs
+    first, pos = {}, 0
+    for i in order:
+        first[i] = pos
+        pos += slots[i]
+    ns, nsf = pos, sum(slots[i] for i in sfs)
+    pbase, poffs = _base([parsed[i][1][0] for i in order])              # .shaf and .rle files: one base
+    pend = max([o + parsed[i][1][0].numel() for o, i in zip(poffs, order)])
+    with torch.cuda.stream(st):
+        # one host read after the parse: the records, the payload sizes and the symbol counts
+        meta = torch.zeros(UNPACK_INFO_WORDS * len(order) + ns + nsf, dtype=torch.int64, device=dev)
+        info_d = meta[:UNPACK_INFO_WORDS * len(order)]
+        d_n = meta[UNPACK_INFO_WORDS * len(order):UNPACK_INFO_WORDS * len(order) + ns]
+        d_nsym = meta[UNPACK_INFO_WORDS * len(order) + ns:]
+        d_off = torch.zeros(ns, dtype=torch.int64, device=dev)
+        d_tab = torch.empty(max(nsf, 1) * tsz, dtype=torch.uint8, device=dev)
+        bt = Batch(ns, 1 << 20)
+        try:
+            if sfs:
+                tb, toffs = _base([parsed[i][1][1] for i in sfs])
+                fi, mb = [first[i] for i in sfs], [slots[i] for i in sfs]
+                bt.unpack_cod_files(st, fi, mb, tb, toffs, [parsed[i][1][1].numel() for i in sfs], info_d, d_nsym, d_tab)
+                bt.unpack_shaf_files(st, fi, mb, pbase, poffs[:len(sfs)], [parsed[i][1][0].numel() for i in sfs],
+                                     info_d[INFO_INDEXED:], d_off, d_n)
+            if rfs:
+                tb, toffs = _base([parsed[i][1][1] for i in rfs])
+                bt.unpack_rle_freq_files(st, [first[i] for i in rfs], [slots[i] for i in rfs], tb, toffs,
+                                         [parsed[i][1][1].numel() for i in rfs], poffs[len(sfs):],
+                                         [parsed[i][1][0].numel() for i in rfs], info_d[UNPACK_INFO_WORDS * len(sfs):],
+                                         d_off, d_n)
+            _, errs = bt.finish(st, ns, raise_on_error=False)           # synchronisation 1
+            m = _u64_host(meta)
+            n_h = m[UNPACK_INFO_WORDS * len(order):UNPACK_INFO_WORDS * len(order) + ns]
+            nsym_h = m[UNPACK_INFO_WORDS * len(order) + ns:]
+            todo = []
+            for k, i in enumerate(order):                                # decompress_files' rules, file by file
+                sf, _, decode_rle = parsed[i]
+                info = m[UNPACK_INFO_WORDS * k:UNPACK_INFO_WORDS * (k + 1)]
+                if info[INFO_STATUS]:
+                    results[i] = ShafaError(FILE_STREAM_FAILED, "decompress_many: bad header")
+                    continue
+                mode = chr(info[INFO_MODE])
+                if not (mode == "R" or (sf and mode == "N" and not decode_rle)):
+                    results[i] = ShafaError(FILE_UNRECOGNIZABLE, f"decompress_many: mode {mode!r}")
+                    continue
+                s0, nidx = first[i], info[INFO_INDEXED]
+                e = errs[s0:s0 + nidx]
+                if sf:
+                    e = [x if x or nsym_h[s0 + b] <= 8 * n_h[s0 + b] else FILE_UNRECOGNIZABLE for b, x in enumerate(e)]
+                fb, perr = _first_error(e)
+                if not perr and info[INFO_COUNT] > nidx:
+                    perr = FILE_STREAM_FAILED
+                if fb == 0:
+                    results[i] = ShafaError(perr, "decompress_many: block 0") if perr else \
+                        torch.empty(0, dtype=torch.uint8, device=dev)
+                    continue
+                todo.append(_Many(i, sf, mode == "R" and decode_rle if sf else True, s0, fb, perr))
+            part, acc = [], 0
+            for f in todo:
+                if part and acc + f.fb > MANY_GROUP_BLOCKS:
+                    _decode_many(bt, st, dev, part, pbase, pend, d_off, d_n, d_nsym, d_tab, n_h, nsym_h, max_bytes, results)
+                    part, acc = [], 0
+                part.append(f)
+                acc += f.fb
+            if part:
+                _decode_many(bt, st, dev, part, pbase, pend, d_off, d_n, d_nsym, d_tab, n_h, nsym_h, max_bytes, results)
+        finally:
+            bt.close()
+
+
+def _pack_files(bt, st, dev, fs, c0, cnt, d_src, src_off, src_cap, d_src_n, totals):
+    """pack_payloads_files(RAW) of files fs (their blocks: c0[f] .. + cnt[f] - 1 of d_src) into exact regions -> views"""
+    import torch
+    doff, dtot = _layout(totals)
+    buf = torch.empty(dtot + 16, dtype=torch.uint8, device=dev)
+    d_len = torch.zeros(len(fs), dtype=torch.int64, device=dev)
+    bt.pack_payloads_files(st, c0, cnt, FRAME_RAW, d_src, src_off, src_cap, d_src_n, buf, doff, totals, d_len)
+    return [buf[o:o + n] for o, n in zip(doff, totals)]
+
+
+def _decode_many(bt, st, dev, part, pbase, pend, d_off, d_n, d_nsym, d_tab, n_h, nsym_h, max_bytes, results):
+    import torch
+    tsz = C.sizeof(CodeTable)
+    sfp = [f for f in part if f.sf]
+    ordered = sfp + [f for f in part if not f.sf]
+    idx = []
+    for f in ordered:                                                   # block c of the part: slot idx[c]
+        f.c0 = len(idx)
+        idx.extend(range(f.slot0, f.slot0 + f.fb))
+    nb, nsfb = len(idx), sum(f.fb for f in sfp)
+    d_idx = torch.tensor(idx, dtype=torch.int64, device=dev)
+    d_pn = d_n.index_select(0, d_idx)
+    pn = [n_h[s] for s in idx]
+    poff, ptot = _layout(pn)
+    d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=dev)
+    bt.unpack_payloads_at(st, pbase, pend, d_off.index_select(0, d_idx), d_pn, d_pay, poff, pn)
+    rle_in = []                                                         # (file, buffer, offsets, sizes, device sizes)
+    if nsfb:
+        sidx = d_idx[:nsfb]
+        d_ns = d_nsym.index_select(0, sidx)
+        d_tb = d_tab.view(-1, tsz).index_select(0, sidx).reshape(-1)
+        nsym = [nsym_h[s] for s in idx[:nsfb]]
+        ooff, otot = _layout(nsym)
+        d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+        bt.sf_decode_dev(st, d_pay, poff[:nsfb], pn[:nsfb], d_pn[:nsfb], d_tb, d_ns, d_sfo, ooff, nsym)
+        plain = [f for f in sfp if not f.rle_after and not f.perr]
+        ptotal = [sum(nsym[f.c0:f.c0 + f.fb]) for f in plain]
+        views = _pack_files(bt, st, dev, plain, [f.c0 for f in plain], [f.fb for f in plain], d_sfo, ooff, nsym, d_ns,
+                            ptotal) if plain else []
+        _, errs = bt.finish(st, nsfb, raise_on_error=False)             # synchronisation 2
+        errs = errs[:nsfb]
+        again = set()
+        for f in sfp:                                                   # the one slot for 33..64-bit codes was taken
+            b, e = _first_error(errs[f.c0:f.c0 + f.fb])
+            while e == LACK_OF_MEMORY and f.c0 + b not in again:
+                g = f.c0 + b
+                bt.sf_decode_dev(st, d_pay, poff[g:g + 1], pn[g:g + 1], d_pn[g:g + 1], d_tb[g * tsz:(g + 1) * tsz],
+                                 d_ns[g:g + 1], d_sfo, ooff[g:g + 1], nsym[g:g + 1])
+                _, one = bt.finish(st, 1, raise_on_error=False)
+                errs[g] = one[0]
+                again.add(g)
+                b, e = _first_error(errs[f.c0:f.c0 + f.fb])
+            f.err = (b, e) if e else None
+        redo = [k for k, f in enumerate(plain) if not f.err and any(g in again for g in range(f.c0, f.c0 + f.fb))]
+        if redo:
+            fs = [plain[k] for k in redo]
+            for k, v in zip(redo, _pack_files(bt, st, dev, fs, [f.c0 for f in fs], [f.fb for f in fs], d_sfo, ooff, nsym,
+                                              d_ns, [ptotal[k] for k in redo])):
+                views[k] = v
+            bt.finish(st, nsfb, raise_on_error=False)
+        for f in sfp:
+            if f.err:
+                results[f.i] = ShafaError(f.err[1], f"decompress_many: block {f.err[0]}")
+            elif f.perr and not f.rle_after:
+                results[f.i] = ShafaError(f.perr, f"decompress_many: block {f.fb}")
+            elif f.rle_after:
+                rle_in.append((f, d_sfo, ooff[f.c0:f.c0 + f.fb], nsym[f.c0:f.c0 + f.fb], d_ns[f.c0:f.c0 + f.fb]))
+        for f, v in zip(plain, views):
+            if not f.err:
+                results[f.i] = v
+    for f in ordered[len(sfp):]:
+        rle_in.append((f, d_pay, poff[f.c0:f.c0 + f.fb], pn[f.c0:f.c0 + f.fb], d_pn[f.c0:f.c0 + f.fb]))
+    if rle_in:
+        _rle_decode_many(bt, st, dev, rle_in, max_bytes, results)
+
+
+def _rle_decode_many(bt, st, dev, rle_in, max_bytes, results):
+    """rle_decode_dev over the blocks of these files in groups whose output capacities fit max_bytes (decompress_files'
+    rule), one synchronisation each, each followed by pack_payloads_files(RAW) of the group's part of every file; one last
+    synchronisation.  A file whose blocks span groups is joined at the end."""
+    import torch
+    bufs = {id(b): b for _, b, _, _, _ in rle_in}
+    lo = min(bufs.values(), key=lambda t: t.data_ptr())                 # inputs addressed from one base
+    in_off, in_n, owner = [], [], []
+    for k, (f, buf, off, n, _) in enumerate(rle_in):
+        a = buf.data_ptr() - lo.data_ptr()
+        in_off += [a + o for o in off]
+        in_n += n
+        owner += [k] * len(n)
+    d_in_n = torch.cat([d for _, _, _, _, d in rle_in])
+    nb = len(in_n)
+    caps = [min(RLE_DECODE_MAX, 85 * n + 2) for n in in_n]
+    # rle_decode_dev's grid is (its largest input's 8 KiB tiles) x (its blocks) workgroups of 256 lanes: a group also keeps
+    # that product within RLE_GRID_TILES, so the grid's lanes stay below 2^32 however many small blocks join a large one
+    tiles = [max(1, -(-n // 8192)) for n in in_n]
+    groups, g0, acc, mt = [], 0, 0, 0
+    for b in range(nb):
+        if b > g0 and (acc + _al16(caps[b]) > max_bytes or max(mt, tiles[b]) * (b - g0 + 1) > RLE_GRID_TILES):
+            groups.append((g0, b))
+            g0, acc, mt = b, 0, 0
+        acc += _al16(caps[b])
+        mt = max(mt, tiles[b])
+    groups.append((g0, nb))
+    biggest = max(_layout(caps[a:z])[1] for a, z in groups)
+    d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
+    d_out_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+    parts = [[] for _ in rle_in]
+    err = [None] * len(rle_in)
+    for a, z in groups:
+        off, _ = _layout(caps[a:z])
+        bt.rle_decode_dev(st, lo, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, caps[a:z], d_out_n[a:z])
+        _, errs = bt.finish(st, z - a, raise_on_error=False)
+        sz = _u64_host(d_out_n[a:z])
+        ks, c0, cnt, tot = [], [], [], []
+        for b in range(a, z):
+            k = owner[b]
+            if err[k] is None and errs[b - a]:
+                err[k] = (b - a, errs[b - a])
+            if not ks or ks[-1] != k:
+                ks.append(k)
+                c0.append(b - a)
+                cnt.append(0)
+                tot.append(0)
+            cnt[-1] += 1
+            tot[-1] += sz[b - a]
+        keep = [j for j, k in enumerate(ks) if err[k] is None]
+        if keep:
+            views = _pack_files(bt, st, dev, keep, [c0[j] for j in keep], [cnt[j] for j in keep], d_out, off, caps[a:z],
+                                d_out_n[a:z], [tot[j] for j in keep])
+            for j, v in zip(keep, views):
+                parts[ks[j]].append(v)
+    bt.finish(st, nb, raise_on_error=False)
+    for k, (f, _, _, _, _) in enumerate(rle_in):
+        if err[k]:
+            results[f.i] = ShafaError(err[k][1], "decompress_many: RLE decoding")
+        elif f.perr:
+            results[f.i] = ShafaError(f.perr, f"decompress_many: block {f.fb}")
+        else:
+            results[f.i] = parts[k][0] if len(parts[k]) == 1 else torch.cat(parts[k])

@@ -17,11 +17,21 @@
 //   unpack_shaf_walk      ONE wave: the dependent chain of the .shaf headers, one 32-byte window per block
 //   unpack_move_plan      a lane per block: the capacity and file checks, two descriptor records for pack.hip's movers
 // The payloads themselves are moved by pack.hip's pack_bulk / pack_seams (pack_move_launch): no second mover.
+// Segmented parses (shafa_hipd_unpack_*_files: many files in one launch sequence) add
+//   unpack_at_count_files  a workgroup per (file, chunk) pair of a host-built list: at_count on that chunk
+//   unpack_at_place_files  a workgroup per pair: at_place with the file's ranks (the unchanged unpack_at_scan runs over the
+//                          whole list in between: a file's ranks are differences of its chunks' bases)
+//   unpack_frames_files    a workgroup per file: unpack_frames' body (frames) on its text
+//   unpack_shaf_walk_files a wave per file: unpack_shaf_walk's body (shaf_walk) on its .shaf
+// and run unpack_tables as it is, once per run of consecutive slots.
 //
 // Reads: every load of a file is a byte load of a byte inside [file, file + n), except pack_bulk's 16-byte words, each of
-// which holds a byte of the payload it moves.  Writes: only the caller's arrays of max_blocks (nblocks) entries and d_info.
+// which holds a byte of the payload it moves.  Writes: only the caller's arrays of max_blocks (nblocks) entries and d_info
+// (segmented: the files' slots and their records).
 #include "common.hpp"
 #include "internal.hpp"
+
+#include <algorithm>
 
 namespace {
 
@@ -48,17 +58,23 @@ struct IdxWs {
 
 __device__ inline bool is_digit(u8 c) { return c >= '0' && c <= '9'; }
 
-__global__ __launch_bounds__(IDX_THREADS) void unpack_at_count(const u8 *__restrict__ t, u64 n, u32 *__restrict__ cnt)
+// chunk c of the text: its '@' count to *out
+__device__ __forceinline__ void at_count(const u8 *__restrict__ t, u64 n, u64 c, u32 *__restrict__ out)
 {
     __shared__ u32 wsum[IDX_THREADS / 64];
-    const u64 p0 = (u64)blockIdx.x * IDX_CHUNK + (u64)threadIdx.x * IDX_BYTES;
+    const u64 p0 = c * IDX_CHUNK + (u64)threadIdx.x * IDX_BYTES;
     u32 k = 0;
     for (u32 i = 0; i < IDX_BYTES; ++i)
         if (p0 + i < n && t[p0 + i] == '@') ++k;
     const u32 incl = dpp_scan_add(k);
     if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
     __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (threadIdx.x == 0) *out = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ __launch_bounds__(IDX_THREADS) void unpack_at_count(const u8 *__restrict__ t, u64 n, u32 *__restrict__ cnt)
+{
+    at_count(t, n, blockIdx.x, cnt + blockIdx.x);
 }
 
 // one workgroup: base[c] = sum of cnt[0 .. c), *total = the text's '@' count
@@ -86,14 +102,12 @@ __global__ __launch_bounds__(IDX_THREADS) void unpack_at_scan(const u32 *__restr
     if (tid == 0) *total = run;
 }
 
-// the positions of the '@' of rank < limit, in text order
-__global__ __launch_bounds__(IDX_THREADS) void unpack_at_place(const u8 *__restrict__ t, u64 n, const u64 *__restrict__ base,
-                                                               u64 limit, u64 *__restrict__ pos)
+// chunk c of the text, whose first '@' has rank b0: the positions of the '@' of rank < limit, in text order
+__device__ __forceinline__ void at_place(const u8 *__restrict__ t, u64 n, u64 c, u64 b0, u64 limit, u64 *__restrict__ pos)
 {
     __shared__ u32 wsum[IDX_THREADS / 64];
-    const u64 b0 = base[blockIdx.x];
     if (b0 >= limit) return;                                     // uniform per workgroup
-    const u64 p0 = (u64)blockIdx.x * IDX_CHUNK + (u64)threadIdx.x * IDX_BYTES;
+    const u64 p0 = c * IDX_CHUNK + (u64)threadIdx.x * IDX_BYTES;
     u32 k = 0;
     for (u32 i = 0; i < IDX_BYTES; ++i)
         if (p0 + i < n && t[p0 + i] == '@') ++k;
@@ -106,6 +120,12 @@ __global__ __launch_bounds__(IDX_THREADS) void unpack_at_place(const u8 *__restr
     u64 r = b0 + before + incl - k;
     for (u32 i = 0; i < IDX_BYTES && r < limit; ++i)
         if (p0 + i < n && t[p0 + i] == '@') pos[r++] = p0 + i;
+}
+
+__global__ __launch_bounds__(IDX_THREADS) void unpack_at_place(const u8 *__restrict__ t, u64 n, const u64 *__restrict__ base,
+                                                               u64 limit, u64 *__restrict__ pos)
+{
+    at_place(t, n, blockIdx.x, base[blockIdx.x], limit, pos);
 }
 
 // saturating sum: associative, so it scans like an ordinary one (.rle offsets from sizes the text may make arbitrary)
@@ -152,7 +172,9 @@ __device__ bool read_header(const u8 *t, u64 n, u8 *mode, u64 *count, u64 *end)
     return x <= (n - p) / 3;                                                     // every block needs "@<digit>@"
 }
 
-__global__ __launch_bounds__(FRAME_THREADS) void unpack_frames(FrameArgs a)
+// the header and every block's frame of one text, by one workgroup.  Spans and .rle offsets of framed blocks are written
+// span_base / off_base bytes further on (the segmented form: from the call's base pointers, not from the file's start).
+__device__ __forceinline__ void frames(const FrameArgs &a, u64 span_base, u64 off_base)
 {
     __shared__ u32 hdr_ok;
     __shared__ u8 mode_sh;
@@ -213,8 +235,8 @@ __global__ __launch_bounds__(FRAME_THREADS) void unpack_frames(FrameArgs a)
         const bool valid = (u64)b < nidx && b < first_bad;
         if (b < a.max_blocks) {
             a.sizes[b] = valid ? size : 0;
-            if (a.spans) a.spans[b] = valid ? TextSpan{ts, tn} : TextSpan{0, 0};
-            if (a.off) a.off[b] = valid ? incl - size : 0;
+            if (a.spans) a.spans[b] = valid ? TextSpan{ts + span_base, tn} : TextSpan{0, 0};
+            if (a.off) a.off[b] = valid ? incl - size + off_base : 0;
             if ((u64)b < nidx && b == first_bad) set_error(a.err + b, SHAFA_FILE_STREAM_FAILED);
             if (valid) atomicMax((unsigned long long *)&maxsz_sh, (unsigned long long)size);
         }
@@ -230,6 +252,11 @@ __global__ __launch_bounds__(FRAME_THREADS) void unpack_frames(FrameArgs a)
         a.info[SHAFA_UNPACK_INFO_FRAMED] = framed;
         a.info[SHAFA_UNPACK_INFO_MAX_SIZE] = maxsz_sh;
     }
+}
+
+__global__ __launch_bounds__(FRAME_THREADS) void unpack_frames(FrameArgs a)
+{
+    frames(a, 0, 0);
 }
 
 // shafa_cod_parse (host/formats.c) on one block's text: only '0', '1' and ';' up to the text's first NUL byte, exactly 255
@@ -330,13 +357,13 @@ __device__ bool shaf_read(const u8 *f, u64 n, u64 p, bool trailing_at, u64 *v, u
     return true;
 }
 
-// "@<n>", then per block "@<size>@" + size payload bytes, for min(*count, max_blocks) blocks: a dependent chain, one wave
-__global__ __launch_bounds__(64) void unpack_shaf_walk(const u8 *__restrict__ f, u64 n, const u64 *__restrict__ count,
-                                                      int max_blocks, u64 *__restrict__ off, u64 *__restrict__ sz,
-                                                      int *__restrict__ err)
+// "@<n>", then per block "@<size>@" + size payload bytes, for min(want, max_blocks) blocks: a dependent chain, one wave.
+// Payload offsets are written off_base bytes further on (the segmented form: from the call's base pointer).
+__device__ __forceinline__ void shaf_walk(const u8 *__restrict__ f, u64 n, u64 want, int max_blocks, u64 *__restrict__ off,
+                                          u64 *__restrict__ sz, int *__restrict__ err, u64 off_base)
 {
-    const u32 lane = threadIdx.x;
-    const u64 want = *count, nb = want < (u64)max_blocks ? want : (u64)max_blocks;
+    const u32 lane = threadIdx.x & 63u;
+    const u64 nb = want < (u64)max_blocks ? want : (u64)max_blocks;
     u64 v = 0, p = 0;
     bool ok = shaf_read(f, n, 0, false, &v, &p);                  // d.c:673: read, then overruled by the .cod's count
     u64 b = 0;
@@ -351,7 +378,7 @@ __global__ __launch_bounds__(64) void unpack_shaf_walk(const u8 *__restrict__ f,
             break;
         }
         if (lane == 0) {
-            off[b] = end;
+            off[b] = end + off_base;
             sz[b] = v;
         }
         p = end + v;
@@ -360,6 +387,101 @@ __global__ __launch_bounds__(64) void unpack_shaf_walk(const u8 *__restrict__ f,
         off[i] = 0;
         sz[i] = 0;
     }
+}
+
+__global__ __launch_bounds__(64) void unpack_shaf_walk(const u8 *__restrict__ f, u64 n, const u64 *__restrict__ count,
+                                                      int max_blocks, u64 *__restrict__ off, u64 *__restrict__ sz,
+                                                      int *__restrict__ err)
+{
+    shaf_walk(f, n, *count, max_blocks, off, sz, err, 0);
+}
+
+// ---- segmented parse: many files in one launch sequence --------------------------------------------------------------
+// File f's bytes are [t, t + n) (the call's base + its offset); its blocks take slots first .. first + max_blocks - 1 of the
+// call's arrays and of the batch's error words.  A text's 4 KiB chunks are entries pair0 .. pair0 + nchunks - 1 of the call's
+// (file, chunk) list, its '@' positions entries pos0 .. pos0 + limit - 1 of the workspace.
+struct TextFile {
+    const u8 *t;
+    u64 n;
+    u64 span_base;           // t - the call's text base: unpack_tables reads the spans as offsets from that base
+    u64 rle_n;               // .freq: its .rle's length
+    u64 off_base;            // .freq: its .rle's offset from the call's .rle base
+    u64 pos0, limit;
+    u32 pair0, nchunks;
+    int first, max_blocks;
+};
+
+struct ShafFile {
+    const u8 *f;
+    u64 n;
+    u64 off_base;            // f - the call's base
+    int first, max_blocks;
+};
+
+// a workgroup per (file, chunk) pair: the chunk's '@' count
+__global__ __launch_bounds__(IDX_THREADS) void unpack_at_count_files(const TextFile *__restrict__ files,
+                                                                     const u32 *__restrict__ pair_file, u32 *__restrict__ cnt)
+{
+    const u32 p = blockIdx.x;
+    const TextFile &tf = files[pair_file[p]];
+    at_count(tf.t, tf.n, p - tf.pair0, cnt + p);
+}
+
+// a workgroup per pair.  base: the exclusive scan of every pair's count (unpack_at_scan over the whole list, base[npairs] =
+// the sum), so a file's ranks are differences from its first chunk's base.  The file's first chunk also writes its total.
+__global__ __launch_bounds__(IDX_THREADS) void unpack_at_place_files(const TextFile *__restrict__ files,
+                                                                     const u32 *__restrict__ pair_file,
+                                                                     const u64 *__restrict__ base, u64 *__restrict__ total,
+                                                                     u64 *__restrict__ pos)
+{
+    const u32 p = blockIdx.x, f = pair_file[p];
+    const TextFile &tf = files[f];
+    const u64 b_file = base[tf.pair0];
+    if (p == tf.pair0 && threadIdx.x == 0) total[f] = base[tf.pair0 + tf.nchunks] - b_file;
+    at_place(tf.t, tf.n, p - tf.pair0, base[p] - b_file, tf.limit, pos + tf.pos0);
+}
+
+struct FramesFilesArgs {
+    const TextFile *files;
+    const u64 *total;        // per file: its '@' count
+    const u64 *pos;
+    u32 field_max;
+    u64 *info;               // SHAFA_UNPACK_INFO_WORDS per file
+    u64 *sizes;              // per slot
+    TextSpan *spans;         // per slot: .cod; nullptr for .freq
+    u64 *off;                // per slot: .freq; nullptr for .cod
+    int *err;                // per slot
+};
+
+// a workgroup per file: unpack_frames on its text
+__global__ __launch_bounds__(FRAME_THREADS) void unpack_frames_files(FramesFilesArgs g)
+{
+    const u32 f = blockIdx.x;
+    const TextFile tf = g.files[f];
+    FrameArgs a = {};
+    a.t = tf.t;
+    a.n = tf.n;
+    a.total = g.total + f;
+    a.pos = g.pos + tf.pos0;
+    a.limit = tf.limit;
+    a.max_blocks = tf.max_blocks;
+    a.field_max = g.field_max;
+    a.info = g.info + (u64)f * SHAFA_UNPACK_INFO_WORDS;
+    a.sizes = g.sizes + tf.first;
+    a.spans = g.spans ? g.spans + tf.first : nullptr;
+    a.off = g.off ? g.off + tf.first : nullptr;
+    a.rle_n = tf.rle_n;
+    a.err = g.err + tf.first;
+    frames(a, tf.span_base, tf.off_base);
+}
+
+// a wave per file: unpack_shaf_walk on its .shaf, its block count at count[f * SHAFA_UNPACK_INFO_WORDS]
+__global__ __launch_bounds__(64) void unpack_shaf_walk_files(const ShafFile *__restrict__ files, const u64 *__restrict__ count,
+                                                            u64 *__restrict__ off, u64 *__restrict__ sz, int *__restrict__ err)
+{
+    const ShafFile sf = files[blockIdx.x];
+    shaf_walk(sf.f, sf.n, count[(u64)blockIdx.x * SHAFA_UNPACK_INFO_WORDS], sf.max_blocks, off + sf.first, sz + sf.first,
+              err + sf.first, sf.off_base);
 }
 
 struct MoveRegion {
@@ -479,6 +601,137 @@ int move_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_file, u64 fi
     return pscope.done();
 }
 
+// the files' slot ranges, (first, max_blocks) sorted by first
+std::vector<std::pair<int, int>> slot_ranges(int nfiles, const int *h_first, const int *h_max_blocks)
+{
+    std::vector<std::pair<int, int>> r((size_t)nfiles);
+    for (int f = 0; f < nfiles; ++f) r[(size_t)f] = {h_first[f], h_max_blocks[f]};
+    std::sort(r.begin(), r.end());
+    return r;
+}
+
+// argument checks shared by the three segmented entries (no HIP call)
+int files_check(const Batch *bt, int nfiles, const int *h_first, const int *h_max_blocks, const void *base, const u64 *h_off,
+                const u64 *h_n)
+{
+    if (!bt || nfiles < 1 || !h_first || !h_max_blocks || !h_off || !h_n) return SHAFA_OUTSIDE_MODULE;
+    long long slots = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        const long long first = h_first[f], mb = h_max_blocks[f];
+        if (mb < 1 || first < 0 || first + mb > bt->max_blocks) return SHAFA_OUTSIDE_MODULE;
+        if (!base && h_n[f]) return SHAFA_OUTSIDE_MODULE;
+        slots += mb;
+    }
+    const std::vector<std::pair<int, int>> r = slot_ranges(nfiles, h_first, h_max_blocks);
+    for (size_t i = 1; i < r.size(); ++i)
+        if ((long long)r[i - 1].first + r[i - 1].second > r[i].first) return SHAFA_OUTSIDE_MODULE;
+    if (slots > 0x7FFFFFFFll) return SHAFA_LACK_OF_MEMORY;
+    return SHAFA_SUCCESS;
+}
+
+// the '@' index of every text, then their frames (and, for .cod, their tables): text_unpack per file, one launch sequence
+int text_files_unpack(Batch *bt, hipStream_t st, int nfiles, const int *h_first, const int *h_max_blocks, const u8 *d_text,
+                      const u64 *h_text_off, const u64 *h_text_n, u32 field_max, u64 *d_info, u64 *d_sizes,
+                      shafa_code_table *d_tables, u64 *d_off, const u64 *h_rle_off, const u64 *h_rle_n)
+{
+    u64 npairs = 0, npos = 0;
+    int slot_end = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        npairs += h_text_n[f] ? ceil_div_u64(h_text_n[f], IDX_CHUNK) : 1;
+        npos += 2 * (u64)h_max_blocks[f] + 4;
+        if (h_first[f] + h_max_blocks[f] > slot_end) slot_end = h_first[f] + h_max_blocks[f];
+    }
+    if (npairs > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    // workspace: [pair bases: npairs + 1][file totals][pair counts][positions][spans per slot, .cod only]
+    const size_t o_total = al16((npairs + 1) * 8), o_cnt = o_total + al16((size_t)nfiles * 8),
+                 o_pos = o_cnt + al16(npairs * 4), o_spans = o_pos + al16(npos * 8),
+                 bytes = o_spans + (d_tables ? (size_t)slot_end * sizeof(TextSpan) : 0);
+    if (int rc = batch_reserve(bt, st, bytes)) return rc;
+    u8 *ws = (u8 *)bt->d_ws;
+    u64 *base = (u64 *)ws, *total = (u64 *)(ws + o_total), *pos = (u64 *)(ws + o_pos);
+    u32 *cnt = (u32 *)(ws + o_cnt);
+    TextSpan *spans = d_tables ? (TextSpan *)(ws + o_spans) : nullptr;
+    const size_t o_pairs = (size_t)nfiles * sizeof(TextFile), par_bytes = o_pairs + npairs * 4;
+    u8 *dpar = batch_params_begin(bt, par_bytes);
+    if (!dpar) return SHAFA_LACK_OF_MEMORY;
+    ParamsScope pscope(bt, st);
+    TextFile *hp = (TextFile *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
+    if (!hp) return SHAFA_LACK_OF_MEMORY;
+    u32 *hpair = (u32 *)((u8 *)hp + o_pairs);
+    u64 pair = 0, p0 = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        const u64 n = h_text_n[f], nch = n ? ceil_div_u64(n, IDX_CHUNK) : 1;
+        TextFile &t = hp[f];
+        t.t = d_text + (n ? h_text_off[f] : 0);
+        t.n = n;
+        t.span_base = n ? h_text_off[f] : 0;
+        t.rle_n = h_rle_n ? h_rle_n[f] : 0;
+        t.off_base = h_rle_off ? h_rle_off[f] : 0;
+        t.pos0 = p0;
+        t.limit = 2 * (u64)h_max_blocks[f] + 4;         // the header's 2 or 3, then two per block, and the last one
+        t.pair0 = (u32)pair;
+        t.nchunks = (u32)nch;
+        t.first = h_first[f];
+        t.max_blocks = h_max_blocks[f];
+        for (u64 c = 0; c < nch; ++c) hpair[pair++] = (u32)f;
+        p0 += t.limit;
+    }
+    if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
+    const TextFile *d_files = (const TextFile *)dpar;
+    const u32 *d_pair = (const u32 *)(dpar + o_pairs);
+    hipLaunchKernelGGL(unpack_at_count_files, dim3((u32)npairs), dim3(IDX_THREADS), 0, st, d_files, d_pair, cnt);
+    hipLaunchKernelGGL(unpack_at_scan, dim3(1), dim3(IDX_THREADS), 0, st, (const u32 *)cnt, npairs, base, base + npairs);
+    hipLaunchKernelGGL(unpack_at_place_files, dim3((u32)npairs), dim3(IDX_THREADS), 0, st, d_files, d_pair, (const u64 *)base,
+                       total, pos);
+    FramesFilesArgs g = {};
+    g.files = d_files;
+    g.total = total;
+    g.pos = pos;
+    g.field_max = field_max;
+    g.info = d_info;
+    g.sizes = d_sizes;
+    g.spans = spans;
+    g.off = d_off;
+    g.err = bt->d_err;
+    hipLaunchKernelGGL(unpack_frames_files, dim3((u32)nfiles), dim3(FRAME_THREADS), 0, st, g);
+    if (d_tables) {                                   // one launch per run of consecutive slots: none between files is written
+        const std::vector<std::pair<int, int>> r = slot_ranges(nfiles, h_first, h_max_blocks);
+        for (size_t i = 0; i < r.size();) {
+            const int s0 = r[i].first;
+            int s1 = s0 + r[i].second;
+            for (++i; i < r.size() && r[i].first == s1; ++i) s1 += r[i].second;
+            hipLaunchKernelGGL(unpack_tables, dim3((u32)(s1 - s0)), dim3(256), 0, st, d_text, (const TextSpan *)(spans + s0),
+                               d_tables + s0, bt->d_err + s0);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return pscope.done();
+}
+
+int shaf_files_unpack(Batch *bt, hipStream_t st, int nfiles, const int *h_first, const int *h_max_blocks, const u8 *d_shaf,
+                      const u64 *h_shaf_off, const u64 *h_shaf_n, const u64 *d_count, u64 *d_off, u64 *d_n)
+{
+    const size_t par_bytes = (size_t)nfiles * sizeof(ShafFile);
+    u8 *dpar = batch_params_begin(bt, par_bytes);
+    if (!dpar) return SHAFA_LACK_OF_MEMORY;
+    ParamsScope pscope(bt, st);
+    ShafFile *hp = (ShafFile *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
+    if (!hp) return SHAFA_LACK_OF_MEMORY;
+    for (int f = 0; f < nfiles; ++f) {
+        const u64 n = h_shaf_n[f], o = n ? h_shaf_off[f] : 0;
+        hp[f].f = d_shaf + o;
+        hp[f].n = n;
+        hp[f].off_base = o;
+        hp[f].first = h_first[f];
+        hp[f].max_blocks = h_max_blocks[f];
+    }
+    if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
+    hipLaunchKernelGGL(unpack_shaf_walk_files, dim3((u32)nfiles), dim3(64), 0, st, (const ShafFile *)dpar, d_count, d_off, d_n,
+                       bt->d_err);
+    HIP_TRY(hipGetLastError());
+    return pscope.done();
+}
+
 }  // namespace
 
 extern "C" {
@@ -529,6 +782,43 @@ int shafa_hipd_unpack_payloads(shafa_hipd_batch *b, void *stream, int nblocks, c
     if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
     return move_launch(bt, (hipStream_t)stream, nblocks, d_file, file_n, d_off, d_n, d_dst, h_dst_off, h_dst_cap);
+}
+
+int shafa_hipd_unpack_cod_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_max_blocks,
+                                const uint8_t *d_text, const uint64_t *h_text_off, const uint64_t *h_text_n,
+                                uint64_t *d_info, uint64_t *d_sizes, shafa_code_table *d_tables)
+{
+    if (!d_info || !d_sizes || !d_tables) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    if (int rc = files_check(bt, nfiles, h_first, h_max_blocks, d_text, h_text_off, h_text_n)) return rc;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return text_files_unpack(bt, (hipStream_t)stream, nfiles, h_first, h_max_blocks, d_text, h_text_off, h_text_n, COD_TEXT_MAX,
+                             d_info, d_sizes, d_tables, nullptr, nullptr, nullptr);
+}
+
+int shafa_hipd_unpack_rle_freq_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first,
+                                     const int *h_max_blocks, const uint8_t *d_text, const uint64_t *h_text_off,
+                                     const uint64_t *h_text_n, const uint64_t *h_rle_off, const uint64_t *h_rle_n,
+                                     uint64_t *d_info, uint64_t *d_off, uint64_t *d_n)
+{
+    if (!h_rle_off || !h_rle_n || !d_info || !d_off || !d_n) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    if (int rc = files_check(bt, nfiles, h_first, h_max_blocks, d_text, h_text_off, h_text_n)) return rc;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return text_files_unpack(bt, (hipStream_t)stream, nfiles, h_first, h_max_blocks, d_text, h_text_off, h_text_n,
+                             FREQ_TEXT_MAX, d_info, d_n, nullptr, d_off, h_rle_off, h_rle_n);
+}
+
+int shafa_hipd_unpack_shaf_files(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_max_blocks,
+                                 const uint8_t *d_shaf, const uint64_t *h_shaf_off, const uint64_t *h_shaf_n,
+                                 const uint64_t *d_count, uint64_t *d_off, uint64_t *d_n)
+{
+    if (!d_count || !d_off || !d_n) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    if (int rc = files_check(bt, nfiles, h_first, h_max_blocks, d_shaf, h_shaf_off, h_shaf_n)) return rc;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return shaf_files_unpack(bt, (hipStream_t)stream, nfiles, h_first, h_max_blocks, d_shaf, h_shaf_off, h_shaf_n, d_count,
+                             d_off, d_n);
 }
 
 }  // extern "C"
