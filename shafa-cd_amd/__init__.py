@@ -115,6 +115,7 @@ def lib():
     L.shafa_hipd_sf_encode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, u8p, u64p, u8p, u64p, u64p, vp]
     L.shafa_hipd_sf_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp, u8p, u64p, u64p]
     L.shafa_hipd_rle_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
+    L.shafa_hipd_rle_decoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -166,7 +167,8 @@ def lib():
                  "shafa_hipd_rle_decode_dev", "shafa_hipd_pack_payloads", "shafa_hipd_pack_cod", "shafa_hipd_pack_freq",
                  "shafa_hipd_pack_payloads_files", "shafa_hipd_pack_cod_files", "shafa_hipd_pack_freq_files",
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
-                 "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files"):
+                 "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
+                 "shafa_hipd_rle_decoded_size_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -383,6 +385,13 @@ class Batch:
         _check(lib().shafa_hipd_rle_decode_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
                                                d_in_n.data_ptr(), d_out.data_ptr(), _p64(oo), _p64(oc),
                                                d_out_n.data_ptr()), "hipd_rle_decode_dev")
+
+    def rle_decoded_size_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_out_n):
+        """d_out_n[b] (int64) = the size rle_decode_dev would leave for block b with out_cap = RLE_DECODE_MAX; nothing is
+        decoded and no output exists.  Enqueues only (include/shafa_hip.h: shafa_hipd_rle_decoded_size_dev)."""
+        io, ic = _u64arr(in_off), _u64arr(in_cap)
+        _check(lib().shafa_hipd_rle_decoded_size_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                                     d_in_n.data_ptr(), d_out_n.data_ptr()), "hipd_rle_decoded_size_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -1025,40 +1034,58 @@ def _first_error(errs):
     return next(((i, e) for i, e in enumerate(errs) if e), (len(errs), SUCCESS))
 
 
-def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, max_bytes):
-    """rle_decode_dev of blocks [0, len(in_n)) in groups whose output capacities (min(RLE_DECODE_MAX, 85 n + 2): a 3-byte
-    triple yields at most 255 bytes) fit max_bytes; each group synchronised, read back and packed into a tensor of exactly
-    its bytes.  -> (outputs, first error: (block, code) or None)"""
+RLE_GRID_TILES = 1 << 22        # rle_decode_dev workgroups per call (x 256 lanes: below 2^32)
+
+
+def _rle_measure(bt, st, d_in, in_off, in_n, d_in_n, n_err):
+    """The size pass (rle_decoded_size_dev) over these RLE blocks and its synchronisation, which reads the sizes back
+    -> (decoded sizes, per-block codes).  n_err: the error words shafa_hipd_finish reads."""
+    import torch
+    d_size = torch.zeros(max(len(in_n), 1), dtype=torch.int64, device=d_in_n.device)
+    bt.rle_decoded_size_dev(st, d_in, in_off, in_n, d_in_n, d_size)
+    _, errs = bt.finish(st, n_err, raise_on_error=False)
+    return _u64_host(d_size)[:len(in_n)], errs[:len(in_n)]
+
+
+def _rle_groups(sizes, in_n, max_bytes):
+    """Consecutive blocks whose exact output regions (_al16(size)) fit max_bytes and whose rle_decode_dev grid — (its largest
+    input's 8 KiB tiles) x (its blocks) workgroups of 256 lanes — stays within RLE_GRID_TILES, so the grid's lanes stay below
+    2^32 however many small blocks join a large one -> [(first, end)]"""
+    groups, g0, acc, mt = [], 0, 0, 0
+    for b, (size, n) in enumerate(zip(sizes, in_n)):
+        t = max(1, -(-n // 8192))
+        if b > g0 and (acc + _al16(size) > max_bytes or max(mt, t) * (b - g0 + 1) > RLE_GRID_TILES):
+            groups.append((g0, b))
+            g0, acc, mt = b, 0, 0
+        acc += _al16(size)
+        mt = max(mt, t)
+    groups.append((g0, len(sizes)))
+    return groups
+
+
+def _rle_decode_exact(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
+    """rle_decode_dev of these blocks into regions of exactly their decoded sizes (_rle_measure's), in groups (_rle_groups)
+    that follow each other on the stream without a synchronisation, each packed into its place in one tensor of exactly the
+    decoded bytes -> that tensor.  Enqueues only: the caller's finish ends it."""
     import torch
     dev = d_in.device
-    nb = len(in_n)
-    caps = [min(RLE_DECODE_MAX, 85 * n + 2) for n in in_n]
-    groups, g0, acc = [], 0, 0
-    for b in range(nb):
-        if b > g0 and acc + _al16(caps[b]) > max_bytes:
-            groups.append((g0, b))
-            g0, acc = b, 0
-        acc += _al16(caps[b])
-    groups.append((g0, nb))
-    biggest = max(_layout(caps[a:z])[1] for a, z in groups)
+    groups = _rle_groups(sizes, in_n, max_bytes)
+    biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
     d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
-    d_out_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-    d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-    outs = []
-    for a, z in groups:
-        off, _ = _layout(caps[a:z])
-        bt.rle_decode_dev(st, d_in, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, caps[a:z], d_out_n[a:z])
-        _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-        b, e = _first_error(errs[:z - a])
-        if e:
-            return outs, (a + b, e)
-        total = sum(_u64_host(d_out_n[a:z]))
-        o = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        bt.pack_payloads(st, FRAME_RAW, d_out, off, caps[a:z], d_out_n[a:z], o, total, d_len)
-        outs.append(o[:total])
-    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-    b, e = _first_error(errs)
-    return outs, ((b, e) if e else None)
+    d_out_n = torch.zeros(len(sizes), dtype=torch.int64, device=dev)
+    d_len = torch.zeros(len(groups), dtype=torch.int64, device=dev)
+    total = sum(sizes)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    pos = 0
+    for g, (a, z) in enumerate(groups):
+        gt = sum(sizes[a:z])
+        if not gt:
+            continue
+        off, _ = _layout(sizes[a:z])
+        bt.rle_decode_dev(st, d_in, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, sizes[a:z], d_out_n[a:z])
+        bt.pack_payloads(st, FRAME_RAW, d_out, off, sizes[a:z], d_out_n[a:z], out[pos:], gt, d_len[g:g + 1])
+        pos += gt
+    return out[:total]
 
 
 def _decode_args(shaf, cod, rle, freq, what):
@@ -1076,6 +1103,138 @@ def _decode_args(shaf, cod, rle, freq, what):
     return sf, files
 
 
+class _Parse:
+    """one file set after the parse's synchronisation: mode, the blocks in front of the first parse fault (fb) with their
+    payload sizes (pn) and symbol counts (nsym, .cod only), that fault (perr), and the device arrays of the parse"""
+
+
+def _open_files(shaf, cod, rle, freq, stream, what):
+    """the argument checks, the stream and the batch of a single-file-set call -> (sf, files, stream, slots, batch)"""
+    import torch
+    sf, files = _decode_args(shaf, cod, rle, freq, what)
+    st = stream if stream is not None else torch.cuda.Stream(device=files[0].device)
+    mb = unpack_max_blocks(files[1].numel(), "cod" if sf else "freq")
+    if mb > 0x7FFFFFFF:
+        raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
+    return sf, files, st, mb, Batch(mb, 1 << 20)
+
+
+def _parse_files(bt, st, sf, files, mb, modes, what):
+    """unpack_cod + unpack_shaf (or unpack_rle_freq), one synchronisation, 16 bytes a block read back -> _Parse.  Raises a
+    bad header, a mode outside `modes` and a parse fault on block 0; fb == 0 without one is the empty file."""
+    import torch
+    dev = files[0].device
+    p = _Parse()
+    d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+    p.d_off = torch.zeros(mb, dtype=torch.int64, device=dev)
+    p.d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
+    if sf:
+        p.d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
+        p.d_tab = torch.empty(mb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.unpack_cod(st, mb, files[1], d_info, p.d_nsym, p.d_tab)
+        bt.unpack_shaf(st, mb, files[0], d_info[INFO_INDEXED:INFO_INDEXED + 1], p.d_off, p.d_n)
+    else:
+        bt.unpack_rle_freq(st, mb, files[1], files[0].numel(), d_info, p.d_off, p.d_n)
+    _, errs = bt.finish(st, mb, raise_on_error=False)                        # the parse's one synchronisation
+    info = _u64_host(d_info)
+    if info[INFO_STATUS]:
+        raise ShafaError(FILE_STREAM_FAILED, f"{what}: bad header")
+    p.mode = chr(info[INFO_MODE])
+    if p.mode not in modes:
+        raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: mode {p.mode!r}")
+    nidx = info[INFO_INDEXED]
+    pn = _u64_host(p.d_n)[:nidx]
+    errs = errs[:nidx]
+    nsym = None
+    if sf:
+        nsym = _u64_host(p.d_nsym)[:nidx]
+        errs = [e if e or nsym[b] <= 8 * pn[b] else FILE_UNRECOGNIZABLE for b, e in enumerate(errs)]
+    p.fb, p.perr = _first_error(errs)
+    if not p.perr and info[INFO_COUNT] > nidx:                               # cannot happen: max_blocks covers any count
+        p.perr = FILE_STREAM_FAILED
+    if p.fb == 0 and p.perr:
+        raise ShafaError(p.perr, f"{what}: block 0")
+    p.pn, p.nsym = pn[:p.fb], nsym[:p.fb] if sf else None
+    return p
+
+
+def _gather_payloads(bt, st, d_file, p, b0, b1):
+    """unpack_payloads of blocks [b0, b1) into exact aligned regions -> (buffer, offsets, sizes, device sizes)"""
+    import torch
+    pn = p.pn[b0:b1]
+    poff, ptot = _layout(pn)
+    d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=d_file.device)
+    bt.unpack_payloads(st, d_file, p.d_off[b0:b1], p.d_n[b0:b1], d_pay, poff, pn)
+    return d_pay, poff, pn, p.d_n[b0:b1]
+
+
+def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what):
+    """Blocks [b0, b1) of a parsed .shaf / .cod pair: unpack_payloads -> sf_decode_dev (-> pack_payloads(RAW) when `pack`) ->
+    one synchronisation; a block whose codes take the decoder's single slot for 33..64-bit codes from another is decoded
+    again on its own.  The first SF error in block order raises.
+    -> (buffer, offsets, sizes, device sizes) of the decoded blocks, and the packed tensor (None without `pack`)"""
+    import torch
+    dev = d_shaf.device
+    tsz = C.sizeof(CodeTable)
+    d_pay, poff, pn, d_n = _gather_payloads(bt, st, d_shaf, p, b0, b1)
+    nsym, d_nsym, d_tab = p.nsym[b0:b1], p.d_nsym[b0:b1], p.d_tab[b0 * tsz:b1 * tsz]
+    ooff, otot = _layout(nsym)
+    d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+    bt.sf_decode_dev(st, d_pay, poff, pn, d_n, d_tab, d_nsym, d_sfo, ooff, nsym)
+    out = None
+    if pack:
+        total = sum(nsym)
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+    errs = errs[:b1 - b0]
+    again = set()
+    b, e = _first_error(errs)
+    while e == LACK_OF_MEMORY and b not in again:                            # the one slot for 33..64-bit codes was taken
+        bt.sf_decode_dev(st, d_pay, poff[b:b + 1], pn[b:b + 1], d_n[b:b + 1], d_tab[b * tsz:(b + 1) * tsz],
+                         d_nsym[b:b + 1], d_sfo, ooff[b:b + 1], nsym[b:b + 1])
+        _, one = bt.finish(st, bt.max_blocks, raise_on_error=False)
+        errs[b] = one[0]
+        again.add(b)
+        b, e = _first_error(errs)
+    if e:
+        raise ShafaError(e, f"{what}: block {b0 + b}")
+    if pack and again:
+        bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+        bt.finish(st, bt.max_blocks)
+    return (d_sfo, ooff, nsym, d_nsym), (out[:total] if pack else None)
+
+
+def _measure_set(bt, st, sf, files, p, what):
+    """The decoded size of every block in front of the first parse fault of a parsed set (fb > 0), and the RLE decoder's
+    inputs (buffer, offsets, sizes, device sizes; None for mode N, whose sizes are the .cod's).  An RLE set goes through
+    unpack_payloads (and sf_decode_dev for .shaf + .cod) and the size pass; the first SF error, then the first RLE error in
+    block order raise."""
+    if sf and p.mode == "N":
+        return list(p.nsym), None
+    if sf:
+        rin, _ = _sf_decode_blocks(bt, st, files[0], p, 0, p.fb, False, what)
+    else:
+        rin = _gather_payloads(bt, st, files[0], p, 0, p.fb)
+    sizes, errs = _rle_measure(bt, st, *rin, bt.max_blocks)
+    b, e = _first_error(errs)
+    if e:
+        raise ShafaError(e, f"{what}: block {b}")
+    return sizes, rin
+
+
+def _rle_decode_range(bt, st, rin, sizes, b0, b1, max_bytes, what):
+    """blocks [b0, b1) of a measured RLE set, decoded and packed -> their bytes; synchronised"""
+    d_in, in_off, in_n, d_in_n = rin
+    out = _rle_decode_exact(bt, st, d_in, in_off[b0:b1], in_n[b0:b1], d_in_n[b0:b1], sizes[b0:b1], max_bytes)
+    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+    _, e = _first_error(errs)
+    if e:                                                                    # the size pass accepted every block: the device
+        raise ShafaError(e, f"{what}: RLE decoding")
+    return out
+
+
 def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
     """The file the CLI's Module D writes, decoded from files held in device memory (contiguous uint8 CUDA tensors, any
     alignment — e.g. compress_files' values):
@@ -1087,105 +1246,99 @@ def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, 
 
     Chain: unpack_cod + unpack_shaf (or unpack_rle_freq) -> one synchronisation, 16 bytes a block read back -> exact
     aligned regions -> unpack_payloads -> sf_decode_dev -> pack_payloads -> finish: two synchronisations without RLE
-    decoding.  RLE decoding runs in groups whose worst-case outputs fit max_bytes (default: a quarter of the free device
-    memory), one synchronisation each.  A symbol count above 8 x the payload's bytes is SHAFA_FILE_UNRECOGNIZABLE without
+    decoding.  RLE decoding first measures every block (rle_decoded_size_dev, one synchronisation that reads the sizes),
+    then decodes into regions of exactly those sizes, in groups that fit max_bytes (default: a quarter of the free device
+    memory) and follow each other without a synchronisation, each packed into its place in the result; one last
+    synchronisation.  A symbol count above 8 x the payload's bytes is SHAFA_FILE_UNRECOGNIZABLE without
     decoding (every code of a table the decoder accepts has >= 1 bit, so the host's decoder runs out of input).  A block whose
     codes take the decoder's single slot for 33..64-bit codes from another is decoded again on its own."""
     import torch
-    sf, files = _decode_args(shaf, cod, rle, freq, "decompress_files")
-    dev = files[0].device
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
-    if max_bytes is None:
-        max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
-    text = files[1]
-    mb = unpack_max_blocks(text.numel(), "cod" if sf else "freq")
-    if mb > 0x7FFFFFFF:
-        raise ShafaError(LACK_OF_MEMORY, "decompress_files: text too long")
-    bt = Batch(mb, 1 << 20)
+    what = "decompress_files"
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
-        d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
-        d_off = torch.zeros(mb, dtype=torch.int64, device=dev)
-        d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
-        tsz = C.sizeof(CodeTable)
-        if sf:
-            d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
-            d_tab = torch.empty(mb * tsz, dtype=torch.uint8, device=dev)
-            bt.unpack_cod(st, mb, files[1], d_info, d_nsym, d_tab)
-            bt.unpack_shaf(st, mb, files[0], d_info[INFO_INDEXED:INFO_INDEXED + 1], d_off, d_n)
-        else:
-            bt.unpack_rle_freq(st, mb, files[1], files[0].numel(), d_info, d_off, d_n)
-        _, errs = bt.finish(st, mb, raise_on_error=False)                    # the parse's one synchronisation
-        info = _u64_host(d_info)
-        if info[INFO_STATUS]:
-            raise ShafaError(FILE_STREAM_FAILED, "decompress_files: bad header")
-        mode = chr(info[INFO_MODE])
-        if not (mode == "R" or (sf and mode == "N" and not decode_rle)):
-            raise ShafaError(FILE_UNRECOGNIZABLE, f"decompress_files: mode {mode!r}")
-        nidx = info[INFO_INDEXED]
-        pn = _u64_host(d_n)[:nidx]
-        errs = errs[:nidx]
-        if sf:
-            nsym = _u64_host(d_nsym)[:nidx]
-            errs = [e if e or nsym[b] <= 8 * pn[b] else FILE_UNRECOGNIZABLE for b, e in enumerate(errs)]
-        fb, parse_err = _first_error(errs)
-        if not parse_err and info[INFO_COUNT] > nidx:                        # cannot happen: max_blocks covers any count
-            parse_err = FILE_STREAM_FAILED
-        if fb == 0:
-            if parse_err:
-                raise ShafaError(parse_err, "decompress_files: block 0")
+        dev = files[0].device
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
+        if p.fb == 0:
             return torch.empty(0, dtype=torch.uint8, device=dev)
-        # ---- the payloads of blocks [0, fb), in exact aligned regions
-        pn = pn[:fb]
-        poff, ptot = _layout(pn)
-        d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=dev)
-        bt.unpack_payloads(st, files[0], d_off, d_n, d_pay, poff, pn)
-        if sf:
-            nsym = nsym[:fb]
-            ooff, otot = _layout(nsym)
-            d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
-            bt.sf_decode_dev(st, d_pay, poff, pn, d_n, d_tab, d_nsym, d_sfo, ooff, nsym)
-            rle_after = mode == "R" and decode_rle
-            if not rle_after:
-                total = sum(nsym)
-                out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-                d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-                if not parse_err:
-                    bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
-            _, errs = bt.finish(st, mb, raise_on_error=False)
-            errs = errs[:fb]
-            again = set()
-            b, e = _first_error(errs)
-            while e == LACK_OF_MEMORY and b not in again:                    # the one slot for 33..64-bit codes was taken
-                bt.sf_decode_dev(st, d_pay, poff[b:b + 1], pn[b:b + 1], d_n[b:b + 1], d_tab[b * tsz:(b + 1) * tsz],
-                                 d_nsym[b:b + 1], d_sfo, ooff[b:b + 1], nsym[b:b + 1])
-                _, one = bt.finish(st, mb, raise_on_error=False)
-                errs[b] = one[0]
-                again.add(b)
-                b, e = _first_error(errs)
-            if e:
-                raise ShafaError(e, f"decompress_files: block {b}")
-            if not rle_after:
-                if parse_err:
-                    raise ShafaError(parse_err, f"decompress_files: block {fb}")
-                if again:
-                    bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
-                    bt.finish(st, mb)
-                return out[:total]
-            d_in, in_off, in_n, d_in_n = d_sfo, ooff, nsym, d_nsym
-        else:
-            d_in, in_off, in_n, d_in_n = d_pay, poff, pn, d_n
-        outs, err = _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, max_bytes)
-        if err:
-            raise ShafaError(err[1], f"decompress_files: block {err[0]}")
-        if parse_err:
-            raise ShafaError(parse_err, f"decompress_files: block {fb}")
-        return outs[0] if len(outs) == 1 else torch.cat(outs)
+        if sf and not (p.mode == "R" and decode_rle):
+            _, out = _sf_decode_blocks(bt, st, files[0], p, 0, p.fb, not p.perr, what)
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+            return out
+        sizes, rin = _measure_set(bt, st, sf, files, p, what)
+        if p.perr:
+            raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        return _rle_decode_range(bt, st, rin, sizes, 0, p.fb, max_bytes, what)
+    finally:
+        bt.close()
+
+
+def decoded_sizes(shaf=None, cod=None, rle=None, freq=None, stream=None):
+    """The decoded size of every block of a file set held in device memory (decompress_files' file arguments), as a list of
+    ints whose sum is the decoded file's length — the original file's: a mode-R .shaf + .cod counts its blocks after RLE
+    decoding, a mode-N pair is what decompress_files(decode_rle=False) returns.  Nothing is decoded that need not be:
+      shaf + cod, mode N   the .cod's block sizes; the .shaf is framed (unpack_shaf), no payload is read
+      rle + freq           unpack_payloads and the size pass (rle_decoded_size_dev)
+      shaf + cod, mode R   unpack_payloads, sf_decode_dev, then the size pass on the RLE bytes; no RLE output is allocated
+    Raises what decompress_files raises for faults in what the call looked at, with its precedence: header, mode, parse
+    faults, and for the two RLE forms the SF and RLE faults of every block."""
+    what = "decoded_sizes"
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
+        sizes = _measure_set(bt, st, sf, files, p, what)[0] if p.fb else []
+        if p.perr:
+            raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        return [int(s) for s in sizes]
+    finally:
+        bt.close()
+
+
+def decompress_range(offset, length, shaf=None, cod=None, rle=None, freq=None, stream=None, max_bytes=None):
+    """Bytes [offset, offset + length) of the decoded file of a file set held in device memory: a uint8 CUDA tensor equal to
+    the same slice of decompress_files' result (decode_rle following the .cod's mode, as in decoded_sizes; Python slice
+    semantics at the end of the file; a negative offset or length raises ValueError).
+    Block-granular: the per-block sizes as in decoded_sizes, a prefix sum on the host, the blocks [b0, b1) that cover the
+    range, and only those go through the expensive stage — mode N: unpack_payloads and sf_decode_dev of blocks b0 .. b1 - 1
+    only; rle + freq: rle_decode_dev of those only; mode-R shaf + cod: every block is SF-decoded (the sizes need it), only the
+    covering ones are RLE-decoded.  Then one pack_payloads(RAW) and a slice (a view of the covering blocks' bytes).
+    Errors: parse faults anywhere in the files, and decode faults in every block the call decoded or measured, raise with
+    decompress_files' code and precedence; a damaged payload in a mode-N block outside the range is, by design, not noticed."""
+    import bisect
+    import itertools
+    import torch
+    what = "decompress_range"
+    if offset < 0 or length < 0:
+        raise ValueError(f"{what}: negative offset or length")
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        dev = files[0].device
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
+        out, lo, hi = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
+        if p.fb:
+            sizes, rin = _measure_set(bt, st, sf, files, p, what)
+            ends = list(itertools.accumulate(sizes))                         # block b is bytes [ends[b] - sizes[b], ends[b])
+            lo, hi = min(offset, ends[-1]), min(offset + length, ends[-1])
+            if lo < hi:
+                b0, b1 = bisect.bisect_right(ends, lo), bisect.bisect_left(ends, hi) + 1
+                if rin is None:
+                    _, out = _sf_decode_blocks(bt, st, files[0], p, b0, b1, True, what)
+                else:
+                    out = _rle_decode_range(bt, st, rin, sizes, b0, b1, max_bytes, what)
+                first = ends[b0] - sizes[b0]
+                lo, hi = lo - first, hi - first
+        if p.perr:
+            raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        return out[lo:hi]
     finally:
         bt.close()
 
 
 MANY_GROUP_SLOTS = 1 << 18      # decompress_many: parse slots per device batch (error words, workspace and tables grow with them)
-RLE_GRID_TILES = 1 << 22        # decompress_many: rle_decode_dev workgroups per call (x 256 lanes: below 2^32)
 
 
 def _many_entry(e):
@@ -1212,10 +1365,12 @@ def decompress_many(entries, stream=None, max_bytes=None):
     the framed blocks of all files gathered onto consecutive indices (index_select) -> one unpack_payloads -> one sf_decode_dev
     over the blocks of every .shaf file -> pack_payloads_files(RAW) for files without RLE decoding -> synchronisation 2 ->
     each block that lost sf_decode_dev's single 33..64-bit slot decoded again alone (one synchronisation each, one more to pack
-    its file again) -> rle_decode_dev in groups bounded by max_bytes (default: a quarter of the free device memory), one
-    synchronisation each, each followed by pack_payloads_files(RAW) into exact per-file regions -> one last synchronisation.
-    Synchronisations per group: 2 without RLE decoding; with it, 3 + the RLE groups with .shaf files and 2 + the RLE groups
-    for .rle + .freq only (4 and 3 in one RLE group).  Decoded blocks are taken MANY_GROUP_BLOCKS at a time (sf_decode_dev puts
+    its file again) -> the size pass over every RLE block (rle_decoded_size_dev) and the synchronisation that reads the sizes
+    -> rle_decode_dev into regions of exactly those sizes, in groups bounded by max_bytes (default: a quarter of the free
+    device memory) that follow each other without a synchronisation, each followed by pack_payloads_files(RAW) into exact
+    per-file regions -> one last synchronisation.
+    Synchronisations per group: 2 without RLE decoding; with it, 4 with .shaf files and 3 for .rle + .freq only, however
+    many RLE groups there are.  Decoded blocks are taken MANY_GROUP_BLOCKS at a time (sf_decode_dev puts
     blocks on the grid's y): a group with more repeats the chain after synchronisation 1.  Per file the error is decompress_files':
     a bad header, the mode rule, a parse fault on block 0, SF errors before the first parse fault, RLE errors there, then the
     parse fault."""
@@ -1415,9 +1570,11 @@ def _decode_many(bt, st, dev, part, pbase, pend, d_off, d_n, d_nsym, d_tab, n_h,
 
 
 def _rle_decode_many(bt, st, dev, rle_in, max_bytes, results):
-    """rle_decode_dev over the blocks of these files in groups whose output capacities fit max_bytes (decompress_files'
-    rule), one synchronisation each, each followed by pack_payloads_files(RAW) of the group's part of every file; one last
-    synchronisation.  A file whose blocks span groups is joined at the end."""
+    """The RLE stage of these files: the size pass over all their blocks and its synchronisation (decompress_files' rule:
+    a file's first refused block in block order is its error), then rle_decode_dev of the files without a fault into regions
+    of exactly the measured sizes, in groups (_rle_groups) that follow each other without a synchronisation, each followed by
+    pack_payloads_files(RAW) of the group's part of every file; one last synchronisation.  A file whose blocks span groups is
+    joined at the end."""
     import torch
     bufs = {id(b): b for _, b, _, _, _ in rle_in}
     lo = min(bufs.values(), key=lambda t: t.data_ptr())                 # inputs addressed from one base
@@ -1429,51 +1586,43 @@ def _rle_decode_many(bt, st, dev, rle_in, max_bytes, results):
         owner += [k] * len(n)
     d_in_n = torch.cat([d for _, _, _, _, d in rle_in])
     nb = len(in_n)
-    caps = [min(RLE_DECODE_MAX, 85 * n + 2) for n in in_n]
-    # rle_decode_dev's grid is (its largest input's 8 KiB tiles) x (its blocks) workgroups of 256 lanes: a group also keeps
-    # that product within RLE_GRID_TILES, so the grid's lanes stay below 2^32 however many small blocks join a large one
-    tiles = [max(1, -(-n // 8192)) for n in in_n]
-    groups, g0, acc, mt = [], 0, 0, 0
-    for b in range(nb):
-        if b > g0 and (acc + _al16(caps[b]) > max_bytes or max(mt, tiles[b]) * (b - g0 + 1) > RLE_GRID_TILES):
-            groups.append((g0, b))
-            g0, acc, mt = b, 0, 0
-        acc += _al16(caps[b])
-        mt = max(mt, tiles[b])
-    groups.append((g0, nb))
-    biggest = max(_layout(caps[a:z])[1] for a, z in groups)
-    d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
-    d_out_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-    parts = [[] for _ in rle_in]
+    sizes, errs = _rle_measure(bt, st, lo, in_off, in_n, d_in_n, nb)
     err = [None] * len(rle_in)
-    for a, z in groups:
-        off, _ = _layout(caps[a:z])
-        bt.rle_decode_dev(st, lo, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, caps[a:z], d_out_n[a:z])
-        _, errs = bt.finish(st, z - a, raise_on_error=False)
-        sz = _u64_host(d_out_n[a:z])
-        ks, c0, cnt, tot = [], [], [], []
-        for b in range(a, z):
-            k = owner[b]
-            if err[k] is None and errs[b - a]:
-                err[k] = (b - a, errs[b - a])
-            if not ks or ks[-1] != k:
-                ks.append(k)
-                c0.append(b - a)
-                cnt.append(0)
-                tot.append(0)
-            cnt[-1] += 1
-            tot[-1] += sz[b - a]
-        keep = [j for j, k in enumerate(ks) if err[k] is None]
-        if keep:
-            views = _pack_files(bt, st, dev, keep, [c0[j] for j in keep], [cnt[j] for j in keep], d_out, off, caps[a:z],
-                                d_out_n[a:z], [tot[j] for j in keep])
-            for j, v in zip(keep, views):
-                parts[ks[j]].append(v)
-    bt.finish(st, nb, raise_on_error=False)
+    for b in range(nb):
+        if errs[b] and err[owner[b]] is None:
+            err[owner[b]] = errs[b]
+    parts = [[] for _ in rle_in]
+    sel = [b for b in range(nb) if err[owner[b]] is None and not rle_in[owner[b]][0].perr]
+    if sel:
+        if len(sel) < nb:
+            in_off, in_n, sizes, owner = ([v[b] for b in sel] for v in (in_off, in_n, sizes, owner))
+            d_in_n = d_in_n.index_select(0, torch.tensor(sel, dtype=torch.int64, device=dev))
+        groups = _rle_groups(sizes, in_n, max_bytes)
+        biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
+        d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
+        d_out_n = torch.zeros(len(sel), dtype=torch.int64, device=dev)
+        for a, z in groups:
+            off, _ = _layout(sizes[a:z])
+            bt.rle_decode_dev(st, lo, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, sizes[a:z], d_out_n[a:z])
+            ks, c0, cnt, tot = [], [], [], []
+            for b in range(a, z):
+                if not ks or ks[-1] != owner[b]:
+                    ks.append(owner[b])
+                    c0.append(b - a)
+                    cnt.append(0)
+                    tot.append(0)
+                cnt[-1] += 1
+                tot[-1] += sizes[b]
+            for k, v in zip(ks, _pack_files(bt, st, dev, ks, c0, cnt, d_out, off, sizes[a:z], d_out_n[a:z], tot)):
+                parts[k].append(v)
+    _, errs = bt.finish(st, nb, raise_on_error=False)
+    _, late = _first_error(errs)                                        # the size pass accepted every block decoded: the device
     for k, (f, _, _, _, _) in enumerate(rle_in):
         if err[k]:
-            results[f.i] = ShafaError(err[k][1], "decompress_many: RLE decoding")
+            results[f.i] = ShafaError(err[k], "decompress_many: RLE decoding")
         elif f.perr:
             results[f.i] = ShafaError(f.perr, f"decompress_many: block {f.fb}")
+        elif late:
+            results[f.i] = ShafaError(late, "decompress_many: RLE decoding")
         else:
             results[f.i] = parts[k][0] if len(parts[k]) == 1 else torch.cat(parts[k])
