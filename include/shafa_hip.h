@@ -288,6 +288,26 @@ int shafa_hipd_rle_decoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                                     uint64_t *d_out_n);
 
+/* The RLE sizes of input blocks without encoding them: d_out_n[b] = the size shafa_hipd_rle_encode leaves for the d_in_n[b]
+ * (<= h_in_cap[b]) bytes at d_in + h_in_off[b] when it is given room enough (block_compression's size, f.c:29-55).  Per
+ * maximal run of byte s with length L that is 3 * (L / 255), plus for m = L % 255: 0 if m == 0; 3 if s == 0 or m >= 4; else m.
+ * Runs end at the block's end.  No byte of output is written anywhere except d_out_n[0 .. nblocks) and the batch's error
+ * words, and d_in is only read.  Per-block codes through shafa_hipd_finish, as for every entry:
+ *   d_in_n[b] > h_in_cap[b]                SHAFA_OUTSIDE_MODULE, d_out_n[b] = 0 (no byte of the block is read).
+ * d_in_n[b] = 0 is size 0 and success.  Any input has an RLE size: no block is ever SHAFA_LACK_OF_MEMORY or
+ * SHAFA_FILE_UNRECOGNIZABLE.  With h_out_cap[b] = d_out_n[b], shafa_hipd_rle_encode[_tiles] fills its region exactly.
+ * Two launches — every 8 KiB tile on its own, then one workgroup per block — in which no workgroup waits for another; the
+ * grid is the tile count of the call, so any nblocks <= max_blocks with any mix of capacities is measured.  The device
+ * workspace is 16 bytes per 8 KiB of sum(h_in_cap) plus 20 bytes per block.
+ * Enqueues only, as shafa_hipd_rle_decoded_size_dev: d_in_n is never read on the host, no device-to-host copy is issued and
+ * nothing is synchronised; the one exception is the batch's growth, from nblocks and h_in_cap.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_in_n, d_out_n,
+ * h_in_off or h_in_cap, or an h_in_off[b] that is not a multiple of 16: SHAFA_OUTSIDE_MODULE (a NULL batch comes first);
+ * nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY (so is a call of 2^31 tiles or more); nblocks <= 0: success. */
+int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                                    uint64_t *d_out_n);
+
 /* ---- Files in device memory: .rle, .shaf, .cod and .freq assembled from what the entries above leave -------------------
  * Each call writes ONE contiguous file at d_dst: every byte equals what the C host writes for the same sizes, tables and
  * counts (host/modules.c's framing around host/formats.c's shafa_cod_format / shafa_freq_format) — empty codes, 255-bit

@@ -116,6 +116,7 @@ def lib():
     L.shafa_hipd_sf_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp, u8p, u64p, u64p]
     L.shafa_hipd_rle_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_rle_decoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
+    L.shafa_hipd_rle_encoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -168,7 +169,7 @@ def lib():
                  "shafa_hipd_pack_payloads_files", "shafa_hipd_pack_cod_files", "shafa_hipd_pack_freq_files",
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
-                 "shafa_hipd_rle_decoded_size_dev"):
+                 "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -392,6 +393,13 @@ class Batch:
         io, ic = _u64arr(in_off), _u64arr(in_cap)
         _check(lib().shafa_hipd_rle_decoded_size_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
                                                      d_in_n.data_ptr(), d_out_n.data_ptr()), "hipd_rle_decoded_size_dev")
+
+    def rle_encoded_size_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_out_n):
+        """d_out_n[b] (int64) = the size rle_encode would leave for the d_in_n[b] bytes of block b with room enough; nothing
+        is encoded and no output exists.  Enqueues only (include/shafa_hip.h: shafa_hipd_rle_encoded_size_dev)."""
+        io, ic = _u64arr(in_off), _u64arr(in_cap)
+        _check(lib().shafa_hipd_rle_encoded_size_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                                     d_in_n.data_ptr(), d_out_n.data_ptr()), "hipd_rle_encoded_size_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -735,10 +743,12 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
     force_freq), {".freq", ".cod", ".shaf"} without.  Each value is a uint8 CUDA tensor holding exactly the file (a view of a
     buffer sized by the pack bounds).
 
-    Block split and RLE rule of the C host (shafa_block_count; shafa_rle_worthwhile on block 0, f.c:250-258).  rle_encode_tiles
-    (and hist256_tiles where the input's histogram is needed) -> one synchronisation to read block 0's RLE size (none with
-    force_rle) -> sf_build_codes -> sf_encode_dev -> the packs -> one finish.  Raises ShafaError(FILE_TOO_SMALL) below 1 KiB
-    (f.c:220,366) and on any block's error."""
+    Block split and RLE rule of the C host (shafa_block_count; shafa_rle_worthwhile on block 0, f.c:250-258).  The choice is
+    settled first: the size pass (rle_encoded_size_dev) over every block -> one synchronisation that reads the sizes -> with
+    RLE, rle_encode_tiles into regions of exactly the measured sizes (hist256_tiles of the input only with force_freq);
+    without, hist256_tiles alone: no RLE launch, no RLE region -> sf_build_codes -> sf_encode_dev -> the packs -> one finish.
+    force_rle keeps the chain without a size pass: rle_encode_tiles into worst-case regions (2 n + 3, f.c:244), one
+    synchronisation in all.  Raises ShafaError(FILE_TOO_SMALL) below 1 KiB (f.c:220,366) and on any block's error."""
     import torch
     dev = d_in.device
     total = int(d_in.numel())
@@ -760,32 +770,31 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
     d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
     bt = Batch(nb, 2 * max(sizes) + 64)
     try:
-        # ---- Module F: RLE of every block with its histogram and tile histograms; the input's where it may be needed
-        rcap = [2 * n + 3 for n in sizes]                                   # f.c:244
-        roff, pos = [], 0
-        for c in rcap:
-            roff.append(pos)
-            pos += _al16(c)
-        d_rle = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-        rthb = [_al16(tile_hist_bytes(c)) for c in rcap]
-        rtoff = [sum(rthb[:b]) for b in range(nb)]
-        d_rth = torch.empty(sum(rthb) + 16, dtype=torch.uint8, device=dev)
-        bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff)
-        need_in = force_freq or not force_rle
-        if need_in:
-            d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-            ithb = [_al16(tile_hist_bytes(n)) for n in sizes]
-            itoff = [sum(ithb[:b]) for b in range(nb)]
-            d_ith = torch.empty(sum(ithb) + 16, dtype=torch.uint8, device=dev)
-            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_ith, itoff)
+        # ---- the choice: forced, or the reference's decision on block 0's RLE size, measured with every other block's
         if force_rle:
             use_rle = True
-        else:                                                               # the reference's decision: block 0's RLE size
+            rcap = [2 * n + 3 for n in sizes]                               # f.c:244
+        else:
+            d_rsize = torch.zeros(nb, dtype=torch.int64, device=dev)
+            bt.rle_encoded_size_dev(st, src_in, off, sizes, d_n_in, d_rsize)
             bt.finish(st, nb)
-            use_rle = bool(host().shafa_rle_worthwhile(sizes[0], int(d_rle_n[0].item()), False))
+            rcap = _u64_host(d_rsize)                                       # exact: the encoder fills these regions
+            use_rle = bool(host().shafa_rle_worthwhile(sizes[0], rcap[0], False))
         mode = b"R" if use_rle else b"N"
+        # ---- Module F: RLE of every block with its histogram and tile histograms, or the input's alone
+        if use_rle:
+            roff, pos = _layout(rcap)
+            d_rle = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+            d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+            d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+            rtoff, pos = _layout([tile_hist_bytes(c) for c in rcap])
+            d_rth = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+            bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff)
+        if force_freq or not use_rle:
+            d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+            itoff, pos = _layout([tile_hist_bytes(n) for n in sizes])
+            d_ith = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_ith, itoff)
         # ---- Module T and Module C from what F left on the device
         if use_rle:
             e_src, e_off, e_cap, e_n, e_freq, e_th, e_toff = d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff
@@ -795,10 +804,7 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
         bt.sf_build_codes(st, nb, e_freq, d_tab)
         # Fano codes average under H + 1 <= 9 bits a symbol: 12 bits leave room (a block that does not fit is an error)
         ocap = [c + c // 2 + 64 for c in e_cap]
-        ooff, pos = [], 0
-        for c in ocap:
-            ooff.append(pos)
-            pos += _al16(c)
+        ooff, pos = _layout(ocap)
         d_enc = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
         d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
         bt.sf_encode_dev(st, e_src, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, e_th, e_toff)
@@ -834,18 +840,12 @@ def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=N
 MANY_GROUP_BLOCKS = 16384      # compress_many: blocks per device batch (the F / T / C launches put blocks on the grid's y)
 
 
-def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_freq=False, stream=None):
-    """compress_files for many files in one device batch.  `d_in` holds the files back to back (a contiguous uint8 CUDA tensor;
-    a list of such tensors is concatenated), `sizes` their lengths (for a list: None = the tensors' lengths).  Returns one entry
-    per file: the dict compress_files returns for that file alone, byte for byte, or a ShafaError instance (not raised) for a
-    file that failed — FILE_TOO_SMALL below 1 KiB, else the first error in the file's block order.  Other files are unaffected.
-
-    Chain per batch of files, its length independent of the file count: block split (shafa_block_count) -> one unpack_payloads
-    gather into 16-aligned regions when some block start is not aligned -> rle_encode_tiles + hist256_tiles over all blocks ->
-    one synchronisation reading every file's block-0 RLE size (none with force_rle) -> sf_build_codes + sf_encode_dev over all
-    blocks, RLE and plain files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena, sizes and
-    counts selected per block on the device) -> the segmented packs, one call per kind of file -> one finish.  Two
-    synchronisations per batch (one with force_rle); files are batched by MANY_GROUP_BLOCKS blocks."""
+def _many_files(name, d_in, sizes, block_size):
+    """compress_many's arguments checked -> (d_in as one tensor, sizes, each file's start in d_in, {file: its block sizes} by
+    the C host's split (shafa_block_count) for the files of 1 KiB or more, groups of those files): a group holds at most
+    MANY_GROUP_BLOCKS blocks, and (its largest block's 8 KiB tiles) x (its blocks) stays within RLE_GRID_TILES, which bounds
+    the grid of rle_encode_tiles' emit pass — (pairs of 4 KiB tiles of the largest block) x (blocks) workgroups of 256 lanes —
+    below 2^32 lanes however many small blocks join a large one."""
     import torch
     if isinstance(d_in, (list, tuple)):
         if sizes is None:
@@ -853,104 +853,195 @@ def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_fre
         d_in = torch.cat([t.reshape(-1) for t in d_in]) if d_in else None
     sizes = [int(n) for n in (sizes or [])]
     if not sizes:
-        raise ValueError("compress_many: no files")
-    if d_in is None or d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
-        raise ValueError("compress_many: d_in is a contiguous uint8 CUDA tensor")
+        raise ValueError(f"{name}: no files")
+    if d_in is None or not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_cuda \
+            or not d_in.is_contiguous():
+        raise ValueError(f"{name}: d_in is a contiguous uint8 CUDA tensor")
     if sum(sizes) > d_in.numel() or min(sizes) < 0:
-        raise ValueError("compress_many: sizes exceed d_in")
-    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
-    results = [None] * len(sizes)
+        raise ValueError(f"{name}: sizes exceed d_in")
     start, pos = [], 0
     for n in sizes:
         start.append(pos)
         pos += n
-    # the C host's block split per file; a file under 1 KiB is refused before any device work (f.c:220,366)
     split = {}
     for f, n in enumerate(sizes):
-        bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
-        nb = int(host().shafa_block_count(n, C.byref(bs), C.byref(last)))
-        if n < 1024:
-            results[f] = ShafaError(FILE_TOO_SMALL, "compress_many: fewer than 1024 bytes")
-        else:
+        if n >= 1024:
+            bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
+            nb = int(host().shafa_block_count(n, C.byref(bs), C.byref(last)))
             split[f] = [bs.value] * (nb - 1) + [last.value]
-    group, acc = [], 0
+    groups, group, acc, mt = [], [], 0, 0
     for f in split:
-        if group and acc + len(split[f]) > MANY_GROUP_BLOCKS:
-            _compress_group(d_in, start, split, group, force_rle, force_freq, st, results)
-            group, acc = [], 0
+        t = max(1, -(-max(split[f]) // 8192))
+        k = len(split[f])
+        if group and (acc + k > MANY_GROUP_BLOCKS or max(mt, t) * (acc + k) > RLE_GRID_TILES):
+            groups.append(group)
+            group, acc, mt = [], 0, 0
         group.append(f)
-        acc += len(split[f])
+        acc += k
+        mt = max(mt, t)
     if group:
+        groups.append(group)
+    return d_in, sizes, start, split, groups
+
+
+def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_freq=False, stream=None):
+    """compress_files for many files in one device batch.  `d_in` holds the files back to back (a contiguous uint8 CUDA tensor;
+    a list of such tensors is concatenated), `sizes` their lengths (for a list: None = the tensors' lengths).  Returns one entry
+    per file: the dict compress_files returns for that file alone, byte for byte, or a ShafaError instance (not raised) for a
+    file that failed — FILE_TOO_SMALL below 1 KiB, else the first error in the file's block order.  Other files are unaffected.
+
+    Chain per batch of files, its length independent of the file count: block split (shafa_block_count) -> one unpack_payloads
+    gather into 16-aligned regions when some block start is not aligned -> the size pass (rle_encoded_size_dev) over all
+    blocks -> one synchronisation reading every block's RLE size; each file's choice is shafa_rle_worthwhile on its block 0 ->
+    rle_encode_tiles over the blocks of the files that take RLE only, into regions of exactly the measured sizes, and
+    hist256_tiles over the blocks of the plain files only (over all of them with force_freq) -> sf_build_codes + sf_encode_dev
+    over all blocks, RLE and plain files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena)
+    -> the segmented packs, one call per kind of file -> one finish.  Two synchronisations per batch.  force_rle keeps the
+    chain without a size pass: rle_encode_tiles over all blocks into worst-case regions (2 n + 3), one synchronisation per
+    batch.  Files are batched by MANY_GROUP_BLOCKS blocks and by the RLE encoder's grid (_many_files)."""
+    import torch
+    d_in, sizes, start, split, groups = _many_files("compress_many", d_in, sizes, block_size)
+    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
+    # a file under 1 KiB is refused before any device work (f.c:220,366)
+    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "compress_many: fewer than 1024 bytes")
+               for f in range(len(sizes))]
+    for group in groups:
         _compress_group(d_in, start, split, group, force_rle, force_freq, st, results)
     return results
+
+
+def rle_encoded_sizes(d_in, sizes=None, block_size=65536, stream=None):
+    """Will these files take RLE, and how large is each .rle?  The files as compress_many takes them; per file
+    (use_rle, [the RLE size of each of its blocks]) — compress_files' choice without force_rle, and the payload sizes its
+    .rle.freq would name — or a ShafaError instance (FILE_TOO_SMALL) for a file under 1 KiB.  One read of the data by the
+    size pass (rle_encoded_size_dev) and one synchronisation per batch of files; nothing is encoded, and beyond the sizes
+    nothing is allocated (block starts that are not 16-aligned are first gathered into aligned regions, as in compress_many)."""
+    import torch
+    d_in, sizes, start, split, groups = _many_files("rle_encoded_sizes", d_in, sizes, block_size)
+    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
+    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "rle_encoded_sizes: fewer than 1024 bytes")
+               for f in range(len(sizes))]
+    for group in groups:
+        g = _GroupBlocks(start, split, group)
+        bt = Batch(g.nb, 2 * max(g.sizes) + 64)
+        try:
+            src_in, off = g.aligned(bt, st, d_in)
+            r, errs = _rle_encoded(bt, st, src_in, off, g.sizes, g.d_n_in(d_in.device))
+        finally:
+            bt.close()
+        for i, f in enumerate(group):
+            lo, hi = g.first[i], g.first[i] + g.count[i]
+            b, e = _first_error(errs[lo:hi])
+            results[f] = ShafaError(e, f"rle_encoded_sizes: block {b}") if e else \
+                (bool(host().shafa_rle_worthwhile(g.sizes[lo], r[lo], False)), r[lo:hi])
+    return results
+
+
+class _GroupBlocks:
+    """the blocks of a group of files, file after file: per block its size and start in d_in, per file its first block and
+    block count"""
+
+    def __init__(self, start, split, files):
+        self.sizes, self.first, self.count, self.src = [], [], [], []
+        for f in files:
+            self.first.append(len(self.sizes))
+            self.count.append(len(split[f]))
+            o = start[f]
+            for n in split[f]:
+                self.src.append(o)
+                self.sizes.append(n)
+                o += n
+        self.nb = len(self.sizes)
+        self._d_n = None
+
+    def d_n_in(self, dev):
+        import torch
+        if self._d_n is None:
+            self._d_n = torch.tensor(self.sizes, dtype=torch.int64, device=dev)
+        return self._d_n
+
+    def aligned(self, bt, st, d_in):
+        """the inputs at 16-byte aligned addresses: in place, or gathered by one unpack_payloads -> (tensor, offsets)"""
+        import torch
+        if d_in.data_ptr() % 16 or any(o % 16 for o in self.src):
+            d_so = torch.tensor(self.src, dtype=torch.int64, device=d_in.device)
+            off, tot = _layout(self.sizes)
+            src_in = torch.empty(tot + 16, dtype=torch.uint8, device=d_in.device)
+            bt.unpack_payloads(st, d_in, d_so, self.d_n_in(d_in.device), src_in, off, self.sizes)
+            return src_in, off
+        return d_in, list(self.src)
+
+
+def _rle_encoded(bt, st, d_in, in_off, in_n, d_in_n):
+    """The size pass (rle_encoded_size_dev) over these input blocks and its synchronisation, which reads the sizes back
+    -> (RLE sizes, per-block codes)"""
+    import torch
+    d_size = torch.zeros(len(in_n), dtype=torch.int64, device=d_in_n.device)
+    bt.rle_encoded_size_dev(st, d_in, in_off, in_n, d_in_n, d_size)
+    _, errs = bt.finish(st, len(in_n), raise_on_error=False)
+    return _u64_host(d_size), errs
 
 
 def _compress_group(d_in, start, split, files, force_rle, force_freq, st, results):
     import torch
     dev = d_in.device
     nf = len(files)
-    sizes, first, count, src = [], [], [], []                   # per block; per file; per block: start in d_in
-    for f in files:
-        first.append(len(sizes))
-        count.append(len(split[f]))
-        o = start[f]
-        for n in split[f]:
-            src.append(o)
-            sizes.append(n)
-            o += n
-    nb = len(sizes)
-    base = d_in.data_ptr()
-    d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
-    rcap = [2 * n + 3 for n in sizes]                                       # f.c:244
-    need_in = force_freq or not force_rle
-    # tile histograms: the RLE outputs' then the inputs', in one arena
-    rthb = [_al16(tile_hist_bytes(c)) for c in rcap]
-    ithb = [_al16(tile_hist_bytes(n)) for n in sizes] if need_in else []
-    th_off, th_tot = _layout(rthb + ithb)
-    rtoff, itoff = th_off[:nb], th_off[nb:]
-    bt = Batch(nb, 2 * max(sizes) + 64)
+    g = _GroupBlocks(start, split, files)
+    nb = g.nb
+    bt = Batch(nb, 2 * max(g.sizes) + 64)
     try:
-        # ---- inputs at 16-byte aligned addresses: in place, or gathered by one unpack_payloads
-        if base % 16 or any(o % 16 for o in src):
-            d_so = torch.tensor(src, dtype=torch.int64, device=dev)
-            off, tot = _layout(sizes)
-            src_in = torch.empty(tot + 16, dtype=torch.uint8, device=dev)
-            bt.unpack_payloads(st, d_in, d_so, d_n_in, src_in, off, sizes)
-        else:
-            src_in, off = d_in, src
-        # ---- Module F over every block of every file
-        roff, rtot = _layout(rcap)
-        d_rle = torch.empty(rtot + 16, dtype=torch.uint8, device=dev)
-        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-        d_th = torch.empty(th_tot + 16, dtype=torch.uint8, device=dev)
-        bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_th, rtoff)
-        d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-        if need_in:
-            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_th, itoff)
+        src_in, off = g.aligned(bt, st, d_in)
+        # ---- the choice per file: forced, or the reference's decision on its block 0's RLE size
         errs0 = [SUCCESS] * nb
         if force_rle:
             use = [True] * nf
-        else:                                                               # the reference's decision: block 0's RLE size
-            _, errs0 = bt.finish(st, nb, raise_on_error=False)
-            r0 = d_rle_n.cpu().tolist()
-            use = [bool(host().shafa_rle_worthwhile(sizes[first[i]], r0[first[i]], False)) for i in range(nf)]
-        blk_rle = [u for u, c in zip(use, count) for _ in range(c)]
-        # ---- Module T and Module C once over all blocks: each block's sizes, counts, source and tile histograms by its file
-        if all(use):                                                        # always so with force_rle: no upload, no wait
-            e_n, e_freq = d_rle_n, d_freq_rle
-        elif not any(use):
-            e_n, e_freq = d_n_in, d_freq_in
+            rcap = [2 * n + 3 for n in g.sizes]                             # f.c:244
         else:
-            with torch.cuda.stream(st):                                     # st has drained: the mask's upload waits for nothing
-                mask = torch.tensor(blk_rle, dtype=torch.bool, device=dev)
-                e_n = torch.where(mask, d_rle_n, d_n_in)
-                e_freq = torch.where(mask[:, None], d_freq_rle.view(nb, 256), d_freq_in.view(nb, 256)).reshape(-1)
+            rcap, errs0 = _rle_encoded(bt, st, src_in, off, g.sizes, g.d_n_in(dev))
+            use = [bool(host().shafa_rle_worthwhile(g.sizes[g.first[i]], rcap[g.first[i]], False)) for i in range(nf)]
+        # ---- the files that take RLE first, the plain ones behind them: the blocks of either kind are one range, so each
+        # stage runs over its range only and a block's error word is the same in every call
+        order = [i for i in range(nf) if use[i]] + [i for i in range(nf) if not use[i]]
+        perm = [b for i in order for b in range(g.first[i], g.first[i] + g.count[i])]
+        files = [files[i] for i in order]
+        use = [use[i] for i in order]
+        count = [g.count[i] for i in order]
+        first, pos = [], 0
+        for c in count:
+            first.append(pos)
+            pos += c
+        sizes, off, errs0 = [g.sizes[b] for b in perm], [off[b] for b in perm], [errs0[b] for b in perm]
+        rcap = [rcap[b] for b in perm]
+        nr = sum(c for u, c in zip(use, count) if u)                        # blocks [0, nr) take RLE, [nr, nb) are plain
+        d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
+        in_lo = 0 if force_freq else nr                                     # the input's histogram: blocks [in_lo, nb)
+        # tile histograms: the RLE outputs' then the inputs', in one arena
+        th_off, th_tot = _layout([tile_hist_bytes(c) for c in rcap[:nr]] + [tile_hist_bytes(n) for n in sizes[in_lo:]])
+        rtoff, itoff = th_off[:nr], [None] * in_lo + th_off[nr:]
+        d_th = torch.empty(th_tot + 16, dtype=torch.uint8, device=dev)
+        # ---- Module F: RLE over the blocks that take it, into exact regions (worst-case ones with force_rle); the input's
+        # histogram over the others
+        roff, rtot = _layout(rcap[:nr])
+        d_rle = torch.empty(rtot + 16, dtype=torch.uint8, device=dev)
+        e_n = d_n_in.clone()                                                # per block: RLE size | input size
+        e_freq = torch.zeros(nb * 256, dtype=torch.int64, device=dev)       # per block: RLE histogram | input histogram
+        if nr:
+            bt.rle_encode_tiles(st, src_in, off[:nr], sizes[:nr], d_rle, roff, rcap[:nr], e_n, e_freq, d_th, rtoff)
+        d_freq_in = e_freq
+        if in_lo < nb:
+            if in_lo < nr:                                                  # force_freq: the RLE files' inputs as well
+                d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+                bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_th, itoff)
+                with torch.cuda.stream(st):
+                    e_freq[nr * 256:].copy_(d_freq_in[nr * 256:])
+            else:
+                bt.hist256_tiles(st, src_in, off[nr:], sizes[nr:], e_freq[nr * 256:], d_th, itoff[nr:])
+        # ---- Module T and Module C once over all blocks: each block's source and tile histograms by its file
         lo = d_rle if d_rle.data_ptr() < src_in.data_ptr() else src_in      # one base for inputs and RLE outputs
         a_in, a_rle = src_in.data_ptr() - lo.data_ptr(), d_rle.data_ptr() - lo.data_ptr()
-        e_off = [a_rle + roff[b] if blk_rle[b] else a_in + off[b] for b in range(nb)]
-        e_cap = [rcap[b] if blk_rle[b] else sizes[b] for b in range(nb)]
-        e_toff = [rtoff[b] if blk_rle[b] else itoff[b] for b in range(nb)]
+        e_off = [a_rle + o for o in roff] + [a_in + o for o in off[nr:]]
+        e_cap = rcap[:nr] + sizes[nr:]
+        e_toff = rtoff + itoff[nr:]
         d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
         bt.sf_build_codes(st, nb, e_freq, d_tab)
         ocap = [c + c // 2 + 64 for c in e_cap]                             # compress_files' bound
@@ -978,7 +1069,7 @@ def _compress_group(d_in, start, split, files, force_rle, force_freq, st, result
         modes = [b"R" if u else b"N" for u in use]
         pack(bt.pack_payloads_files, use, lambda i: ".rle", lambda i: pack_payloads_max([rcap[b] for b in blocks(i)],
                                                                                         FRAME_RAW),
-             lambda fs: (FRAME_RAW, d_rle, roff, rcap, d_rle_n))
+             lambda fs: (FRAME_RAW, d_rle, roff + [0] * (nb - nr), rcap, e_n))
         pack(bt.pack_freq_files, [True] * nf, lambda i: ".rle.freq" if use[i] else ".freq", lambda i: pack_freq_max(count[i]),
              lambda fs: ([modes[i] for i in fs], e_n, e_freq))
         if force_freq:

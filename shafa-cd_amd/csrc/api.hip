@@ -437,6 +437,20 @@ int shafa_hipd_rle_decoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
     return rlemeasure_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
 }
 
+int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                                    uint64_t *d_out_n)
+{
+    if (!b || !d_in_n || !d_out_n) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || !h_in_cap) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return rleesize_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
+}
+
 }  // extern "C"
 
 // the call itself (not a block) failed: no block has a result — every block reports the call's code
