@@ -206,6 +206,21 @@ void batch_stage_retire(Batch *b, hipStream_t st)
     if (segs.empty()) b->stage_used = 0;
 }
 
+// the argument checks of the two size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev), then the pass
+static int size_pass_dev(int (*launch)(Batch *, hipStream_t, int, const u8 *, const u64 *, const u64 *, const u64 *, u64 *),
+                         Batch *b, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                         const u64 *d_in_n, u64 *d_out_n)
+{
+    if (!b || !d_in_n || !d_out_n) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > b->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || !h_in_cap) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter(b, st)) return rc;
+    return launch(b, st, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
+}
+
 extern "C" {
 
 int shafa_hip_abi_version(void) { return SHAFA_HIP_ABI_VERSION; }
@@ -232,7 +247,6 @@ int shafa_hip_set_option(const char *name, long value)
         return SHAFA_SUCCESS;
     }
     if (name && !strcmp(name, "sf_encode_lanes")) {
-        extern int g_sfe_lanes;
         if (value != 0 && value != 256 && value != 512) return SHAFA_OUTSIDE_MODULE;
         g_sfe_lanes = (int)value;
         return SHAFA_SUCCESS;
@@ -427,28 +441,16 @@ int shafa_hipd_rle_decoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                                     uint64_t *d_out_n)
 {
-    if (!b || !d_in_n || !d_out_n) return SHAFA_OUTSIDE_MODULE;
-    if (nblocks <= 0) return SHAFA_SUCCESS;
-    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
-    if (!h_in_off || !h_in_cap) return SHAFA_OUTSIDE_MODULE;
-    for (int i = 0; i < nblocks; ++i)
-        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
-    return rlemeasure_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
+    return size_pass_dev(rlemeasure_launch_dev, (Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n,
+                         d_out_n);
 }
 
 int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                                     const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                                     uint64_t *d_out_n)
 {
-    if (!b || !d_in_n || !d_out_n) return SHAFA_OUTSIDE_MODULE;
-    if (nblocks <= 0) return SHAFA_SUCCESS;
-    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
-    if (!h_in_off || !h_in_cap) return SHAFA_OUTSIDE_MODULE;
-    for (int i = 0; i < nblocks; ++i)
-        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
-    return rleesize_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
+    return size_pass_dev(rleesize_launch_dev, (Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n,
+                         d_out_n);
 }
 
 }  // extern "C"

@@ -185,6 +185,17 @@ int rleenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const 
 int sfdec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                      const u64 *d_in_n, const shafa_code_table *d_tables, const u64 *d_n_symbols, u8 *d_out,
                      const u64 *h_out_off, const u64 *h_out_cap);
+// Module C's kernel families behind sfenc_launch / sfenc_launch_dev: count / scan / pack (sf_encode3.hip), the one-pass chained
+// encoder for codes of <= 16 and of 17..32 bits (sf_encode4.hip), the tile-histogram one-shot (sf_encode6.hip) and the generic
+// form for device-planned lists (sf_encode.hip)
+void sfenc3_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 *d_tile_bits, u64 *d_tile_off, bool lut64);
+int sfenc4_launch(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
+int sfenc4_launch_long(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
+bool sfenc4_needs_redo(u32 lmax);
+bool sfenc4_long_ok();
+int sfenc6_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 lmax, bool any_ragged, u32 *d_tbits, u64 *d_toff);
+void sfenc_generic_launch_dev(hipStream_t st, const EncBlk *dblk, u32 grid, u64 *d_desc, u32 *d_tickets, const u32 *d_plan);
+extern int g_sfe_lanes;     // sf_encode4.hip: 0, or the workgroup width the one-pass encoder is held to (256 / 512)
 // rledec_launch with the block sizes in DEVICE memory (descriptors laid out from h_in_cap)
 int rledec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                       const u64 *d_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n);
@@ -215,3 +226,7 @@ void sfdec_configure(int speculate);
 void sfdec_configure_path(int path);
 void rleenc_configure(int force_general);
 int gen_launch(hipStream_t st, u64 seed, u64 first, const u8 *d_map, u8 *d_out, size_t n);
+
+// ---- api.hip, for layer 3 (pipe.hip) ----------------------------------------------------------------
+int api_lazy_init();                          // shafa_hip_init(0) unless a device was selected already
+int api_pipe_device(int slot, int n_slots);   // device of slot `slot` of a pipe of n_slots (shafa_hip_init_devices), else the layer-1 device

@@ -17,9 +17,9 @@
 //   pack_text<CodText | FreqText>          one workgroup per block, a lane per symbol: header and fields
 // Every later kernel reads the verdict word first and returns when the plan refused the file: then no byte of d_dst is written.
 // Segmented packs (shafa_hipd_pack_*_files: many files in one launch sequence) add
-//   pack_file_plan                         one workgroup per file: pack_plan's scan and checks over the file's blocks, its
-//                                          length and its verdict; a refused file's descriptors get n = 0, hdr_len = 0
-//   pack_file_text<CodText | FreqText>     pack_text without the file's head and tail, per descriptor slot
+//   pack_file_plan                         one workgroup per file: pack_plan's scan and checks (plan_frames) over the file's
+//                                          blocks, its length and its verdict; a refused file's descriptors get n = 0, hdr_len = 0
+//   pack_file_text<CodText | FreqText>     pack_text without the file's head and tail (text_frame), per descriptor slot
 //   pack_file_ends                         a lane per file: its "@<n>" / "@<mode>@<n>" head and its "@0" tail
 // and run pack_measure, pack_bulk and pack_seams as they are.
 //
@@ -54,19 +54,24 @@ struct PackSrc {
     u64 cap;
 };
 
-struct PlanArgs {
-    int nblocks;
+// what a plan reads per block of the call, for one file (pack_plan) or many (pack_file_plan)
+struct PlanBlocks {
     u32 hdr;                 // 1: every block's frame starts with "@<size>@"
     const PackSrc *srcs;     // payloads: sources and capacities; text: nullptr
     const u64 *n;            // body sizes: d_src_n (payloads) or the measure kernel's lengths (text)
     const u64 *hdr_vals;     // the numbers of the block headers: nullptr = the body sizes
+    PackDesc *desc;
+    u32 *verdict;            // the movers' word.  One file: 1 to write it, 0: refused (bad size, or too long for dst_cap)
+    int *err;                // per block
+};
+
+struct PlanArgs {
+    PlanBlocks blk;
+    int nblocks;
     u64 head_len, tail_len;  // the file's prefix and suffix ("@<n>", "@<mode>@<n>", "@0")
     u8 *dst;
     u64 dst_cap;
     u64 *dst_n;
-    PackDesc *desc;
-    u32 *verdict;            // 1: write the file; 0: refused (bad size, or too long for dst_cap)
-    int *err;
 };
 
 __host__ __device__ inline u32 dec_digits(u64 v)
@@ -101,19 +106,24 @@ __device__ inline u64 wg_excl_scan(u64 v, u64 *wsum, u64 *total)
     return base + incl - v;
 }
 
-__global__ __launch_bounds__(PLAN_THREADS) void pack_plan(PlanArgs a)
+// One workgroup plans one file: blocks first .. first + count - 1 of the call's arrays, their descriptors at desc[0 .. count),
+// their frames back to back from dst + head_len.  Header lengths, the exclusive scan of the frames, the capacity checks, *dst_n
+// and the verdict, which thread 0 returns (1: write the file); a file too long for cap is reported in *err_long.
+__device__ __forceinline__ u32 plan_frames(const PlanBlocks &a, int first, int count, PackDesc *desc, u8 *dst, u64 cap,
+                                           u64 head_len, u64 tail_len, u64 *dst_n, int *err_long)
 {
     __shared__ u64 wsum[PLAN_THREADS / 64];
     __shared__ u32 bad_sh;
     const u32 tid = threadIdx.x;
     if (tid == 0) bad_sh = 0;
     __syncthreads();
-    u64 pos = a.head_len;                            // the next frame's offset in the file
-    for (int b0 = 0; b0 < a.nblocks; b0 += PLAN_THREADS) {
-        const int b = b0 + (int)tid;
+    u64 pos = head_len;                              // the next frame's offset in the file
+    for (int i0 = 0; i0 < count; i0 += PLAN_THREADS) {
+        const int i = i0 + (int)tid;
         u64 frame = 0;
         PackDesc d = {};
-        if (b < a.nblocks) {
+        if (i < count) {
+            const int b = first + i;
             const u64 n = a.n[b];
             if (a.srcs) {
                 const PackSrc s = a.srcs[b];
@@ -130,28 +140,34 @@ __global__ __launch_bounds__(PLAN_THREADS) void pack_plan(PlanArgs a)
         }
         u64 sum;
         const u64 off = pos + wg_excl_scan(frame, wsum, &sum);
-        if (b < a.nblocks) {
-            d.dst = a.dst + off;
-            a.desc[b] = d;
+        if (i < count) {
+            d.dst = dst + off;
+            desc[i] = d;
         }
         pos += sum;
     }
     __syncthreads();
+    u32 go = 1;
     if (tid == 0) {
-        const u64 total = pos + a.tail_len;
-        u32 go = 1;
+        const u64 total = pos + tail_len;
         if (bad_sh) {
             go = 0;
-            *a.dst_n = 0;
+            *dst_n = 0;
         } else {
-            *a.dst_n = total;
-            if (total > a.dst_cap) {
-                set_error(a.err, SHAFA_LACK_OF_MEMORY);
+            *dst_n = total;
+            if (total > cap) {
+                set_error(err_long, SHAFA_LACK_OF_MEMORY);
                 go = 0;
             }
         }
-        *a.verdict = go;
     }
+    return go;
+}
+
+__global__ __launch_bounds__(PLAN_THREADS) void pack_plan(PlanArgs a)
+{
+    const u32 go = plan_frames(a.blk, 0, a.nblocks, a.blk.desc, a.dst, a.dst_cap, a.head_len, a.tail_len, a.dst_n, a.blk.err);
+    if (threadIdx.x == 0) *a.blk.verdict = go;
 }
 
 // the destination words of a payload that lie entirely inside it: [w_lo, w_hi) in units of 16 bytes of address
@@ -304,15 +320,12 @@ __global__ __launch_bounds__(256) void pack_measure(Text tx, u64 *__restrict__ b
     if (threadIdx.x == 0) body[b] = total;
 }
 
-// block b's frame: "@<size>@" + fields; block 0 also the file's head "@<mode>@<n>", the last block the file's "@0"
+// block b's frame at its descriptor: "@<size>@" + fields
 template <typename Text>
-__global__ __launch_bounds__(256) void pack_text(Text tx, const PackDesc *__restrict__ desc, int nblocks,
-                                                 const u32 *__restrict__ verdict, u8 *dst, char mode)
+__device__ __forceinline__ void text_frame(const Text &tx, int b, const PackDesc &d)
 {
     __shared__ u32 wsum32[4];
-    if (*verdict == 0) return;
-    const int b = blockIdx.x, s = (int)threadIdx.x;
-    const PackDesc d = desc[b];
+    const int s = (int)threadIdx.x;
     u32 total;
     const u32 off = field_scan(tx.len(b, s), wsum32, &total);
     u8 *body = d.dst + d.hdr_len;
@@ -324,6 +337,17 @@ __global__ __launch_bounds__(256) void pack_text(Text tx, const PackDesc *__rest
         o = put_dec(o, d.hdr_val);
         *o = '@';
     }
+}
+
+// block b's frame; block 0 also the file's head "@<mode>@<n>", the last block the file's "@0"
+template <typename Text>
+__global__ __launch_bounds__(256) void pack_text(Text tx, const PackDesc *__restrict__ desc, int nblocks,
+                                                 const u32 *__restrict__ verdict, u8 *dst, char mode)
+{
+    if (*verdict == 0) return;
+    const int b = blockIdx.x, s = (int)threadIdx.x;
+    const PackDesc d = desc[b];
+    text_frame(tx, b, d);
     if (s == 1 && b == 0) {
         dst[0] = '@';
         dst[1] = (u8)mode;
@@ -331,7 +355,7 @@ __global__ __launch_bounds__(256) void pack_text(Text tx, const PackDesc *__rest
         put_dec(dst + 3, (u64)nblocks);
     }
     if (s == 2 && b == nblocks - 1) {
-        u8 *e = body + d.n;
+        u8 *e = d.dst + d.hdr_len + d.n;
         e[0] = '@';
         e[1] = '0';
     }
@@ -356,6 +380,38 @@ int pack_ws(Batch *bt, hipStream_t st, int nblocks, PackWs &w)
     return SHAFA_SUCCESS;
 }
 
+PlanBlocks plan_blocks(u32 hdr, const PackSrc *srcs, const u64 *n, const u64 *hdr_vals, PackDesc *desc, u32 *verdict, int *err)
+{
+    PlanBlocks p = {};
+    p.hdr = hdr;
+    p.srcs = srcs;
+    p.n = n;
+    p.hdr_vals = hdr_vals;
+    p.desc = desc;
+    p.verdict = verdict;
+    p.err = err;
+    return p;
+}
+
+// pack_bulk's grid x: the chunks of the largest of nb payload regions
+int bulk_chunks(int nb, const u64 *h_src_cap, u64 &max_chunks)
+{
+    max_chunks = 1;
+    for (int b = 0; b < nb; ++b) {
+        const u64 c = ceil_div_u64(h_src_cap[b] / 16 + 1, BULK_CHUNK_WORDS);
+        if (c > max_chunks) max_chunks = c;
+    }
+    return max_chunks > 0x7FFFFFFFull ? SHAFA_LACK_OF_MEMORY : SHAFA_SUCCESS;
+}
+
+void stage_srcs(PackSrc *hp, int nb, const u8 *d_src, const u64 *h_src_off, const u64 *h_src_cap)
+{
+    for (int b = 0; b < nb; ++b) {
+        hp[b].src = d_src + h_src_off[b];
+        hp[b].cap = h_src_cap[b];
+    }
+}
+
 template <typename Text>
 int text_launch(Batch *bt, hipStream_t st, int nblocks, char mode, const u64 *d_sizes, Text tx, u8 *d_dst, u64 dst_cap,
                 u64 *d_dst_n)
@@ -365,19 +421,13 @@ int text_launch(Batch *bt, hipStream_t st, int nblocks, char mode, const u64 *d_
     if (int rc = pack_ws(bt, st, nblocks, w)) return rc;
     hipLaunchKernelGGL(pack_measure<Text>, dim3((u32)nblocks), dim3(256), 0, st, tx, w.body);
     PlanArgs a = {};
+    a.blk = plan_blocks(1, nullptr, w.body, d_sizes, w.desc, w.verdict, bt->d_err);
     a.nblocks = nblocks;
-    a.hdr = 1;
-    a.srcs = nullptr;
-    a.n = w.body;
-    a.hdr_vals = d_sizes;
     a.head_len = 3 + dec_digits((u64)nblocks);       // "@<mode>@<n>"
     a.tail_len = 2;                                  // "@0"
     a.dst = d_dst;
     a.dst_cap = dst_cap;
     a.dst_n = d_dst_n;
-    a.desc = w.desc;
-    a.verdict = w.verdict;
-    a.err = bt->d_err;
     hipLaunchKernelGGL(pack_plan, dim3(1), dim3(PLAN_THREADS), 0, st, a);
     hipLaunchKernelGGL(pack_text<Text>, dim3((u32)nblocks), dim3(256), 0, st, tx, (const PackDesc *)w.desc, nblocks,
                        (const u32 *)w.verdict, d_dst, mode);
@@ -391,38 +441,25 @@ int payload_launch(Batch *bt, hipStream_t st, int nblocks, int framing, const u8
     if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
     PackWs w;
     if (int rc = pack_ws(bt, st, nblocks, w)) return rc;
-    u64 max_chunks = 1;
-    for (int b = 0; b < nblocks; ++b) {
-        const u64 c = ceil_div_u64(h_src_cap[b] / 16 + 1, BULK_CHUNK_WORDS);
-        if (c > max_chunks) max_chunks = c;
-    }
-    if (max_chunks > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    u64 max_chunks;
+    if (int rc = bulk_chunks(nblocks, h_src_cap, max_chunks)) return rc;
     const size_t par_bytes = (size_t)nblocks * sizeof(PackSrc);
     u8 *dpar = batch_params_begin(bt, par_bytes);
     if (!dpar) return SHAFA_LACK_OF_MEMORY;
     ParamsScope pscope(bt, st);
     PackSrc *hp = (PackSrc *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
     if (!hp) return SHAFA_LACK_OF_MEMORY;
-    for (int b = 0; b < nblocks; ++b) {
-        hp[b].src = d_src + h_src_off[b];
-        hp[b].cap = h_src_cap[b];
-    }
+    stage_srcs(hp, nblocks, d_src, h_src_off, h_src_cap);
     if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
     const bool shaf = framing == SHAFA_FRAME_SHAF;
     PlanArgs a = {};
+    a.blk = plan_blocks(shaf ? 1u : 0u, (const PackSrc *)dpar, d_src_n, nullptr, w.desc, w.verdict, bt->d_err);
     a.nblocks = nblocks;
-    a.hdr = shaf ? 1u : 0u;
-    a.srcs = (const PackSrc *)dpar;
-    a.n = d_src_n;
-    a.hdr_vals = nullptr;
     a.head_len = shaf ? 1 + dec_digits((u64)nblocks) : 0;     // "@<n>"
     a.tail_len = 0;
     a.dst = d_dst;
     a.dst_cap = dst_cap;
     a.dst_n = d_dst_n;
-    a.desc = w.desc;
-    a.verdict = w.verdict;
-    a.err = bt->d_err;
     hipLaunchKernelGGL(pack_plan, dim3(1), dim3(PLAN_THREADS), 0, st, a);
     hipLaunchKernelGGL(pack_bulk, dim3((u32)max_chunks, (u32)nblocks), dim3(BULK_THREADS), 0, st, (const PackDesc *)w.desc,
                        (const u32 *)w.verdict);
@@ -446,19 +483,13 @@ struct FileRec {
 };
 
 struct FilesPlanArgs {
+    PlanBlocks blk;          // desc: per slot; verdict: 1
     const FileRec *files;
-    u32 hdr;                 // 1: every block's frame starts with "@<size>@"
     u32 head;                // the file's prefix: 0 none, 1 "@<n>", 2 "@<mode>@<n>"
     u64 tail_len;            // "@0": 2, else 0
-    const PackSrc *srcs;     // payloads: sources and capacities per block; text: nullptr
-    const u64 *n;            // body sizes per block
-    const u64 *hdr_vals;     // the numbers of the block headers per block: nullptr = the body sizes
     u64 *dst_n;              // per file
-    PackDesc *desc;          // per slot
     u32 *slot_file;          // per slot: its file
     u32 *fverdict;           // per file
-    u32 *verdict;            // the movers' word: 1
-    int *err;                // per block
 };
 
 __device__ inline u64 file_head_len(u32 head, int count)
@@ -469,66 +500,25 @@ __device__ inline u64 file_head_len(u32 head, int count)
 // one workgroup per file: pack_plan's scan and checks over the file's blocks
 __global__ __launch_bounds__(PLAN_THREADS) void pack_file_plan(FilesPlanArgs a)
 {
-    __shared__ u64 wsum[PLAN_THREADS / 64];
-    __shared__ u32 bad_sh, go_sh;
+    __shared__ u32 go_sh;
     const u32 tid = threadIdx.x, f = blockIdx.x;
     const FileRec fr = a.files[f];
-    if (tid == 0) bad_sh = 0;
-    __syncthreads();
-    u64 pos = file_head_len(a.head, fr.count);
-    for (int i0 = 0; i0 < fr.count; i0 += PLAN_THREADS) {
-        const int i = i0 + (int)tid;
-        u64 frame = 0;
-        PackDesc d = {};
-        if (i < fr.count) {
-            const int b = fr.first + i;
-            const u64 n = a.n[b];
-            if (a.srcs) {
-                const PackSrc s = a.srcs[b];
-                if (n > s.cap) {
-                    set_error(a.err + b, SHAFA_OUTSIDE_MODULE);
-                    atomicOr(&bad_sh, 1u);
-                }
-                d.src = s.src;
-            }
-            d.n = n;
-            d.hdr_val = a.hdr_vals ? a.hdr_vals[b] : n;
-            d.hdr_len = a.hdr ? 2u + dec_digits(d.hdr_val) : 0u;
-            frame = d.hdr_len + n;
-        }
-        u64 sum;
-        const u64 off = pos + wg_excl_scan(frame, wsum, &sum);
-        if (i < fr.count) {
-            d.dst = fr.dst + off;
-            a.desc[fr.slot + i] = d;
-            a.slot_file[fr.slot + i] = f;
-        }
-        pos += sum;
-    }
-    __syncthreads();
+    PackDesc *desc = a.blk.desc + fr.slot;
+    const u32 go = plan_frames(a.blk, fr.first, fr.count, desc, fr.dst, fr.cap, file_head_len(a.head, fr.count), a.tail_len,
+                               a.dst_n + f, a.blk.err + fr.first);
     if (tid == 0) {
-        const u64 total = pos + a.tail_len;
-        u32 go = 1;
-        if (bad_sh) {
-            go = 0;
-            a.dst_n[f] = 0;
-        } else {
-            a.dst_n[f] = total;
-            if (total > fr.cap) {
-                set_error(a.err + fr.first, SHAFA_LACK_OF_MEMORY);
-                go = 0;
-            }
-        }
         go_sh = go;
         a.fverdict[f] = go;
-        if (f == 0) *a.verdict = 1;
+        if (f == 0) *a.blk.verdict = 1;
     }
     __syncthreads();
-    if (!go_sh)                                      // each lane rewrites the slots it wrote above
-        for (int i = (int)tid; i < fr.count; i += PLAN_THREADS) {
-            a.desc[fr.slot + i].n = 0;
-            a.desc[fr.slot + i].hdr_len = 0;
+    for (int i = (int)tid; i < fr.count; i += PLAN_THREADS) {      // each lane: the slots it wrote in plan_frames
+        a.slot_file[fr.slot + i] = f;
+        if (!go_sh) {
+            desc[i].n = 0;
+            desc[i].hdr_len = 0;
         }
+    }
 }
 
 // a lane per file: its prefix ("@<n>" / "@<mode>@<n>") and, for text, its "@0"
@@ -559,23 +549,10 @@ template <typename Text>
 __global__ __launch_bounds__(256) void pack_file_text(Text tx, const PackDesc *__restrict__ desc, const FileRec *__restrict__ files,
                                                       const u32 *__restrict__ slot_file, const u32 *__restrict__ fverdict)
 {
-    __shared__ u32 wsum32[4];
     const u32 i = blockIdx.x, f = slot_file[i];
     if (fverdict[f] == 0) return;
     const FileRec fr = files[f];
-    const int b = fr.first + (int)(i - fr.slot), s = (int)threadIdx.x;
-    const PackDesc d = desc[i];
-    u32 total;
-    const u32 off = field_scan(tx.len(b, s), wsum32, &total);
-    u8 *body = d.dst + d.hdr_len;
-    tx.put(b, s, body + off);
-    if (s != 255) body[off + tx.len(b, s)] = ';';
-    if (s == 0) {
-        u8 *o = d.dst;
-        *o++ = '@';
-        o = put_dec(o, d.hdr_val);
-        *o = '@';
-    }
+    text_frame(tx, fr.first + (int)(i - fr.slot), desc[i]);
 }
 
 // the host's view of a segmented call: the blocks it reads ([0, nb)) and its descriptor slots
@@ -661,19 +638,13 @@ int text_files_launch(Batch *bt, hipStream_t st, int nfiles, const FilesShape &s
     const FileRec *d_files = (const FileRec *)dpar;
     hipLaunchKernelGGL(pack_measure<Text>, dim3((u32)sh.nb), dim3(256), 0, st, tx, w.body);
     FilesPlanArgs a = {};
+    a.blk = plan_blocks(1, nullptr, w.body, d_sizes, w.desc, w.verdict, bt->d_err);
     a.files = d_files;
-    a.hdr = 1;
     a.head = 2;                                      // "@<mode>@<n>"
     a.tail_len = 2;                                  // "@0"
-    a.srcs = nullptr;
-    a.n = w.body;
-    a.hdr_vals = d_sizes;
     a.dst_n = d_dst_n;
-    a.desc = w.desc;
     a.slot_file = w.slot_file;
     a.fverdict = w.fverdict;
-    a.verdict = w.verdict;
-    a.err = bt->d_err;
     hipLaunchKernelGGL(pack_file_plan, dim3((u32)nfiles), dim3(PLAN_THREADS), 0, st, a);
     hipLaunchKernelGGL(pack_file_text<Text>, dim3(sh.slots), dim3(256), 0, st, tx, (const PackDesc *)w.desc, d_files,
                        (const u32 *)w.slot_file, (const u32 *)w.fverdict);
@@ -687,12 +658,8 @@ int payload_files_launch(Batch *bt, hipStream_t st, int nfiles, const FilesShape
                          int framing, const u8 *d_src, const u64 *h_src_off, const u64 *h_src_cap, const u64 *d_src_n, u8 *d_dst,
                          const u64 *h_dst_off, const u64 *h_dst_cap, u64 *d_dst_n)
 {
-    u64 max_chunks = 1;
-    for (int b = 0; b < sh.nb; ++b) {
-        const u64 c = ceil_div_u64(h_src_cap[b] / 16 + 1, BULK_CHUNK_WORDS);
-        if (c > max_chunks) max_chunks = c;
-    }
-    if (max_chunks > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    u64 max_chunks;
+    if (int rc = bulk_chunks(sh.nb, h_src_cap, max_chunks)) return rc;
     int max_y = 0;
     HIP_TRY(hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, bt->device));
     if (max_y < 1) max_y = 1;
@@ -705,28 +672,18 @@ int payload_files_launch(Batch *bt, hipStream_t st, int nfiles, const FilesShape
     FileRec *hp = (FileRec *)batch_stage(bt, bt->par_inline ? st : bt->copy_st, par_bytes);
     if (!hp) return SHAFA_LACK_OF_MEMORY;
     files_records(hp, nfiles, h_first, h_count, nullptr, d_dst, h_dst_off, h_dst_cap);
-    PackSrc *hs = (PackSrc *)((u8 *)hp + o_src);
-    for (int b = 0; b < sh.nb; ++b) {
-        hs[b].src = d_src + h_src_off[b];
-        hs[b].cap = h_src_cap[b];
-    }
+    stage_srcs((PackSrc *)((u8 *)hp + o_src), sh.nb, d_src, h_src_off, h_src_cap);
     if (int rc = batch_params_commit(bt, st, hp, par_bytes)) return rc;
     const FileRec *d_files = (const FileRec *)dpar;
     const bool shaf = framing == SHAFA_FRAME_SHAF;
     FilesPlanArgs a = {};
+    a.blk = plan_blocks(shaf ? 1u : 0u, (const PackSrc *)(dpar + o_src), d_src_n, nullptr, w.desc, w.verdict, bt->d_err);
     a.files = d_files;
-    a.hdr = shaf ? 1u : 0u;
     a.head = shaf ? 1u : 0u;                         // "@<n>"
     a.tail_len = 0;
-    a.srcs = (const PackSrc *)(dpar + o_src);
-    a.n = d_src_n;
-    a.hdr_vals = nullptr;
     a.dst_n = d_dst_n;
-    a.desc = w.desc;
     a.slot_file = w.slot_file;
     a.fverdict = w.fverdict;
-    a.verdict = w.verdict;
-    a.err = bt->d_err;
     hipLaunchKernelGGL(pack_file_plan, dim3((u32)nfiles), dim3(PLAN_THREADS), 0, st, a);
     // the bulk grid puts slots on y: in slices of at most the device's grid height
     for (u32 s0 = 0; s0 < sh.slots; s0 += (u32)max_y) {

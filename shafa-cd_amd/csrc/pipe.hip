@@ -19,10 +19,6 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-int shafa_set_hip_error(hipError_t e, const char *what);
-int api_lazy_init();      // api.hip: shafa_hip_init(0) unless a device was selected already
-int api_pipe_device(int slot, int n_slots);   // api.hip: device of slot `slot` of a pipe of n_slots (shafa_hip_init_devices), else the layer-1 device
-
 #define PIPE_GROUP_MAX SHAFA_PIPE_GROUP_MAX
 
 namespace {

@@ -7,12 +7,14 @@
 #pragma once
 
 #include "common.hpp"
+#include "tile_pass.hpp"
 
 namespace {
 
-constexpr int RLD_THREADS = 256;
-constexpr int RLD_BPL = 32;                        // bytes per lane
-constexpr int RLD_TILE = RLD_THREADS * RLD_BPL;
+// the decoder's tile is the size pass's: its exact output regions are measured tile by tile
+constexpr int RLD_THREADS = TP_THREADS;
+constexpr int RLD_BPL = TP_BPL;                    // bytes per lane (fsm32 takes a lane's zero mask)
+constexpr int RLD_TILE = TP_TILE;
 constexpr u32 FN_IDENT = 0u | (1u << 2) | (2u << 4);
 
 // per 8-bit zero mask (bit i = byte i is 0) and entry state s: bits [10 s, 10 s + 8) = token starts, [10 s + 8, 10 s + 10) = exit

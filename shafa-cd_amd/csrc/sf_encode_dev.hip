@@ -144,12 +144,6 @@ __global__ __launch_bounds__(256) void sfe_plan_kernel(const PlanBlk *__restrict
 
 }  // namespace
 
-void sfenc3_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 *d_tile_bits, u64 *d_tile_off, bool lut64);
-int sfenc4_launch(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
-int sfenc4_launch_long(hipStream_t st, const EncBlk *dblk, int count, u64 *d_desc, u32 *d_tickets, u32 lmax, u32 ragged, const SfeRedo &x);
-int sfenc6_launch(hipStream_t st, const EncBlk *dblk, int count, u32 max_tiles, u32 lmax, bool any_ragged, u32 *d_tbits, u64 *d_toff);
-void sfenc_generic_launch_dev(hipStream_t st, const EncBlk *dblk, u32 grid, u64 *d_desc, u32 *d_tickets, const u32 *d_plan);
-
 int sfenc_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                      const u64 *d_in_n, const shafa_code_table *d_tables, u8 *d_out, const u64 *h_out_off,
                      const u64 *h_out_cap, u64 *d_out_n, const u8 *d_thist, const u64 *h_thist_off)
