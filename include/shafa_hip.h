@@ -308,6 +308,45 @@ int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                                     uint64_t *d_out_n);
 
+/* The histograms of the blocks' RLE bytes without the RLE bytes: d_freq[b * 256 + s] = the count shafa_hipd_rle_encode leaves
+ * in its d_freq for the d_in_n[b] (<= h_in_cap[b]) bytes at d_in + h_in_off[b] when it is given room enough, and d_out_n[b] =
+ * the size shafa_hipd_rle_encoded_size_dev leaves, which is the sum of the block's 256 counts.  Per maximal run of byte s with
+ * length L, q = L / 255 and m = L % 255 (f.c:29-55): q to each of the counts of 0, s and 255; then, for m > 0, one to each of
+ * 0, s and m if s == 0 or m >= 4, else m to s.  Runs end at the block's end; counts that coincide (s == 0, s == 255, s == m)
+ * stack.  d_freq[0 .. 256 nblocks) is overwritten, not added to.  No byte of output is written anywhere except d_freq,
+ * d_out_n[0 .. nblocks) and the batch's error words, and d_in is only read.  Per-block codes through shafa_hipd_finish:
+ *   d_in_n[b] > h_in_cap[b]                SHAFA_OUTSIDE_MODULE, d_out_n[b] = 0 and 256 zeros (no byte of the block is read).
+ * d_in_n[b] = 0 is size 0, 256 zeros and success.  No block is ever SHAFA_LACK_OF_MEMORY or SHAFA_FILE_UNRECOGNIZABLE.
+ * With these counts Module T (shafa_hipd_sf_build_codes) and shafa_hipd_sf_encoded_size_dev complete for an RLE file
+ * without its .rle bytes.
+ * Two launches, as shafa_hipd_rle_encoded_size_dev — every 8 KiB tile on its own (its bytes and the runs inside it, counted
+ * in local memory and added to the block's counts with at most 256 atomics per workgroup and block), then one workgroup per
+ * block (the runs that touch a tile border: at most two per tile) — in which no workgroup waits for another; the grid is the
+ * tile count of the call, so any nblocks <= max_blocks with any mix of capacities is measured.  The device workspace is 16
+ * bytes per 8 KiB of sum(h_in_cap) plus 20 bytes per block.
+ * Enqueues only, as shafa_hipd_rle_encoded_size_dev: d_in_n is never read on the host, no device-to-host copy is issued and
+ * nothing is synchronised; the one exception is the batch's growth, from nblocks and h_in_cap.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_in_n, d_out_n,
+ * d_freq, h_in_off or h_in_cap, or an h_in_off[b] that is not a multiple of 16: SHAFA_OUTSIDE_MODULE (a NULL batch comes
+ * first); nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY (so is a call of 2^31 tiles or more); nblocks <= 0: success. */
+int shafa_hipd_rle_encoded_hist_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                                    uint64_t *d_out_n, uint64_t *d_freq);
+
+/* The Shannon-Fano sizes of blocks without encoding them: d_out_n[b] = the d_out_n[b] shafa_hipd_sf_encode_dev leaves for a
+ * block whose histogram is d_freq[b * 256 ..] (what shafa_hipd_hist256 or shafa_hipd_rle_encoded_hist_dev leaves), encoded
+ * with d_tables[b] into room enough: ceil(sum over s of d_freq[b * 256 + s] * len[s] / 8), the bits summed in 64 bits.
+ * Per-block codes through shafa_hipd_finish, by binary_coding's rules:
+ *   every code of the table is empty       size 0 and success (a block of one symbol);
+ *   a symbol with a count and no code, in a table that holds a code
+ *                                          SHAFA_FILE_UNRECOGNIZABLE, d_out_n[b] = 0;
+ *   the bits do not fit 64 bits            SHAFA_OUTSIDE_MODULE, d_out_n[b] = 0 (never for a block's own histogram).
+ * One workgroup per block.  Enqueues only, as shafa_hipd_sf_build_codes: nothing is read on the host or synchronised.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_freq, d_tables or
+ * d_out_n: SHAFA_OUTSIDE_MODULE; nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY; nblocks <= 0: success. */
+int shafa_hipd_sf_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
+                                   const shafa_code_table *d_tables, uint64_t *d_out_n);
+
 /* ---- Files in device memory: .rle, .shaf, .cod and .freq assembled from what the entries above leave -------------------
  * Each call writes ONE contiguous file at d_dst: every byte equals what the C host writes for the same sizes, tables and
  * counts (host/modules.c's framing around host/formats.c's shafa_cod_format / shafa_freq_format) — empty codes, 255-bit

@@ -117,6 +117,8 @@ def lib():
     L.shafa_hipd_rle_decode_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_rle_decoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_rle_encoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
+    L.shafa_hipd_rle_encoded_hist_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp]
+    L.shafa_hipd_sf_encoded_size_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -169,7 +171,8 @@ def lib():
                  "shafa_hipd_pack_payloads_files", "shafa_hipd_pack_cod_files", "shafa_hipd_pack_freq_files",
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
-                 "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev"):
+                 "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
+                 "shafa_hipd_sf_encoded_size_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -400,6 +403,22 @@ class Batch:
         io, ic = _u64arr(in_off), _u64arr(in_cap)
         _check(lib().shafa_hipd_rle_encoded_size_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
                                                      d_in_n.data_ptr(), d_out_n.data_ptr()), "hipd_rle_encoded_size_dev")
+
+    def rle_encoded_hist_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_out_n, d_freq):
+        """d_freq[b * 256 + s] (int64) = the histogram rle_encode would leave for the d_in_n[b] bytes of block b with room
+        enough, d_out_n[b] its size; nothing is encoded and no output exists.  d_freq is overwritten.  Enqueues only
+        (include/shafa_hip.h: shafa_hipd_rle_encoded_hist_dev)."""
+        io, ic = _u64arr(in_off), _u64arr(in_cap)
+        _check(lib().shafa_hipd_rle_encoded_hist_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                                     d_in_n.data_ptr(), d_out_n.data_ptr(), d_freq.data_ptr()),
+               "hipd_rle_encoded_hist_dev")
+
+    def sf_encoded_size_dev(self, stream, nblocks, d_freq, d_tables, d_out_n):
+        """d_out_n[b] (int64) = the size sf_encode_dev would leave for a block with histogram d_freq[b * 256 ..] and table
+        d_tables[b] with room enough; nothing is encoded.  Enqueues only (include/shafa_hip.h:
+        shafa_hipd_sf_encoded_size_dev)."""
+        _check(lib().shafa_hipd_sf_encoded_size_dev(self.h, self._st(stream), nblocks, d_freq.data_ptr(), d_tables.data_ptr(),
+                                                    d_out_n.data_ptr()), "hipd_sf_encoded_size_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -935,6 +954,122 @@ def rle_encoded_sizes(d_in, sizes=None, block_size=65536, stream=None):
             results[f] = ShafaError(e, f"rle_encoded_sizes: block {b}") if e else \
                 (bool(host().shafa_rle_worthwhile(g.sizes[lo], r[lo], False)), r[lo:hi])
     return results
+
+
+def shaf_file_bytes(block_sizes):
+    """The length of a .shaf file whose blocks have these payload sizes: "@<blocks>", then "@<size>@" + payload per block
+    (c.c:351,256-258)."""
+    return 1 + len(str(len(block_sizes))) + sum(2 + len(str(int(n))) + int(n) for n in block_sizes)
+
+
+def compressed_sizes(d_in, sizes=None, block_size=65536, force_rle=False, force_freq=False, stream=None):
+    """How large will the files be?  compress_many's arguments and file split; one entry per file: a dict with the keys of
+    compress_many's dict for that file, each value the file's length in bytes (an int), or a ShafaError instance with the
+    code compress_many's entry has.  No payload byte is written or allocated: the data is read by rle_encoded_hist_dev (the
+    RLE histogram and size of every block) and by hist256 (the input's), neither an RLE stream nor a Shannon-Fano stream
+    exists.
+
+    Chain per batch of files: the two histogram passes over all blocks -> one synchronisation reading every block's RLE size;
+    each file's choice is shafa_rle_worthwhile on its block 0 -> each block's chosen histogram and size picked on the device
+    -> sf_build_codes -> sf_encoded_size_dev -> the .cod and .freq texts through the segmented packs (a few KiB a block:
+    writing them measures them) -> one finish.  ".rle" is the sum of the file's RLE sizes, ".shaf" shaf_file_bytes of its
+    Shannon-Fano sizes.  Two synchronisations per batch, one with force_rle, as compress_many; the same batches
+    (_many_files)."""
+    import torch
+    d_in, sizes, start, split, groups = _many_files("compressed_sizes", d_in, sizes, block_size)
+    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
+    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "compressed_sizes: fewer than 1024 bytes")
+               for f in range(len(sizes))]
+    for group in groups:
+        _sizes_group(d_in, start, split, group, force_rle, force_freq, st, results)
+    return results
+
+
+def _sizes_group(d_in, start, split, files, force_rle, force_freq, st, results):
+    import torch
+    dev = d_in.device
+    nf = len(files)
+    g = _GroupBlocks(start, split, files)
+    nb = g.nb
+    bt = Batch(nb, 2 * max(g.sizes) + 64)
+    try:
+        src_in, off = g.aligned(bt, st, d_in)
+        d_n_in = g.d_n_in(dev)
+        # ---- Module F's two histograms of every block, without an RLE stream: the choice needs the RLE sizes on the host,
+        # and a histogram of the input that ran before it costs no synchronisation of its own
+        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        d_freq_rle = torch.empty(nb * 256, dtype=torch.int64, device=dev)
+        d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+        bt.rle_encoded_hist_dev(st, src_in, off, g.sizes, d_n_in, d_rle_n, d_freq_rle)
+        errs0 = [SUCCESS] * nb
+        if force_rle:
+            use = [True] * nf
+        else:
+            bt.hist256(st, src_in, off, g.sizes, d_freq_in)
+            _, errs0 = bt.finish(st, nb, raise_on_error=False)
+            rsize = _u64_host(d_rle_n)
+            use = [bool(host().shafa_rle_worthwhile(g.sizes[g.first[i]], rsize[g.first[i]], False)) for i in range(nf)]
+        if force_rle and force_freq:
+            bt.hist256(st, src_in, off, g.sizes, d_freq_in)
+        # ---- per block: the RLE histogram and size, or the input's
+        if all(use):
+            e_n, e_freq = d_rle_n, d_freq_rle
+        elif not any(use):
+            e_n, e_freq = d_n_in, d_freq_in
+        else:
+            pick = torch.tensor([u for i, u in enumerate(use) for _ in range(g.count[i])], dtype=torch.bool, device=dev)
+            with torch.cuda.stream(st):
+                e_n = torch.where(pick, d_rle_n, d_n_in)
+                e_freq = torch.where(pick.repeat_interleave(256), d_freq_rle, d_freq_in)
+        # ---- Module T, and Module C's sizes
+        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.sf_build_codes(st, nb, e_freq, d_tab)
+        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+        bt.sf_encoded_size_dev(st, nb, e_freq, d_tab, d_enc_n)
+        # ---- the texts, for their lengths
+        lens = torch.zeros(3 * nf, dtype=torch.int64, device=dev)
+        kinds = []                                                          # per pack call: (its files, their keys)
+
+        def pack(call, sel, keys, cap, args):
+            fs = [i for i in range(nf) if sel[i]]
+            if not fs:
+                return
+            caps = [cap(g.count[i]) for i in fs]
+            doff, dtot = _layout(caps)
+            buf = torch.empty(dtot + 16, dtype=torch.uint8, device=dev)
+            n = lens[len(kinds) * nf:(len(kinds) + 1) * nf]
+            call(st, [g.first[i] for i in fs], [g.count[i] for i in fs], *args(fs), buf, doff, caps, n)
+            kinds.append((fs, [keys(i) for i in fs]))
+
+        modes = [b"R" if u else b"N" for u in use]
+        stem = lambda i: ".rle" if use[i] else ""                           # noqa: E731
+        pack(bt.pack_freq_files, [True] * nf, lambda i: stem(i) + ".freq", pack_freq_max,
+             lambda fs: ([modes[i] for i in fs], e_n, e_freq))
+        if force_freq:
+            pack(bt.pack_freq_files, use, lambda i: ".freq", pack_freq_max,
+                 lambda fs: ([b"N"] * len(fs), d_n_in, d_freq_in))
+        pack(bt.pack_cod_files, [True] * nf, lambda i: stem(i) + ".cod", pack_cod_max,
+             lambda fs: ([modes[i] for i in fs], e_n, d_tab))
+        _, errs = bt.finish(st, nb, raise_on_error=False)
+        got = lens.cpu().tolist()
+        rsize, esize = _u64_host(d_rle_n), _u64_host(d_enc_n)
+        out = [{} for _ in range(nf)]
+        for i in range(nf):
+            lo, hi = g.first[i], g.first[i] + g.count[i]
+            if use[i]:
+                out[i][".rle"] = int(sum(rsize[lo:hi]))
+            out[i][stem(i) + ".shaf"] = shaf_file_bytes(esize[lo:hi])
+        for k, (fs, keys) in enumerate(kinds):
+            for j, i in enumerate(fs):
+                out[i][keys[j]] = int(got[k * nf + j])
+        for i, f in enumerate(files):
+            lo, hi = g.first[i], g.first[i] + g.count[i]
+            b, e = _first_error(errs0[lo:hi])
+            if not e:
+                b, e = _first_error(errs[lo:hi])
+            results[f] = ShafaError(e, f"compressed_sizes: block {b}") if e else out[i]
+    finally:
+        bt.close()
 
 
 class _GroupBlocks:

@@ -206,18 +206,30 @@ void batch_stage_retire(Batch *b, hipStream_t st)
     if (segs.empty()) b->stage_used = 0;
 }
 
-// the argument checks of the two size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev), then the pass
+// the argument checks of the size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev,
+// shafa_hipd_rle_encoded_hist_dev), before HIP is touched: true = launch the pass, false = the call returns *rc
+static bool size_pass_enter(Batch *b, hipStream_t st, int nblocks, const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n,
+                            const u64 *d_out_n, int *rc)
+{
+    *rc = SHAFA_OUTSIDE_MODULE;
+    if (!b || !d_in_n || !d_out_n) return false;
+    *rc = SHAFA_SUCCESS;
+    if (nblocks <= 0) return false;
+    *rc = SHAFA_LACK_OF_MEMORY;
+    if (nblocks > b->max_blocks) return false;
+    *rc = SHAFA_OUTSIDE_MODULE;
+    if (!h_in_off || !h_in_cap) return false;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_in_off[i] & 15) return false;
+    return (*rc = batch_enter(b, st)) == SHAFA_SUCCESS;
+}
+
 static int size_pass_dev(int (*launch)(Batch *, hipStream_t, int, const u8 *, const u64 *, const u64 *, const u64 *, u64 *),
                          Batch *b, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                          const u64 *d_in_n, u64 *d_out_n)
 {
-    if (!b || !d_in_n || !d_out_n) return SHAFA_OUTSIDE_MODULE;
-    if (nblocks <= 0) return SHAFA_SUCCESS;
-    if (nblocks > b->max_blocks) return SHAFA_LACK_OF_MEMORY;
-    if (!h_in_off || !h_in_cap) return SHAFA_OUTSIDE_MODULE;
-    for (int i = 0; i < nblocks; ++i)
-        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-    if (int rc = batch_enter(b, st)) return rc;
+    int rc;
+    if (!size_pass_enter(b, st, nblocks, h_in_off, h_in_cap, d_in_n, d_out_n, &rc)) return rc;
     return launch(b, st, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n);
 }
 
@@ -451,6 +463,26 @@ int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
 {
     return size_pass_dev(rleesize_launch_dev, (Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n,
                          d_out_n);
+}
+
+int shafa_hipd_rle_encoded_hist_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
+                                    const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
+                                    uint64_t *d_out_n, uint64_t *d_freq)
+{
+    if (!b || !d_freq) return SHAFA_OUTSIDE_MODULE;
+    int rc;
+    if (!size_pass_enter((Batch *)b, (hipStream_t)stream, nblocks, h_in_off, h_in_cap, d_in_n, d_out_n, &rc)) return rc;
+    return rleehist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n, d_freq);
+}
+
+int shafa_hipd_sf_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
+                                   const shafa_code_table *d_tables, uint64_t *d_out_n)
+{
+    if (!b || !d_freq || !d_tables || !d_out_n) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return sfesize_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_freq, d_tables, d_out_n);
 }
 
 }  // extern "C"

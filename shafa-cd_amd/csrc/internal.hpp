@@ -207,6 +207,12 @@ int rlemeasure_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in
 // the sizes rleenc_launch would leave for these input blocks with room enough, without an output (rle_encode_measure.hip)
 int rleesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                         const u64 *d_in_n, u64 *d_out_n);
+// the histograms and sizes rleenc_launch would leave for these input blocks with room enough, without an output
+// (rle_encode_hist.hip); d_freq is overwritten
+int rleehist_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                        const u64 *d_in_n, u64 *d_out_n, u64 *d_freq);
+// the sizes sfenc_launch_dev would leave for blocks with these histograms and tables and room enough (sf_encoded_size.hip)
+int sfesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u64 *d_freq, const shafa_code_table *d_tables, u64 *d_out_n);
 // pack.hip's payload movers (pack_bulk, pack_seams) on records laid out elsewhere (unpack.hip): block b moves n bytes from src
 // to dst, no header.  pack_bulk writes the 16-byte destination words inside [dst, dst + n) and needs src 16-aligned whenever
 // (src - dst) is not a multiple of 16 — read the record of d_bulk; pack_seams writes every other byte — from d_seam.  Both
