@@ -457,6 +457,16 @@ int shafa_hipd_unpack_cod(shafa_hipd_batch *b, void *stream, int max_blocks, con
  * [d_off[b], d_off[b] + d_n[b]) in a .rle file of rle_n bytes.  max_blocks = freq_n / 4 + 1 covers any count likewise. */
 int shafa_hipd_unpack_rle_freq(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_freq, uint64_t freq_n,
                                uint64_t rle_n, uint64_t *d_info, uint64_t *d_off, uint64_t *d_n);
+/* .freq or .rle.freq of freq_n bytes, its counts parsed (Module T's input, as get_shafa_codes reads it) -> d_info, d_sizes[b]
+ * (the "@<size>@" number) and d_counts[b * 256 + s] (the layout shafa_hipd_hist256 leaves, which shafa_hipd_sf_build_codes and
+ * shafa_hipd_pack_freq take as it lies), for b < max_blocks.  Header and frames as unpack_rle_freq (max field 5 375), without
+ * a .rle to measure against.  Block b's text follows shafa_freq_parse (host/formats.c): cut at its first NUL byte, it holds
+ * 256 fields of digits separated by exactly 255 ';'; field 0 is not empty, an empty field repeats the nearest non-empty one
+ * before it, a field has any number of digits and its value wraps modulo 2^64.  A text that fails this:
+ * SHAFA_FILE_UNRECOGNIZABLE on block b and 256 zero counts; the blocks after it are parsed all the same (a block's own fault,
+ * not a framing failure).  Blocks after the first framing failure get size 0 and 256 zero counts, and report nothing. */
+int shafa_hipd_unpack_freq(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_freq_text, uint64_t freq_n,
+                           uint64_t *d_info, uint64_t *d_sizes, uint64_t *d_counts /* max_blocks x 256 */);
 /* .shaf of shaf_n bytes -> block b's payload [d_off[b], d_off[b] + d_n[b]) for the first min(*d_count, max_blocks) blocks
  * (d_count: the .cod's count, e.g. d_info + SHAFA_UNPACK_INFO_INDEXED of shafa_hipd_unpack_cod).  The headers form a
  * dependent chain: one wave walks them, about one memory latency per block. */

@@ -136,6 +136,7 @@ def lib():
     L.shafa_hipd_pack_freq_files.argtypes = [vp, vp, C.c_int, i32p, i32p, C.c_char_p, vp, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_unpack_cod.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_rle_freq.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, C.c_uint64, vp, vp, vp]
+    L.shafa_hipd_unpack_freq.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_shaf.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, vp]
     L.shafa_hipd_unpack_payloads.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, vp, vp, u8p, u64p, u64p]
     L.shafa_hipd_unpack_cod_files.argtypes = [vp, vp, C.c_int, i32p, i32p, u8p, u64p, u64p, vp, vp, vp]
@@ -172,7 +173,7 @@ def lib():
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
-                 "shafa_hipd_sf_encoded_size_dev"):
+                 "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -490,6 +491,12 @@ class Batch:
         """.rle.freq file -> header info and block b's payload [d_off[b], d_off[b] + d_n[b]) in a .rle file of rle_n bytes."""
         _check(lib().shafa_hipd_unpack_rle_freq(self.h, self._st(stream), max_blocks, _ptr(d_freq), d_freq.numel(), int(rle_n),
                                                 d_info.data_ptr(), d_off.data_ptr(), d_n.data_ptr()), "hipd_unpack_rle_freq")
+
+    def unpack_freq(self, stream, max_blocks, d_freq_text, d_info, d_sizes, d_counts):
+        """.freq / .rle.freq file, its counts parsed -> header info, block sizes and d_counts (max_blocks x 256 int64: what
+        sf_build_codes and pack_freq take)."""
+        _check(lib().shafa_hipd_unpack_freq(self.h, self._st(stream), max_blocks, _ptr(d_freq_text), d_freq_text.numel(),
+                                            d_info.data_ptr(), d_sizes.data_ptr(), d_counts.data_ptr()), "hipd_unpack_freq")
 
     def unpack_shaf(self, stream, max_blocks, d_shaf, d_count, d_off, d_n):
         """.shaf file -> block b's payload [d_off[b], d_off[b] + d_n[b]) for min(d_count[0], max_blocks) blocks."""
@@ -1238,9 +1245,10 @@ INFO_STATUS, INFO_MODE, INFO_COUNT, INFO_INDEXED, INFO_FRAMED, INFO_MAX_SIZE = r
 
 
 def unpack_max_blocks(text_n, kind):
-    """max_blocks for Batch.unpack_cod ("cod": a parsable block takes >= 258 bytes, "@d@" and 255 ';') or unpack_rle_freq
-    ("freq": >= 4 bytes, "@d@x"): a header that announces more blocks leaves a failing block among those indexed."""
-    return int(text_n) // (258 if kind == "cod" else 4) + 1
+    """max_blocks for Batch.unpack_cod ("cod": a parsable block takes >= 258 bytes, "@d@" and 255 ';'), unpack_rle_freq
+    ("freq": >= 4 bytes, "@d@x") or unpack_freq ("counts": >= 259 bytes, "@d@", a digit and 255 ';'): a header that announces
+    more blocks leaves a failing block among those indexed."""
+    return int(text_n) // {"cod": 258, "counts": 259}.get(kind, 4) + 1
 
 
 def _layout(caps):
@@ -1852,3 +1860,172 @@ def _rle_decode_many(bt, st, dev, rle_in, max_bytes, results):
             results[f.i] = ShafaError(late, "decompress_many: RLE decoding")
         else:
             results[f.i] = parts[k][0] if len(parts[k]) == 1 else torch.cat(parts[k])
+
+
+# ------------------------------------------------------------------ Modules T and C alone, on files in device memory
+GRID_BLOCKS = 65535             # hist256_tiles and the encoders put blocks on the grid's y
+
+
+def _file_tensors(what, **files):
+    """a module's file arguments checked, before any device work -> them, flattened"""
+    import torch
+    out = []
+    for name, t in files.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} is a contiguous uint8 CUDA tensor")
+        if out and t.device != out[0].device:
+            raise ValueError(f"{what}: the files are on one device")
+        out.append(t.reshape(-1))
+    return out
+
+
+def _bytes_tensor(b, dev):
+    import torch
+    return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+
+
+def build_cod(freq, stream=None):
+    """Module T alone: the .cod that `shafa X.freq -m t` (get_shafa_codes, host/modules.c) writes for the .freq / .rle.freq
+    held in `freq` (a contiguous uint8 CUDA tensor, any alignment), as a uint8 CUDA tensor holding exactly the file.
+
+    Chain: unpack_freq (unpack_max_blocks(n, "counts") slots) -> one synchronisation that reads the header record and the
+    blocks' codes -> sf_build_codes -> pack_cod with the file's own mode and sizes -> finish: two synchronisations.
+    Errors raise ShafaError with the host's code; Module T handles the blocks strictly one after another, so the first error
+    in block order is the host's answer on files with several faults too: a bad header or a mode other than R / N is
+    FILE_UNRECOGNIZABLE (modules.c:713), a block whose frame fails FILE_STREAM_FAILED, a block whose counts fail
+    shafa_freq_parse FILE_UNRECOGNIZABLE.  A header count of 0 gives the host's "@<mode>@0@0".
+    The one divergence: counts whose sum does not fit 64 bits are OUTSIDE_MODULE (sf_build_codes), where the host's sum
+    wraps; a block's own histogram cannot get there."""
+    import torch
+    what = "build_cod"
+    f, = _file_tensors(what, freq=freq)
+    dev = f.device
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    mb = unpack_max_blocks(f.numel(), "counts")
+    if mb > 0x7FFFFFFF:
+        raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
+    bt = Batch(mb, 1 << 20)
+    try:
+        d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+        d_sizes = torch.zeros(mb, dtype=torch.int64, device=dev)
+        d_counts = torch.empty(mb * 256, dtype=torch.int64, device=dev)
+        bt.unpack_freq(st, mb, f, d_info, d_sizes, d_counts)
+        _, errs = bt.finish(st, mb, raise_on_error=False)
+        info = _u64_host(d_info)
+        mode = chr(info[INFO_MODE])
+        if info[INFO_STATUS] or mode not in "RN":
+            raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: header")
+        nb = info[INFO_INDEXED]
+        if info[INFO_COUNT] == 0:
+            return _bytes_tensor(f"@{mode}@0@0".encode(), dev)
+        b, e = _first_error(errs[:nb])
+        if not e and info[INFO_COUNT] > nb:                                  # cannot happen: the slots cover any count
+            e = FILE_STREAM_FAILED
+        if e:
+            raise ShafaError(e, f"{what}: block {b}")
+        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.sf_build_codes(st, nb, d_counts, d_tab)
+        buf = torch.empty(pack_cod_max(nb), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        bt.pack_cod(st, nb, mode.encode(), d_sizes, d_tab, buf, buf.numel(), d_len)
+        _, errs = bt.finish(st, nb, raise_on_error=False)
+        b, e = _first_error(errs)
+        if e:
+            raise ShafaError(e, f"{what}: block {b}")
+        return buf[:int(d_len.item())]
+    finally:
+        bt.close()
+
+
+def encode_files(d_in, cod, stream=None):
+    """Module C alone: the .shaf that `shafa X -m c` (shafa_compress, host/modules.c) writes for the bytes of `d_in` (the
+    original, or its .rle) with the code tables of the .cod held in `cod` (contiguous uint8 CUDA tensors on one device, any
+    alignment), as a uint8 CUDA tensor holding exactly the file.  Block b encodes the size_b bytes of d_in behind the sum of
+    the earlier sizes; bytes of d_in beyond the sum of the sizes are ignored, as the host ignores them.
+
+    Chain: unpack_cod -> a synchronisation that reads the sizes and the blocks' codes (16 bytes a block) -> the blocks'
+    inputs in 16-aligned regions (in place when they are, else gathered by unpack_payloads from the prefix sums) ->
+    hist256_tiles -> sf_encoded_size_dev -> a synchronisation that reads the encoded sizes -> sf_encode_dev with the parsed
+    device tables into regions of those sizes -> pack_payloads(FRAME_SHAF) -> finish: three synchronisations, and output
+    memory of the encoded size (the alternative, the host's bound size * Lmax / 8 + 16 of modules.c:859, saves the second
+    one and costs up to 32 bytes of output region per input byte).
+    Errors raise ShafaError with the host's code, the first in block order, which is the host's answer on files with a single
+    fault (with several, the host's depends on how far it reads ahead): a bad header is FILE_UNRECOGNIZABLE (modules.c:808;
+    the mode is not judged); a block whose frame fails, or whose size exceeds the input bytes that remain, is
+    FILE_STREAM_FAILED, also over a table error of the same block; a text that fails shafa_cod_parse, or a data symbol
+    without a code, is FILE_UNRECOGNIZABLE.  A header count of 0 gives "@0".  More than GRID_BLOCKS blocks in one file are
+    LACK_OF_MEMORY (one launch takes the file's blocks)."""
+    import itertools
+    import torch
+    what = "encode_files"
+    src, text = _file_tensors(what, d_in=d_in, cod=cod)
+    dev = src.device
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    mb = unpack_max_blocks(text.numel(), "cod")
+    if mb > 0x7FFFFFFF:
+        raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
+    bt = Batch(mb, 1 << 20)
+    try:
+        d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+        d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
+        d_tab = torch.empty(mb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+        bt.unpack_cod(st, mb, text, d_info, d_n, d_tab)
+        _, errs = bt.finish(st, mb, raise_on_error=False)
+        info = _u64_host(d_info)
+        if info[INFO_STATUS]:
+            raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: header")
+        if info[INFO_COUNT] == 0:
+            return _bytes_tensor(b"@0", dev)
+        nidx = info[INFO_INDEXED]
+        sizes = _u64_host(d_n)[:nidx]
+        # the host's walk: frame, table, then the input's budget, which overrules the table (c_prepare)
+        fb, perr, left = nidx, SUCCESS, src.numel()
+        if info[INFO_COUNT] > nidx:                                          # cannot happen: the slots cover any count
+            perr = FILE_STREAM_FAILED
+        for b in range(nidx):
+            e = errs[b]
+            if e != FILE_STREAM_FAILED and sizes[b] > left:
+                e = FILE_STREAM_FAILED
+            if e:
+                fb, perr = b, e
+                break
+            left -= sizes[b]
+        if fb > GRID_BLOCKS:
+            raise ShafaError(LACK_OF_MEMORY, f"{what}: more than {GRID_BLOCKS} blocks")
+        if fb == 0:
+            raise ShafaError(perr, f"{what}: block 0")
+        sizes = sizes[:fb]
+        start = [0] + list(itertools.accumulate(sizes))[:-1]
+        if src.data_ptr() % 16 or any(o % 16 for o in start):
+            off, pos = _layout(sizes)
+            buf = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+            d_start = torch.tensor(start, dtype=torch.int64, device=dev)
+            bt.unpack_payloads(st, src, d_start, d_n[:fb], buf, off, sizes)
+            src = buf
+        else:
+            off = start
+        d_freq = torch.zeros(fb * 256, dtype=torch.int64, device=dev)
+        toff, pos = _layout([tile_hist_bytes(n) for n in sizes])
+        d_th = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+        d_esize = torch.zeros(fb, dtype=torch.int64, device=dev)
+        bt.hist256_tiles(st, src, off, sizes, d_freq, d_th, toff)
+        bt.sf_encoded_size_dev(st, fb, d_freq, d_tab, d_esize)
+        _, errs = bt.finish(st, fb, raise_on_error=False)
+        b, e = _first_error(errs)
+        if e or perr:
+            raise ShafaError(e or perr, f"{what}: block {b}")
+        ocap = [_al16(n) + 16 for n in _u64_host(d_esize)]
+        ooff, pos = _layout(ocap)
+        d_enc = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+        d_enc_n = torch.zeros(fb, dtype=torch.int64, device=dev)
+        bt.sf_encode_dev(st, src, off, sizes, d_n[:fb], d_tab, d_enc, ooff, ocap, d_enc_n, d_th, toff)
+        out = torch.empty(pack_payloads_max(ocap, FRAME_SHAF), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        bt.pack_payloads(st, FRAME_SHAF, d_enc, ooff, ocap, d_enc_n, out, out.numel(), d_len)
+        _, errs = bt.finish(st, fb, raise_on_error=False)
+        b, e = _first_error(errs)
+        if e:
+            raise ShafaError(e, f"{what}: block {b}")
+        return out[:int(d_len.item())]
+    finally:
+        bt.close()

@@ -1,9 +1,11 @@
 // unpack.hip — the inverse of pack.hip: the project's files, held in device memory, parsed into what the device decoders take
-// (shafa_hipd_unpack_cod / _unpack_rle_freq / _unpack_shaf / _unpack_payloads).
+// (shafa_hipd_unpack_cod / _unpack_rle_freq / _unpack_freq / _unpack_shaf / _unpack_payloads).
 //
-// The rules are those of the C host (host/modules.c read_header / read_block / shaf_read_u64, host/formats.c shafa_cod_parse):
+// The rules are those of the C host (host/modules.c read_header / read_block / shaf_read_u64, host/formats.c shafa_cod_parse
+// and shafa_freq_parse):
 //   .cod   "@<mode>@<n>", then "@<size>@" + "c0;c1;...;c255" per block        -> sizes, binary tables
 //   .freq  "@<mode>@<n>", then "@<size>@" + fields per block (framing only)   -> sizes, offsets of the payloads in the .rle
+//   .freq  the same text, fields parsed (unpack_freq)                         -> sizes, 256 counts per block
 //   .shaf  "@<n>", then "@<size>@" + payload per block                         -> offsets and sizes of the payloads
 //
 // Kernels (stable names for rocprofv3):
@@ -14,6 +16,7 @@
 //   unpack_frames         ONE workgroup looping over the blocks: the header, every block's frame as read_block checks it, the
 //                         first failing block (block order), sizes, text spans, the .rle offsets, d_info
 //   unpack_tables         a workgroup per block, a lane per symbol: shafa_cod_parse in LDS -> the binary table
+//   unpack_counts         a workgroup per block, a lane per field: shafa_freq_parse in LDS -> the 256 counts
 //   unpack_shaf_walk      ONE wave: the dependent chain of the .shaf headers, one 32-byte window per block
 //   unpack_move_plan      a lane per block: the capacity and file checks, two descriptor records for pack.hip's movers
 // The payloads themselves are moved by pack.hip's pack_bulk / pack_seams (pack_move_launch): no second mover.
@@ -25,8 +28,8 @@
 //   unpack_shaf_walk_files a wave per file: unpack_shaf_walk's body (shaf_walk) on its .shaf
 // and run unpack_tables as it is, once per run of consecutive slots.
 //
-// Reads: every load of a file is a byte load of a byte inside [file, file + n), except pack_bulk's 16-byte words, each of
-// which holds a byte of the payload it moves.  Writes: only the caller's arrays of max_blocks (nblocks) entries and d_info
+// Reads: every load of a file is a byte load of a byte inside [file, file + n), except pack_bulk's and unpack_counts' aligned
+// 16-byte words, each of which holds a byte of the payload it moves / of the block text it parses.  Writes: only the caller's arrays of max_blocks (nblocks) entries and d_info
 // (segmented: the files' slots and their records).
 #include "common.hpp"
 #include "internal.hpp"
@@ -41,6 +44,7 @@ constexpr u64 IDX_CHUNK = (u64)IDX_THREADS * IDX_BYTES;      // 4 KiB of text pe
 constexpr int FRAME_THREADS = 256;
 constexpr u32 COD_TEXT_MAX = 33151;                           // SHAFA_COD_BLOCK_MAX (host/shafa_host.h)
 constexpr u32 FREQ_TEXT_MAX = 256 * 20 + 255;                 // SHAFA_FREQ_BLOCK_MAX
+constexpr u32 FREQ_TEXT_WORDS = (15 + FREQ_TEXT_MAX + 15) / 16;  // 16-byte words that hold a block text at any alignment
 
 struct TextSpan {
     u64 start;               // the block's text: [start, start + n) of the file, after its "@<size>@"
@@ -152,8 +156,8 @@ struct FrameArgs {
     u32 field_max;           // read_block's max_payload
     u64 *info;               // SHAFA_UNPACK_INFO_WORDS words
     u64 *sizes;              // the "@<size>@" numbers
-    TextSpan *spans;         // .cod: the block texts for unpack_tables; nullptr for .freq
-    u64 *off;                // .freq: the payload offsets in the .rle; nullptr for .cod
+    TextSpan *spans;         // the block texts for unpack_tables / unpack_counts; nullptr for a .freq read for its framing
+    u64 *off;                // .rle.freq: the payload offsets in the .rle; else nullptr
     u64 rle_n;
     int *err;
 };
@@ -323,6 +327,94 @@ __global__ __launch_bounds__(256) void unpack_tables(const u8 *__restrict__ t, c
         }
         tb->bits[s][q] = (u8)byte;
     }
+    if (s == 0 && bad) set_error(err + b, SHAFA_FILE_UNRECOGNIZABLE);
+}
+
+// inclusive max-scan over the 64 lanes of a wave: dpp_scan_add's steps with max (0 is the identity: a lane without a source
+// gets `old` = 0)
+__device__ __forceinline__ u32 dpp_scan_max(u32 v)
+{
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false));   // row_shr:1
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false));   // row_shr:2
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false));   // row_shr:4
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false));   // row_shr:8
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1,3
+    v = max(v, (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2,3
+    return v;
+}
+
+// shafa_freq_parse (host/formats.c) on one block's text: up to the text's first NUL byte only digits and exactly 255 ';', and a
+// first field that is not empty.  A field's value is v = v * 10 + d over its digits (any number of them, wrapping); an empty
+// field repeats the nearest non-empty one before it.  Anything else: 256 zero counts and SHAFA_FILE_UNRECOGNIZABLE.  A block
+// that was not framed (span of 0 bytes) gets 256 zero counts and no error.
+// The text comes in as the aligned 16-byte words of memory that hold it (each holds a byte of it), so it sits in LDS `lead`
+// bytes behind the first word's start.
+__global__ __launch_bounds__(256) void unpack_counts(const u8 *__restrict__ t, const TextSpan *__restrict__ spans,
+                                                     u64 *__restrict__ counts, int *__restrict__ err)
+{
+    __shared__ uint4 words[FREQ_TEXT_WORDS];
+    __shared__ u64 val[256];
+    __shared__ u32 semi[256];
+    __shared__ u32 wsum[4], wlast[4];
+    __shared__ u32 nul, bad;
+    const int b = blockIdx.x;
+    const u32 s = threadIdx.x, lane = s & 63u, wv = s >> 6;
+    const TextSpan sp = spans[b];
+    const u32 n = (u32)sp.n;                                      // <= FREQ_TEXT_MAX (unpack_frames checked it)
+    const u32 lead = n ? (u32)((uintptr_t)(t + sp.start) & 15) : 0;
+    const u32 nw = (lead + n + 15) / 16;                          // <= FREQ_TEXT_WORDS
+    if (s == 0) {
+        nul = n;
+        bad = 0;
+    }
+    for (u32 i = s; i < nw; i += 256) words[i] = gload<uint4>(t + sp.start - lead + (u64)i * 16);
+    __syncthreads();
+    const u8 *txt = (const u8 *)words + lead;
+    // a lane per stretch of the text: its ';', its bytes that are neither ';' nor digit, up to its first NUL
+    const u32 seg = (n + 255) / 256, lo = s * seg < n ? s * seg : n, hi = lo + seg < n ? lo + seg : n;
+    u32 k = 0;
+    bool odd = false;
+    for (u32 i = lo; i < hi; ++i) {
+        const u8 c = txt[i];
+        if (c == 0) {
+            atomicMin(&nul, i);
+            break;
+        }
+        if (c == ';') ++k;
+        else if (!is_digit(c)) odd = true;
+    }
+    __syncthreads();
+    const u32 L = nul;                                            // the host parses a NUL-terminated string
+    if (lo >= L) {                                                // behind the first NUL: not looked at
+        k = 0;
+        odd = false;
+    }
+    const u32 incl = dpp_scan_add(k);
+    if (lane == 63) wsum[wv] = incl;
+    if (odd || (s == 0 && n && (L == 0 || txt[0] == ';'))) atomicOr(&bad, 1u);      // field 0 must not be empty
+    __syncthreads();
+    u32 r = incl - k;
+    for (u32 w = 0; w < wv; ++w) r += wsum[w];
+    const u32 total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    if (s == 0 && n && total != 255) atomicOr(&bad, 1u);
+    if (total == 255)
+        for (u32 i = lo; i < hi && i < L; ++i)
+            if (txt[i] == ';') semi[r++] = i;
+    __syncthreads();
+    const bool ok = n && !bad;
+    u64 v = 0;
+    u32 last = 0;                                                 // the last non-empty field up to this one (field 0 is one)
+    if (ok) {
+        const u32 f0 = s == 0 ? 0 : semi[s - 1] + 1, f1 = s == 255 ? L : semi[s];
+        for (u32 i = f0; i < f1; ++i) v = v * 10 + (u64)(txt[i] - '0');
+        if (f1 > f0) last = s;
+    }
+    val[s] = v;
+    last = dpp_scan_max(last);
+    if (lane == 63) wlast[wv] = last;
+    __syncthreads();
+    for (u32 w = 0; w < wv; ++w) last = max(last, wlast[w]);
+    counts[(u64)b * 256 + s] = ok ? val[last] : 0;
     if (s == 0 && bad) set_error(err + b, SHAFA_FILE_UNRECOGNIZABLE);
 }
 
@@ -537,13 +629,13 @@ int idx_ws(Batch *bt, hipStream_t st, u64 n, int max_blocks, bool spans, u64 lim
     return SHAFA_SUCCESS;
 }
 
-// the '@' index of a text, then its frames (and, for a .cod, its tables)
+// the '@' index of a text, then its frames (and, for a .cod, its tables; for a .freq's fields, its counts)
 int text_unpack(Batch *bt, hipStream_t st, int max_blocks, const u8 *d_text, u64 n, u32 field_max, u64 *d_info, u64 *d_sizes,
-                shafa_code_table *d_tables, u64 *d_off, u64 rle_n)
+                shafa_code_table *d_tables, u64 *d_off, u64 rle_n, u64 *d_counts = nullptr)
 {
     IdxWs w;
     const u64 limit = 2 * (u64)max_blocks + 4;                    // the header's 2 or 3, then two per block, and the last one
-    if (int rc = idx_ws(bt, st, n, max_blocks, d_tables != nullptr, limit, w)) return rc;
+    if (int rc = idx_ws(bt, st, n, max_blocks, d_tables || d_counts, limit, w)) return rc;
     const u64 nchunks = n ? ceil_div_u64(n, IDX_CHUNK) : 1;
     if (nchunks > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
     hipLaunchKernelGGL(unpack_at_count, dim3((u32)nchunks), dim3(IDX_THREADS), 0, st, d_text, n, w.cnt);
@@ -567,6 +659,9 @@ int text_unpack(Batch *bt, hipStream_t st, int max_blocks, const u8 *d_text, u64
     hipLaunchKernelGGL(unpack_frames, dim3(1), dim3(FRAME_THREADS), 0, st, a);
     if (d_tables)
         hipLaunchKernelGGL(unpack_tables, dim3((u32)max_blocks), dim3(256), 0, st, d_text, (const TextSpan *)w.spans, d_tables,
+                           bt->d_err);
+    if (d_counts)
+        hipLaunchKernelGGL(unpack_counts, dim3((u32)max_blocks), dim3(256), 0, st, d_text, (const TextSpan *)w.spans, d_counts,
                            bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
@@ -754,6 +849,17 @@ int shafa_hipd_unpack_rle_freq(shafa_hipd_batch *b, void *stream, int max_blocks
     if (max_blocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
     return text_unpack(bt, (hipStream_t)stream, max_blocks, d_freq, freq_n, FREQ_TEXT_MAX, d_info, d_n, nullptr, d_off, rle_n);
+}
+
+int shafa_hipd_unpack_freq(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_freq_text, uint64_t freq_n,
+                           uint64_t *d_info, uint64_t *d_sizes, uint64_t *d_counts)
+{
+    if (!b || max_blocks < 1 || (!d_freq_text && freq_n) || !d_info || !d_sizes || !d_counts) return SHAFA_OUTSIDE_MODULE;
+    Batch *bt = (Batch *)b;
+    if (max_blocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (int rc = batch_enter(bt, (hipStream_t)stream)) return rc;
+    return text_unpack(bt, (hipStream_t)stream, max_blocks, d_freq_text, freq_n, FREQ_TEXT_MAX, d_info, d_sizes, nullptr,
+                       nullptr, 0, d_counts);
 }
 
 int shafa_hipd_unpack_shaf(shafa_hipd_batch *b, void *stream, int max_blocks, const uint8_t *d_shaf, uint64_t shaf_n,
