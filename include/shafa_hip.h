@@ -141,7 +141,8 @@ int shafa_hip_rle_decode(const uint8_t *in, size_t in_n, uint8_t *out, size_t ou
  * Calls enqueue work on `stream` (a hipStream_t passed as void*; NULL = the null stream) and
  * return without synchronising; results in device memory are valid after the stream is synchronised.
  * shafa_hipd_finish() synchronises the stream and returns the batch's first error, filling the
- * optional host arrays.
+ * optional host arrays.  shafa_hipd_compare_dev alone has a second operand that needs no alignment: the original a decoder's
+ * output is checked against, read in place.
  */
 typedef struct shafa_hipd_batch shafa_hipd_batch;
 
@@ -332,6 +333,30 @@ int shafa_hipd_rle_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nbloc
 int shafa_hipd_rle_encoded_hist_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                                     const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                                     uint64_t *d_out_n, uint64_t *d_freq);
+
+/* Where a decoder's output first differs from an original: block b compares the d_a_n[b] (<= h_a_cap[b]) bytes at
+ * d_a + h_a_off[b] — a device decoder's output region: d_a and every h_a_off[b] are multiples of 16, the size is device
+ * resident — with the h_ref_n[b] bytes at d_ref + h_ref_off[b], which may have ANY byte alignment and lie anywhere in a
+ * buffer of any size (64-bit offsets).  With m = min(d_a_n[b], h_ref_n[b]), d_first[b] = the smallest i < m at which the two
+ * differ, or m when the first m bytes agree: the blocks are equal iff d_first[b] == d_a_n[b] == h_ref_n[b].  With several
+ * differences the first is returned, whatever the scheduling (no atomics).
+ * A difference is data, not an error: it sets no error word.  Per-block codes through shafa_hipd_finish:
+ *   d_a_n[b] > h_a_cap[b]                  SHAFA_OUTSIDE_MODULE, d_first[b] = 0 (no byte of the block is read).
+ * Bytes of a region behind d_a_n[b] (the slack of an exact region is uninitialised) and bytes of ref behind h_ref_n[b] never
+ * influence the result.  Neither operand is copied or written.  ref is read in aligned 16-byte words that each hold at least
+ * one byte of [ref, ref + h_ref_n[b]), shifted into place; no other byte of it is touched.  Nothing is written except
+ * d_first[0 .. nblocks) and the batch's error words.
+ * Two launches — every 8 KiB tile on its own, then one workgroup per block — in which no workgroup waits for another; the
+ * grid is the tile count of the call.  The device workspace is 16 bytes per 8 KiB of sum(h_a_cap) plus 36 bytes per block.
+ * Enqueues only: d_a_n is never read on the host, no device-to-host copy is issued and nothing is synchronised; the one
+ * exception is the batch's growth, from nblocks and h_a_cap.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL d_a or d_ref, a d_a
+ * that is not a multiple of 16, NULL b, d_a_n, d_first, h_a_off, h_a_cap, h_ref_off or h_ref_n, or an h_a_off[b] that is not
+ * a multiple of 16: SHAFA_OUTSIDE_MODULE; nblocks > the batch's max_blocks, or 2^31 tiles or more in sum(h_a_cap):
+ * SHAFA_LACK_OF_MEMORY; nblocks <= 0 (with b and the four device pointers given): success. */
+int shafa_hipd_compare_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_a, const uint64_t *h_a_off,
+                           const uint64_t *h_a_cap, const uint64_t *d_a_n, const uint8_t *d_ref, const uint64_t *h_ref_off,
+                           const uint64_t *h_ref_n, uint64_t *d_first);
 
 /* The Shannon-Fano sizes of blocks without encoding them: d_out_n[b] = the d_out_n[b] shafa_hipd_sf_encode_dev leaves for a
  * block whose histogram is d_freq[b * 256 ..] (what shafa_hipd_hist256 or shafa_hipd_rle_encoded_hist_dev leaves), encoded

@@ -10,6 +10,7 @@ itself as ``shafa_cd_amd``.
 
 There is NO CPU fallback: if the HIP library is missing, importing ``hip`` members raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -119,6 +120,7 @@ def lib():
     L.shafa_hipd_rle_encoded_size_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_rle_encoded_hist_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp]
     L.shafa_hipd_sf_encoded_size_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp]
+    L.shafa_hipd_compare_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -173,7 +175,7 @@ def lib():
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
-                 "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq"):
+                 "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -420,6 +422,15 @@ class Batch:
         shafa_hipd_sf_encoded_size_dev)."""
         _check(lib().shafa_hipd_sf_encoded_size_dev(self.h, self._st(stream), nblocks, d_freq.data_ptr(), d_tables.data_ptr(),
                                                     d_out_n.data_ptr()), "hipd_sf_encoded_size_dev")
+
+    def compare_dev(self, stream, d_a, a_off, a_cap, d_a_n, d_ref, ref_off, ref_n, d_first):
+        """d_first[b] (int64) = where the d_a_n[b] (int64, device; <= a_cap[b]) bytes of a decoder's region d_a + a_off[b]
+        first differ from the ref_n[b] bytes at d_ref + ref_off[b] (any alignment, read in place), or the smaller of the two
+        sizes.  A difference sets no error word.  Enqueues only (include/shafa_hip.h: shafa_hipd_compare_dev)."""
+        ao, ac, ro, rn = _u64arr(a_off), _u64arr(a_cap), _u64arr(ref_off), _u64arr(ref_n)
+        _check(lib().shafa_hipd_compare_dev(self.h, self._st(stream), len(ao), d_a.data_ptr(), _p64(ao), _p64(ac),
+                                            d_a_n.data_ptr(), d_ref.data_ptr(), _p64(ro), _p64(rn), d_first.data_ptr()),
+               "hipd_compare_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -1281,43 +1292,59 @@ def _rle_measure(bt, st, d_in, in_off, in_n, d_in_n, n_err):
     return _u64_host(d_size)[:len(in_n)], errs[:len(in_n)]
 
 
+def _groups(cost, max_bytes, tiles=None):
+    """Consecutive blocks whose costs (bytes) fit max_bytes — a block above it is a group of its own — and, with `tiles`
+    (one count per block), whose (largest count) x (blocks) stays within RLE_GRID_TILES -> [(first, end)]"""
+    groups, g0, acc, mt = [], 0, 0, 0
+    for b, c in enumerate(cost):
+        t = tiles[b] if tiles else 0
+        if b > g0 and (acc + c > max_bytes or max(mt, t) * (b - g0 + 1) > RLE_GRID_TILES):
+            groups.append((g0, b))
+            g0, acc, mt = b, 0, 0
+        acc += c
+        mt = max(mt, t)
+    groups.append((g0, len(cost)))
+    return groups
+
+
 def _rle_groups(sizes, in_n, max_bytes):
     """Consecutive blocks whose exact output regions (_al16(size)) fit max_bytes and whose rle_decode_dev grid — (its largest
     input's 8 KiB tiles) x (its blocks) workgroups of 256 lanes — stays within RLE_GRID_TILES, so the grid's lanes stay below
     2^32 however many small blocks join a large one -> [(first, end)]"""
-    groups, g0, acc, mt = [], 0, 0, 0
-    for b, (size, n) in enumerate(zip(sizes, in_n)):
-        t = max(1, -(-n // 8192))
-        if b > g0 and (acc + _al16(size) > max_bytes or max(mt, t) * (b - g0 + 1) > RLE_GRID_TILES):
-            groups.append((g0, b))
-            g0, acc, mt = b, 0, 0
-        acc += _al16(size)
-        mt = max(mt, t)
-    groups.append((g0, len(sizes)))
-    return groups
+    return _groups([_al16(s) for s in sizes], max_bytes, [max(1, -(-n // 8192)) for n in in_n])
 
 
-def _rle_decode_exact(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
-    """rle_decode_dev of these blocks into regions of exactly their decoded sizes (_rle_measure's), in groups (_rle_groups)
-    that follow each other on the stream without a synchronisation, each packed into its place in one tensor of exactly the
-    decoded bytes -> that tensor.  Enqueues only: the caller's finish ends it."""
+def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
+    """rle_decode_dev of these blocks into regions of exactly their decoded sizes (_rle_measure's), group after group
+    (_rle_groups) into one buffer sized for the largest group.  Yields (first, end, buffer, offsets, device sizes) once a
+    group's decode is enqueued; what the caller enqueues then reads the buffer before the next group's decode overwrites
+    it.  Groups that decode to nothing are left out.  Enqueues only."""
     import torch
     dev = d_in.device
     groups = _rle_groups(sizes, in_n, max_bytes)
     biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
     d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
     d_out_n = torch.zeros(len(sizes), dtype=torch.int64, device=dev)
-    d_len = torch.zeros(len(groups), dtype=torch.int64, device=dev)
-    total = sum(sizes)
-    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-    pos = 0
-    for g, (a, z) in enumerate(groups):
-        gt = sum(sizes[a:z])
-        if not gt:
+    for a, z in groups:
+        if not sum(sizes[a:z]):
             continue
         off, _ = _layout(sizes[a:z])
         bt.rle_decode_dev(st, d_in, in_off[a:z], in_n[a:z], d_in_n[a:z], d_out, off, sizes[a:z], d_out_n[a:z])
-        bt.pack_payloads(st, FRAME_RAW, d_out, off, sizes[a:z], d_out_n[a:z], out[pos:], gt, d_len[g:g + 1])
+        yield a, z, d_out, off, d_out_n[a:z]
+
+
+def _rle_decode_exact(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
+    """_rle_decode_groups, each group packed into its place in one tensor of exactly the decoded bytes -> that tensor; the
+    groups follow each other on the stream without a synchronisation.  Enqueues only: the caller's finish ends it."""
+    import torch
+    dev = d_in.device
+    d_len = torch.zeros(max(len(sizes), 1), dtype=torch.int64, device=dev)       # a group's length, at its first block
+    total = sum(sizes)
+    out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+    pos = 0
+    for a, z, d_out, off, d_out_n in _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
+        gt = sum(sizes[a:z])
+        bt.pack_payloads(st, FRAME_RAW, d_out, off, sizes[a:z], d_out_n, out[pos:], gt, d_len[a:a + 1])
         pos += gt
     return out[:total]
 
@@ -1402,10 +1429,11 @@ def _gather_payloads(bt, st, d_file, p, b0, b1):
     return d_pay, poff, pn, p.d_n[b0:b1]
 
 
-def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what):
-    """Blocks [b0, b1) of a parsed .shaf / .cod pair: unpack_payloads -> sf_decode_dev (-> pack_payloads(RAW) when `pack`) ->
-    one synchronisation; a block whose codes take the decoder's single slot for 33..64-bit codes from another is decoded
-    again on its own.  The first SF error in block order raises.
+def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what, then=None):
+    """Blocks [b0, b1) of a parsed .shaf / .cod pair: unpack_payloads -> sf_decode_dev (-> pack_payloads(RAW) when `pack`;
+    -> then(buffer, offsets, sizes, device sizes), which enqueues a reader of the decoded regions, when given) -> one
+    synchronisation; a block whose codes take the decoder's single slot for 33..64-bit codes from another is decoded
+    again on its own (and the pack and `then` run again).  The first SF error in block order raises.
     -> (buffer, offsets, sizes, device sizes) of the decoded blocks, and the packed tensor (None without `pack`)"""
     import torch
     dev = d_shaf.device
@@ -1421,6 +1449,8 @@ def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what):
         out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         d_len = torch.zeros(1, dtype=torch.int64, device=dev)
         bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+    if then:
+        then(d_sfo, ooff, nsym, d_nsym)
     _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
     errs = errs[:b1 - b0]
     again = set()
@@ -1434,8 +1464,11 @@ def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what):
         b, e = _first_error(errs)
     if e:
         raise ShafaError(e, f"{what}: block {b0 + b}")
-    if pack and again:
-        bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+    if again and (pack or then):
+        if pack:
+            bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+        if then:
+            then(d_sfo, ooff, nsym, d_nsym)
         bt.finish(st, bt.max_blocks)
     return (d_sfo, ooff, nsym, d_nsym), (out[:total] if pack else None)
 
@@ -1568,6 +1601,84 @@ def decompress_range(offset, length, shaf=None, cod=None, rle=None, freq=None, s
         if p.perr:
             raise ShafaError(p.perr, f"{what}: block {p.fb}")
         return out[lo:hi]
+    finally:
+        bt.close()
+
+
+Verify = collections.namedtuple("Verify", "equal first_diff decoded_size")
+
+
+def _ref_spans(sizes, ref_len):
+    """What each of these decoded blocks, laid end to end, is compared with in an original of ref_len bytes: (offsets,
+    sizes) — a block that starts at or behind the original's end with no byte, one that straddles it with what remains"""
+    off, n, pos = [], [], 0
+    for s in sizes:
+        o = min(pos, ref_len)
+        off.append(o)
+        n.append(min(s, ref_len - o))
+        pos += s
+    return off, n
+
+
+def verify_files(d_in, shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
+    """Whether a file set held in device memory (decompress_files' file arguments and decode_rle) still decodes to d_in, a
+    contiguous uint8 CUDA tensor on the files' device (any alignment, may be empty) -> Verify(equal, first_diff,
+    decoded_size).  With out = decompress_files(the same files): decoded_size = out.numel(); equal = the two are the same
+    bytes; first_diff = None when equal, else the smallest index at which they differ, or the smaller length when one is a
+    prefix of the other.  Raises what decompress_files raises: every block is decoded, so faults come before any difference,
+    wherever it lies.
+    Neither the decoded file nor a copy of d_in ever exists: blocks are decoded in groups that fit max_bytes (default: a
+    quarter of the free device memory) into exact aligned regions, which compare_dev reads against d_in in place.
+      shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload); each runs unpack_payloads ->
+                                  sf_decode_dev -> compare_dev -> one synchronisation, which also reads its results
+      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files (a mode-R set keeps its .rle bytes resident),
+                                  then per group of _rle_groups rle_decode_dev -> compare_dev into one reused buffer, back to
+                                  back on the stream; one synchronisation ends the call and the results are read once
+    No pack_payloads(RAW) runs.  A mode-R .cod with decode_rle=False is compared as the .rle bytes, group by group as mode N."""
+    import torch
+    what = "verify_files"
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        dev = files[0].device
+        if not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_contiguous() or d_in.device != dev:
+            raise ValueError(f"{what}: d_in is a contiguous uint8 CUDA tensor on the files' device")
+        d_in = d_in.reshape(-1)
+        ref_len = d_in.numel()
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
+        sizes, first = [], []
+        if p.fb and sf and not (p.mode == "R" and decode_rle):
+            sizes = list(p.nsym)
+            ref_off, ref_n = _ref_spans(sizes, ref_len)
+            d_first = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+            for a, z in _groups([_al16(s) + _al16(n) for s, n in zip(sizes, p.pn)], max_bytes):
+                def compare(d_a, a_off, a_cap, d_a_n):
+                    bt.compare_dev(st, d_a, a_off, a_cap, d_a_n, d_in if ref_len else d_a, ref_off[a:z], ref_n[a:z], d_first[a:z])
+                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=compare)
+                first += _u64_host(d_first[a:z])
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        elif p.fb:
+            sizes, rin = _measure_set(bt, st, sf, files, p, what)
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+            ref_off, ref_n = _ref_spans(sizes, ref_len)
+            d_first = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
+                bt.compare_dev(st, d_a, a_off, sizes[a:z], d_a_n, d_in if ref_len else d_a, ref_off[a:z], ref_n[a:z], d_first[a:z])
+            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+            _, e = _first_error(errs)
+            if e:                                                                # the size pass accepted every block: the device
+                raise ShafaError(e, f"{what}: RLE decoding")
+            first = _u64_host(d_first)
+        # the first block that is not its span of d_in; behind the last one d_in may go on
+        pos = 0
+        for s, r, f in zip(sizes, ref_n if sizes else [], first):
+            if f < s or r != s:
+                return Verify(False, pos + f, sum(sizes))
+            pos += s
+        return Verify(ref_len == pos, None if ref_len == pos else pos, pos)
     finally:
         bt.close()
 

@@ -207,8 +207,9 @@ void batch_stage_retire(Batch *b, hipStream_t st)
 }
 
 // the argument checks of the size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev,
-// shafa_hipd_rle_encoded_hist_dev), before HIP is touched: true = launch the pass, false = the call returns *rc
-static bool size_pass_enter(Batch *b, hipStream_t st, int nblocks, const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n,
+// shafa_hipd_rle_encoded_hist_dev) and of shafa_hipd_compare_dev's side a, before HIP is touched: true = go on, false = the
+// call returns *rc
+static bool size_pass_check(Batch *b, int nblocks, const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n,
                             const u64 *d_out_n, int *rc)
 {
     *rc = SHAFA_OUTSIDE_MODULE;
@@ -221,7 +222,15 @@ static bool size_pass_enter(Batch *b, hipStream_t st, int nblocks, const u64 *h_
     if (!h_in_off || !h_in_cap) return false;
     for (int i = 0; i < nblocks; ++i)
         if (h_in_off[i] & 15) return false;
-    return (*rc = batch_enter(b, st)) == SHAFA_SUCCESS;
+    *rc = SHAFA_SUCCESS;
+    return true;
+}
+
+// those checks, then the batch's: true = launch the pass
+static bool size_pass_enter(Batch *b, hipStream_t st, int nblocks, const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n,
+                            const u64 *d_out_n, int *rc)
+{
+    return size_pass_check(b, nblocks, h_in_off, h_in_cap, d_in_n, d_out_n, rc) && (*rc = batch_enter(b, st)) == SHAFA_SUCCESS;
 }
 
 static int size_pass_dev(int (*launch)(Batch *, hipStream_t, int, const u8 *, const u64 *, const u64 *, const u64 *, u64 *),
@@ -473,6 +482,22 @@ int shafa_hipd_rle_encoded_hist_dev(shafa_hipd_batch *b, void *stream, int nbloc
     int rc;
     if (!size_pass_enter((Batch *)b, (hipStream_t)stream, nblocks, h_in_off, h_in_cap, d_in_n, d_out_n, &rc)) return rc;
     return rleehist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out_n, d_freq);
+}
+
+int shafa_hipd_compare_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_a, const uint64_t *h_a_off,
+                           const uint64_t *h_a_cap, const uint64_t *d_a_n, const uint8_t *d_ref, const uint64_t *h_ref_off,
+                           const uint64_t *h_ref_n, uint64_t *d_first)
+{
+    if (!d_a || !d_ref || ((uintptr_t)d_a & 15)) return SHAFA_OUTSIDE_MODULE;
+    int rc;
+    if (!size_pass_check((Batch *)b, nblocks, h_a_off, h_a_cap, d_a_n, d_first, &rc)) return rc;
+    if (!h_ref_off || !h_ref_n) return SHAFA_OUTSIDE_MODULE;
+    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (compare.hip numbers them in 31 bits)
+    for (int i = 0; i < nblocks; ++i)
+        if ((ntiles += h_a_cap[i] / 8192 + (h_a_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
+    return compare_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_a, h_a_off, h_a_cap, d_a_n, d_ref, h_ref_off, h_ref_n,
+                              d_first);
 }
 
 int shafa_hipd_sf_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,

@@ -169,6 +169,20 @@ __device__ __forceinline__ u32 funnel_r(u32 hi, u32 lo, u32 sh)
     return __builtin_amdgcn_alignbit(hi, lo, sh);
 }
 
+// bytes m .. m + 15 of the 32 bytes a:b (m = 4q + r), by v_alignbyte per dword: an unaligned 16-byte read out of the two
+// aligned words around it (pack.hip: pack_bulk, compare.hip)
+template <int Q>
+__device__ __forceinline__ uint4 shift_words(const uint4 &a, const uint4 &b, u32 r)
+{
+    const u32 c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint4 o;
+    o.x = __builtin_amdgcn_alignbyte(c[Q + 1], c[Q + 0], r);
+    o.y = __builtin_amdgcn_alignbyte(c[Q + 2], c[Q + 1], r);
+    o.z = __builtin_amdgcn_alignbyte(c[Q + 3], c[Q + 2], r);
+    o.w = __builtin_amdgcn_alignbyte(c[Q + 4], c[Q + 3], r);
+    return o;
+}
+
 // Pointers that reach a kernel inside a parameter record are "generic" to the compiler, which then
 // emits flat_load/flat_store: those count on BOTH vmcnt and lgkmcnt and retire out of order, so every
 // later LDS wait also waits for the HBM access (no prefetch overlap).  These helpers state the global

@@ -211,6 +211,10 @@ int rleesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, 
 // (rle_encode_hist.hip); d_freq is overwritten
 int rleehist_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                         const u64 *d_in_n, u64 *d_out_n, u64 *d_freq);
+// where block b of a decoder's output (d_a_n[b] <= h_a_cap[b] bytes at d_a + h_a_off[b]) first differs from the h_ref_n[b] bytes
+// at d_ref + h_ref_off[b], any alignment (compare.hip); the capacities' 8 KiB tiles number fewer than 2^31
+int compare_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_a, const u64 *h_a_off, const u64 *h_a_cap,
+                       const u64 *d_a_n, const u8 *d_ref, const u64 *h_ref_off, const u64 *h_ref_n, u64 *d_first);
 // the sizes sfenc_launch_dev would leave for blocks with these histograms and tables and room enough (sf_encoded_size.hip)
 int sfesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u64 *d_freq, const shafa_code_table *d_tables, u64 *d_out_n);
 // pack.hip's payload movers (pack_bulk, pack_seams) on records laid out elsewhere (unpack.hip): block b moves n bytes from src

@@ -179,19 +179,6 @@ __device__ inline void whole_words(const PackDesc &d, u64 &w_lo, u64 &w_hi)
     if (w_hi < w_lo) w_hi = w_lo;
 }
 
-// bytes m .. m + 15 of the 32 bytes a:b (m = 4q + r), by v_alignbyte per dword
-template <int Q>
-__device__ __forceinline__ uint4 shift_words(const uint4 &a, const uint4 &b, u32 r)
-{
-    const u32 c[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-    uint4 o;
-    o.x = __builtin_amdgcn_alignbyte(c[Q + 1], c[Q + 0], r);
-    o.y = __builtin_amdgcn_alignbyte(c[Q + 2], c[Q + 1], r);
-    o.z = __builtin_amdgcn_alignbyte(c[Q + 3], c[Q + 2], r);
-    o.w = __builtin_amdgcn_alignbyte(c[Q + 4], c[Q + 3], r);
-    return o;
-}
-
 template <int Q>
 __device__ __forceinline__ void bulk_pass(const u8 *src, u64 p, u64 w_lo, u64 words, u64 k0, u32 r)
 {
