@@ -358,6 +358,38 @@ int shafa_hipd_compare_dev(shafa_hipd_batch *b, void *stream, int nblocks, const
                            const uint64_t *h_a_cap, const uint64_t *d_a_n, const uint8_t *d_ref, const uint64_t *h_ref_off,
                            const uint64_t *h_ref_n, uint64_t *d_first);
 
+/* CRC-32 (the zlib / PNG / gzip one: polynomial 0xEDB88320 reflected, init and final XOR 0xFFFFFFFF; the CRC of no byte is 0,
+ * of "123456789" 0xCBF43926) of byte regions in device memory: d_crc[b] = the CRC of the d_in_n[b] (<= h_in_cap[b], device
+ * resident) bytes at d_in + h_in_off[b].  The offsets are 64-bit and need NO alignment: originals, the segments of a
+ * concatenation and decoder regions are digested where they lie.  The region is read as shafa_hipd_compare_dev reads its ref
+ * side: in aligned 16-byte words that each hold at least one byte of it, shifted into place; no other byte is touched,
+ * nothing is copied, and bytes behind d_in_n[b] (the slack of an exact region, a neighbouring segment) never influence the
+ * result.  Nothing is written except d_crc[0 .. nblocks) and the batch's error words.  Per-block codes through
+ * shafa_hipd_finish:
+ *   d_in_n[b] > h_in_cap[b]                SHAFA_OUTSIDE_MODULE, d_crc[b] = 0 (no byte of the block is read).
+ * Two launches — every 8 KiB tile on its own, then one workgroup per block — in which no workgroup waits for another and
+ * no atomic is used: the result does not depend on scheduling.  The device workspace is 16 bytes per 8 KiB of sum(h_in_cap)
+ * plus 20 bytes per block.  Enqueues only: d_in_n is never read on the host, no device-to-host copy is issued and nothing is
+ * synchronised; the one exception is the batch's growth, from nblocks and h_in_cap.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_in, d_in_n, d_crc,
+ * h_in_off or h_in_cap: SHAFA_OUTSIDE_MODULE (a NULL batch comes first); nblocks > the batch's max_blocks, or 2^31 tiles or
+ * more in sum(h_in_cap): SHAFA_LACK_OF_MEMORY; nblocks <= 0 (with b, d_in, d_in_n and d_crc given): success. */
+int shafa_hipd_crc32_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                         const uint64_t *h_in_cap, const uint64_t *d_in_n, uint32_t *d_crc);
+
+/* The CRC-32 of concatenations, from the parts' finished CRCs and lengths alone (zlib's crc32_combine: crc(A || B) =
+ * crc(A) x^(8 |B|) mod P ^ crc(B)).  File f is blocks h_first[f] .. h_first[f] + h_count[f] - 1 of d_crc / d_n, in
+ * shafa_hipd_pack_*_files' convention (any blocks, the same block in several files included): d_file_n[f] = the sum of their
+ * d_n (64-bit: a file may exceed 4 GiB, a block may have 0 bytes), d_file_crc[f] = the CRC-32 of the bytes they stand for, one
+ * after the other.  h_count[f] = 0 is CRC 0 and length 0.  The rule is associative: a call's outputs may be the next call's
+ * inputs, which is how groups of blocks digested apart are joined.  No data byte is read.
+ * One workgroup per file.  Enqueues only; the device workspace is 8 bytes per file.  No per-block code is set.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_crc, d_n, d_file_crc,
+ * d_file_n, h_first or h_count, a negative h_first[f] or h_count[f], or a block range past 2^31 - 1: SHAFA_OUTSIDE_MODULE (a
+ * NULL batch or device array comes first); nfiles > the batch's max_blocks: SHAFA_LACK_OF_MEMORY; nfiles <= 0: success. */
+int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                                 const uint32_t *d_crc, const uint64_t *d_n, uint32_t *d_file_crc, uint64_t *d_file_n);
+
 /* The Shannon-Fano sizes of blocks without encoding them: d_out_n[b] = the d_out_n[b] shafa_hipd_sf_encode_dev leaves for a
  * block whose histogram is d_freq[b * 256 ..] (what shafa_hipd_hist256 or shafa_hipd_rle_encoded_hist_dev leaves), encoded
  * with d_tables[b] into room enough: ceil(sum over s of d_freq[b * 256 + s] * len[s] / 8), the bits summed in 64 bits.

@@ -121,6 +121,8 @@ def lib():
     L.shafa_hipd_rle_encoded_hist_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, vp]
     L.shafa_hipd_sf_encoded_size_dev.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     L.shafa_hipd_compare_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
+    L.shafa_hipd_crc32_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
+    L.shafa_hipd_crc32_combine_dev.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -175,7 +177,8 @@ def lib():
                  "shafa_hipd_unpack_cod", "shafa_hipd_unpack_rle_freq", "shafa_hipd_unpack_shaf", "shafa_hipd_unpack_payloads",
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
-                 "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev"):
+                 "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
+                 "shafa_hipd_crc32_combine_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -431,6 +434,22 @@ class Batch:
         _check(lib().shafa_hipd_compare_dev(self.h, self._st(stream), len(ao), d_a.data_ptr(), _p64(ao), _p64(ac),
                                             d_a_n.data_ptr(), d_ref.data_ptr(), _p64(ro), _p64(rn), d_first.data_ptr()),
                "hipd_compare_dev")
+
+    def crc32_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_crc):
+        """d_crc[b] (int32, the CRC's 32 bits) = zlib.crc32 of the d_in_n[b] (int64, device; <= in_cap[b]) bytes at
+        d_in + in_off[b] (any alignment, read in place).  Enqueues only (include/shafa_hip.h: shafa_hipd_crc32_dev)."""
+        io, ic = _u64arr(in_off), _u64arr(in_cap)
+        _check(lib().shafa_hipd_crc32_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                          d_in_n.data_ptr(), d_crc.data_ptr()), "hipd_crc32_dev")
+
+    def crc32_combine_dev(self, stream, first, count, d_crc, d_n, d_file_crc, d_file_n):
+        """file f = blocks first[f] .. first[f] + count[f] - 1 of d_crc (int32) / d_n (int64): d_file_crc[f] (int32) = the
+        CRC-32 of their concatenation, d_file_n[f] (int64) its length, from the blocks' CRCs and lengths alone.  Enqueues only
+        (include/shafa_hip.h: shafa_hipd_crc32_combine_dev)."""
+        fi, co = _i32arr(first), _i32arr(count)
+        _check(lib().shafa_hipd_crc32_combine_dev(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), d_crc.data_ptr(),
+                                                  d_n.data_ptr(), d_file_crc.data_ptr(), d_file_n.data_ptr()),
+               "hipd_crc32_combine_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -1679,6 +1698,146 @@ def verify_files(d_in, shaf=None, cod=None, rle=None, freq=None, decode_rle=True
                 return Verify(False, pos + f, sum(sizes))
             pos += s
         return Verify(ref_len == pos, None if ref_len == pos else pos, pos)
+    finally:
+        bt.close()
+
+
+# ------------------------------------------------------------------ CRC-32
+_CRC_POLY = 0xEDB88320
+
+
+def _crc_mul(a, b):
+    """a b mod P; a 32-bit value is a polynomial over GF(2), bit 31 = x^0 (the reflected form of zlib's register)"""
+    p = 0
+    for i in range(32):
+        if a & (0x80000000 >> i):
+            p ^= b
+        b = (b >> 1) ^ _CRC_POLY if b & 1 else b >> 1
+    return p
+
+
+def _crc_x_pow(e):
+    """x^e mod P"""
+    r, s = 0x80000000, 0x40000000
+    while e:
+        if e & 1:
+            r = _crc_mul(r, s)
+        s = _crc_mul(s, s)
+        e >>= 1
+    return r
+
+
+def crc32_combine(crc1, crc2, len2):
+    """zlib.crc32(A + B) from crc1 = zlib.crc32(A), crc2 = zlib.crc32(B) and len2 = len(B): crc1 x^(8 len2) mod P ^ crc2, on
+    finished values (zlib's crc32_combine).  Plain integers, no device; len2 of any size.  Associative, so per-part digests
+    join in any grouping; Batch.crc32_combine_dev is the same rule on device arrays."""
+    if len2 < 0:
+        raise ValueError("crc32_combine: negative length")
+    return _crc_mul(_crc_x_pow(8 * int(len2) % 0xFFFFFFFF), int(crc1) & 0xFFFFFFFF) ^ (int(crc2) & 0xFFFFFFFF)
+
+
+CRC_PIECE = 1 << 26             # crc32: a segment is digested in pieces of 64 MiB (8192 tiles: 2^18 pieces stay below 2^31 tiles)
+Checksum = collections.namedtuple("Checksum", "crc32 decoded_size")
+
+
+def crc32(d_in, sizes=None, stream=None, _piece=None):
+    """zlib.crc32 of a contiguous uint8 CUDA tensor, digested where it lies (any alignment, nothing is copied) -> int.  With
+    `sizes`: of each of the consecutive segments of these lengths (compress_many's convention, the segments at whatever
+    alignment they fall) -> a list of ints.  An empty tensor or segment gives 0.
+    A segment longer than CRC_PIECE (64 MiB) is cut into pieces of that size, one block each for crc32_dev, and the pieces'
+    CRCs are joined by crc32_combine_dev; a call of crc32_dev takes at most 2^17 pieces (2^30 tiles).  One synchronisation,
+    which reads 4 bytes per segment."""
+    import torch
+    if not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+        raise ValueError("crc32: d_in is a contiguous uint8 CUDA tensor")
+    d_in = d_in.reshape(-1)
+    segs = [int(d_in.numel())] if sizes is None else [int(n) for n in sizes]
+    if any(n < 0 for n in segs) or sum(segs) > d_in.numel():
+        raise ValueError("crc32: sizes exceed d_in")
+    piece = int(_piece) if _piece else CRC_PIECE
+    off, cap, first, count, pos = [], [], [], [], 0
+    for n in segs:
+        first.append(len(off))
+        for a in range(0, n, piece):
+            off.append(pos + a)
+            cap.append(min(piece, n - a))
+        count.append(len(off) - first[-1])
+        pos += n
+    out = [0] * len(segs)
+    if off:
+        dev = d_in.device
+        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        bt = Batch(max(len(off), len(segs)), piece)
+        try:
+            d_n = torch.tensor(cap, dtype=torch.int64).to(dev)
+            d_crc = torch.zeros(len(off), dtype=torch.int32, device=dev)
+            d_file_crc = torch.zeros(len(segs), dtype=torch.int32, device=dev)
+            d_file_n = torch.zeros(len(segs), dtype=torch.int64, device=dev)
+            calls = max(1, (1 << 30) // max(1, -(-piece // 8192)))           # pieces per crc32_dev call
+            for a in range(0, len(off), calls):
+                z = min(a + calls, len(off))
+                bt.crc32_dev(st, d_in, off[a:z], cap[a:z], d_n[a:z], d_crc[a:z])
+            bt.crc32_combine_dev(st, first, count, d_crc, d_n, d_file_crc, d_file_n)
+            bt.finish(st, len(off))
+            out = [int(c) & 0xFFFFFFFF for c in d_file_crc.cpu().tolist()]
+        finally:
+            bt.close()
+    return out[0] if sizes is None else out
+
+
+def checksum_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
+    """The CRC-32 and the length of the file a file set held in device memory decodes to (decompress_files' file arguments
+    and decode_rle) -> Checksum(crc32, decoded_size).  With out = decompress_files(the same arguments): decoded_size =
+    out.numel(), crc32 = zlib.crc32 of out's bytes; raises what that call raises — every block is decoded, so a fault is
+    reported whichever group it lies in.  The original need not exist any more: a digest taken from it (shafa.crc32, or
+    zlib.crc32 on any host) is what the answer is checked against.
+    The decoded file never exists, nor a tensor of its size: verify_files' structure with crc32_dev where compare_dev is.
+      shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload) that fit max_bytes (default: a quarter
+                                  of the free device memory); each runs unpack_payloads -> sf_decode_dev -> crc32_dev -> one
+                                  synchronisation; the last group's also covers the combine
+      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files, then per group of _rle_groups rle_decode_dev
+                                  -> crc32_dev out of one reused buffer, back to back on the stream, the combine, and one
+                                  synchronisation
+    The blocks' CRCs (4 bytes a block) and their device-resident decoded sizes gather on the device; one crc32_combine_dev
+    over all blocks ends the call.  No pack_payloads(RAW) runs; the synchronisations are verify_files'."""
+    import torch
+    what = "checksum_files"
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        dev = files[0].device
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
+        if p.fb == 0:
+            return Checksum(0, 0)
+        d_crc = torch.zeros(p.fb, dtype=torch.int32, device=dev)
+        d_file_crc = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_file_n = torch.zeros(1, dtype=torch.int64, device=dev)
+        if sf and not (p.mode == "R" and decode_rle):
+            d_n = p.d_nsym[:p.fb]
+            for a, z in _groups([_al16(s) + _al16(n) for s, n in zip(p.nsym, p.pn)], max_bytes):
+                def digest(d_a, a_off, a_cap, d_a_n):
+                    bt.crc32_dev(st, d_a, a_off, a_cap, d_a_n, d_crc[a:z])
+                    if z == p.fb:                                            # the earlier groups' CRCs are in front on the stream
+                        bt.crc32_combine_dev(st, [0], [p.fb], d_crc, d_n, d_file_crc, d_file_n)
+                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=digest)
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        else:
+            sizes, rin = _measure_set(bt, st, sf, files, p, what)
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+            d_n = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
+                bt.crc32_dev(st, d_a, a_off, sizes[a:z], d_a_n, d_crc[a:z])
+                with torch.cuda.stream(st):
+                    d_n[a:z].copy_(d_a_n)                                    # the decoder's own sizes, device to device
+            bt.crc32_combine_dev(st, [0], [p.fb], d_crc, d_n, d_file_crc, d_file_n)
+            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+            _, e = _first_error(errs)
+            if e:                                                                # the size pass accepted every block: the device
+                raise ShafaError(e, f"{what}: RLE decoding")
+        return Checksum(int(d_file_crc.cpu()[0]) & 0xFFFFFFFF, int(d_file_n.cpu()[0]))
     finally:
         bt.close()
 

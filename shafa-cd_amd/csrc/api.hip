@@ -207,10 +207,10 @@ void batch_stage_retire(Batch *b, hipStream_t st)
 }
 
 // the argument checks of the size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev,
-// shafa_hipd_rle_encoded_hist_dev) and of shafa_hipd_compare_dev's side a, before HIP is touched: true = go on, false = the
-// call returns *rc
+// shafa_hipd_rle_encoded_hist_dev), of shafa_hipd_compare_dev's side a and of shafa_hipd_crc32_dev (whose regions need no
+// alignment: aligned = false), before HIP is touched: true = go on, false = the call returns *rc
 static bool size_pass_check(Batch *b, int nblocks, const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n,
-                            const u64 *d_out_n, int *rc)
+                            const void *d_out_n, int *rc, bool aligned = true)
 {
     *rc = SHAFA_OUTSIDE_MODULE;
     if (!b || !d_in_n || !d_out_n) return false;
@@ -220,7 +220,7 @@ static bool size_pass_check(Batch *b, int nblocks, const u64 *h_in_off, const u6
     if (nblocks > b->max_blocks) return false;
     *rc = SHAFA_OUTSIDE_MODULE;
     if (!h_in_off || !h_in_cap) return false;
-    for (int i = 0; i < nblocks; ++i)
+    for (int i = 0; aligned && i < nblocks; ++i)
         if (h_in_off[i] & 15) return false;
     *rc = SHAFA_SUCCESS;
     return true;
@@ -498,6 +498,32 @@ int shafa_hipd_compare_dev(shafa_hipd_batch *b, void *stream, int nblocks, const
     if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
     return compare_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_a, h_a_off, h_a_cap, d_a_n, d_ref, h_ref_off, h_ref_n,
                               d_first);
+}
+
+int shafa_hipd_crc32_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                         const uint64_t *h_in_cap, const uint64_t *d_in_n, uint32_t *d_crc)
+{
+    if (!b || !d_in) return SHAFA_OUTSIDE_MODULE;
+    int rc;
+    if (!size_pass_check((Batch *)b, nblocks, h_in_off, h_in_cap, d_in_n, d_crc, &rc, false)) return rc;
+    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (tile_pass.hpp numbers them in 31 bits)
+    for (int i = 0; i < nblocks; ++i)
+        if ((ntiles += h_in_cap[i] / 8192 + (h_in_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
+    return crc32_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_crc);
+}
+
+int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
+                                 const uint32_t *d_crc, const uint64_t *d_n, uint32_t *d_file_crc, uint64_t *d_file_n)
+{
+    if (!b || !d_crc || !d_n || !d_file_crc || !d_file_n) return SHAFA_OUTSIDE_MODULE;
+    if (nfiles <= 0) return SHAFA_SUCCESS;
+    if (nfiles > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_first || !h_count) return SHAFA_OUTSIDE_MODULE;
+    for (int f = 0; f < nfiles; ++f)
+        if (h_first[f] < 0 || h_count[f] < 0 || h_count[f] > 0x7FFFFFFF - h_first[f]) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return crc32_combine_launch_dev((Batch *)b, (hipStream_t)stream, nfiles, h_first, h_count, d_crc, d_n, d_file_crc, d_file_n);
 }
 
 int shafa_hipd_sf_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,

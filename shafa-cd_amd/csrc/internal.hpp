@@ -215,6 +215,13 @@ int rleehist_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, 
 // at d_ref + h_ref_off[b], any alignment (compare.hip); the capacities' 8 KiB tiles number fewer than 2^31
 int compare_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_a, const u64 *h_a_off, const u64 *h_a_cap,
                        const u64 *d_a_n, const u8 *d_ref, const u64 *h_ref_off, const u64 *h_ref_n, u64 *d_first);
+// d_crc[b] = the CRC-32 of block b's d_in_n[b] <= h_in_cap[b] bytes at d_in + h_in_off[b], any alignment (crc32.hip); the
+// capacities' 8 KiB tiles number fewer than 2^31
+int crc32_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                     const u64 *d_in_n, u32 *d_crc);
+// file f = blocks h_first[f] .. + h_count[f] of d_crc / d_n: the CRC-32 and the length of their concatenation (crc32.hip)
+int crc32_combine_launch_dev(Batch *bt, hipStream_t st, int nfiles, const int *h_first, const int *h_count, const u32 *d_crc,
+                             const u64 *d_n, u32 *d_file_crc, u64 *d_file_n);
 // the sizes sfenc_launch_dev would leave for blocks with these histograms and tables and room enough (sf_encoded_size.hip)
 int sfesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u64 *d_freq, const shafa_code_table *d_tables, u64 *d_out_n);
 // pack.hip's payload movers (pack_bulk, pack_seams) on records laid out elsewhere (unpack.hip): block b moves n bytes from src
