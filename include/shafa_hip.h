@@ -390,6 +390,79 @@ int shafa_hipd_crc32_dev(shafa_hipd_batch *b, void *stream, int nblocks, const u
 int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
                                  const uint32_t *d_crc, const uint64_t *d_n, uint32_t *d_file_crc, uint64_t *d_file_n);
 
+/* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
+ * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
+ * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every
+ * block's SF-decoded bytes (the original for a mode-N .shaf, the .rle bytes for a mode-R one; for a .rle + .freq set the grid
+ * runs over the .rle bytes themselves).  `span` is a power of two, 256 .. 8192.  A block of n symbols has
+ * max(1, ceil(n / span)) checkpoints; checkpoint k describes the position just in front of symbol k * span of the block.
+ * A checkpoint is 16 bytes, two little-endian 64-bit words:
+ *   w0 bits  0..47   bit offset, within the block's .shaf payload, of the code of symbol k * span (the encoder's bit order:
+ *                    MSB first); 8 * k * span for a .rle + .freq set
+ *      bits 48..55   pending symbol: the RLE byte at k * span - 1; meaningful only when the state is 2 (0 otherwise)
+ *      bits 56..57   RLE state in front of the symbol: 0 = outside a triple, 1 = the byte before was the escape 0, 2 = the next
+ *                    byte is a count.  Always 0 without SHAFA_SEEK_RLE
+ *      bits 58..63   0
+ *   w1               decoded offset, within the block, of the first output byte produced by bytes at or behind the checkpoint
+ *                    (a run is charged to its COUNT byte; a count of 0 acts as 1); k * span without SHAFA_SEEK_RLE
+ * Checkpoint 0 is {0, 0}.  The blocks' checkpoints lie one after the other in one device array (block b's first one at index
+ * h_ckpt_first[b], in checkpoints); the array is plain data that a caller may keep, copy and hand back later.
+ *
+ * shafa_hipd_seek_index_dev builds the checkpoints of nblocks blocks from their SF-decoded bytes: block b's are the d_in_n[b]
+ * (<= h_in_cap[b], device resident) bytes at d_in + h_in_off[b] — a region of shafa_hipd_sf_decode_dev, or a .rle payload
+ * gathered by shafa_hipd_unpack_payloads; d_in and every offset are multiples of 16.  flags: SHAFA_SEEK_SF = the bit
+ * offsets are sums of d_tables[b].len[] over the bytes (else 8 a byte, d_tables is not looked at); SHAFA_SEEK_RLE = the bytes
+ * are RLE bytes.  Block b's region of d_ckpt, from checkpoint h_ckpt_first[b], holds max(1, ceil(h_in_cap[b] / span))
+ * checkpoints; max(1, ceil(d_in_n[b] / span)) are written.  d_out_n[b] = the block's decoded size (what
+ * shafa_hipd_rle_decoded_size_dev leaves with SHAFA_SEEK_RLE, d_in_n[b] without).  d_status[b] = SHAFA_SEEK_UNINDEXED when
+ * SHAFA_SEEK_SF is set and the block's table holds a code of more than 32 bits or one of its bytes has no code: such a block
+ * gets checkpoint 0 only and is read by the block decoders; else 0.  Per-block codes through shafa_hipd_finish:
+ *   d_in_n[b] > h_in_cap[b]                SHAFA_OUTSIDE_MODULE, d_out_n[b] = 0, checkpoint 0 only (no byte of the block is read);
+ *   with SHAFA_SEEK_RLE, the bytes end inside a {0, symbol, count} triple or decode to more than SHAFA_RLE_DECODE_MAX
+ *                                          SHAFA_FILE_UNRECOGNIZABLE, d_out_n[b] = 0 (as shafa_hipd_rle_decoded_size_dev).
+ * Two launches — one wave per span, then one workgroup per block — in which no workgroup waits for another and no atomic is
+ * used: the result does not depend on scheduling.  The device workspace is 16 bytes per span of the capacities plus 28 bytes
+ * per block.  Enqueues only: nothing is read on the host or synchronised; the one exception is the batch's growth.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_in, d_in_n, d_ckpt,
+ * d_status or d_out_n, a span that is no power of two in 256 .. 8192, unknown flags, SHAFA_SEEK_SF without d_tables:
+ * SHAFA_OUTSIDE_MODULE; then nblocks <= 0: success; nblocks > the batch's max_blocks, or 2^31 spans or more in the capacities:
+ * SHAFA_LACK_OF_MEMORY; NULL h_in_off, h_in_cap or h_ckpt_first, a d_in or h_in_off[b] that is no multiple of 16:
+ * SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_SEEK_SF 1
+#define SHAFA_SEEK_RLE 2
+#define SHAFA_SEEK_UNINDEXED 1u
+int shafa_hipd_seek_index_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                              const uint64_t *h_in_cap, const uint64_t *d_in_n, const shafa_code_table *d_tables, uint32_t span,
+                              int flags, const uint64_t *h_ckpt_first, uint64_t *d_ckpt, uint32_t *d_status, uint64_t *d_out_n);
+
+/* The ranged decoder.  The file set is described by host arrays of nblocks entries — block b's payload is the h_pay_n[b]
+ * bytes at d_file + h_pay_off[b] (the .shaf or the .rle file where it lies, any alignment, file_n bytes in all), it has
+ * h_n_symbols[b] symbols and its checkpoints start at h_ckpt_first[b] of d_ckpt — and by d_tables (SHAFA_SEEK_SF: what
+ * shafa_hipd_unpack_cod leaves), span and flags as the index was built with.  Item i reads the bytes whose decoded offset
+ * within block h_item_block[i] lies in [h_item_lo[i], h_item_hi[i]) and writes them to d_out + h_item_dst[i] + (offset - lo);
+ * h_item_first[i] .. h_item_last[i] are the checkpoints of that block whose spans produce them (first: the last checkpoint
+ * whose decoded offset is <= lo; last: the last one whose decoded offset is < hi).  Every span of every item is decoded on
+ * its own, 64 spans of one block to a workgroup: its symbols from the checkpoint's bit offset, through the RLE machine from
+ * the checkpoint's state and pending symbol with SHAFA_SEEK_RLE, until the span or the range ends.  No payload byte outside
+ * [h_pay_off[b], + h_pay_n[b]) is read and no byte outside [dst, dst + hi - lo) is written, whatever the files and the index
+ * hold.  Conditions that files other than the indexed ones can cause set SHAFA_FILE_UNRECOGNIZABLE for the ITEM (item i's
+ * code is word i of shafa_hipd_finish) and end that span's writing: a window that matches no code, a walk past the payload's
+ * end, a span whose end (bit offset, decoded offset, RLE state) disagrees with the next checkpoint, a block that ends inside
+ * a triple.  A block whose table holds a code of more than 32 bits: SHAFA_OUTSIDE_MODULE for its items, nothing written.
+ * One launch, no workgroup waits for another, no atomics; the device workspace is 32 bytes per block and per item plus 8
+ * bytes per span read.  Enqueues only, as shafa_hipd_seek_index_dev.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched): NULL b, d_ckpt or d_out, a NULL
+ * d_file with file_n > 0, a bad span or flags, SHAFA_SEEK_SF without d_tables: SHAFA_OUTSIDE_MODULE; then nitems <= 0:
+ * success; nitems or nblocks > the batch's max_blocks, or 2^31 spans or more: SHAFA_LACK_OF_MEMORY; a NULL host array,
+ * nblocks <= 0, a payload outside [0, file_n), an item whose block, checkpoints (first <= last < the block's count) or range
+ * (lo <= hi, dst + hi - lo <= out_n) is out of bounds: SHAFA_OUTSIDE_MODULE. */
+int shafa_hipd_read_spans_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_file, uint64_t file_n,
+                              const uint64_t *h_pay_off, const uint64_t *h_pay_n, const uint64_t *h_n_symbols,
+                              const uint64_t *h_ckpt_first, const shafa_code_table *d_tables, uint32_t span, int flags,
+                              const uint64_t *d_ckpt, int nitems, const int *h_item_block, const uint64_t *h_item_first,
+                              const uint64_t *h_item_last, const uint64_t *h_item_lo, const uint64_t *h_item_hi,
+                              const uint64_t *h_item_dst, uint8_t *d_out, uint64_t out_n);
+
 /* The Shannon-Fano sizes of blocks without encoding them: d_out_n[b] = the d_out_n[b] shafa_hipd_sf_encode_dev leaves for a
  * block whose histogram is d_freq[b * 256 ..] (what shafa_hipd_hist256 or shafa_hipd_rle_encoded_hist_dev leaves), encoded
  * with d_tables[b] into room enough: ceil(sum over s of d_freq[b * 256 + s] * len[s] / 8), the bits summed in 64 bits.

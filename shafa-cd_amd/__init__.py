@@ -123,6 +123,9 @@ def lib():
     L.shafa_hipd_compare_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_crc32_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_crc32_combine_dev.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp]
+    L.shafa_hipd_seek_index_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
+    L.shafa_hipd_read_spans_dev.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, u64p, u64p, u64p, u64p, vp, C.c_uint32, C.c_int, vp,
+                                            C.c_int, C.POINTER(C.c_int), u64p, u64p, u64p, u64p, u64p, u8p, C.c_uint64]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
     L.shafa_hip_pack_payloads_max.argtypes = [C.c_int, u64p, C.c_int]
     L.shafa_hip_pack_payloads_max.restype = C.c_size_t
@@ -178,7 +181,7 @@ def lib():
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
                  "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
-                 "shafa_hipd_crc32_combine_dev"):
+                 "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -450,6 +453,30 @@ class Batch:
         _check(lib().shafa_hipd_crc32_combine_dev(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), d_crc.data_ptr(),
                                                   d_n.data_ptr(), d_file_crc.data_ptr(), d_file_n.data_ptr()),
                "hipd_crc32_combine_dev")
+
+    def seek_index_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, span, flags, ckpt_first, d_ckpt, d_status, d_out_n):
+        """The checkpoints, every `span` symbols, of blocks of SF-decoded bytes: block b's d_in_n[b] (int64, device; <=
+        in_cap[b]) bytes at d_in + in_off[b], with d_tables[b] (device; None without SEEK_SF) -> d_ckpt (int64, two words a
+        checkpoint, block b's from checkpoint ckpt_first[b]), d_status[b] (int32) and d_out_n[b] (int64, the decoded size).
+        Enqueues only (include/shafa_hip.h: "Seek index")."""
+        io, ic, cf = _u64arr(in_off), _u64arr(in_cap), _u64arr(ckpt_first)
+        _check(lib().shafa_hipd_seek_index_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic),
+                                               d_in_n.data_ptr(), None if d_tables is None else d_tables.data_ptr(), span,
+                                               flags, _p64(cf), d_ckpt.data_ptr(), d_status.data_ptr(), d_out_n.data_ptr()),
+               "hipd_seek_index_dev")
+
+    def read_spans_dev(self, stream, d_file, pay_off, pay_n, n_symbols, ckpt_first, d_tables, span, flags, d_ckpt, items, d_out):
+        """The ranged decoder: items = (block, first checkpoint, last checkpoint, lo, hi, destination offset), the blocks
+        described by the four host sequences; item i's code is word i of finish.  Enqueues only (include/shafa_hip.h:
+        shafa_hipd_read_spans_dev)."""
+        po, pn, ns, cf = _u64arr(pay_off), _u64arr(pay_n), _u64arr(n_symbols), _u64arr(ckpt_first)
+        it = np.asarray(items, dtype=np.uint64).reshape(-1, 6)
+        blk = _i32arr(it[:, 0])
+        col = [_u64arr(it[:, k]) for k in range(1, 6)]
+        _check(lib().shafa_hipd_read_spans_dev(self.h, self._st(stream), len(po), _ptr(d_file), d_file.numel(), _p64(po), _p64(pn),
+                                               _p64(ns), _p64(cf), None if d_tables is None else d_tables.data_ptr(), span, flags,
+                                               d_ckpt.data_ptr(), len(blk), _p32(blk), *[_p64(c) for c in col], d_out.data_ptr(),
+                                               d_out.numel()), "hipd_read_spans_dev")
 
     def sf_decode(self, stream, d_in, in_off, in_n, tables, n_symbols, d_out, out_off):
         io, il, oo, ns = _u64arr(in_off), _u64arr(in_n), _u64arr(out_off), _u64arr(n_symbols)
@@ -1840,6 +1867,187 @@ def checksum_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, st
         return Checksum(int(d_file_crc.cpu()[0]) & 0xFFFFFFFF, int(d_file_n.cpu()[0]))
     finally:
         bt.close()
+
+
+# ------------------------------------------------------------------ seek index
+SEEK_SF, SEEK_RLE, SEEK_UNINDEXED = 1, 2, 1
+SeekBlock = collections.namedtuple("SeekBlock", "decoded_size n_symbols payload_offset payload_size first_checkpoint indexed")
+
+
+class SeekIndex:
+    """What build_index leaves: `checkpoints`, the device tensor (int64, two words a checkpoint: include/shafa_hip.h, "Seek
+    index"); `blocks`, the host-side block table (a SeekBlock per block); `span`; `mode` ("N" or "R" for a .shaf + .cod pair,
+    "rle" for .rle + .freq); `decoded_size`; `file_lengths`, of the payload file and the text file it was built from.  For
+    the two RLE forms the checkpoints' decoded offsets are also kept on the host (8 bytes a checkpoint): read_ranges finds
+    the checkpoints that cover a range there."""
+
+    def __init__(self, checkpoints, blocks, span, mode, file_lengths, offsets=None):
+        self.checkpoints, self.blocks, self.span, self.mode = checkpoints, list(blocks), int(span), mode
+        self.file_lengths = tuple(int(n) for n in file_lengths)
+        self.starts = [0]
+        for blk in self.blocks:
+            self.starts.append(self.starts[-1] + blk.decoded_size)
+        self.decoded_size = self.starts[-1]
+        self.offsets = offsets
+
+    @property
+    def nbytes(self):
+        return self.checkpoints.numel() * 8
+
+
+def _seek_span(span, what):
+    if not isinstance(span, int) or not 256 <= span <= 8192 or span & (span - 1):
+        raise ValueError(f"{what}: span is a power of two, 256 .. 8192")
+
+
+def build_index(shaf=None, cod=None, rle=None, freq=None, span=1024, stream=None, max_bytes=None):
+    """A seek index of a file set held in device memory (decoded_sizes' file arguments and mode rules) -> SeekIndex: one
+    checkpoint every `span` SF symbols of every block (RLE bytes for .rle + .freq), with which read_ranges decodes byte ranges
+    from the few hundred stream bytes that cover them.
+    Every block is decoded exactly once, in groups that fit max_bytes (default: a quarter of the free device memory) as in
+    verify_files' mode-N path — unpack_payloads -> sf_decode_dev -> seek_index_dev on the decoded regions (.rle + .freq:
+    unpack_payloads -> seek_index_dev) — so neither the decoded file nor, for a mode-R pair, the .rle stream ever exists.
+    Raises what decompress_files raises for the same files, with its precedence (header, mode, SF faults, RLE faults, parse
+    faults behind good blocks): after a successful build the files are known to be good.  A block whose table holds a code
+    of more than 32 bits is marked unindexed (SeekBlock.indexed is False); read_ranges serves it through decompress_range."""
+    import torch
+    what = "build_index"
+    _seek_span(span, what)
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        dev = files[0].device
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
+        mode = p.mode if sf else "rle"
+        is_rle = mode != "N"
+        flags = (SEEK_SF if sf else 0) | (SEEK_RLE if is_rle else 0)
+        lengths = (files[0].numel(), files[1].numel())
+        if p.fb == 0:
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block 0")
+            return SeekIndex(torch.zeros(0, dtype=torch.int64, device=dev), [], span, mode, lengths,
+                             np.zeros(0, dtype=np.int64) if is_rle else None)
+        nsym = list(p.nsym if sf else p.pn)
+        nck = [max(1, -(-n // span)) for n in nsym]
+        first = [0]
+        for c in nck:
+            first.append(first[-1] + c)
+        d_ckpt = torch.zeros(2 * first[-1], dtype=torch.int64, device=dev)
+        d_status = torch.zeros(p.fb, dtype=torch.int32, device=dev)
+        d_size = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+        tsz = C.sizeof(CodeTable)
+        cost = [_al16(s) + _al16(n) for s, n in zip(nsym, p.pn)] if sf else [_al16(n) for n in p.pn]
+        rle_errs = []
+        for a, z in _groups(cost, max_bytes):
+            def index(d_a, a_off, a_cap, d_a_n):
+                bt.seek_index_dev(st, d_a, a_off, a_cap, d_a_n, p.d_tab[a * tsz:z * tsz] if sf else None, span, flags,
+                                  first[a:z], d_ckpt, d_status[a:z], d_size[a:z])
+            if not is_rle:                                                   # no fault of its own: within the group's one synchronisation
+                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=index)
+                continue
+            # SF faults are raised by the group's decode; the RLE faults wait for the SF faults of the groups behind
+            rin = _sf_decode_blocks(bt, st, files[0], p, a, z, False, what)[0] if sf else _gather_payloads(bt, st, files[0], p, a, z)
+            index(*rin)
+            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+            rle_errs += errs[:z - a]
+        b, e = _first_error(rle_errs)
+        if e:
+            raise ShafaError(e, f"{what}: block {b}")
+        if p.perr:
+            raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        sizes, status, poff = _u64_host(d_size), d_status.cpu().tolist(), _u64_host(p.d_off)
+        blocks = [SeekBlock(sizes[i], nsym[i], poff[i], p.pn[i], first[i], status[i] != SEEK_UNINDEXED) for i in range(p.fb)]
+        # int64, as the bounds searchsorted is given: another type would make it convert the slice for every range
+        offsets = np.ascontiguousarray(d_ckpt.cpu().numpy()[1::2]) if is_rle else None
+        return SeekIndex(d_ckpt, blocks, span, mode, lengths, offsets)
+    finally:
+        bt.close()
+
+
+def _seek_items(index, spans):
+    """(lo, hi, destination) spans of the decoded file -> read_spans' items over the indexed blocks, and (block, lo, hi,
+    destination) for the pieces that lie in unindexed blocks"""
+    import bisect
+    items, other = [], []
+    starts, span = index.starts, index.span
+    for lo, hi, dst in spans:
+        b = bisect.bisect_right(starts, lo) - 1
+        while b < len(index.blocks) and starts[b] < hi:
+            blk, s0 = index.blocks[b], starts[b]
+            l, h = max(lo, s0) - s0, min(hi, starts[b + 1]) - s0
+            if l < h:
+                at = dst + (s0 + l - lo)
+                if not blk.indexed:
+                    other.append((b, l, h, at))
+                elif index.offsets is None:
+                    items.append((b, l // span, (h - 1) // span, l, h, at))
+                else:
+                    n = max(1, -(-blk.n_symbols // span))
+                    w = index.offsets[blk.first_checkpoint:blk.first_checkpoint + n]
+                    items.append((b, int(np.searchsorted(w, l, "right")) - 1, int(np.searchsorted(w, h, "left")) - 1, l, h, at))
+            b += 1
+    return items, other
+
+
+def read_ranges(index, ranges, shaf=None, cod=None, rle=None, freq=None, stream=None):
+    """The byte ranges `ranges` — a sequence of (offset, length), in any order, overlapping or not — of the decoded file of
+    the file set `index` was built from -> (out, offsets): range i is out[offsets[i]:offsets[i + 1]] and equals
+    decompress_files(...)[offset:offset + length] (Python slice semantics at the end of the file).  A negative offset or
+    length, files of another form or of other lengths than the index's: ValueError, before a device is touched.
+    One parse of the .cod's tables (unpack_cod, enqueued), ONE read_spans_dev for all ranges and one synchronisation
+    (finish); per range only the spans that cover it are decoded, out of the stream bytes where they lie, and nothing
+    proportional to a block is allocated.  Pieces in unindexed blocks go through decompress_range, block by block, and are
+    copied into place.  Files that are not the indexed ones give other bytes or ShafaError(SHAFA_FILE_UNRECOGNIZABLE)."""
+    import torch
+    what = "read_ranges"
+    if not isinstance(index, SeekIndex):
+        raise ValueError(f"{what}: index is a SeekIndex")
+    rs = [(int(o), int(n)) for o, n in ranges]
+    if any(o < 0 or n < 0 for o, n in rs):
+        raise ValueError(f"{what}: negative offset or length")
+    sf, files = _decode_args(shaf, cod, rle, freq, what)
+    if sf != (index.mode != "rle") or (files[0].numel(), files[1].numel()) != index.file_lengths:
+        raise ValueError(f"{what}: these are not the files the index was built from")
+    dev, total = files[0].device, index.decoded_size
+    offsets, spans = [0], []
+    for o, n in rs:
+        lo, hi = min(o, total), min(o + n, total)
+        if lo < hi:
+            spans.append((lo, hi, offsets[-1]))
+        offsets.append(offsets[-1] + hi - lo)
+    out = torch.empty(offsets[-1], dtype=torch.uint8, device=dev)
+    items, other = _seek_items(index, spans)
+    if items:
+        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        mb = unpack_max_blocks(files[1].numel(), "cod") if sf else 1
+        bt = Batch(max(mb, len(index.blocks), len(items)), 1 << 20)
+        try:
+            d_tab = None
+            if sf:
+                d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+                d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
+                d_tab = torch.empty(mb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+                bt.unpack_cod(st, mb, files[1], d_info, d_nsym, d_tab)
+            blocks = index.blocks
+            bt.read_spans_dev(st, files[0], [k.payload_offset for k in blocks], [k.payload_size for k in blocks],
+                              [k.n_symbols for k in blocks], [k.first_checkpoint for k in blocks], d_tab, index.span,
+                              (SEEK_SF if sf else 0) | (SEEK_RLE if index.mode != "N" else 0), index.checkpoints, items, out)
+            _, errs = bt.finish(st, max(mb, len(items)), raise_on_error=False)
+            i, e = _first_error(errs[:len(items)])
+            if e:
+                raise ShafaError(e, f"{what}: block {items[i][0]}")
+        finally:
+            bt.close()
+    for b, l, h, at in other:
+        piece = decompress_range(index.starts[b] + l, h - l, shaf=shaf, cod=cod, rle=rle, freq=freq, stream=stream)
+        out[at:at + h - l].copy_(piece)
+    return out, offsets
+
+
+def read_range(index, offset, length, **files):
+    """read_ranges for one range -> its bytes"""
+    return read_ranges(index, [(offset, length)], **files)[0]
 
 
 MANY_GROUP_SLOTS = 1 << 18      # decompress_many: parse slots per device batch (error words, workspace and tables grow with them)

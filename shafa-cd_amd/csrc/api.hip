@@ -526,6 +526,61 @@ int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, 
     return crc32_combine_launch_dev((Batch *)b, (hipStream_t)stream, nfiles, h_first, h_count, d_crc, d_n, d_file_crc, d_file_n);
 }
 
+// span: a power of two, 256 .. 8192; flags: SHAFA_SEEK_SF / SHAFA_SEEK_RLE only
+static bool seek_shape_ok(uint32_t span, int flags)
+{
+    return span >= 256 && span <= 8192 && (span & (span - 1)) == 0 && (flags & ~(SHAFA_SEEK_SF | SHAFA_SEEK_RLE)) == 0;
+}
+
+int shafa_hipd_seek_index_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                              const uint64_t *h_in_cap, const uint64_t *d_in_n, const shafa_code_table *d_tables, uint32_t span,
+                              int flags, const uint64_t *h_ckpt_first, uint64_t *d_ckpt, uint32_t *d_status, uint64_t *d_out_n)
+{
+    if (!b || !d_in || !d_in_n || !d_ckpt || !d_status || !d_out_n) return SHAFA_OUTSIDE_MODULE;
+    if (!seek_shape_ok(span, flags) || ((flags & SHAFA_SEEK_SF) && !d_tables)) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || !h_in_cap || !h_ckpt_first || ((uintptr_t)d_in & 15)) return SHAFA_OUTSIDE_MODULE;
+    u64 nspans = 0;
+    for (int i = 0; i < nblocks; ++i) {
+        if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
+        if ((nspans += h_in_cap[i] / span + (h_in_cap[i] % span != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    }
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return seek_index_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n,
+                                 (flags & SHAFA_SEEK_SF) ? d_tables : nullptr, span, flags, h_ckpt_first, d_ckpt, d_status, d_out_n);
+}
+
+int shafa_hipd_read_spans_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_file, uint64_t file_n,
+                              const uint64_t *h_pay_off, const uint64_t *h_pay_n, const uint64_t *h_n_symbols,
+                              const uint64_t *h_ckpt_first, const shafa_code_table *d_tables, uint32_t span, int flags,
+                              const uint64_t *d_ckpt, int nitems, const int *h_item_block, const uint64_t *h_item_first,
+                              const uint64_t *h_item_last, const uint64_t *h_item_lo, const uint64_t *h_item_hi,
+                              const uint64_t *h_item_dst, uint8_t *d_out, uint64_t out_n)
+{
+    if (!b || !d_ckpt || !d_out || (!d_file && file_n)) return SHAFA_OUTSIDE_MODULE;
+    if (!seek_shape_ok(span, flags) || ((flags & SHAFA_SEEK_SF) && !d_tables)) return SHAFA_OUTSIDE_MODULE;
+    if (nitems <= 0) return SHAFA_SUCCESS;
+    if (nitems > ((Batch *)b)->max_blocks || nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (nblocks <= 0 || !h_pay_off || !h_pay_n || !h_n_symbols || !h_ckpt_first || !h_item_block || !h_item_first ||
+        !h_item_last || !h_item_lo || !h_item_hi || !h_item_dst)
+        return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_pay_n[i] > file_n || h_pay_off[i] > file_n - h_pay_n[i] || h_pay_n[i] >= (1ull << 45)) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nitems; ++i) {
+        const int blk = h_item_block[i];
+        if (blk < 0 || blk >= nblocks) return SHAFA_OUTSIDE_MODULE;
+        const u64 ns = h_n_symbols[blk], nck = ns ? ns / span + (ns % span != 0) : 1;
+        if (h_item_first[i] > h_item_last[i] || h_item_last[i] >= nck || h_item_last[i] > 0xFFFFFFFFull) return SHAFA_OUTSIDE_MODULE;
+        if (h_item_lo[i] > h_item_hi[i] || h_item_dst[i] > out_n || h_item_hi[i] - h_item_lo[i] > out_n - h_item_dst[i])
+            return SHAFA_OUTSIDE_MODULE;
+    }
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return read_spans_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_file, h_pay_off, h_pay_n, h_n_symbols, h_ckpt_first,
+                                 (flags & SHAFA_SEEK_SF) ? d_tables : nullptr, span, flags, d_ckpt, nitems, h_item_block,
+                                 h_item_first, h_item_last, h_item_lo, h_item_hi, h_item_dst, d_out);
+}
+
 int shafa_hipd_sf_encoded_size_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
                                    const shafa_code_table *d_tables, uint64_t *d_out_n)
 {

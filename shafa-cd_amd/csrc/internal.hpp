@@ -222,6 +222,16 @@ int crc32_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, con
 // file f = blocks h_first[f] .. + h_count[f] of d_crc / d_n: the CRC-32 and the length of their concatenation (crc32.hip)
 int crc32_combine_launch_dev(Batch *bt, hipStream_t st, int nfiles, const int *h_first, const int *h_count, const u32 *d_crc,
                              const u64 *d_n, u32 *d_file_crc, u64 *d_file_n);
+// the checkpoints of blocks of SF-decoded bytes, every `span` symbols (seek.hip); the capacities' spans number fewer than 2^31
+int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                          const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,
+                          u64 *d_ckpt, u32 *d_status, u64 *d_out_n);
+// the bytes [lo, hi) of the items' blocks, decoded from the checkpoints that cover them (seek.hip); every item has been checked
+// against its block
+int read_spans_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_file, const u64 *h_pay_off, const u64 *h_pay_n,
+                          const u64 *h_n_symbols, const u64 *h_ckpt_first, const shafa_code_table *d_tables, u32 span, int flags,
+                          const u64 *d_ckpt, int nitems, const int *h_item_block, const u64 *h_item_first,
+                          const u64 *h_item_last, const u64 *h_item_lo, const u64 *h_item_hi, const u64 *h_item_dst, u8 *d_out);
 // the sizes sfenc_launch_dev would leave for blocks with these histograms and tables and room enough (sf_encoded_size.hip)
 int sfesize_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u64 *d_freq, const shafa_code_table *d_tables, u64 *d_out_n);
 // pack.hip's payload movers (pack_bulk, pack_seams) on records laid out elsewhere (unpack.hip): block b moves n bytes from src
