@@ -390,6 +390,49 @@ int shafa_hipd_crc32_dev(shafa_hipd_batch *b, void *stream, int nblocks, const u
 int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, const int *h_first, const int *h_count,
                                  const uint32_t *d_crc, const uint64_t *d_n, uint32_t *d_file_crc, uint64_t *d_file_n);
 
+/* The positions of a byte pattern (h_pat, pat_n = 1 .. SHAFA_FIND_MAX_PATTERN bytes, on the host) in byte regions in device
+ * memory, addressed as shafa_hipd_crc32_dev's: region b is the d_in_n[b] (<= h_in_cap[b], device resident) bytes at
+ * d_in + h_in_off[b]; the offsets are 64-bit and need NO alignment, nothing is copied, and bytes behind d_in_n[b] never influence
+ * the result.
+ * What a match is.  The SHAFA_FIND_NEXT bits of h_flags (NULL = all 0) cut the regions into maximal chains of consecutive
+ * regions: region b + 1 continues region b's stream iff h_flags[b] has the bit.  A chain stands for the concatenation of its
+ * regions' bytes; empty regions contribute nothing.  A match is every i at which the chain's bytes [i, i + pat_n) equal the
+ * pattern; overlapping matches all count ("aaaa" in ten 'a's is 7 matches).  Each match is charged to the region that holds its
+ * first byte, at offset o in that region, and is reported as h_pos[b] + o.  Matches charged to a SHAFA_FIND_CONTEXT region are
+ * dropped: such a region only supplies bytes to matches that start before it.  Without h_flags every region is its own chain
+ * and a match lies wholly inside one region.
+ * Outputs.  d_count[b] = the number of matches charged to region b (0 for a context region).  With T = the value of *d_total
+ * on the device when the call executes, the call's matches are numbered T, T + 1, ... by region ascending and by offset
+ * ascending within a region; match number k is stored at d_hits[k] iff k < max_hits, and *d_total becomes T + sum(d_count).
+ * Calls enqueued back to back on one stream with the same d_hits / d_total therefore append (a caller zeroes *d_total once),
+ * with no synchronisation in between.  Nothing else is written: d_hits[k] for k >= the new total and for k >= max_hits stays
+ * untouched.  d_hits may be NULL iff max_hits == 0 (counts only; no emit launch runs).
+ * A match is data and sets no error word.  Per-block codes through shafa_hipd_finish:
+ *   d_in_n[b] > h_in_cap[b]                SHAFA_OUTSIDE_MODULE, d_count[b] = 0; no byte of the block is read and the block
+ *                                          counts as empty in its chain.
+ * Launches, in none of which a workgroup waits for another or an atomic is used — the result does not depend on scheduling
+ * and the same call gives the same d_hits: every 8 KiB tile (numbered from the capacities) counts the matches that lie wholly
+ * inside its region; one workgroup per block puts its tiles' counts in order and finds the matches that start in the region's
+ * last pat_n - 1 bytes and run into the following regions of the chain (at most 2 (pat_n - 1) bytes, empty regions skipped,
+ * up to the first region without SHAFA_FIND_NEXT); one workgroup runs over the blocks' counts; with max_hits > 0 the tiles
+ * that hold a match find them again and store them — a tile without one is not read a second time.  A region is read in
+ * aligned 16-byte words that each hold at least one byte of it, shifted into place, and in single bytes inside it; no other
+ * byte is touched.  The device workspace is at most 16 bytes per 8 KiB of sum(h_in_cap) plus 72 bytes per block plus 512.
+ * Enqueues only: d_in_n and *d_total are never read on the host, no device-to-host copy is issued and nothing is synchronised;
+ * the one exception is the batch's growth, from nblocks and h_in_cap.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), in this order: NULL b (first),
+ * d_in, d_in_n, d_count, d_total or h_pat, pat_n of 0 or above SHAFA_FIND_MAX_PATTERN, NULL d_hits with max_hits > 0:
+ * SHAFA_OUTSIDE_MODULE; then nblocks <= 0: success (*d_total is left as it is, the host arrays may be NULL); nblocks > the
+ * batch's max_blocks, or 2^31 tiles or more in sum(h_in_cap): SHAFA_LACK_OF_MEMORY; NULL h_in_off, h_in_cap or h_pos, a flag
+ * bit other than the two defined, SHAFA_FIND_NEXT on the last region: SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_FIND_MAX_PATTERN 256
+#define SHAFA_FIND_NEXT 1    /* h_flags[b]: region b + 1 continues region b's stream */
+#define SHAFA_FIND_CONTEXT 2 /* h_flags[b]: matches that START in region b are not reported */
+int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                        const uint64_t *h_in_cap, const uint64_t *d_in_n, const uint8_t *h_flags, const uint64_t *h_pos,
+                        const uint8_t *h_pat, uint32_t pat_n, uint64_t max_hits, uint64_t *d_hits, uint64_t *d_count,
+                        uint64_t *d_total);
+
 /* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
  * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
  * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every

@@ -123,7 +123,9 @@ def lib():
     L.shafa_hipd_compare_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, u8p, u64p, u64p, vp]
     L.shafa_hipd_crc32_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_crc32_combine_dev.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp]
-    L.shafa_hipd_seek_index_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
+    L.shafa_hipd_find_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, C.c_char_p, u64p, C.c_char_p, C.c_uint32, C.c_uint64,
+                                      vp, vp, vp]
+    L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
     L.shafa_hipd_read_spans_dev.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, u64p, u64p, u64p, u64p, vp, C.c_uint32, C.c_int, vp,
                                             C.c_int, C.POINTER(C.c_int), u64p, u64p, u64p, u64p, u64p, u8p, C.c_uint64]
     L.shafa_hipd_finish.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int)]
@@ -181,7 +183,8 @@ def lib():
                  "shafa_hipd_unpack_cod_files", "shafa_hipd_unpack_rle_freq_files", "shafa_hipd_unpack_shaf_files",
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
                  "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
-                 "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev"):
+                 "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev",
+                 "shafa_hipd_find_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -453,6 +456,19 @@ class Batch:
         _check(lib().shafa_hipd_crc32_combine_dev(self.h, self._st(stream), len(fi), _p32(fi), _p32(co), d_crc.data_ptr(),
                                                   d_n.data_ptr(), d_file_crc.data_ptr(), d_file_n.data_ptr()),
                "hipd_crc32_combine_dev")
+
+    def find_dev(self, stream, d_in, in_off, in_cap, d_in_n, flags, pos, pattern, max_hits, d_hits, d_count, d_total):
+        """The positions of `pattern` (1 .. 256 bytes) in the d_in_n[b] (int64, device; <= in_cap[b]) bytes at d_in + in_off[b]
+        (any alignment, read in place), as pos[b] + the offset in the region: appended to d_hits (int64; None iff max_hits is 0)
+        from index d_total[0] (int64, device) on while the index is below max_hits; d_count[b] (int64) = region b's matches,
+        d_total[0] += their sum.  flags (None = all 0): FIND_NEXT = region b + 1 continues region b's stream, FIND_CONTEXT =
+        matches that start in region b are not reported.  Enqueues only (include/shafa_hip.h: shafa_hipd_find_dev)."""
+        io, ic, po = _u64arr(in_off), _u64arr(in_cap), _u64arr(pos)
+        fl = None if flags is None else bytes(bytearray(flags))
+        pat = bytes(pattern)
+        _check(lib().shafa_hipd_find_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic), d_in_n.data_ptr(),
+                                         fl, _p64(po), pat, len(pat), int(max_hits), None if d_hits is None else d_hits.data_ptr(),
+                                         d_count.data_ptr(), d_total.data_ptr()), "hipd_find_dev")
 
     def seek_index_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, span, flags, ckpt_first, d_ckpt, d_status, d_out_n):
         """The checkpoints, every `span` symbols, of blocks of SF-decoded bytes: block b's d_in_n[b] (int64, device; <=
@@ -1865,6 +1881,218 @@ def checksum_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, st
             if e:                                                                # the size pass accepted every block: the device
                 raise ShafaError(e, f"{what}: RLE decoding")
         return Checksum(int(d_file_crc.cpu()[0]) & 0xFFFFFFFF, int(d_file_n.cpu()[0]))
+    finally:
+        bt.close()
+
+
+# ------------------------------------------------------------------ pattern search
+FIND_NEXT, FIND_CONTEXT, FIND_MAX_PATTERN = 1, 2, 256
+FIND_PIECE = 1 << 26            # find: a segment is searched in chained pieces of 64 MiB (8192 tiles each)
+Found = collections.namedtuple("Found", "count positions size")
+
+
+def _find_args(pattern, max_hits, what):
+    """the pattern as bytes and max_hits as an int, or ValueError"""
+    try:
+        pat = memoryview(pattern).tobytes()
+    except TypeError:
+        raise ValueError(f"{what}: pattern is bytes-like") from None
+    if not 1 <= len(pat) <= FIND_MAX_PATTERN:
+        raise ValueError(f"{what}: pattern of 1 .. {FIND_MAX_PATTERN} bytes")
+    try:
+        hits = -1 if isinstance(max_hits, bool) else max_hits.__index__()
+    except (AttributeError, TypeError):
+        hits = -1
+    if hits < 0:
+        raise ValueError(f"{what}: max_hits is a non-negative int")
+    return pat, hits
+
+
+def find(d_in, pattern, sizes=None, max_hits=65536, stream=None, _piece=None):
+    """Where `pattern` (bytes-like, 1 .. 256 bytes) occurs in a contiguous uint8 CUDA tensor, searched where it lies (any
+    alignment, nothing is copied) -> Found(count, positions, size): count = the number of occurrences, overlapping ones
+    included (exact, however small max_hits is), positions = the first min(count, max_hits) of them as an ascending numpy
+    int64 array of indices into the tensor, size = the bytes searched.  With `sizes` (crc32's convention): each of the
+    consecutive segments of these lengths is searched on its own — an occurrence that straddles two segments is none — and
+    the call returns a list of Found, positions relative to the segment, max_hits per segment.
+    A segment longer than FIND_PIECE (64 MiB) is cut into pieces of that size, one region each for find_dev, chained with
+    FIND_NEXT, so an occurrence over a piece seam is found.  With max_hits = 0 all segments go through one find_dev call
+    and the counts are the regions'; else one call per segment appends into the segment's own part of one array (at most
+    min(max_hits, size - len(pattern) + 1) entries: a segment has no more occurrences).  One synchronisation, then the
+    counts and the positions kept are read."""
+    import itertools
+    import torch
+    if not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_cuda or not d_in.is_contiguous():
+        raise ValueError("find: d_in is a contiguous uint8 CUDA tensor")
+    pat, max_hits = _find_args(pattern, max_hits, "find")
+    d_in = d_in.reshape(-1)
+    segs = [int(d_in.numel())] if sizes is None else [int(n) for n in sizes]
+    if any(n < 0 for n in segs) or sum(segs) > d_in.numel():
+        raise ValueError("find: sizes exceed d_in")
+    piece = int(_piece) if _piece else FIND_PIECE
+    m = len(pat)
+    off, cap, flags, pos, first, start = [], [], [], [], [], 0
+    for n in segs:
+        first.append(len(off))
+        for a in range(0, n, piece):
+            off.append(start + a)
+            cap.append(min(piece, n - a))
+            pos.append(a)
+            flags.append(FIND_NEXT if a + piece < n else 0)
+        start += n
+    first.append(len(off))
+    counts, kept, hoff, h = [0] * len(segs), [0] * len(segs), [0] * len(segs), np.empty(0, dtype=np.int64)
+    if off:
+        dev = d_in.device
+        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        bt = Batch(len(off), piece)
+        try:
+            d_n = torch.tensor(cap, dtype=torch.int64).to(dev)
+            d_count = torch.zeros(len(off), dtype=torch.int64, device=dev)
+            d_total = torch.zeros(len(segs), dtype=torch.int64, device=dev)
+            if max_hits == 0:
+                bt.find_dev(st, d_in, off, cap, d_n, flags, pos, pat, 0, None, d_count, d_total)
+                bt.finish(st, len(off))
+                c = d_count.cpu().tolist()
+                counts = [sum(c[a:z]) for a, z in zip(first, first[1:])]
+            else:
+                room = [min(max_hits, max(0, n - m + 1)) for n in segs]
+                hoff = list(itertools.accumulate(room, initial=0))
+                d_hits = torch.empty(max(hoff[-1], 1), dtype=torch.int64, device=dev)
+                for i, (a, z) in enumerate(zip(first, first[1:])):
+                    if a < z:
+                        bt.find_dev(st, d_in, off[a:z], cap[a:z], d_n[a:z], flags[a:z], pos[a:z], pat, room[i],
+                                    d_hits[hoff[i]:] if room[i] else None, d_count[a:z], d_total[i:i + 1])
+                bt.finish(st, len(off))
+                counts = d_total.cpu().tolist()
+                kept = [min(c, r) for c, r in zip(counts, room)]
+                h = d_hits[:max((o + k for o, k in zip(hoff, kept) if k), default=0)].cpu().numpy()
+        finally:
+            bt.close()
+    out = [Found(int(c), h[o:o + k].copy(), n) for c, k, o, n in zip(counts, kept, hoff, segs)]
+    return out[0] if sizes is None else out
+
+
+def find_files(pattern, shaf=None, cod=None, rle=None, freq=None, decode_rle=True, max_hits=65536, stream=None, max_bytes=None):
+    """Where `pattern` occurs in the file a file set held in device memory decodes to (decompress_files' file arguments and
+    decode_rle) -> Found(count, positions, size).  With out = decompress_files(the same arguments) the answer is
+    find(out, pattern, max_hits=max_hits), size = out.numel(); raises what that call raises — every block is decoded, so a
+    fault is reported whichever group it lies in.  Together with build_index / read_ranges this is the complete "locate, then
+    fetch" pair: the positions found here are the ranges read there, and the decoded file never exists for either.
+    Neither the decoded file nor a tensor of its size ever exists: verify_files' structure with find_dev where compare_dev is.
+      shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload) that fit max_bytes (default: a quarter
+                                  of the free device memory); each runs unpack_payloads -> sf_decode_dev -> find_dev -> one
+                                  synchronisation
+      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files, then per group of _rle_groups rle_decode_dev
+                                  -> find_dev out of one reused buffer, back to back on the stream, and one synchronisation
+    A group's blocks are one chain (FIND_NEXT), each reported at its offset in the decoded file.  Occurrences over a GROUP
+    seam: behind a group's find_dev the last len(pattern) - 1 bytes of the stream so far are copied to a carry (stream
+    ordered, before the buffer is used again); in front of the next group's find_dev a seam tensor of that carry and the
+    group's first len(pattern) - 1 bytes is searched as two regions, {FIND_NEXT} and {FIND_CONTEXT}.  All calls append into
+    one array and one total on the device, so the positions come out ascending without a sort and without a
+    synchronisation of their own; behind the last synchronisation the total is read, then the positions kept.  No
+    pack_payloads(RAW) runs; the synchronisations are verify_files'."""
+    import itertools
+    import torch
+    what = "find_files"
+    pat, max_hits = _find_args(pattern, max_hits, what)
+    m = len(pat)
+    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
+    try:
+        dev = files[0].device
+        if max_bytes is None:
+            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
+        if p.fb == 0:
+            return Found(0, np.empty(0, dtype=np.int64), 0)
+        res = torch.empty(1 + max_hits, dtype=torch.int64, device=dev)           # the total, then the positions
+        d_total, d_hits = res[:1], res[1:] if max_hits else None
+        d_total.zero_()
+        d_save = torch.zeros(1, dtype=torch.int64, device=dev)
+        d_count = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+        d_count2 = torch.zeros(2, dtype=torch.int64, device=dev)
+        carry = [torch.empty(m, dtype=torch.uint8, device=dev) for _ in range(2)]
+        d_seam = torch.empty(2 * m + 16, dtype=torch.uint8, device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))                           # the zeroing above, in front of the stream's work
+
+        def seam_sizes(groups):
+            """per group: the carry's and the head's lengths, on the device (from the host's sizes)"""
+            t = [[min(m - 1, starts[a]), min(m - 1, starts[z] - starts[a])] for a, z in groups]
+            return {a: d for (a, _), d in zip(groups, torch.tensor(t, dtype=torch.int64).reshape(-1, 2).to(dev))}
+
+        def search(a, d_a, a_off, a_n, d_a_n, cin):
+            """enqueue, for the group of blocks from a on: the seam's search, the group's own, the copy of the new carry
+            -> the carry behind the group (which of the two buffers, its length)"""
+            ci, cl = cin
+            nb, total = len(a_n), sum(a_n)
+            with torch.cuda.stream(st):
+                if m > 1 and cl and total:
+                    d_seam[:cl].copy_(carry[ci][:cl])
+                    hl = 0
+                    for o, n in zip(a_off, a_n):                             # the head may span several short blocks
+                        take = min(n, m - 1 - hl)
+                        if take:
+                            d_seam[cl + hl:cl + hl + take].copy_(d_a[o:o + take])
+                            hl += take
+                        if hl == m - 1:
+                            break
+                    bt.find_dev(st, d_seam, [0, cl], [cl, hl], d_seam_n[a], [FIND_NEXT, FIND_CONTEXT],
+                                [starts[a] - cl, starts[a]], pat, max_hits, d_hits, d_count2, d_total)
+                bt.find_dev(st, d_a, a_off, a_n, d_a_n, [FIND_NEXT] * (nb - 1) + [0], starts[a:a + nb], pat, max_hits, d_hits,
+                            d_count[a:a + nb], d_total)
+                if m == 1:
+                    return cin
+                tail, have = [], 0
+                for o, n in zip(reversed(a_off), reversed(a_n)):
+                    take = min(n, m - 1 - have)
+                    if take:
+                        tail.append((o + n - take, take))
+                        have += take
+                    if have == m - 1:
+                        break
+                old = min(cl, m - 1 - have)                                  # a group shorter than the carry keeps some of it
+                nxt = carry[1 - ci]
+                if old:
+                    nxt[:old].copy_(carry[ci][cl - old:cl])
+                for o, t in reversed(tail):
+                    nxt[old:old + t].copy_(d_a[o:o + t])
+                    old += t
+                return 1 - ci, old
+
+        cur = (0, 0)
+        if sf and not (p.mode == "R" and decode_rle):
+            sizes = list(p.nsym)
+            starts = list(itertools.accumulate(sizes, initial=0))
+            groups = _groups([_al16(s) + _al16(n) for s, n in zip(sizes, p.pn)], max_bytes)
+            d_seam_n = seam_sizes(groups)
+            for a, z in groups:
+                nxt = []
+
+                def then(d_a, a_off, a_n, d_a_n):
+                    with torch.cuda.stream(st):
+                        d_total.copy_(d_save)                                # a group decoded again is searched again
+                    nxt.append(search(a, d_a, a_off, a_n, d_a_n, cur))
+                with torch.cuda.stream(st):
+                    d_save.copy_(d_total)
+                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=then)
+                cur = nxt[-1]
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        else:
+            sizes, rin = _measure_set(bt, st, sf, files, p, what)
+            if p.perr:
+                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+            starts = list(itertools.accumulate(sizes, initial=0))
+            d_seam_n = seam_sizes(_rle_groups(sizes, rin[2], max_bytes))
+            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
+                cur = search(a, d_a, a_off, sizes[a:z], d_a_n, cur)
+            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+            _, e = _first_error(errs)
+            if e:                                                                # the size pass accepted every block: the device
+                raise ShafaError(e, f"{what}: RLE decoding")
+        total = int(res[:1].cpu()[0])
+        kept = min(total, max_hits)
+        return Found(total, res[1:1 + kept].cpu().numpy().copy() if kept else np.empty(0, dtype=np.int64), starts[-1])
     finally:
         bt.close()
 

@@ -526,6 +526,28 @@ int shafa_hipd_crc32_combine_dev(shafa_hipd_batch *b, void *stream, int nfiles, 
     return crc32_combine_launch_dev((Batch *)b, (hipStream_t)stream, nfiles, h_first, h_count, d_crc, d_n, d_file_crc, d_file_n);
 }
 
+int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in, const uint64_t *h_in_off,
+                        const uint64_t *h_in_cap, const uint64_t *d_in_n, const uint8_t *h_flags, const uint64_t *h_pos,
+                        const uint8_t *h_pat, uint32_t pat_n, uint64_t max_hits, uint64_t *d_hits, uint64_t *d_count,
+                        uint64_t *d_total)
+{
+    if (!b || !d_in || !d_in_n || !d_count || !d_total || !h_pat) return SHAFA_OUTSIDE_MODULE;
+    if (pat_n == 0 || pat_n > SHAFA_FIND_MAX_PATTERN || (max_hits && !d_hits)) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_cap) return SHAFA_OUTSIDE_MODULE;
+    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (tile_pass.hpp numbers them in 31 bits)
+    for (int i = 0; i < nblocks; ++i)
+        if ((ntiles += h_in_cap[i] / 8192 + (h_in_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || !h_pos) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; h_flags && i < nblocks; ++i)
+        if (h_flags[i] & ~(SHAFA_FIND_NEXT | SHAFA_FIND_CONTEXT)) return SHAFA_OUTSIDE_MODULE;
+    if (h_flags && (h_flags[nblocks - 1] & SHAFA_FIND_NEXT)) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return find_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, h_flags, h_pos, h_pat,
+                           pat_n, max_hits, d_hits, d_count, d_total);
+}
+
 // span: a power of two, 256 .. 8192; flags: SHAFA_SEEK_SF / SHAFA_SEEK_RLE only
 static bool seek_shape_ok(uint32_t span, int flags)
 {

@@ -222,6 +222,11 @@ int crc32_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, con
 // file f = blocks h_first[f] .. + h_count[f] of d_crc / d_n: the CRC-32 and the length of their concatenation (crc32.hip)
 int crc32_combine_launch_dev(Batch *bt, hipStream_t st, int nfiles, const int *h_first, const int *h_count, const u32 *d_crc,
                              const u64 *d_n, u32 *d_file_crc, u64 *d_file_n);
+// the positions of the pat_n pattern bytes in the blocks' regions (d_in_n[b] <= h_in_cap[b] bytes at d_in + h_in_off[b], any
+// alignment), chained by h_flags (NULL = none), appended to d_hits from *d_total on (find.hip); the arguments have been checked
+int find_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
+                    const u64 *d_in_n, const u8 *h_flags, const u64 *h_pos, const u8 *h_pat, u32 pat_n, u64 max_hits, u64 *d_hits,
+                    u64 *d_count, u64 *d_total);
 // the checkpoints of blocks of SF-decoded bytes, every `span` symbols (seek.hip); the capacities' spans number fewer than 2^31
 int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                           const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,
