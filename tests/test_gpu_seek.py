@@ -185,10 +185,8 @@ def _rld(rle):
     return np.array(out, dtype=np.uint8)
 
 
-@pytest.fixture(scope="module")
-def hand(shafa):
-    """the hand-made .rle with its .freq, and the .shaf + .cod that Modules T and C make of them"""
-    blocks = _hand_blocks()
+def _hand_files(shafa, blocks):
+    """hand-made .rle blocks with their .freq, and the .shaf + .cod that Modules T and C make of them"""
     rle = np.concatenate(blocks)
     freq = _text_file(b"R", [len(b) for b in blocks],
                       [shafa.freq_format(np.bincount(b, minlength=256).astype(np.uint64)) for b in blocks])
@@ -199,6 +197,11 @@ def hand(shafa):
     tabs = [shafa.cod_parse(t) for t in _bytes(cod).split(b"@")[4::2] if t]
     assert all(rc == 0 for rc, _ in tabs)
     return blocks, data, dict(rle=d_rle, freq=d_freq), dict(shaf=shaf, cod=cod), [_lens(t) for _, t in tabs]
+
+
+@pytest.fixture(scope="module")
+def hand(shafa):
+    return _hand_files(shafa, _hand_blocks())
 
 
 def test_the_shapes_occur(hand):
@@ -306,12 +309,17 @@ def test_build_index_raises_what_decompress_files_raises(shafa, oracle):
 
 @pytest.mark.parametrize("name", ["N", "R", "rle+freq"])
 def test_overwritten_payloads_give_bytes_or_an_error(shafa, oracle, name, monkeypatch):
-    import torch
     n = 3 * BS + 33
     data, kw, _ = _sets(shafa, oracle, n, BS)[name]
     idx = shafa.build_index(span=256, **kw)
+    _overwrite_payloads(shafa, monkeypatch, name, kw, idx, n, _ranges(n, BS, 256, 5), range(6))
+
+
+def _overwrite_payloads(shafa, monkeypatch, name, kw, idx, n, ranges, trials):
+    """per trial: 64 payload bytes of one block overwritten after indexing, one read_ranges call over `ranges` whose out lies
+    inside guard bytes -> bytes or FILE_UNRECOGNIZABLE, and the guards are what they were"""
+    import torch
     pay = "shaf" if "shaf" in kw else "rle"
-    ranges = _ranges(n, BS, 256, 5)
     want_n = sum(min(o + k, n) - min(o, n) for o, k in ranges)
     guard = 4096
     real_empty = torch.empty
@@ -325,7 +333,7 @@ def test_overwritten_payloads_give_bytes_or_an_error(shafa, oracle, name, monkey
 
     rng = np.random.default_rng(17)
     outcomes = set()
-    for trial in range(6):
+    for trial in trials:
         raw = bytearray(_bytes(kw[pay]))
         blk = idx.blocks[trial % len(idx.blocks)]
         a = blk.payload_offset + int(rng.integers(0, max(1, blk.payload_size - 64)))
