@@ -938,6 +938,9 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_ends(const DecBlk *__restrict
 // dynamic LDS: rows | sym3 (tab_bytes) | long table (LONG) | image (cap bytes) | wsum[4], next
 // The host sizes the image for the launch's average symbols per tile plus a margin (LDS is what limits the waves per
 // CU); a tile with more symbols than it holds goes in several rounds of consecutive lanes.
+// A workgroup runs up to 16 tiles and asks for the next tile's rows in front of a tile's walk; the image's stores are
+// issued as a fixed number of unbranched buffer stores per wave, so that the wait for those rows leaves them in flight
+// (the counted wait).
 // ------------------------------------------------------------------------------------------------
 // LDS words per chunk row: the chunk and the words behind it that the last fetch of the walk may read — two, or three when a
 // code longer than the window (ESC: read as 32 bits) may start in them.  Rows 10 words apart would put lanes 16 apart on one
@@ -949,6 +952,11 @@ constexpr int ws_rows_bytes(bool esc)               // 16 in front: the window a
     return 16 + (DEC_THREADS * ws_row(esc) + (esc ? 0 : DEC_THREADS / 16)) * 4;
 }
 constexpr int WS_MISC = 32;
+typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
+// the image's read-out: store instructions per wave and pass; the offset of a lane that has nothing to store (outside every
+// window, and far from wrapping); a raw buffer of dwords (DATA_FORMAT 32); the non-temporal bit of a buffer store
+constexpr u32 WS_NST = 4, WS_DROP = 0x7FFFFFF0u;
+constexpr int WS_RSRC_FLAGS = 0x00020000, WS_AUX_NT = 2;
 
 // ESC: some code of the launch may be longer than its block's sym3 window (then a look-up can return no symbol)
 template <int LONG, bool ESC>
@@ -1000,18 +1008,44 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
         return make_uint4(w[0], w[1], w[2], w[3]);
     };
     // a tile's inputs travel through registers: they are requested while the tile before is being decoded
-    uint4 pf0, pf1, pf2 = make_uint4(0, 0, 0, 0);
-    u32 pf_entry = 0, pf_cnt = 0, pf_next = 0;
+    uint4 pf0, pf1;
+    u32 pf2[ESC ? 3 : 2] = {};                          // (loaded no wider than it is used: a loaded register that nothing reads is
+                                                        //  soon written by something else, which has to wait for the load first)
+    // the two (ESC: three) stream words at `off` (zeros past the end)
+    auto fetch_ahead = [&](const u64 off) {
+        constexpr int NB = ESC ? 12 : 8;
+        if (off + NB <= blk.in_n) {
+            if constexpr (ESC) {
+                const u32x3_t v = __builtin_nontemporal_load((const GLOBAL_AS u32x3_t *)(unsigned long long)(blk.in + off));
+                pf2[0] = v.x; pf2[1] = v.y; pf2[2] = v.z;
+            } else {
+                const uint2 v = gload_nt<uint2>(blk.in + off);
+                pf2[0] = v.x; pf2[1] = v.y;
+            }
+            return;
+        }
+        u32 w[3] = {0, 0, 0};
+        if (off < blk.in_n) {
+            const int nv = (int)(blk.in_n - off);
+#pragma unroll
+            for (int q = 0; q < NB; ++q)
+                if (q < nv) w[q >> 2] |= (u32)gload<u8>(blk.in + off + q) << (8 * (q & 3));
+        }
+#pragma unroll
+        for (int q = 0; q < NB / 4; ++q) pf2[q] = w[q];
+    };
+    u8 pf_entry = 0, pf_next = 0;                       // (as narrow as they are loaded: widening them here would be a use of
+    u16 pf_cnt = 0;                                     //  the loaded registers, and so a full wait, right behind the loads)
     auto prefetch = [&](const u32 tile) {
         const u64 base = (u64)tile * DTILE;
-        pf0 = fetch16(base + 16ull * tid);
-        pf1 = fetch16(base + 16ull * (tid + DEC_THREADS));
-        if (tid == 0) pf2 = fetch16(base + DTILE);      // the last row's look-ahead word
         const size_t g = ((size_t)blk.tile_base + tile) * DEC_THREADS + tid;
         pf_entry = chunk_entry[g];
         pf_cnt = chunk_cnt[g];
         // the entry of the chunk behind this one = where this chunk's codes end (not asked for in a block's last tile)
-        pf_next = (tile + 1 < blk.n_tiles || tid + 1 < (u32)DEC_THREADS) ? chunk_entry[g + 1] : 0u;
+        pf_next = (tile + 1 < blk.n_tiles || tid + 1 < (u32)DEC_THREADS) ? chunk_entry[g + 1] : (u8)0;
+        pf0 = fetch16(base + 16ull * tid);
+        pf1 = fetch16(base + 16ull * (tid + DEC_THREADS));
+        if (tid == 0) fetch_ahead(base + DTILE);        // the last row's look-ahead words
     };
     // tile word f -> word f % 8 of row f / 8; a row's first two (ESC: three) words are also the look-ahead words of the row before
     auto put16 = [&](const u32 i, const uint4 v) {
@@ -1040,6 +1074,11 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
     u32 carry_n = 0, carry_lo = 0;                      // (uniform) piece 0 of the image holds bytes [carry_lo, carry_n) of the
     u8 *carry_g = nullptr;                              //   output piece at carry_g, kept from the round before
     prefetch(first_tile);
+    // The first tile's rows are waited for here, in full.  Inside the loop a tile's rows were asked for in front of the
+    // image stores of the tile before (one in-order vmcnt for loads and stores), so the wait for them can be a counted one,
+    // vmcnt(WS_NST) at the end of a tile, that leaves those stores in flight — as long as no path into the loop arrives
+    // with loads that have no stores behind them, and no path through a tile issues fewer stores than that.
+    __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), nothing else
     for (u32 it = 0; it < tpw; ++it) {
         const u32 tile = first_tile + it;
         if (tile >= blk.n_tiles) break;
@@ -1049,7 +1088,7 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
         lds_barrier();                                // the previous tile's rows and image are done with
         put16(tid, pf0);
         put16(tid + DEC_THREADS, pf1);
-        if (tid == 0) put16(DTILE / 16, pf2);
+        if (tid == 0) put16(DTILE / 16, make_uint4(pf2[0], pf2[1], ESC ? pf2[ESC ? 2 : 0] : 0u, 0u));
         const u32 entry = pf_entry, cnt = pf_cnt, nent = pf_next;
         if (it + 1 < tpw && tile + 1 < blk.n_tiles) prefetch(tile + 1);
         const u32 incl = wave_incl_scan_add<u32>(cnt);
@@ -1058,7 +1097,7 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
         u32 pre = incl - cnt, total = 0;
         for (u32 w = 0; w < 4; ++w) { if (w < wv) pre += wsum[w]; total += wsum[w]; }
         const u64 room = blk.n_sym - toff;              // symbols of this tile that exist in the block
-        const u32 tot_c = room < (u64)total ? (u32)room : total;
+        const u32 tot_c = (u32)__builtin_amdgcn_readfirstlane((int)(room < (u64)total ? (u32)room : total));  // (uniform, and known to be)
         u32 want = pre >= tot_c ? 0u : (tot_c - pre < cnt ? tot_c - pre : cnt);
         u32 q2 = q2row + entry;
         // A lane that emits all of its chunk's codes, in a tile behind which the stream goes on, knows where they end: the
@@ -1069,7 +1108,8 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
         // run on zero fill past the lane's count; the counted loop is exact there)
         const bool by_pos = want == cnt && tile + 1 < blk.n_tiles && nent != spec_emask<LONG>();
         const u32 q2end = q2row + 256u + nent;
-        for (u32 done = 0; done < tot_c;) {
+        u32 done = 0;
+        do {                                            // (at least one round, so that every tile issues its WS_NST stores)
             u8 *gout = blk.out + toff + done;
             const u32 mis = (u32)((uintptr_t)gout & 15u);
             if (carry_g && (carry_n != mis || carry_g != gout - mis)) {      // (uniform) the kept pieces are not where this round
@@ -1090,7 +1130,7 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
                 lds_barrier();
                 if (want && pre >= done && mis + (pre - done) + want > capw) atomicMin(next, pre);
                 lds_barrier();
-                nxt = *next;
+                nxt = (u32)__builtin_amdgcn_readfirstlane((int)*next);
                 lds_barrier();
             }
             if (want && pre >= done && pre + want <= nxt) {
@@ -1194,12 +1234,43 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
             const u32 lo0 = (carry_n == mis && carry_n) ? carry_lo : mis;     // piece 0: bytes [lo0, 16) are this workgroup's
             const u32 nfull = end >> 4;
             u8 *const g0 = gout - mis;
-            for (u32 u = tid; u < nfull; u += DEC_THREADS) {
-                uint4 *ip = (uint4 *)(smem + img_off + 16 * u);
-                const uint4 v = *ip;
-                *ip = make_uint4(0, 0, 0, 0);
-                if (u == 0 && lo0) store_bytes(g0, v, lo0, 16u);
-                else gstore_nt<uint4>(g0 + 16 * u, v);
+            // The pieces leave through a buffer descriptor that spans exactly [g0, g0 + 16 nfull): a store whose offset is
+            // outside it is dropped by the hardware, so a lane without a piece needs no branch around its store and every
+            // wave issues exactly WS_NST store instructions per pass (one pass unless the image is larger than
+            // WS_NST * DEC_THREADS pieces) — a number the compiler can count when it places the wait for the next tile's rows.
+            // (LONG == 2 keeps the plain loop: its walk calls the 32-bit look-up as a function and spills registers around the
+            // call, and scratch traffic counts in vmcnt too — there is no wait left to count there)
+            if constexpr (LONG == 2) {
+                for (u32 u = tid; u < nfull; u += DEC_THREADS) {
+                    uint4 *ip = (uint4 *)(smem + img_off + 16 * u);
+                    const uint4 v = *ip;
+                    *ip = make_uint4(0, 0, 0, 0);
+                    if (u == 0 && lo0) store_bytes(g0, v, lo0, 16u);
+                    else gstore_nt<uint4>(g0 + 16 * u, v);
+                }
+            } else {
+                const __amdgpu_buffer_rsrc_t win = __builtin_amdgcn_make_buffer_rsrc(g0, 0, (int)(16u * nfull), WS_RSRC_FLAGS);
+                u32 ub = tid;
+                do {
+#pragma unroll
+                    for (u32 s = 0; s < WS_NST; ++s) {
+                        const u32 u = ub + s * DEC_THREADS;
+                        u32x4_t x = {0u, 0u, 0u, 0u};
+                        u32 off = WS_DROP;
+                        if (u < nfull) {
+                            uint4 *ip = (uint4 *)(smem + img_off + 16 * u);
+                            const uint4 v = *ip;
+                            *ip = make_uint4(0, 0, 0, 0);
+                            if (s == 0 && u == 0 && lo0) store_bytes(g0, v, lo0, 16u);
+                            else {
+                                x.x = v.x; x.y = v.y; x.z = v.z; x.w = v.w;
+                                off = 16u * u;
+                            }
+                        }
+                        __builtin_amdgcn_raw_buffer_store_b128(x, win, (int)off, 0, WS_AUX_NT);
+                    }
+                    ub += WS_NST * DEC_THREADS;
+                } while (__builtin_amdgcn_readfirstlane((int)(ub - tid)) < (int)nfull);
             }
             if (tid == 0 && nfull) {                    // the piece the round ends in and the one behind it (symbols of the next
                 uint4 *ip = (uint4 *)(smem + img_off);  //   chunk that the round's last lane has already placed there) move to
@@ -1214,7 +1285,7 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
             carry_g = g0 + 16 * nfull;
             done = nxt;
             if (done < tot_c) lds_barrier();          // the image is in place again before the next round's ORs
-        }
+        } while (done < tot_c);
     }
     if (tid == 0 && carry_n) {                          // the last piece of the workgroup's run of tiles
         const uint4 v = *(const uint4 *)(smem + img_off);
