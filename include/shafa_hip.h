@@ -433,6 +433,43 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
                         const uint8_t *h_pat, uint32_t pat_n, uint64_t max_hits, uint64_t *d_hits, uint64_t *d_count,
                         uint64_t *d_total);
 
+/* ---- Byte planes: arrays of typed elements <-> one byte string per byte of the element ------------------------------------
+ * The codec is order-0 over bytes; the bytes of a typed element (the sign and exponent byte of a float, its mantissa bytes, the
+ * high bytes of small integers) have very different histograms, so each is coded apart.  Block b is d_n[b] (<= h_cap[b],
+ * device resident) ELEMENTS of `elem` = 1, 2, 4 or 8 bytes; elem = 1 is a plain copy through the same code.
+ *   element side   the block's elem * d_n[b] bytes at d_in (d_out) + h_in_off[b] (h_out_off[b]); the offsets are 64-bit and
+ *                  need NO alignment, as shafa_hipd_crc32_dev's: tensors are transposed where they lie.
+ *   plane side     plane j of block b = byte j of every element, little-endian (plane 0 is the least significant byte):
+ *                  d_n[b] bytes at d_planes + h_plane_off[b * elem + j].  d_planes and every plane offset are multiples of 16
+ *                  (the caller allocates this side).
+ * shafa_hipd_split_planes_dev reads the element side and writes the planes; shafa_hipd_merge_planes_dev is its inverse.
+ * What is read.  split reads the element side in aligned 16-byte words that each hold at least one byte of the region, shifted
+ * into place; no other byte is touched, nothing is copied, and bytes outside the region never influence the result.  merge
+ * reads a plane in aligned 16-byte words that each hold at least one of its d_n[b] bytes.
+ * What is written.  split writes the d_n[b] bytes of each plane and nothing behind them (whole 16-byte words, single bytes
+ * in the last one).  merge writes the elem * d_n[b] bytes of the region and nothing else: aligned 16-byte words that lie
+ * wholly inside it, single bytes at its two ends; the up to 15 bytes on either side of an unaligned region are untouched.
+ * Per-block codes through shafa_hipd_finish:
+ *   d_n[b] > h_cap[b]                      SHAFA_OUTSIDE_MODULE; no byte of the block is read or written, other blocks are
+ *                                          unaffected.
+ * One launch for all blocks, in which no workgroup waits for another: tiles of SHAFA_PLANES_TILE elements, numbered from the
+ * capacities, a lane transposing 16 elements at a time in registers (elem words of the element side, one word of each plane:
+ * per plane a wave's stores are 1 KiB contiguous); a tile at or behind d_n[b] exits.  The only atomic is the error word above.
+ * The device workspace is (20 + 8 elem) bytes per block plus 20.  Enqueues only: d_n is never read on the host, no
+ * device-to-host copy is issued and nothing is synchronised; the one exception is the batch's growth, from nblocks.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), in this order: NULL b (first),
+ * d_in / d_out, d_planes or d_n, an elem other than 1, 2, 4, 8: SHAFA_OUTSIDE_MODULE; then nblocks <= 0: success (the host
+ * arrays may be NULL); nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY; NULL h_cap: SHAFA_OUTSIDE_MODULE; an
+ * elem * h_cap[b] or their sum past 64 bits, or 2^31 tiles or more in the capacities: SHAFA_LACK_OF_MEMORY; NULL h_in_off /
+ * h_out_off or h_plane_off, a d_planes or an h_plane_off[b * elem + j] that is no multiple of 16: SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_PLANES_TILE 8192 /* elements */
+int shafa_hipd_split_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
+                                const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                const uint64_t *h_plane_off);
+int shafa_hipd_merge_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
+                                const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
+                                const uint64_t *h_out_off);
+
 /* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
  * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
  * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every

@@ -125,6 +125,8 @@ def lib():
     L.shafa_hipd_crc32_combine_dev.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), vp, vp, vp, vp]
     L.shafa_hipd_find_dev.argtypes = [vp, vp, C.c_int, u8p, u64p, u64p, vp, C.c_char_p, u64p, C.c_char_p, C.c_uint32, C.c_uint64,
                                       vp, vp, vp]
+    L.shafa_hipd_split_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
     L.shafa_hipd_read_spans_dev.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, u64p, u64p, u64p, u64p, vp, C.c_uint32, C.c_int, vp,
                                             C.c_int, C.POINTER(C.c_int), u64p, u64p, u64p, u64p, u64p, u8p, C.c_uint64]
@@ -184,7 +186,7 @@ def lib():
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
                  "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
                  "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev",
-                 "shafa_hipd_find_dev"):
+                 "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -288,6 +290,11 @@ def _p32(a):
 def _ptr(t):
     """a tensor's address, None for an empty one (a file of 0 bytes may have no storage)"""
     return t.data_ptr() if t.numel() else None
+
+
+def _addr(t):
+    """a device address: a tensor's, or an int as it is (None for 0)"""
+    return (t or None) if isinstance(t, int) else t.data_ptr()
 
 
 class Batch:
@@ -469,6 +476,25 @@ class Batch:
         _check(lib().shafa_hipd_find_dev(self.h, self._st(stream), len(io), d_in.data_ptr(), _p64(io), _p64(ic), d_in_n.data_ptr(),
                                          fl, _p64(po), pat, len(pat), int(max_hits), None if d_hits is None else d_hits.data_ptr(),
                                          d_count.data_ptr(), d_total.data_ptr()), "hipd_find_dev")
+
+    def split_planes_dev(self, stream, elem, d_in, in_off, cap, d_n, d_planes, plane_off):
+        """Block b's d_n[b] (int64, device; <= cap[b]) elements of `elem` = 1, 2, 4 or 8 bytes at d_in + in_off[b] (bytes, any
+        alignment, read in place) -> their byte planes: plane j (byte j of every element, plane 0 the least significant) is
+        d_n[b] bytes at d_planes + plane_off[b * elem + j].  d_planes and every plane offset are multiples of 16; nothing behind
+        a plane's d_n[b] bytes is written.  d_in and d_planes are tensors or device addresses (int: the base that offsets into
+        several tensors are measured from).  Enqueues only (include/shafa_hip.h: "Byte planes")."""
+        io, ic, po = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off)
+        _check(lib().shafa_hipd_split_planes_dev(self.h, self._st(stream), len(io), elem, _addr(d_in), _p64(io), _p64(ic),
+                                                 d_n.data_ptr(), _addr(d_planes), _p64(po)), "hipd_split_planes_dev")
+
+    def merge_planes_dev(self, stream, elem, d_planes, plane_off, cap, d_n, d_out, out_off):
+        """split_planes_dev's inverse: block b's planes (d_n[b] bytes each at d_planes + plane_off[b * elem + j], multiples of
+        16) -> its elem * d_n[b] bytes at d_out + out_off[b] (any alignment); no other byte of d_out is written, the up to 15
+        bytes on either side of an unaligned region included.  d_planes and d_out are tensors or device addresses (int).
+        Enqueues only (include/shafa_hip.h: "Byte planes")."""
+        po, ic, oo = _u64arr(plane_off), _u64arr(cap), _u64arr(out_off)
+        _check(lib().shafa_hipd_merge_planes_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po), _p64(ic),
+                                                 d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_dev")
 
     def seek_index_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, span, flags, ckpt_first, d_ckpt, d_status, d_out_n):
         """The checkpoints, every `span` symbols, of blocks of SF-decoded bytes: block b's d_in_n[b] (int64, device; <=
@@ -2735,3 +2761,297 @@ def encode_files(d_in, cod, stream=None):
         return out[:int(d_len.item())]
     finally:
         bt.close()
+
+
+# ------------------------------------------------------------------ typed tensors, one file set per byte plane
+PLANES_TILE = 8192              # SHAFA_PLANES_TILE: the elements of one tile of split_planes_dev / merge_planes_dev
+PLANES_ELEM = (1, 2, 4, 8)      # the element sizes they take
+
+
+class CompressedTensor:
+    """A tensor compressed by byte plane (compress_tensors), in memory: `dtype` and `shape` of the original, `planes` — one
+    entry per byte of the element, plane 0 the least significant: the dict compress_many returns for that plane's bytes, or the
+    plane itself (a uint8 CUDA tensor) where coding it would not shrink it — and `nbytes`, the sum of the file lengths and of
+    the raw planes' lengths."""
+    __slots__ = ("dtype", "shape", "planes", "nbytes")
+
+    def __init__(self, dtype, shape, planes, nbytes):
+        self.dtype, self.shape, self.planes, self.nbytes = dtype, tuple(shape), list(planes), int(nbytes)
+
+    def __repr__(self):
+        kinds = ["raw" if not isinstance(p, dict) else "+".join(sorted(p)) for p in self.planes]
+        return f"CompressedTensor({self.dtype}, {self.shape}, planes={kinds}, nbytes={self.nbytes})"
+
+
+def plane_files(entry):
+    """The file arguments of decompress_files / decompress_many for one compressed plane of a CompressedTensor (compress_many's
+    dict: with RLE the .rle.shaf decodes through both stages, without the .shaf is the plane)."""
+    if ".rle.shaf" in entry:
+        return dict(shaf=entry[".rle.shaf"], cod=entry[".rle.cod"])
+    return dict(shaf=entry[".shaf"], cod=entry[".cod"], decode_rle=False)
+
+
+def _plane_tensors(what, ts):
+    """the tensors byte planes are taken of, checked before any device work -> a list"""
+    import torch
+    if isinstance(ts, torch.Tensor):
+        ts = [ts]
+    if not isinstance(ts, (list, tuple)):
+        raise ValueError(f"{what}: a tensor or a list of tensors")
+    for t in ts:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{what}: contiguous CUDA tensors")
+        if t.element_size() not in PLANES_ELEM:
+            raise ValueError(f"{what}: {t.dtype} has elements of {t.element_size()} bytes, not 1, 2, 4 or 8")
+        if t.device != ts[0].device:
+            raise ValueError(f"{what}: the tensors are on one device")
+    return list(ts)
+
+
+def _plane_stream(dev, stream):
+    """the stream a driver works on, ordered behind the caller's current one (which produced the arguments)"""
+    import torch
+    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    st.wait_stream(torch.cuda.current_stream(dev))
+    return st
+
+
+def _by_elem(sizes):
+    """indices of the non-empty tensors, grouped by element size -> [(elem, [index, ...])]"""
+    return [(k, idx) for k in PLANES_ELEM for idx in [[i for i, (e, n) in enumerate(sizes) if e == k and n]] if idx]
+
+
+def _split_into(bt, st, dev, ts):
+    """one split_planes_dev per element size over ts (blocks addressed from the lowest tensor address: nothing is
+    concatenated) -> the planes buffer and each tensor's plane offsets in it, all multiples of 16"""
+    import torch
+    poff, pos = [], 0
+    for t in ts:
+        step = _al16(t.numel())
+        poff.append([pos + j * step for j in range(t.element_size())])
+        pos += t.element_size() * step
+    buf = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
+    groups = _by_elem([(t.element_size(), t.numel()) for t in ts])
+    if groups:
+        d_n = torch.tensor([ts[i].numel() for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+    at = 0
+    for k, idx in groups:
+        base = min(ts[i].data_ptr() for i in idx)
+        bt.split_planes_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx],
+                            d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+        at += len(idx)
+    return buf, poff
+
+
+def _merge_into(bt, st, dev, planes, outs):
+    """one merge_planes_dev per element size: planes[i] (the 1-D uint8 plane tensors of tensor i, each of outs[i].numel()
+    bytes) -> outs[i].  A plane that is not 16-aligned is copied first."""
+    import torch
+    groups = _by_elem([(o.element_size(), o.numel()) for o in outs])
+    if not groups:
+        return
+    planes = [[p if p.data_ptr() % 16 == 0 else p.clone() for p in ps] for ps in planes]
+    d_n = torch.tensor([outs[i].numel() for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+    at = 0
+    for k, idx in groups:
+        pbase = min(p.data_ptr() for i in idx for p in planes[i])
+        obase = min(outs[i].data_ptr() for i in idx)
+        bt.merge_planes_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]],
+                            [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
+                            [outs[i].data_ptr() - obase for i in idx])
+        at += len(idx)
+
+
+def split_planes(t, stream=None):
+    """The byte planes of a contiguous CUDA tensor with elements of k = 1, 2, 4 or 8 bytes: a uint8 tensor [k, numel], row j
+    byte j of every element (row 0 the least significant).  Rows start at multiples of 16 bytes: with a numel that is no
+    multiple of 16 the result is a view with padded rows.  One split_planes_dev launch, one synchronisation."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("split_planes: a contiguous CUDA tensor")
+    t = _plane_tensors("split_planes", t)[0]
+    dev, k, n = t.device, t.element_size(), t.numel()
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        bt = Batch(1, 1 << 20)
+        try:
+            buf, _ = _split_into(bt, st, dev, [t])
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return buf[:k * _al16(n)].view(k, _al16(n))[:, :n]
+
+
+def _numel(shape):
+    n = 1
+    for d in shape:
+        n *= int(d)
+    return n
+
+
+def _plane_dtype(what, dtype, shape):
+    """dtype and shape of a tensor to be put together from planes, checked -> (element size, shape, numel)"""
+    import torch
+    if not isinstance(dtype, torch.dtype):
+        raise ValueError(f"{what}: dtype is a torch.dtype")
+    k = torch.empty((), dtype=dtype).element_size()
+    if k not in PLANES_ELEM:
+        raise ValueError(f"{what}: {dtype} has elements of {k} bytes, not 1, 2, 4 or 8")
+    try:
+        shape = tuple(int(d) for d in shape)
+    except TypeError:
+        raise ValueError(f"{what}: shape is a sequence of ints") from None
+    if any(d < 0 for d in shape):
+        raise ValueError(f"{what}: negative dimension")
+    return k, shape, _numel(shape)
+
+
+def merge_planes(planes, dtype, shape, stream=None):
+    """split_planes' inverse for one tensor: `planes` is a uint8 CUDA tensor [k, numel] with unit stride along a row (rows may
+    be padded, as split_planes leaves them; rows that do not start at a multiple of 16 bytes are copied first) -> a tensor of
+    `dtype` (elements of k bytes) and `shape` (numel elements).  One merge_planes_dev launch, one synchronisation."""
+    import torch
+    k, shape, n = _plane_dtype("merge_planes", dtype, shape)
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
+            or (planes.shape[1] > 1 and planes.stride(1) != 1):
+        raise ValueError("merge_planes: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
+    if tuple(planes.shape) != (k, n):
+        raise ValueError(f"merge_planes: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
+    dev = planes.device
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        bt = Batch(1, 1 << 20)
+        try:
+            _merge_into(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out])
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return out
+
+
+def _back_to_back(buf, spans):
+    """compress_many's / compressed_sizes' first two arguments for the byte ranges `spans` = [(offset, length)] of buf: the
+    buffer and the lengths where the ranges follow each other without a gap, else a list of views (which those concatenate)"""
+    if all(spans[i][0] + spans[i][1] == spans[i + 1][0] for i in range(len(spans) - 1)):
+        return buf[spans[0][0]:spans[-1][0] + spans[-1][1]], [n for _, n in spans]
+    return [buf[o:o + n] for o, n in spans], None
+
+
+def compress_tensors(tensors, block_size=8 << 20, stream=None):
+    """Compress typed tensors by byte plane.  `tensors` is a tensor or a list of tensors: contiguous CUDA tensors on one
+    device, any mix of dtypes with elements of 1, 2, 4 or 8 bytes, any shape, empty ones included.  Returns one
+    CompressedTensor per tensor; decompress_tensors gives the tensors back bit for bit.
+
+    An order-0 coder sees every byte of an element through one histogram; taken apart, a float's sign and exponent byte codes
+    to a fraction of its size while its mantissa bytes do not shrink at all and are kept as they are.  Chain, its number of
+    launches independent of the number of tensors: one split_planes_dev per distinct element size over all tensors of that size
+    (blocks addressed from the lowest tensor address: nothing is concatenated) into one planes buffer at 16-aligned offsets ->
+    compressed_sizes over all planes of 1 KiB or more in one call -> compress_many over exactly the planes whose file set comes
+    out smaller than the plane.  Every other plane — one that does not shrink, one under 1 KiB (FILE_TOO_SMALL), an empty one —
+    stays raw, as a view of the planes buffer; no payload is ever written for it.  compressed_sizes and compress_many take
+    files back to back: they get the planes buffer itself where the planes they are to look at follow each other without a gap
+    (every numel a multiple of 16, none skipped), and otherwise a list of views, which they concatenate — one copy of those
+    planes.  `block_size` is theirs (the C host's split of a plane into blocks)."""
+    import torch
+    ts = _plane_tensors("compress_tensors", tensors)
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
+        raise ValueError("compress_tensors: block_size is a size in bytes (shafa_block_count's uint64_t)")
+    if not ts:
+        return []
+    dev = ts[0].device
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        bt = Batch(len(ts), 1 << 20)
+        try:
+            buf, poff = _split_into(bt, st, dev, ts)
+            bt.finish(st, len(ts))
+        finally:
+            bt.close()
+        entries = [[buf[o:o + t.numel()] for o in poff[i]] for i, t in enumerate(ts)]
+        cand = [(i, j) for i, t in enumerate(ts) if t.numel() >= 1024 for j in range(t.element_size())]
+        if cand:
+            spans = [(poff[i][j], ts[i].numel()) for i, j in cand]
+            d_in, sizes = _back_to_back(buf, spans)
+            sized = compressed_sizes(d_in, sizes, block_size=block_size, stream=st)
+            keep = [c for c, e in zip(cand, sized) if isinstance(e, dict) and sum(e.values()) < ts[c[0]].numel()]
+        else:
+            keep = []
+        if keep:
+            d_in, sizes = _back_to_back(buf, [(poff[i][j], ts[i].numel()) for i, j in keep])
+            for (i, j), e in zip(keep, compress_many(d_in, sizes, block_size=block_size, stream=st)):
+                if isinstance(e, ShafaError):
+                    raise e
+                entries[i][j] = e
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return [CompressedTensor(t.dtype, t.shape, ps, sum(sum(int(f.numel()) for f in p.values()) if isinstance(p, dict)
+                                                        else int(p.numel()) for p in ps))
+            for t, ps in zip(ts, entries)]
+
+
+def decompress_tensors(items, stream=None):
+    """compress_tensors' inverse: `items` is a CompressedTensor or a list of them (their planes on one device) -> the list of
+    tensors, each equal to the original bit for bit (NaN payloads, signed zeros, denormals: torch.equal on the bytes).
+
+    Chain: decompress_many over all compressed planes of all items in one call -> one merge_planes_dev per element size,
+    straight into the freshly allocated result tensors (a plane tensor that is not 16-aligned is copied first; fresh torch
+    allocations are aligned).  A plane entry that is a ShafaError instance, or whose file set fails to decode, raises that
+    ShafaError; a decoded or raw plane whose length is not the tensor's numel raises ShafaError(FILE_UNRECOGNIZABLE).  Malformed
+    items raise ValueError before any device work."""
+    import torch
+    if isinstance(items, CompressedTensor):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedTensor) for it in items):
+        raise ValueError("decompress_tensors: a CompressedTensor or a list of them")
+    metas, dev = [], None
+    for it in items:
+        k, shape, n = _plane_dtype("decompress_tensors", it.dtype, it.shape)
+        if not isinstance(it.planes, (list, tuple)) or len(it.planes) != k:
+            raise ValueError(f"decompress_tensors: {it.dtype} has {k} planes")
+        for p in it.planes:
+            if isinstance(p, ShafaError):
+                continue
+            if isinstance(p, dict):
+                fs = [f for f in p.values() if isinstance(f, torch.Tensor)]
+                if not ({".shaf", ".cod"} <= set(p) or {".rle.shaf", ".rle.cod"} <= set(p)) or len(fs) != len(p):
+                    raise ValueError("decompress_tensors: a compressed plane is compress_many's dict of files")
+            elif isinstance(p, torch.Tensor) and p.dtype == torch.uint8 and p.dim() == 1 and p.is_contiguous():
+                fs = [p]
+            else:
+                raise ValueError("decompress_tensors: a plane is a dict of files or a contiguous 1-D uint8 tensor")
+            for f in fs:
+                if not f.is_cuda:
+                    raise ValueError("decompress_tensors: planes are CUDA tensors")
+                if dev is not None and f.device != dev:
+                    raise ValueError("decompress_tensors: the planes are on one device")
+                dev = f.device
+        metas.append((shape, n))
+    for it in items:
+        for p in it.planes:
+            if isinstance(p, ShafaError):
+                raise p
+    if not items:
+        return []
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        coded = [(i, j) for i, it in enumerate(items) for j, p in enumerate(it.planes) if isinstance(p, dict)]
+        planes = [list(it.planes) for it in items]
+        if coded:
+            for (i, j), r in zip(coded, decompress_many([plane_files(items[i].planes[j]) for i, j in coded], stream=st)):
+                if isinstance(r, ShafaError):
+                    raise r
+                planes[i][j] = r
+        for (_, n), ps in zip(metas, planes):
+            if any(int(p.numel()) != n for p in ps):
+                raise ShafaError(FILE_UNRECOGNIZABLE, "decompress_tensors: a plane's length is not the tensor's numel")
+        outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _) in zip(items, metas)]
+        bt = Batch(len(items), 1 << 20)
+        try:
+            _merge_into(bt, st, dev, planes, outs)
+            bt.finish(st, len(items))
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return outs

@@ -1,0 +1,342 @@
+// planes.hip — arrays of E-byte elements <-> their E byte planes (shafa_hipd_split_planes_dev, shafa_hipd_merge_planes_dev).
+//
+// Block b is d_n[b] (<= cap[b]) elements of E = 1, 2, 4 or 8 bytes.  ELEMENT SIDE: its E d_n[b] bytes at d_el + off[b], at ANY
+// byte alignment, never copied: split reads the aligned 16-byte words around what a lane wants and shifts them into place
+// (shift_words, as find.hip and crc32.hip do); merge stores aligned 16-byte words that lie wholly inside the region and single
+// bytes at its two ends.  PLANE SIDE: plane j (byte j of every element, plane 0 the least significant) is d_n[b] bytes at
+// d_planes + poff[b E + j], every one a multiple of 16, so a lane's 16 bytes of a plane are one aligned word.
+//
+// The unit is 16 elements a lane: E words of the element side, v_perm_b32 in registers, one word of each plane — per plane a
+// wave's 64 words are 1 KiB contiguous.  A tile is tile_pass.hpp's 256 lanes x 32, here ELEMENTS: two units a lane, 4096
+// elements apart, so that both passes over a plane stay contiguous across the workgroup.  The tiles of all blocks are numbered
+// from the capacities on the host (TpWalk) and dealt to the workgroups in equal runs; an empty or short tile exits.  One
+// launch, no workgroup waits for another; the only atomic is the error word of a block with d_n[b] > cap[b], of which no byte
+// is read or written.
+//
+// What the measurements settled.  split's element-side loads: a lane's E words are 16 E bytes apart from its
+// neighbour's, so one load instruction touches every E-th word of the lines it reads; a whole pass of a 16-aligned region goes
+// through LDS instead (split_pass_lds: coalesced loads, 4.8 -> 5.4 TB/s at 2 bytes, 3.6 -> 5.1 TB/s at 4), every other unit —
+// an unaligned region, the pass a block ends in — loads directly.  Stores: the planes' are whole lines and streamed
+// (non-temporal: + 5 .. 8 %); merge's element-side stores are the strided ones, and non-temporal they leave L2 a word at a
+// time (1.3 TB/s at 4 bytes against 4.3 TB/s plain, where L2 puts the lines together): plain.
+//
+// merge: a lane's 16 E bytes start at byte 16 g E of the region (g the unit's number in the block), i.e. sh = (address of the
+// region) mod 16 bytes behind an aligned word.  The lane owns the E aligned words that START in its unit's span shifted down by
+// sh: their first sh bytes are the last bytes of unit g - 1 — the lane in front's, by four shuffles; a wave's first lane loads
+// and merges that unit's tail itself — and the unit's own last sh bytes are left to the lane behind, or, in the block's last
+// unit, stored as bytes.  A word that reaches in front of the region or past the unit's last element is stored as bytes too.
+// Algorithmic HBM bytes: every element read once and written once.
+#include "common.hpp"
+#include "internal.hpp"
+#include "tile_pass.hpp"
+
+namespace {
+
+constexpr int PL_UNIT = 16;                                     // elements a lane transposes at a time
+constexpr int PL_PASS = TP_THREADS * PL_UNIT;                   // elements the workgroup covers with one unit a lane
+constexpr int PL_UNITS = TP_TILE / PL_PASS;
+static_assert(TP_TILE == SHAFA_PLANES_TILE && PL_UNITS * PL_PASS == TP_TILE, "the tile the header names");
+
+// bytes s0 .. s3 (byte s & 3 of dword s >> 2) of w as one dword, low byte first.  The positions are constants once the
+// callers' loops are unrolled: one v_perm_b32 when two dwords hold the four bytes, else three.
+__device__ __forceinline__ u32 pick4(const u32 *w, int s0, int s1, int s2, int s3)
+{
+    const int d[4] = {s0 >> 2, s1 >> 2, s2 >> 2, s3 >> 2};
+    const u32 by[4] = {(u32)s0 & 3u, (u32)s1 & 3u, (u32)s2 & 3u, (u32)s3 & 3u};
+    int other = d[0];
+    for (int k = 1; k < 4; ++k)
+        if (d[k] != d[0]) other = d[k];
+    if ((d[1] == d[0] || d[1] == other) && (d[2] == d[0] || d[2] == other)) {
+        u32 sel = 0;
+        for (int k = 0; k < 4; ++k) sel |= (d[k] == d[0] ? by[k] : 4u + by[k]) << (8 * k);
+        return __builtin_amdgcn_perm(w[other], w[d[0]], sel);  // selector 0..3: the second operand's bytes, 4..7: the first's
+    }
+    const u32 lo = __builtin_amdgcn_perm(w[d[1]], w[d[0]], by[0] | (4u + by[1]) << 8);
+    const u32 hi = __builtin_amdgcn_perm(w[d[3]], w[d[2]], by[2] | (4u + by[3]) << 8);
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+}
+
+// dword q of plane j of the 16 elements in w
+template <int E>
+__device__ __forceinline__ u32 split_dword(const u32 (&w)[4 * E], int j, int q)
+{
+    return pick4(w, (4 * q) * E + j, (4 * q + 1) * E + j, (4 * q + 2) * E + j, (4 * q + 3) * E + j);
+}
+
+// dword d of the 16 elements whose plane j is p[4 j .. 4 j + 3]: byte s of the elements is byte s / E of plane s % E
+template <int E>
+__device__ __forceinline__ u32 merge_dword(const u32 (&p)[4 * E], int d)
+{
+    int s[4];
+    for (int k = 0; k < 4; ++k) s[k] = 16 * ((4 * d + k) % E) + (4 * d + k) / E;
+    return pick4(p, s[0], s[1], s[2], s[3]);
+}
+
+__device__ __forceinline__ u8 byte_of(const uint4 &v, int k)
+{
+    const u32 x[4] = {v.x, v.y, v.z, v.w};
+    return (u8)(x[k >> 2] >> (8 * (k & 3)));
+}
+
+// the 16 elements w from element e0 < n -> one word of each plane; single bytes where the block ends inside the unit
+template <int E>
+__device__ __forceinline__ void split_store(const u32 (&w)[4 * E], u64 n, u64 e0, u8 *d_planes, const u64 *poff)
+{
+    const u32 c = n - e0 >= PL_UNIT ? PL_UNIT : (u32)(n - e0);
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const uint4 o = make_uint4(split_dword<E>(w, j, 0), split_dword<E>(w, j, 1), split_dword<E>(w, j, 2), split_dword<E>(w, j, 3));
+        u8 *dst = d_planes + poff[j] + e0;
+        if (c == PL_UNIT) gstore_nt<uint4>(dst, o);           // 1 KiB a wave, whole lines: streamed
+        else {
+#pragma unroll
+            for (int k = 0; k < PL_UNIT; ++k)
+                if ((u32)k < c) gstore<u8>(dst + k, byte_of(o, k));
+        }
+    }
+}
+
+// The unit of 16 elements from element e0 < n of a region of n elements at src (src mod 16 = 4 Q + r) -> its E plane words.
+// An aligned word of the element side is read only where it holds a byte of the region; what such a word holds behind the
+// region ends up in plane bytes behind n, which are not stored.
+template <int E, int Q>
+__device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, u8 *d_planes, const u64 *poff)
+{
+    const u32 sh = 4u * Q + r;
+    const u64 nbytes = n * E, p = e0 * E;
+    const u8 *s16 = (const u8 *)(((u64)(uintptr_t)src + p) & ~(u64)15);
+    uint4 a[E + 1];
+#pragma unroll
+    for (int i = 0; i <= E; ++i) {
+        a[i] = make_uint4(0, 0, 0, 0);
+        if (i == 0 || (p + 16u * i - sh < nbytes && (i < E || sh != 0))) a[i] = gload_nt<uint4>(s16 + 16 * i);
+    }
+    u32 w[4 * E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        const uint4 v = shift_words<Q>(a[i], a[i + 1], r);
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    split_store<E>(w, n, e0, d_planes, poff);
+}
+
+// A whole pass (every lane a whole unit) of a 16-aligned region: the pass's 4096 E bytes are loaded as E coalesced words a
+// lane (a wave reads 1 KiB contiguous) and handed over through LDS, where lane l reads its own words l E .. l E + E - 1.  One
+// slot of padding every 16 keeps both sides free of bank conflicts: a 16-lane group of the strided reads covers 16 rows or all
+// 16 slots of E rows.
+constexpr int PL_LDS_SLOTS = TP_THREADS + TP_THREADS / 16;      // per byte of the element
+template <int E>
+__device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass, u8 *d_planes, const u64 *poff, uint4 *lds)
+{
+    const u32 tid = threadIdx.x;
+    const u8 *base = src + e0_pass * E;
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        const u32 wd = (u32)i * TP_THREADS + tid;
+        lds[wd + (wd >> 4)] = gload_nt<uint4>(base + 16ull * wd);
+    }
+    lds_barrier();
+    u32 w[4 * E];
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+        const u32 wd = tid * E + (u32)i;
+        const uint4 v = lds[wd + (wd >> 4)];
+        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    lds_barrier();
+    split_store<E>(w, n, e0_pass + (u64)tid * PL_UNIT, d_planes, poff);
+}
+
+template <int E, int Q>
+__device__ __forceinline__ void split_tile(const TpWalk &wk, u32 r, u8 *d_planes, const u64 *poff, uint4 *lds)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        if (Q == 0 && r == 0 && wk.pos0 + (u64)(u + 1) * PL_PASS <= wk.n) {          // (uniform) the barriers are inside
+            split_pass_lds<E>(wk.in, wk.n, wk.pos0 + (u64)u * PL_PASS, d_planes, poff, lds);
+            continue;
+        }
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 < wk.n) split_unit<E, Q>(wk.in, wk.n, e0, r, d_planes, poff);
+    }
+}
+
+// a block whose size is past its capacity: the walk has skipped its tiles (a capacity of 0 has none), this reports it
+__device__ __forceinline__ void planes_errors(const u64 *__restrict__ cap, const u64 *__restrict__ d_n, int nblk, int *__restrict__ err)
+{
+    for (u64 b = (u64)blockIdx.x * TP_THREADS + threadIdx.x; b < (u64)nblk; b += (u64)gridDim.x * TP_THREADS)
+        if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
+}
+
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                           const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                           const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                           const u64 *__restrict__ d_poff, int *__restrict__ err, u32 n_tiles,
+                                                           u32 per_wg)
+{
+    __shared__ uint4 lds[PL_LDS_SLOTS * E];
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile<E, 0>(wk, r, d_planes, poff, lds); break;
+        case 1: split_tile<E, 1>(wk, r, d_planes, poff, lds); break;
+        case 2: split_tile<E, 2>(wk, r, d_planes, poff, lds); break;
+        default: split_tile<E, 3>(wk, r, d_planes, poff, lds); break;
+        }
+    }
+    planes_errors(cap, d_n, nblk, err);
+}
+
+// bytes 4 Q + r .. + 15 of the dwords at x (Q = 4: r = 0, the word behind)
+template <int Q>
+__device__ __forceinline__ uint4 shift_at(const u32 *x, u32 r)
+{
+    return make_uint4(__builtin_amdgcn_alignbyte(x[Q + 1], x[Q], r), __builtin_amdgcn_alignbyte(x[Q + 2], x[Q + 1], r),
+                      __builtin_amdgcn_alignbyte(x[Q + 3], x[Q + 2], r), __builtin_amdgcn_alignbyte(x[Q + 4], x[Q + 3], r));
+}
+
+// The unit of 16 elements from element e0 of a region of n elements at dst (sh = dst mod 16, 16 - sh = 4 Q + r) <- its E plane
+// words.  Every lane of the wave calls (the shuffles); a lane with e0 >= n loads and stores nothing.
+template <int E, int Q>
+__device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r, const u8 *d_planes, const u64 *poff)
+{
+    const bool active = e0 < n;
+    // x: [the 16 bytes in front of the unit][the unit's 16 E bytes][zeros]
+    u32 x[4 * E + 12];
+    u32 p[4 * E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (active) v = gload_nt<uint4>(d_planes + poff[j] + e0);
+        p[4 * j] = v.x; p[4 * j + 1] = v.y; p[4 * j + 2] = v.z; p[4 * j + 3] = v.w;
+    }
+#pragma unroll
+    for (int d = 0; d < 4 * E; ++d) x[4 + d] = merge_dword<E>(p, d);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[4 * E + 4 + k] = 0;
+    if (sh != 0) {                                   // (uniform) the last bytes of the unit in front
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = (u32)__shfl_up((int)x[4 * E + k], 1, 64);
+        if (lane_id() == 0 && active && e0 != 0) {   // the lane in front is another wave's: that unit is whole
+            u32 pp[4 * E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const uint4 v = gload<uint4>(d_planes + poff[j] + e0 - PL_UNIT);
+                pp[4 * j] = v.x; pp[4 * j + 1] = v.y; pp[4 * j + 2] = v.z; pp[4 * j + 3] = v.w;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = merge_dword<E>(pp, 4 * E - 4 + k);
+        }
+    }
+    if (!active) return;
+    const int cb = (int)(n - e0 >= PL_UNIT ? PL_UNIT : (u32)(n - e0)) * E;      // the unit's bytes
+    const bool last = n - e0 <= PL_UNIT;                                       // no lane behind
+    const long long ub = (long long)(e0 * E);                                  // the unit's first byte in the region
+    // word i holds the region's bytes ub + lo .. + 15, lo = 16 i - sh; word E starts inside the unit only when sh != 0
+#pragma unroll
+    for (int i = 0; i <= E; ++i) {
+        if (i == E && !(last && sh != 0)) break;
+        const uint4 o = shift_at<Q>(x + 4 * i, r);
+        const int lo = 16 * i - (int)sh;
+        if (i < E && ub + lo >= 0 && lo + 16 <= cb) gstore<uint4>(dst + (ub + lo), o);     // plain: see the head of the file
+        else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (ub + lo + k >= 0 && lo + k < cb) gstore<u8>(dst + (ub + lo + k), byte_of(o, k));
+        }
+    }
+}
+
+template <int E, int Q>
+__device__ __forceinline__ void merge_tile(const TpWalk &wk, u32 sh, u32 r, const u8 *d_planes, const u64 *poff)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0w = wk.pos0 + (u64)u * PL_PASS + (u64)(threadIdx.x & ~63u) * PL_UNIT;
+        if (e0w >= wk.n) continue;                   // (wave uniform) no lane of the wave has an element
+        merge_unit<E, Q>((u8 *)wk.in, wk.n, e0w + (u64)lane_id() * PL_UNIT, sh, r, d_planes, poff);
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_merge(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                           const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                           const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
+                                                           const u64 *__restrict__ d_poff, int *__restrict__ err, u32 n_tiles,
+                                                           u32 per_wg)
+{
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), m = (16u - sh) & 15u, r = m & 3u;
+        switch (sh == 0 ? 4u : m >> 2) {             // uniform
+        case 0: merge_tile<E, 0>(wk, sh, r, d_planes, poff); break;
+        case 1: merge_tile<E, 1>(wk, sh, r, d_planes, poff); break;
+        case 2: merge_tile<E, 2>(wk, sh, r, d_planes, poff); break;
+        case 3: merge_tile<E, 3>(wk, sh, r, d_planes, poff); break;
+        default: merge_tile<E, 4>(wk, sh, r, d_planes, poff); break;
+        }
+    }
+    planes_errors(cap, d_n, nblk, err);
+}
+
+template <int E>
+void planes_launch(bool merge, u32 wgs, hipStream_t st, u8 *d_el, const u64 *off, const u64 *cap, const u32 *tbase, int nblk,
+                   const u64 *d_n, u8 *d_planes, const u64 *poff, int *err, u32 nt, u32 per_wg)
+{
+    if (merge)
+        hipLaunchKernelGGL(planes_merge<E>, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, off, cap, tbase, nblk, d_n,
+                           (const u8 *)d_planes, poff, err, nt, per_wg);
+    else
+        hipLaunchKernelGGL(planes_split<E>, dim3(wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, off, cap, tbase, nblk, d_n,
+                           d_planes, poff, err, nt, per_wg);
+}
+
+}  // namespace
+
+// workspace, all of it uploaded by the host: [offsets][capacities][plane offsets: elem a block][tbase, zero padded to 16].  The
+// caller has checked the arguments and that the tiles number fewer than 2^31.
+int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
+                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off)
+{
+    u64 ntiles = 0;
+    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_cap[b], TP_TILE);
+    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    const size_t nb = (size_t)nblocks;
+    const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_base = u_poff + nb * elem * 8;
+    const size_t up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
+    int rc = batch_reserve(bt, st, up_bytes);
+    if (rc) return rc;
+    u8 *ws = (u8 *)bt->d_ws;
+    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
+    if (!hs) return SHAFA_LACK_OF_MEMORY;
+    memcpy(hs + u_off, h_off, nb * 8);
+    memcpy(hs + u_cap, h_cap, nb * 8);
+    memcpy(hs + u_poff, h_plane_off, nb * elem * 8);
+    u32 *hb = (u32 *)(hs + u_base);
+    u32 base = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        hb[b] = base;
+        base += (u32)ceil_div_u64(h_cap[b], TP_TILE);
+    }
+    hb[nblocks] = base;
+    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
+    if ((rc = batch_upload(bt, st, ws, hs, up_bytes))) return rc;
+    const u64 *d_off = (const u64 *)(ws + u_off), *d_cap = (const u64 *)(ws + u_cap), *d_poff = (const u64 *)(ws + u_poff);
+    const u32 *d_base = (const u32 *)(ws + u_base);
+    // without a tile one workgroup still looks for blocks past a capacity of 0
+    const u32 nt = (u32)ntiles, per_wg = nt ? (nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1, wgs = nt ? (nt + per_wg - 1) / per_wg : 1;
+    switch (elem) {
+    case 1: planes_launch<1>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
+    case 2: planes_launch<2>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
+    case 4: planes_launch<4>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
+    default: planes_launch<8>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}

@@ -1,0 +1,114 @@
+"""The byte-plane transposes (split_planes_dev / merge_planes_dev; csrc/planes.hip) on a 1 GiB bf16 and a 1 GiB fp32 tensor,
+next to what a user has without them and next to a plain copy.  Standalone; one process on one MI355X; HIP events around one
+enqueue on a stream (no batch set-up, no synchronisation inside), the median of --reps calls after --warmup untimed ones.
+
+  python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover]
+
+Legs, per dtype; the rate is (bytes read + bytes written) / time = 2 x the tensor's bytes / time:
+  split_planes_dev   one block, the whole tensor
+  merge_planes_dev   its inverse
+  torch_split        x.view(torch.uint8).reshape(-1, k).t().contiguous()      (the generic strided copy)
+  torch_merge        planes.t().contiguous().view(dtype)                       (its inverse)
+  torch_copy         y.copy_(x): the same bytes moved and nothing else
+and once: `mover`, the one-shot copy figure of tools/ubench/mover (a fraction of 8 TB/s, as a child process after everything
+timed here) when its binary is present.  Every answer is checked against the torch expression before it is timed.  --lib
+measures another build of the library (an experiment's).  Prints one JSON document."""
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def timed(torch, st, fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    st.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(st)
+        fn()
+        b.record(st)
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
+def mover_one_shot():
+    exe = os.path.join(ROOT, "tools", "ubench", "mover")
+    if not os.path.exists(exe):
+        return None
+    r = subprocess.run([exe, "headline"], capture_output=True, text=True, timeout=120)
+    fr = [float(l.rsplit(":", 1)[1].strip(" )")) for l in r.stdout.splitlines() if "of 8 TB/s" in l]
+    return fr[0] if fr else None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--mib", type=int, default=1024)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--no-mover", action="store_true")
+    args = ap.parse_args()
+    import torch
+    torch.cuda.init()
+    import pkgload
+    pkg = pkgload.load()
+    if args.lib:
+        pkg.LIB_PATH = os.path.abspath(args.lib)
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.Stream(device=dev)
+    nbytes = args.mib << 20
+    res = {"bytes": nbytes, "reps": args.reps, "warmup": args.warmup, "lib": pkg.LIB_PATH, "legs": {}}
+    bt = pkg.Batch(1, 1 << 20)
+    with torch.cuda.stream(st):
+        for name, dtype in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
+            k = torch.empty((), dtype=dtype).element_size()
+            n = nbytes // k
+            x = torch.empty(n, dtype=torch.float32, device=dev).normal_(0, 0.02).to(dtype)
+            d_n = torch.tensor([n], dtype=torch.int64, device=dev)
+            planes = torch.empty(k * n, dtype=torch.uint8, device=dev)
+            back = torch.empty_like(x)
+            poff = [j * n for j in range(k)]
+            split = lambda: bt.split_planes_dev(st, k, x, [0], [n], d_n, planes, poff)
+            merge = lambda: bt.merge_planes_dev(st, k, planes, poff, [n], d_n, back, [0])
+            t_split = lambda: x.view(torch.uint8).reshape(-1, k).t().contiguous()
+            want = t_split()
+            t_merge = lambda: want.t().contiguous().view(-1).view(dtype)
+            other = torch.empty_like(x)
+            split()
+            merge()
+            bt.finish(st, 1)
+            if not torch.equal(planes.view(k, n), want) or not torch.equal(back.view(torch.uint8), x.view(torch.uint8)) \
+                    or not torch.equal(t_merge().view(torch.uint8), x.view(torch.uint8)):
+                sys.exit(f"{name}: the planes differ from the torch expression")
+            legs = {}
+            for leg, fn in (("split_planes_dev", split), ("merge_planes_dev", merge), ("torch_split", t_split),
+                            ("torch_merge", t_merge), ("torch_copy", lambda: other.copy_(x))):
+                ms = timed(torch, st, fn, args.reps, args.warmup)
+                med = statistics.median(ms)
+                legs[leg] = {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+                             "GB_s": round(2 * n * k / (med / 1e3) / 1e9, 1)}
+            bt.finish(st, 1)
+            res["legs"][name] = legs
+            del x, planes, back, want, other
+            torch.cuda.empty_cache()
+    bt.close()
+    res["done"] = all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
+                      for ours, theirs in (("split_planes_dev", "torch_split"), ("merge_planes_dev", "torch_merge")))
+    if not args.no_mover:
+        torch.cuda.synchronize()
+        fr = mover_one_shot()
+        if fr is not None:
+            res["mover"] = {"one_shot_frac_of_8TBs": fr, "GB_s": round(fr * 8000, 1)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
