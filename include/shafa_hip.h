@@ -470,6 +470,43 @@ int shafa_hipd_merge_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, 
                                 const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                 const uint64_t *h_out_off);
 
+/* ---- Byte planes of deltas: the same transposes with every element XORed with the element of a base ------------------------
+ * A checkpoint follows a checkpoint and a fine-tune its base model: against such a base most elements are bit-identical and
+ * the others share their high bytes, so the planes of (element XOR base element) are long runs of zero — what RLE and the
+ * Shannon-Fano coder behind it shrink most.  The XOR is done inside the transposes, which touch every element once anyway: no
+ * temporary, 3 bytes of traffic per tensor byte in either direction.
+ * shafa_hipd_split_planes_xor_dev: plane j of block b = byte j of (element XOR base element).
+ * shafa_hipd_merge_planes_xor_dev: its inverse, element = (the element put together from the planes) XOR base element.
+ * Everything said above of the plain entries holds: the blocks, the element side, the plane side, the capacities, what is
+ * written (exactly what the plain entries write), the per-block code, one launch in which no workgroup waits for another.
+ *   base side      block b's base is elem * d_n[b] bytes at d_base + h_base_off[b]; the offsets are 64-bit and need NO
+ *                  alignment, and a base's alignment is independent of its element side's.  h_base_off[b] ==
+ *                  SHAFA_PLANES_NO_BASE: the block has none; its result is the plain entry's byte for byte and no byte is
+ *                  read through d_base for it, so one launch takes new tensors and changed ones together.
+ * What is read.  The base side is read the way split reads its element side: aligned 16-byte words that each hold at least
+ * one byte of the region, shifted into place; bytes outside the region never influence a result.  Every base element is read
+ * once (merge into an unaligned region reads 16 base bytes a wave twice, as it does 16 bytes of each plane).  A pass of split
+ * in which both the element side and the base are 16-aligned takes its coalesced path, as in the plain entry.
+ * No overlap.  The base regions must not overlap what the call writes: the planes for split, the output regions for merge.
+ * Into an unaligned output a lane stores the word that holds the tail of its neighbour's unit, which the neighbour may not
+ * have read from the base yet: merging in place (d_out the base) is NOT supported.
+ * Per-block codes through shafa_hipd_finish:
+ *   d_n[b] > h_cap[b]                      SHAFA_OUTSIDE_MODULE; no byte of the block, its base included, is read or written.
+ * The device workspace is (28 + 8 elem) bytes per block plus 20: the plain entries' and 8 bytes per block for the base
+ * offsets.  Enqueues only, as the plain entries.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), in the plain entries' order:
+ * NULL b (first), d_in / d_out, d_planes, d_n or d_base, an elem other than 1, 2, 4, 8: SHAFA_OUTSIDE_MODULE; then
+ * nblocks <= 0: success; nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY; NULL h_cap: SHAFA_OUTSIDE_MODULE; the
+ * capacities' bounds: SHAFA_LACK_OF_MEMORY; NULL h_in_off / h_out_off, h_plane_off or h_base_off, a d_planes or a plane
+ * offset that is no multiple of 16: SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_PLANES_NO_BASE UINT64_MAX /* h_base_off[b]: block b has no base */
+int shafa_hipd_split_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
+                                    const uint64_t *h_in_off, const uint8_t *d_base, const uint64_t *h_base_off,
+                                    const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes, const uint64_t *h_plane_off);
+int shafa_hipd_merge_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
+                                    const uint64_t *h_plane_off, const uint8_t *d_base, const uint64_t *h_base_off,
+                                    const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
+
 /* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
  * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
  * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every

@@ -127,6 +127,8 @@ def lib():
                                       vp, vp, vp]
     L.shafa_hipd_split_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
     L.shafa_hipd_read_spans_dev.argtypes = [vp, vp, C.c_int, u8p, C.c_uint64, u64p, u64p, u64p, u64p, vp, C.c_uint32, C.c_int, vp,
                                             C.c_int, C.POINTER(C.c_int), u64p, u64p, u64p, u64p, u64p, u8p, C.c_uint64]
@@ -186,7 +188,8 @@ def lib():
                  "shafa_hipd_rle_decoded_size_dev", "shafa_hipd_rle_encoded_size_dev", "shafa_hipd_rle_encoded_hist_dev",
                  "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
                  "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev",
-                 "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev"):
+                 "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev",
+                 "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -495,6 +498,30 @@ class Batch:
         po, ic, oo = _u64arr(plane_off), _u64arr(cap), _u64arr(out_off)
         _check(lib().shafa_hipd_merge_planes_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po), _p64(ic),
                                                  d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_dev")
+
+    def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
+        """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
+        at any alignment of its own, read in place and once; base_off[b] == PLANES_NO_BASE: the block has none and comes out as
+        split_planes_dev's, nothing is read through d_base for it.  The bases must not overlap the planes.  d_base is a tensor
+        or a device address (int).  Enqueues only (include/shafa_hip.h: "Byte planes of deltas")."""
+        io, bo, ic, po = _u64arr(in_off), _u64arr(base_off), _u64arr(cap), _u64arr(plane_off)
+        if len(bo) != len(io):
+            raise ValueError("split_planes_xor_dev: one base offset per block")
+        _check(lib().shafa_hipd_split_planes_xor_dev(self.h, self._st(stream), len(io), elem, _addr(d_in), _p64(io), _addr(d_base),
+                                                     _p64(bo), _p64(ic), d_n.data_ptr(), _addr(d_planes), _p64(po)),
+               "hipd_split_planes_xor_dev")
+
+    def merge_planes_xor_dev(self, stream, elem, d_planes, plane_off, d_base, base_off, cap, d_n, d_out, out_off):
+        """split_planes_xor_dev's inverse: (the elements put together from block b's planes) XOR its base at d_base +
+        base_off[b] (any alignment; PLANES_NO_BASE: none, merge_planes_dev's result) -> d_out + out_off[b]; no other byte of
+        d_out is written.  The bases must not overlap the output regions: merging in place is not supported.  Enqueues only
+        (include/shafa_hip.h: "Byte planes of deltas")."""
+        po, bo, ic, oo = _u64arr(plane_off), _u64arr(base_off), _u64arr(cap), _u64arr(out_off)
+        if len(bo) != len(oo):
+            raise ValueError("merge_planes_xor_dev: one base offset per block")
+        _check(lib().shafa_hipd_merge_planes_xor_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po),
+                                                     _addr(d_base), _p64(bo), _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)),
+               "hipd_merge_planes_xor_dev")
 
     def seek_index_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, span, flags, ckpt_first, d_ckpt, d_status, d_out_n):
         """The checkpoints, every `span` symbols, of blocks of SF-decoded bytes: block b's d_in_n[b] (int64, device; <=
@@ -2766,6 +2793,7 @@ def encode_files(d_in, cod, stream=None):
 # ------------------------------------------------------------------ typed tensors, one file set per byte plane
 PLANES_TILE = 8192              # SHAFA_PLANES_TILE: the elements of one tile of split_planes_dev / merge_planes_dev
 PLANES_ELEM = (1, 2, 4, 8)      # the element sizes they take
+PLANES_NO_BASE = (1 << 64) - 1  # SHAFA_PLANES_NO_BASE: the base offset of a block without a base (the _xor_dev entries)
 
 
 class CompressedTensor:
@@ -2781,6 +2809,21 @@ class CompressedTensor:
     def __repr__(self):
         kinds = ["raw" if not isinstance(p, dict) else "+".join(sorted(p)) for p in self.planes]
         return f"CompressedTensor({self.dtype}, {self.shape}, planes={kinds}, nbytes={self.nbytes})"
+
+
+class CompressedDelta(CompressedTensor):
+    """A tensor compressed by byte plane as its XOR with a base tensor (compress_deltas): CompressedTensor's fields, the
+    planes being those of (element XOR base element), and `base_crc`, the zlib CRC-32 of the base's bytes, or None where the
+    base was not digested.  Only decompress_deltas, given that base again, gives the tensor back."""
+    __slots__ = ("base_crc",)
+
+    def __init__(self, dtype, shape, planes, nbytes, base_crc=None):
+        CompressedTensor.__init__(self, dtype, shape, planes, nbytes)
+        self.base_crc = None if base_crc is None else int(base_crc) & 0xFFFFFFFF
+
+    def __repr__(self):
+        crc = "None" if self.base_crc is None else f"{self.base_crc:#010x}"
+        return "CompressedDelta" + CompressedTensor.__repr__(self)[len("CompressedTensor"):-1] + f", base_crc={crc})"
 
 
 def plane_files(entry):
@@ -2821,9 +2864,20 @@ def _by_elem(sizes):
     return [(k, idx) for k in PLANES_ELEM for idx in [[i for i, (e, n) in enumerate(sizes) if e == k and n]] if idx]
 
 
-def _split_into(bt, st, dev, ts):
+def _base_side(bases, idx):
+    """the base arguments of a split_planes_xor_dev / merge_planes_xor_dev launch over the tensors idx: the lowest base address
+    and each block's offset from it (PLANES_NO_BASE where bases[i] is None); None where no tensor of idx has a base"""
+    have = [bases[i].data_ptr() for i in idx if bases[i] is not None] if bases is not None else []
+    if not have:
+        return None
+    return min(have), [PLANES_NO_BASE if bases[i] is None else bases[i].data_ptr() - min(have) for i in idx]
+
+
+def _split_into(bt, st, dev, ts, bases=None):
     """one split_planes_dev per element size over ts (blocks addressed from the lowest tensor address: nothing is
-    concatenated) -> the planes buffer and each tensor's plane offsets in it, all multiples of 16"""
+    concatenated) -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  With `bases` (one entry per
+    tensor: None or a tensor of the same dtype and numel) a size with a base among its tensors takes one split_planes_xor_dev
+    instead, the bases addressed from the lowest base address."""
     import torch
     poff, pos = [], 0
     for t in ts:
@@ -2837,15 +2891,21 @@ def _split_into(bt, st, dev, ts):
     at = 0
     for k, idx in groups:
         base = min(ts[i].data_ptr() for i in idx)
-        bt.split_planes_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx],
-                            d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+        side = _base_side(bases, idx)
+        if side is None:
+            bt.split_planes_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx],
+                                d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+        else:
+            bt.split_planes_xor_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], side[0], side[1],
+                                    [ts[i].numel() for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
         at += len(idx)
     return buf, poff
 
 
-def _merge_into(bt, st, dev, planes, outs):
+def _merge_into(bt, st, dev, planes, outs, bases=None):
     """one merge_planes_dev per element size: planes[i] (the 1-D uint8 plane tensors of tensor i, each of outs[i].numel()
-    bytes) -> outs[i].  A plane that is not 16-aligned is copied first."""
+    bytes) -> outs[i].  A plane that is not 16-aligned is copied first.  With `bases` (as _split_into's) a size with a base
+    among its tensors takes one merge_planes_xor_dev instead."""
     import torch
     groups = _by_elem([(o.element_size(), o.numel()) for o in outs])
     if not groups:
@@ -2856,9 +2916,15 @@ def _merge_into(bt, st, dev, planes, outs):
     for k, idx in groups:
         pbase = min(p.data_ptr() for i in idx for p in planes[i])
         obase = min(outs[i].data_ptr() for i in idx)
-        bt.merge_planes_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]],
-                            [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
-                            [outs[i].data_ptr() - obase for i in idx])
+        side = _base_side(bases, idx)
+        if side is None:
+            bt.merge_planes_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]],
+                                [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
+                                [outs[i].data_ptr() - obase for i in idx])
+        else:
+            bt.merge_planes_xor_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], side[0], side[1],
+                                    [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
+                                    [outs[i].data_ptr() - obase for i in idx])
         at += len(idx)
 
 
@@ -2940,33 +3006,20 @@ def _back_to_back(buf, spans):
     return [buf[o:o + n] for o, n in spans], None
 
 
-def compress_tensors(tensors, block_size=8 << 20, stream=None):
-    """Compress typed tensors by byte plane.  `tensors` is a tensor or a list of tensors: contiguous CUDA tensors on one
-    device, any mix of dtypes with elements of 1, 2, 4 or 8 bytes, any shape, empty ones included.  Returns one
-    CompressedTensor per tensor; decompress_tensors gives the tensors back bit for bit.
-
-    An order-0 coder sees every byte of an element through one histogram; taken apart, a float's sign and exponent byte codes
-    to a fraction of its size while its mantissa bytes do not shrink at all and are kept as they are.  Chain, its number of
-    launches independent of the number of tensors: one split_planes_dev per distinct element size over all tensors of that size
-    (blocks addressed from the lowest tensor address: nothing is concatenated) into one planes buffer at 16-aligned offsets ->
-    compressed_sizes over all planes of 1 KiB or more in one call -> compress_many over exactly the planes whose file set comes
-    out smaller than the plane.  Every other plane — one that does not shrink, one under 1 KiB (FILE_TOO_SMALL), an empty one —
-    stays raw, as a view of the planes buffer; no payload is ever written for it.  compressed_sizes and compress_many take
-    files back to back: they get the planes buffer itself where the planes they are to look at follow each other without a gap
-    (every numel a multiple of 16, none skipped), and otherwise a list of views, which they concatenate — one copy of those
-    planes.  `block_size` is theirs (the C host's split of a plane into blocks)."""
+def _plane_entries(what, ts, bases, block_size, stream):
+    """compress_tensors' chain over the checked tensors ts, or with `bases` (_split_into's) compress_deltas': the split, the
+    sizes, the file sets of the planes that shrink -> per tensor its plane entries, and their bytes"""
     import torch
-    ts = _plane_tensors("compress_tensors", tensors)
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
-        raise ValueError("compress_tensors: block_size is a size in bytes (shafa_block_count's uint64_t)")
+        raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
     if not ts:
-        return []
+        return [], []
     dev = ts[0].device
     st = _plane_stream(dev, stream)
     with torch.cuda.stream(st):
         bt = Batch(len(ts), 1 << 20)
         try:
-            buf, poff = _split_into(bt, st, dev, ts)
+            buf, poff = _split_into(bt, st, dev, ts, bases)
             bt.finish(st, len(ts))
         finally:
             bt.close()
@@ -2986,46 +3039,134 @@ def compress_tensors(tensors, block_size=8 << 20, stream=None):
                     raise e
                 entries[i][j] = e
     torch.cuda.current_stream(dev).wait_stream(st)
-    return [CompressedTensor(t.dtype, t.shape, ps, sum(sum(int(f.numel()) for f in p.values()) if isinstance(p, dict)
-                                                        else int(p.numel()) for p in ps))
-            for t, ps in zip(ts, entries)]
+    return entries, [sum(sum(int(f.numel()) for f in p.values()) if isinstance(p, dict) else int(p.numel()) for p in ps)
+                     for ps in entries]
 
 
-def decompress_tensors(items, stream=None):
-    """compress_tensors' inverse: `items` is a CompressedTensor or a list of them (their planes on one device) -> the list of
-    tensors, each equal to the original bit for bit (NaN payloads, signed zeros, denormals: torch.equal on the bytes).
+def compress_tensors(tensors, block_size=8 << 20, stream=None):
+    """Compress typed tensors by byte plane.  `tensors` is a tensor or a list of tensors: contiguous CUDA tensors on one
+    device, any mix of dtypes with elements of 1, 2, 4 or 8 bytes, any shape, empty ones included.  Returns one
+    CompressedTensor per tensor; decompress_tensors gives the tensors back bit for bit.
 
-    Chain: decompress_many over all compressed planes of all items in one call -> one merge_planes_dev per element size,
-    straight into the freshly allocated result tensors (a plane tensor that is not 16-aligned is copied first; fresh torch
-    allocations are aligned).  A plane entry that is a ShafaError instance, or whose file set fails to decode, raises that
-    ShafaError; a decoded or raw plane whose length is not the tensor's numel raises ShafaError(FILE_UNRECOGNIZABLE).  Malformed
-    items raise ValueError before any device work."""
+    An order-0 coder sees every byte of an element through one histogram; taken apart, a float's sign and exponent byte codes
+    to a fraction of its size while its mantissa bytes do not shrink at all and are kept as they are.  Chain, its number of
+    launches independent of the number of tensors: one split_planes_dev per distinct element size over all tensors of that size
+    (blocks addressed from the lowest tensor address: nothing is concatenated) into one planes buffer at 16-aligned offsets ->
+    compressed_sizes over all planes of 1 KiB or more in one call -> compress_many over exactly the planes whose file set comes
+    out smaller than the plane.  Every other plane — one that does not shrink, one under 1 KiB (FILE_TOO_SMALL), an empty one —
+    stays raw, as a view of the planes buffer; no payload is ever written for it.  compressed_sizes and compress_many take
+    files back to back: they get the planes buffer itself where the planes they are to look at follow each other without a gap
+    (every numel a multiple of 16, none skipped), and otherwise a list of views, which they concatenate — one copy of those
+    planes.  `block_size` is theirs (the C host's split of a plane into blocks)."""
+    ts = _plane_tensors("compress_tensors", tensors)
+    entries, nbytes = _plane_entries("compress_tensors", ts, None, block_size, stream)
+    return [CompressedTensor(t.dtype, t.shape, ps, nb) for t, ps, nb in zip(ts, entries, nbytes)]
+
+
+def _base_tensors(what, bases, metas):
+    """the bases of a delta call, checked before any device work: a list as long as metas = [(dtype, numel, device)], each
+    entry None or a contiguous CUDA tensor of that dtype and numel on that device (a device of None: any one device)"""
     import torch
-    if isinstance(items, CompressedTensor):
-        items = [items]
-    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedTensor) for it in items):
-        raise ValueError("decompress_tensors: a CompressedTensor or a list of them")
+    if isinstance(bases, torch.Tensor):
+        bases = [bases]
+    if not isinstance(bases, (list, tuple)) or len(bases) != len(metas):
+        raise ValueError(f"{what}: bases is a list with one entry (a tensor or None) per tensor")
+    dev = None
+    for i, (b, (dtype, n, d)) in enumerate(zip(bases, metas)):
+        if b is None:
+            continue
+        if not isinstance(b, torch.Tensor):
+            raise ValueError(f"{what}: base {i} is None or a contiguous CUDA tensor")
+        if b.dtype != dtype or b.numel() != n:
+            raise ValueError(f"{what}: base {i} is {b.dtype} x {b.numel()}, its tensor {dtype} x {n}")
+        if not b.is_cuda or not b.is_contiguous():
+            raise ValueError(f"{what}: base {i} is None or a contiguous CUDA tensor")
+        if b.device != (d if d is not None else dev if dev is not None else b.device):
+            raise ValueError(f"{what}: the tensors and their bases are on one device")
+        dev = b.device
+    return list(bases)
+
+
+def _base_crcs(bases, stream):
+    """zlib.crc32 of each base's bytes (None for None), digested where they lie: one crc32 call with `sizes` where the bases
+    lie back to back in one storage, else one call per base"""
+    import torch
+    views = [(i, b.reshape(-1).view(torch.uint8)) for i, b in enumerate(bases) if b is not None]
+    out = [None] * len(bases)
+    if not views:
+        return out
+    vs = [v for _, v in views]
+    joined = all(a.untyped_storage().data_ptr() == vs[0].untyped_storage().data_ptr() and
+                 a.data_ptr() + a.numel() == b.data_ptr() for a, b in zip(vs, vs[1:]))
+    if joined:
+        total = sum(int(v.numel()) for v in vs)
+        whole = torch.empty(0, dtype=torch.uint8, device=vs[0].device).set_(vs[0].untyped_storage(), vs[0].storage_offset(),
+                                                                            (total,))
+        crcs = crc32(whole, [int(v.numel()) for v in vs], stream=stream)
+    else:
+        crcs = [crc32(v, stream=stream) for v in vs]
+    for (i, _), c in zip(views, crcs):
+        out[i] = c
+    return out
+
+
+def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=None):
+    """compress_tensors of every tensor's XOR with a base — the checkpoint before it, the model it was tuned from — without
+    the XOR ever being stored.  `tensors` as compress_tensors takes them; `bases` is a list as long, each entry None or a
+    contiguous CUDA tensor on the same device with its tensor's dtype and numel, at any address (a slice at an odd storage
+    offset too).  Returns a CompressedTensor where the base is None — exactly compress_tensors' — and a CompressedDelta
+    elsewhere; decompress_deltas with the same bases gives the tensors back bit for bit.  A mismatch raises ValueError before
+    any device work.
+
+    Against such a base most elements are bit-identical and the others keep their sign and exponent byte, so the planes of
+    the XOR are long runs of zero, which RLE and the Shannon-Fano coder behind it shrink most.  Chain: compress_tensors', with
+    one split_planes_xor_dev per element size in place of the plain split (tensors addressed from the lowest tensor address,
+    bases from the lowest base address: nothing is concatenated, no temporary of the XOR exists) -> compressed_sizes ->
+    compress_many, as there.  With `check_base` the bases are digested first (crc32, where they lie) and every
+    CompressedDelta carries its base's zlib CRC-32 as `base_crc`, which decompress_deltas checks: this adds ONE
+    synchronisation where the bases lie back to back in one storage (one crc32 call with `sizes`) and one per base otherwise.
+    Without it `base_crc` is None and nothing is added."""
+    ts = _plane_tensors("compress_deltas", tensors)
+    bs = _base_tensors("compress_deltas", bases, [(t.dtype, t.numel(), t.device) for t in ts])
+    if not isinstance(check_base, bool):
+        raise ValueError("compress_deltas: check_base is a bool")
+    crcs = _base_crcs(bs, stream) if check_base and ts else [None] * len(ts)
+    entries, nbytes = _plane_entries("compress_deltas", ts, bs, block_size, stream)
+    return [CompressedTensor(t.dtype, t.shape, ps, nb) if b is None else CompressedDelta(t.dtype, t.shape, ps, nb, c)
+            for t, b, ps, nb, c in zip(ts, bs, entries, nbytes, crcs)]
+
+
+def _merge_items(what, items, bases, check_base, stream):
+    """decompress_tensors' checks and chain over the list `items`, or with `bases` (one entry per item) decompress_deltas'"""
+    import torch
+    if bases is not None:
+        for i, (it, b) in enumerate(zip(items, bases)):
+            if isinstance(it, CompressedDelta) and b is None:
+                raise ValueError(f"{what}: item {i} is a CompressedDelta and needs its base")
+            if not isinstance(it, CompressedDelta) and b is not None:
+                raise ValueError(f"{what}: item {i} is a plain CompressedTensor and takes no base")
+        bases = _base_tensors(what, bases, [(it.dtype, _plane_dtype(what, it.dtype, it.shape)[2], None) for it in items])
     metas, dev = [], None
     for it in items:
-        k, shape, n = _plane_dtype("decompress_tensors", it.dtype, it.shape)
+        k, shape, n = _plane_dtype(what, it.dtype, it.shape)
         if not isinstance(it.planes, (list, tuple)) or len(it.planes) != k:
-            raise ValueError(f"decompress_tensors: {it.dtype} has {k} planes")
+            raise ValueError(f"{what}: {it.dtype} has {k} planes")
         for p in it.planes:
             if isinstance(p, ShafaError):
                 continue
             if isinstance(p, dict):
                 fs = [f for f in p.values() if isinstance(f, torch.Tensor)]
                 if not ({".shaf", ".cod"} <= set(p) or {".rle.shaf", ".rle.cod"} <= set(p)) or len(fs) != len(p):
-                    raise ValueError("decompress_tensors: a compressed plane is compress_many's dict of files")
+                    raise ValueError(f"{what}: a compressed plane is compress_many's dict of files")
             elif isinstance(p, torch.Tensor) and p.dtype == torch.uint8 and p.dim() == 1 and p.is_contiguous():
                 fs = [p]
             else:
-                raise ValueError("decompress_tensors: a plane is a dict of files or a contiguous 1-D uint8 tensor")
+                raise ValueError(f"{what}: a plane is a dict of files or a contiguous 1-D uint8 tensor")
             for f in fs:
                 if not f.is_cuda:
-                    raise ValueError("decompress_tensors: planes are CUDA tensors")
+                    raise ValueError(f"{what}: planes are CUDA tensors")
                 if dev is not None and f.device != dev:
-                    raise ValueError("decompress_tensors: the planes are on one device")
+                    raise ValueError(f"{what}: the planes are on one device")
                 dev = f.device
         metas.append((shape, n))
     for it in items:
@@ -3034,6 +3175,16 @@ def decompress_tensors(items, stream=None):
                 raise p
     if not items:
         return []
+    if bases is not None:
+        if any(b is not None and b.device != dev for b in bases):
+            raise ValueError(f"{what}: the planes and the bases are on one device")
+        if check_base:
+            want = [it.base_crc if isinstance(it, CompressedDelta) else None for it in items]
+            have = _base_crcs([b if w is not None else None for b, w in zip(bases, want)], stream)
+            for i, (w, h) in enumerate(zip(want, have)):
+                if w != h:
+                    raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: item {i}: the base's CRC-32 is {h:#010x}, the item was "
+                                                          f"made against one of {w:#010x}")
     st = _plane_stream(dev, stream)
     with torch.cuda.stream(st):
         coded = [(i, j) for i, it in enumerate(items) for j, p in enumerate(it.planes) if isinstance(p, dict)]
@@ -3045,13 +3196,58 @@ def decompress_tensors(items, stream=None):
                 planes[i][j] = r
         for (_, n), ps in zip(metas, planes):
             if any(int(p.numel()) != n for p in ps):
-                raise ShafaError(FILE_UNRECOGNIZABLE, "decompress_tensors: a plane's length is not the tensor's numel")
+                raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: a plane's length is not the tensor's numel")
         outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs)
+            _merge_into(bt, st, dev, planes, outs, bases)
             bt.finish(st, len(items))
         finally:
             bt.close()
     torch.cuda.current_stream(dev).wait_stream(st)
     return outs
+
+
+def decompress_tensors(items, stream=None):
+    """compress_tensors' inverse: `items` is a CompressedTensor or a list of them (their planes on one device) -> the list of
+    tensors, each equal to the original bit for bit (NaN payloads, signed zeros, denormals: torch.equal on the bytes).
+
+    Chain: decompress_many over all compressed planes of all items in one call -> one merge_planes_dev per element size,
+    straight into the freshly allocated result tensors (a plane tensor that is not 16-aligned is copied first; fresh torch
+    allocations are aligned).  A plane entry that is a ShafaError instance, or whose file set fails to decode, raises that
+    ShafaError; a decoded or raw plane whose length is not the tensor's numel raises ShafaError(FILE_UNRECOGNIZABLE).  Malformed
+    items raise ValueError before any device work."""
+    if isinstance(items, CompressedTensor):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedTensor) for it in items):
+        raise ValueError("decompress_tensors: a CompressedTensor or a list of them")
+    if any(isinstance(it, CompressedDelta) for it in items):
+        raise ValueError("decompress_tensors: a CompressedDelta needs its base: decompress_deltas")
+    return _merge_items("decompress_tensors", items, None, False, stream)
+
+
+def decompress_deltas(items, bases, check_base=True, stream=None):
+    """compress_deltas' inverse: `items` is its result (CompressedDelta and CompressedTensor items in any mix, or a single
+    one), `bases` the list of their bases — the tensor the item was made against for a CompressedDelta, None for a plain
+    CompressedTensor -> the list of tensors, each equal to the original bit for bit.
+
+    Chain: decompress_tensors', with one merge_planes_xor_dev per element size in place of the plain merge: decompress_many
+    over all coded planes -> the merge straight into fresh tensors, the bases read where they lie (any alignment; they never
+    overlap the fresh results).  Before any device work, each a ValueError: a CompressedDelta whose base is None, a base of
+    another dtype or numel, a plain CompressedTensor with a base.  With `check_base` the base of every CompressedDelta that
+    carries a `base_crc` is digested first (compress_deltas' rule: one synchronisation more where the bases lie back to back,
+    else one per base), and one that digests to another value raises ShafaError(FILE_UNRECOGNIZABLE) naming the item's index,
+    before anything is decoded or merged: the XOR with a wrong base is a wrong tensor, not an error any later stage could
+    see.  decompress_tensors' errors otherwise."""
+    if isinstance(items, CompressedTensor):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedTensor) for it in items):
+        raise ValueError("decompress_deltas: a CompressedDelta / CompressedTensor or a list of them")
+    if not isinstance(check_base, bool):
+        raise ValueError("decompress_deltas: check_base is a bool")
+    import torch
+    if bases is None or isinstance(bases, torch.Tensor):
+        bases = [bases]
+    if not isinstance(bases, (list, tuple)) or len(bases) != len(items):
+        raise ValueError("decompress_deltas: bases is a list with one entry (a tensor or None) per item")
+    return _merge_items("decompress_deltas", items, list(bases), check_base, stream)

@@ -229,9 +229,10 @@ int find_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, cons
                     u64 *d_count, u64 *d_total);
 // block b's d_n[b] <= h_cap[b] elements of `elem` bytes at d_el + h_off[b] (any alignment) <-> their byte planes, plane j at
 // d_planes + h_plane_off[b * elem + j] (multiples of 16): split reads d_el, merge writes it (planes.hip); the arguments have been
-// checked and the capacities' tiles of SHAFA_PLANES_TILE elements number fewer than 2^31
+// checked and the capacities' tiles of SHAFA_PLANES_TILE elements number fewer than 2^31.  h_base_off non-NULL: every element is
+// XORed with the element of the block's base region at d_base + h_base_off[b] (any alignment; SHAFA_PLANES_NO_BASE: none)
 int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
-                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off);
+                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off);
 // the checkpoints of blocks of SF-decoded bytes, every `span` symbols (seek.hip); the capacities' spans number fewer than 2^31
 int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                           const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,

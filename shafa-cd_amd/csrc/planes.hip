@@ -1,4 +1,5 @@
-// planes.hip — arrays of E-byte elements <-> their E byte planes (shafa_hipd_split_planes_dev, shafa_hipd_merge_planes_dev).
+// planes.hip — arrays of E-byte elements <-> their E byte planes (shafa_hipd_split_planes_dev, shafa_hipd_merge_planes_dev), and
+// the same with every element XORed with the element of a base region (the _xor_dev entries: tensor deltas).
 //
 // Block b is d_n[b] (<= cap[b]) elements of E = 1, 2, 4 or 8 bytes.  ELEMENT SIDE: its E d_n[b] bytes at d_el + off[b], at ANY
 // byte alignment, never copied: split reads the aligned 16-byte words around what a lane wants and shifts them into place
@@ -26,6 +27,13 @@
 // and merges that unit's tail itself — and the unit's own last sh bytes are left to the lane behind, or, in the block's last
 // unit, stored as bytes.  A word that reaches in front of the region or past the unit's last element is stored as bytes too.
 // Algorithmic HBM bytes: every element read once and written once.
+//
+// With a base (template XOR): block b's base region is its own E d_n[b] bytes at d_base + boff[b], at an alignment of
+// ITS own, read once the way split reads the element side (xor_base); a block whose boff is SHAFA_PLANES_NO_BASE has none and
+// goes through as in the plain kernels.  split XORs the base onto the elements right after they are shifted into place — in a
+// pass where both regions are 16-aligned the base takes the coalesced path through LDS behind the element side — and merge onto
+// the rebuilt elements in front of the shift to the output's alignment.  3 bytes of traffic per tensor byte.  The plain entries
+// launch the XOR = false instantiations, from which every trace of the base is compiled out.
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -96,37 +104,79 @@ __device__ __forceinline__ void split_store(const u32 (&w)[4 * E], u64 n, u64 e0
     }
 }
 
+// The aligned words around bytes p .. p + 16 W - 1 (p a multiple of 16, below nbytes) of a region of nbytes bytes at src,
+// src mod 16 = sh: word i is read only where it holds a byte of the region, the others are 0.  NT: streamed loads.
+template <int W, bool NT>
+__device__ __forceinline__ void load_words(const u8 *src, u64 nbytes, u64 p, u32 sh, uint4 (&a)[W + 1])
+{
+    const u8 *s16 = (const u8 *)(((u64)(uintptr_t)src + p) & ~(u64)15);
+#pragma unroll
+    for (int i = 0; i <= W; ++i) {
+        a[i] = make_uint4(0, 0, 0, 0);
+        if (i == 0 || (p + 16u * i - sh < nbytes && (i < W || sh != 0)))
+            a[i] = NT ? gload_nt<uint4>(s16 + 16 * i) : gload<uint4>(s16 + 16 * i);
+    }
+}
+
+// bytes 4 Q + r .. + 16 W - 1 of the words a -> the dwords w, or (XOR) onto them
+template <int W, int Q, bool XOR>
+__device__ __forceinline__ void shift_into(const uint4 (&a)[W + 1], u32 r, u32 *w)
+{
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+        const uint4 v = shift_words<Q>(a[i], a[i + 1], r);
+        if (XOR) { w[4 * i] ^= v.x; w[4 * i + 1] ^= v.y; w[4 * i + 2] ^= v.z; w[4 * i + 3] ^= v.w; }
+        else { w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w; }
+    }
+}
+
+// w ^= bytes p .. p + 16 W - 1 of the base region of nbytes bytes at bs, which lies at an alignment of its own: read as split
+// reads its element side, the quarter of the shift (uniform) picked around the shifts alone.  The loads are plain: a lane's words
+// are 16 W bytes from its neighbour's, the rest of a line comes with the instructions that follow, and streamed loads let the
+// line go in between (8 to 22 % slower).  Base bytes behind the region end up in dwords of w behind the block's
+// last element, which no caller stores.
+template <int W>
+__device__ __forceinline__ void xor_base(const u8 *bs, u64 nbytes, u64 p, u32 *w)
+{
+    const u32 sh = (u32)((uintptr_t)bs & 15u), r = sh & 3u;
+    uint4 a[W + 1];
+    load_words<W, false>(bs, nbytes, p, sh, a);
+    switch (sh >> 2) {                               // uniform
+    case 0: shift_into<W, 0, true>(a, r, w); break;
+    case 1: shift_into<W, 1, true>(a, r, w); break;
+    case 2: shift_into<W, 2, true>(a, r, w); break;
+    default: shift_into<W, 3, true>(a, r, w); break;
+    }
+}
+
 // The unit of 16 elements from element e0 < n of a region of n elements at src (src mod 16 = 4 Q + r) -> its E plane words.
 // An aligned word of the element side is read only where it holds a byte of the region; what such a word holds behind the
-// region ends up in plane bytes behind n, which are not stored.
-template <int E, int Q>
-__device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, u8 *d_planes, const u64 *poff)
+// region ends up in plane bytes behind n, which are not stored.  bs (XOR: the block's base region, or NULL): the elements are
+// XORed with the base's in element order as soon as they are in place, so only one side's E + 1 words are live at a time.
+template <int E, int Q, bool XOR>
+__device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, const u8 *bs, u8 *d_planes, const u64 *poff)
 {
-    const u32 sh = 4u * Q + r;
     const u64 nbytes = n * E, p = e0 * E;
-    const u8 *s16 = (const u8 *)(((u64)(uintptr_t)src + p) & ~(u64)15);
-    uint4 a[E + 1];
-#pragma unroll
-    for (int i = 0; i <= E; ++i) {
-        a[i] = make_uint4(0, 0, 0, 0);
-        if (i == 0 || (p + 16u * i - sh < nbytes && (i < E || sh != 0))) a[i] = gload_nt<uint4>(s16 + 16 * i);
-    }
     u32 w[4 * E];
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-        const uint4 v = shift_words<Q>(a[i], a[i + 1], r);
-        w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    {
+        uint4 a[E + 1];
+        load_words<E, true>(src, nbytes, p, 4u * Q + r, a);
+        shift_into<E, Q, false>(a, r, w);
     }
+    if (XOR && bs) xor_base<E>(bs, nbytes, p, w);    // (uniform)
     split_store<E>(w, n, e0, d_planes, poff);
 }
 
 // A whole pass (every lane a whole unit) of a 16-aligned region: the pass's 4096 E bytes are loaded as E coalesced words a
 // lane (a wave reads 1 KiB contiguous) and handed over through LDS, where lane l reads its own words l E .. l E + E - 1.  One
 // slot of padding every 16 keeps both sides free of bank conflicts: a 16-lane group of the strided reads covers 16 rows or all
-// 16 slots of E rows.
+// 16 slots of E rows.  bs (XOR: the base region, 16-aligned too, or NULL): the base's pass follows through the same rows in a
+// second round and is XORed onto the lane's words.  (XORing the two coalesced words in front of one round through LDS is
+// less LDS traffic and two barriers fewer, but keeps 2 E loads in flight a lane: 6 % slower at 4 bytes, no faster at 2.)
 constexpr int PL_LDS_SLOTS = TP_THREADS + TP_THREADS / 16;      // per byte of the element
-template <int E>
-__device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass, u8 *d_planes, const u64 *poff, uint4 *lds)
+template <int E, bool XOR>
+__device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass, const u8 *bs, u8 *d_planes, const u64 *poff,
+                                               uint4 *lds)
 {
     const u32 tid = threadIdx.x;
     const u8 *base = src + e0_pass * E;
@@ -144,21 +194,44 @@ __device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass
         w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
     }
     lds_barrier();
+    if (XOR && bs) {                                 // (uniform)
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const u32 wd = (u32)i * TP_THREADS + tid;
+            lds[wd + (wd >> 4)] = gload_nt<uint4>(bs + e0_pass * E + 16ull * wd);
+        }
+        lds_barrier();
+#pragma unroll
+        for (int i = 0; i < E; ++i) {
+            const u32 wd = tid * E + (u32)i;
+            const uint4 v = lds[wd + (wd >> 4)];
+            w[4 * i] ^= v.x; w[4 * i + 1] ^= v.y; w[4 * i + 2] ^= v.z; w[4 * i + 3] ^= v.w;
+        }
+        lds_barrier();
+    }
     split_store<E>(w, n, e0_pass + (u64)tid * PL_UNIT, d_planes, poff);
 }
 
-template <int E, int Q>
-__device__ __forceinline__ void split_tile(const TpWalk &wk, u32 r, u8 *d_planes, const u64 *poff, uint4 *lds)
+template <int E, int Q, bool XOR>
+__device__ __forceinline__ void split_tile(const TpWalk &wk, u32 r, const u8 *bs, u8 *d_planes, const u64 *poff, uint4 *lds)
 {
+    const bool both16 = Q == 0 && r == 0 && (!XOR || ((uintptr_t)bs & 15u) == 0);     // a block without a base: bs is NULL
 #pragma nounroll
     for (int u = 0; u < PL_UNITS; ++u) {
-        if (Q == 0 && r == 0 && wk.pos0 + (u64)(u + 1) * PL_PASS <= wk.n) {          // (uniform) the barriers are inside
-            split_pass_lds<E>(wk.in, wk.n, wk.pos0 + (u64)u * PL_PASS, d_planes, poff, lds);
+        if (both16 && wk.pos0 + (u64)(u + 1) * PL_PASS <= wk.n) {                    // (uniform) the barriers are inside
+            split_pass_lds<E, XOR>(wk.in, wk.n, wk.pos0 + (u64)u * PL_PASS, bs, d_planes, poff, lds);
             continue;
         }
         const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 < wk.n) split_unit<E, Q>(wk.in, wk.n, e0, r, d_planes, poff);
+        if (e0 < wk.n) split_unit<E, Q, XOR>(wk.in, wk.n, e0, r, bs, d_planes, poff);
     }
+}
+
+// block b's base region (the XOR launches): NULL where its offset says that it has none, and then d_base is not looked at
+__device__ __forceinline__ const u8 *base_of(const u8 *d_base, const u64 *d_boff, int b)
+{
+    const u64 o = d_boff[b];
+    return o == SHAFA_PLANES_NO_BASE ? nullptr : d_base + o;
 }
 
 // a block whose size is past its capacity: the walk has skipped its tiles (a capacity of 0 has none), this reports it
@@ -168,23 +241,26 @@ __device__ __forceinline__ void planes_errors(const u64 *__restrict__ cap, const
         if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
 }
 
-template <int E>
+// XOR: the _xor entry's launch, block b's base region at d_base + d_boff[b]; the plain entry's passes neither
+template <int E, bool XOR>
 __global__ __launch_bounds__(TP_THREADS) void planes_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                            const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                            const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
                                                            const u64 *__restrict__ d_poff, int *__restrict__ err, u32 n_tiles,
-                                                           u32 per_wg)
+                                                           u32 per_wg, const u8 *__restrict__ d_base,
+                                                           const u64 *__restrict__ d_boff)
 {
     __shared__ uint4 lds[PL_LDS_SLOTS * E];
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
         const u64 *poff = d_poff + (u64)wk.b * E;
+        const u8 *bs = XOR ? base_of(d_base, d_boff, wk.b) : nullptr;
         const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
         switch (sh >> 2) {                           // uniform
-        case 0: split_tile<E, 0>(wk, r, d_planes, poff, lds); break;
-        case 1: split_tile<E, 1>(wk, r, d_planes, poff, lds); break;
-        case 2: split_tile<E, 2>(wk, r, d_planes, poff, lds); break;
-        default: split_tile<E, 3>(wk, r, d_planes, poff, lds); break;
+        case 0: split_tile<E, 0, XOR>(wk, r, bs, d_planes, poff, lds); break;
+        case 1: split_tile<E, 1, XOR>(wk, r, bs, d_planes, poff, lds); break;
+        case 2: split_tile<E, 2, XOR>(wk, r, bs, d_planes, poff, lds); break;
+        default: split_tile<E, 3, XOR>(wk, r, bs, d_planes, poff, lds); break;
         }
     }
     planes_errors(cap, d_n, nblk, err);
@@ -199,9 +275,12 @@ __device__ __forceinline__ uint4 shift_at(const u32 *x, u32 r)
 }
 
 // The unit of 16 elements from element e0 of a region of n elements at dst (sh = dst mod 16, 16 - sh = 4 Q + r) <- its E plane
-// words.  Every lane of the wave calls (the shuffles); a lane with e0 >= n loads and stores nothing.
-template <int E, int Q>
-__device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r, const u8 *d_planes, const u64 *poff)
+// words.  Every lane of the wave calls (the shuffles); a lane with e0 >= n loads and stores nothing.  bs (XOR: the block's base
+// region, or NULL): the unit's bytes are XORed with the base's before they are shifted to dst's alignment, so what a lane hands
+// to the lane behind is finished; the tail a wave's first lane rebuilds takes the 16 base bytes in front of the unit.
+template <int E, int Q, bool XOR>
+__device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r, const u8 *bs, const u8 *d_planes,
+                                           const u64 *poff)
 {
     const bool active = e0 < n;
     // x: [the 16 bytes in front of the unit][the unit's 16 E bytes][zeros]
@@ -215,6 +294,7 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
     }
 #pragma unroll
     for (int d = 0; d < 4 * E; ++d) x[4 + d] = merge_dword<E>(p, d);
+    if (XOR && bs && active) xor_base<E>(bs, n * E, e0 * E, x + 4);
 #pragma unroll
     for (int k = 0; k < 4; ++k) x[k] = 0;
 #pragma unroll
@@ -231,6 +311,7 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
             }
 #pragma unroll
             for (int k = 0; k < 4; ++k) x[k] = merge_dword<E>(pp, 4 * E - 4 + k);
+            if (XOR && bs) xor_base<1>(bs, n * E, e0 * E - 16, x);
         }
     }
     if (!active) return;
@@ -252,63 +333,69 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
     }
 }
 
-template <int E, int Q>
-__device__ __forceinline__ void merge_tile(const TpWalk &wk, u32 sh, u32 r, const u8 *d_planes, const u64 *poff)
+template <int E, int Q, bool XOR>
+__device__ __forceinline__ void merge_tile(const TpWalk &wk, u32 sh, u32 r, const u8 *bs, const u8 *d_planes, const u64 *poff)
 {
 #pragma nounroll
     for (int u = 0; u < PL_UNITS; ++u) {
         const u64 e0w = wk.pos0 + (u64)u * PL_PASS + (u64)(threadIdx.x & ~63u) * PL_UNIT;
         if (e0w >= wk.n) continue;                   // (wave uniform) no lane of the wave has an element
-        merge_unit<E, Q>((u8 *)wk.in, wk.n, e0w + (u64)lane_id() * PL_UNIT, sh, r, d_planes, poff);
+        merge_unit<E, Q, XOR>((u8 *)wk.in, wk.n, e0w + (u64)lane_id() * PL_UNIT, sh, r, bs, d_planes, poff);
     }
 }
 
-template <int E>
+template <int E, bool XOR>
 __global__ __launch_bounds__(TP_THREADS) void planes_merge(u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                            const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                            const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
                                                            const u64 *__restrict__ d_poff, int *__restrict__ err, u32 n_tiles,
-                                                           u32 per_wg)
+                                                           u32 per_wg, const u8 *__restrict__ d_base,
+                                                           const u64 *__restrict__ d_boff)
 {
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
         const u64 *poff = d_poff + (u64)wk.b * E;
+        const u8 *bs = XOR ? base_of(d_base, d_boff, wk.b) : nullptr;
         const u32 sh = (u32)((uintptr_t)wk.in & 15u), m = (16u - sh) & 15u, r = m & 3u;
         switch (sh == 0 ? 4u : m >> 2) {             // uniform
-        case 0: merge_tile<E, 0>(wk, sh, r, d_planes, poff); break;
-        case 1: merge_tile<E, 1>(wk, sh, r, d_planes, poff); break;
-        case 2: merge_tile<E, 2>(wk, sh, r, d_planes, poff); break;
-        case 3: merge_tile<E, 3>(wk, sh, r, d_planes, poff); break;
-        default: merge_tile<E, 4>(wk, sh, r, d_planes, poff); break;
+        case 0: merge_tile<E, 0, XOR>(wk, sh, r, bs, d_planes, poff); break;
+        case 1: merge_tile<E, 1, XOR>(wk, sh, r, bs, d_planes, poff); break;
+        case 2: merge_tile<E, 2, XOR>(wk, sh, r, bs, d_planes, poff); break;
+        case 3: merge_tile<E, 3, XOR>(wk, sh, r, bs, d_planes, poff); break;
+        default: merge_tile<E, 4, XOR>(wk, sh, r, bs, d_planes, poff); break;
         }
     }
     planes_errors(cap, d_n, nblk, err);
 }
 
+// d_boff non-NULL: the XOR kernels
 template <int E>
 void planes_launch(bool merge, u32 wgs, hipStream_t st, u8 *d_el, const u64 *off, const u64 *cap, const u32 *tbase, int nblk,
-                   const u64 *d_n, u8 *d_planes, const u64 *poff, int *err, u32 nt, u32 per_wg)
+                   const u64 *d_n, u8 *d_planes, const u64 *poff, int *err, u32 nt, u32 per_wg, const u8 *d_base,
+                   const u64 *d_boff)
 {
     if (merge)
-        hipLaunchKernelGGL(planes_merge<E>, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, off, cap, tbase, nblk, d_n,
-                           (const u8 *)d_planes, poff, err, nt, per_wg);
+        hipLaunchKernelGGL((d_boff ? planes_merge<E, true> : planes_merge<E, false>), dim3(wgs), dim3(TP_THREADS), 0, st, d_el, off,
+                           cap, tbase, nblk, d_n, (const u8 *)d_planes, poff, err, nt, per_wg, d_base, d_boff);
     else
-        hipLaunchKernelGGL(planes_split<E>, dim3(wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, off, cap, tbase, nblk, d_n,
-                           d_planes, poff, err, nt, per_wg);
+        hipLaunchKernelGGL((d_boff ? planes_split<E, true> : planes_split<E, false>), dim3(wgs), dim3(TP_THREADS), 0, st,
+                           (const u8 *)d_el, off, cap, tbase, nblk, d_n, d_planes, poff, err, nt, per_wg, d_base, d_boff);
 }
 
 }  // namespace
 
-// workspace, all of it uploaded by the host: [offsets][capacities][plane offsets: elem a block][tbase, zero padded to 16].  The
-// caller has checked the arguments and that the tiles number fewer than 2^31.
+// workspace, all of it uploaded by the host: [offsets][capacities][plane offsets: elem a block][base offsets: with h_base_off]
+// [tbase, zero padded to 16].  h_base_off (and d_base) non-NULL: the XOR kernels.  The caller has checked the arguments and that
+// the tiles number fewer than 2^31.
 int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
-                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off)
+                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off)
 {
     u64 ntiles = 0;
     for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_cap[b], TP_TILE);
     if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
     const size_t nb = (size_t)nblocks;
-    const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_base = u_poff + nb * elem * 8;
+    const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_boff = u_poff + nb * elem * 8;
+    const size_t u_base = u_boff + (h_base_off ? nb * 8 : 0);
     const size_t up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
     int rc = batch_reserve(bt, st, up_bytes);
     if (rc) return rc;
@@ -318,6 +405,7 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
     memcpy(hs + u_off, h_off, nb * 8);
     memcpy(hs + u_cap, h_cap, nb * 8);
     memcpy(hs + u_poff, h_plane_off, nb * elem * 8);
+    if (h_base_off) memcpy(hs + u_boff, h_base_off, nb * 8);
     u32 *hb = (u32 *)(hs + u_base);
     u32 base = 0;
     for (int b = 0; b < nblocks; ++b) {
@@ -328,14 +416,15 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
     memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
     if ((rc = batch_upload(bt, st, ws, hs, up_bytes))) return rc;
     const u64 *d_off = (const u64 *)(ws + u_off), *d_cap = (const u64 *)(ws + u_cap), *d_poff = (const u64 *)(ws + u_poff);
-    const u32 *d_base = (const u32 *)(ws + u_base);
+    const u64 *d_bo = h_base_off ? (const u64 *)(ws + u_boff) : nullptr;
+    const u32 *d_tb = (const u32 *)(ws + u_base);
     // without a tile one workgroup still looks for blocks past a capacity of 0
     const u32 nt = (u32)ntiles, per_wg = nt ? (nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1, wgs = nt ? (nt + per_wg - 1) / per_wg : 1;
     switch (elem) {
-    case 1: planes_launch<1>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
-    case 2: planes_launch<2>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
-    case 4: planes_launch<4>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
-    default: planes_launch<8>(merge, wgs, st, d_el, d_off, d_cap, d_base, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg); break;
+    case 1: planes_launch<1>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
+    case 2: planes_launch<2>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
+    case 4: planes_launch<4>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
+    default: planes_launch<8>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;

@@ -2,7 +2,7 @@
 next to what a user has without them and next to a plain copy.  Standalone; one process on one MI355X; HIP events around one
 enqueue on a stream (no batch set-up, no synchronisation inside), the median of --reps calls after --warmup untimed ones.
 
-  python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover]
+  python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover] [--xor-only]
 
 Legs, per dtype; the rate is (bytes read + bytes written) / time = 2 x the tensor's bytes / time:
   split_planes_dev   one block, the whole tensor
@@ -10,6 +10,15 @@ Legs, per dtype; the rate is (bytes read + bytes written) / time = 2 x the tenso
   torch_split        x.view(torch.uint8).reshape(-1, k).t().contiguous()      (the generic strided copy)
   torch_merge        planes.t().contiguous().view(dtype)                       (its inverse)
   torch_copy         y.copy_(x): the same bytes moved and nothing else
+The transposes against a base (split_planes_xor_dev / merge_planes_xor_dev), per dtype with the base 16-aligned ("aligned") and
+one byte behind that ("base+1"), each next to what a user has without them, timed alternately with it in the same loop:
+  split_xor          one launch: planes of (x XOR base), base read in place          3 x the tensor's bytes
+  xor_then_split     torch.bitwise_xor into a temporary, then split_planes_dev       5 x
+  merge_xor          one launch: (planes merged) XOR base                            3 x
+  merge_then_xor     merge_planes_dev, then bitwise_xor_ in place                    5 x
+The rate of all four is the JOB's bytes, 3 x the tensor's, over the time, so that the two forms compare; `ratio` is the two-step
+time over the fused time.  torch XORs integers of the element's width where the base can be viewed as such, and bytes at
+base+1, where it cannot.  --xor-only leaves out the plain legs and the mover.
 and once: `mover`, the one-shot copy figure of tools/ubench/mover (a fraction of 8 TB/s, as a child process after everything
 timed here) when its binary is present.  Every answer is checked against the torch expression before it is timed.  --lib
 measures another build of the library (an experiment's).  Prints one JSON document."""
@@ -39,6 +48,86 @@ def timed(torch, st, fn, reps, warmup):
     return out
 
 
+def timed_pair(torch, st, fa, fb, reps, warmup):
+    """fa and fb alternately in one loop -> their times"""
+    for _ in range(warmup):
+        fa()
+        fb()
+    st.synchronize()
+    out = ([], [])
+    for _ in range(reps):
+        for fn, ms in ((fa, out[0]), (fb, out[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(st)
+            fn()
+            b.record(st)
+            b.synchronize()
+            ms.append(a.elapsed_time(b))
+    return out
+
+
+def leg(ms, nbytes):
+    med = statistics.median(ms)
+    return {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+            "GB_s": round(nbytes / (med / 1e3) / 1e9, 1)}
+
+
+def xor_legs(torch, pkg, bt, st, args, x, dtype, k, n, d_n, planes, back, poff):
+    """the four XOR legs for the base 16-aligned and one byte behind"""
+    dev = x.device
+    ity = {2: torch.int16, 4: torch.int32}[k]
+    store = torch.empty(n * k + 32, dtype=torch.uint8, device=dev)
+    res = {}
+    for name, shift in (("aligned", 0), ("base+1", 1)):
+        o = (-store.data_ptr()) % 16 + shift
+        base8 = store[o:o + n * k]
+        # a checkpoint's base: the tensor with one element in sixteen redrawn
+        base8.copy_(x.view(torch.uint8))
+        base8.view(-1, 16 * k)[:, :k] = torch.randint(0, 256, (n // 16, k), dtype=torch.uint8, device=dev)
+        if shift == 0:
+            bi = base8.view(ity)
+            t_xor = lambda: torch.bitwise_xor(x.view(ity), bi)
+            t_unxor = lambda: back.view(ity).bitwise_xor_(bi)
+        else:
+            t_xor = lambda: torch.bitwise_xor(x.view(torch.uint8), base8)
+            t_unxor = lambda: back.view(torch.uint8).bitwise_xor_(base8)
+        split_x = lambda: bt.split_planes_xor_dev(st, k, x, [0], base8, [0], [n], d_n, planes, poff)
+        merge_x = lambda: bt.merge_planes_xor_dev(st, k, planes, poff, base8, [0], [n], d_n, back, [0])
+
+        def two_split():
+            tmp = t_xor()
+            bt.split_planes_dev(st, k, tmp, [0], [n], d_n, planes, poff)
+
+        def two_merge():
+            bt.merge_planes_dev(st, k, planes, poff, [n], d_n, back, [0])
+            t_unxor()
+
+        want = t_xor().view(torch.uint8).reshape(-1, k).t().contiguous()
+        split_x()
+        bt.finish(st, 1)
+        ok = torch.equal(planes.view(k, n), want)
+        merge_x()
+        bt.finish(st, 1)
+        ok = ok and torch.equal(back.view(torch.uint8), x.view(torch.uint8))
+        two_split()
+        bt.finish(st, 1)
+        ok = ok and torch.equal(planes.view(k, n), want)
+        two_merge()
+        bt.finish(st, 1)
+        if not ok or not torch.equal(back.view(torch.uint8), x.view(torch.uint8)):
+            sys.exit(f"{name}: the XOR legs differ from the torch expression")
+        del want
+        legs = {}
+        for fused, two, fa, fb in (("split_xor", "xor_then_split", split_x, two_split),
+                                   ("merge_xor", "merge_then_xor", merge_x, two_merge)):
+            ma, mb = timed_pair(torch, st, fa, fb, args.reps, args.warmup)
+            legs[fused], legs[two] = leg(ma, 3 * n * k), leg(mb, 3 * n * k)
+            legs[fused]["ratio"] = round(statistics.median(mb) / statistics.median(ma), 3)
+        bt.finish(st, 1)
+        res[name] = legs
+    return res
+
+
 def mover_one_shot():
     exe = os.path.join(ROOT, "tools", "ubench", "mover")
     if not os.path.exists(exe):
@@ -55,6 +144,7 @@ def main():
     ap.add_argument("--mib", type=int, default=1024)
     ap.add_argument("--lib", default=None)
     ap.add_argument("--no-mover", action="store_true")
+    ap.add_argument("--xor-only", action="store_true")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -89,20 +179,21 @@ def main():
                     or not torch.equal(t_merge().view(torch.uint8), x.view(torch.uint8)):
                 sys.exit(f"{name}: the planes differ from the torch expression")
             legs = {}
-            for leg, fn in (("split_planes_dev", split), ("merge_planes_dev", merge), ("torch_split", t_split),
-                            ("torch_merge", t_merge), ("torch_copy", lambda: other.copy_(x))):
-                ms = timed(torch, st, fn, args.reps, args.warmup)
-                med = statistics.median(ms)
-                legs[leg] = {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
-                             "GB_s": round(2 * n * k / (med / 1e3) / 1e9, 1)}
+            for what, fn in (("split_planes_dev", split), ("merge_planes_dev", merge), ("torch_split", t_split),
+                             ("torch_merge", t_merge), ("torch_copy", lambda: other.copy_(x))):
+                if not args.xor_only:
+                    legs[what] = leg(timed(torch, st, fn, args.reps, args.warmup), 2 * n * k)
             bt.finish(st, 1)
+            del want, other
+            torch.cuda.empty_cache()
+            legs["xor"] = xor_legs(torch, pkg, bt, st, args, x, dtype, k, n, d_n, planes, back, poff)
             res["legs"][name] = legs
-            del x, planes, back, want, other
+            del x, planes, back
             torch.cuda.empty_cache()
     bt.close()
-    res["done"] = all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
+    res["done"] = not args.xor_only and all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
                       for ours, theirs in (("split_planes_dev", "torch_split"), ("merge_planes_dev", "torch_merge")))
-    if not args.no_mover:
+    if not args.no_mover and not args.xor_only:
         torch.cuda.synchronize()
         fr = mover_one_shot()
         if fr is not None:
