@@ -507,6 +507,46 @@ int shafa_hipd_merge_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_plane_off, const uint8_t *d_base, const uint64_t *h_base_off,
                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
 
+/* ---- Byte planes of differences: the same transposes of every element's difference to the element in front ------------------
+ * Data that runs along the element axis — document offsets, position ids, sorted ids and COO / CSR indices, timestamps, sampled
+ * signals — has a low byte that walks through all 256 values even where every step is + 1, and an order-0 coder gains nothing
+ * from it; the difference to the element in front is small, and its planes are what RLE and Shannon-Fano shrink.  The
+ * transform, with M = 2^(8 elem) and x[i] element i of the block read as an unsigned little-endian integer (the bit pattern,
+ * whatever the dtype), x[-1] = 0 — every block starts afresh:
+ *   d[i] = (x[i] - x[i-1]) mod M
+ *   z[i] = ((d[i] << 1) mod M) XOR (M - 1 if d[i] >= M / 2, else 0)      the zigzag fold: small differences of either sign
+ *                                                                         become small z
+ *   plane j of the block = byte j of z[i]
+ * and back:
+ *   d[i] = (z[i] >> 1) XOR (M - 1 if z[i] is odd, else 0)
+ *   x[i] = (x[i-1] + d[i]) mod M
+ * It is a bijection on any input: random bit patterns come back bit for bit.
+ * shafa_hipd_split_planes_diff_dev writes the planes of z; shafa_hipd_merge_planes_diff_dev is its inverse.
+ * Everything said above of the plain entries holds, with their arguments in their order: the blocks, the element side at ANY
+ * alignment, the plane side at multiples of 16, elem = 1, 2, 4 or 8, the capacities on the host and the sizes device resident,
+ * what is written — exactly the plain entries' bytes: merge leaves the up to 15 bytes on either side of an unaligned region
+ * untouched, split writes nothing behind a plane's d_n[b] bytes — and the per-block code:
+ *   d_n[b] > h_cap[b]                      SHAFA_OUTSIDE_MODULE; no byte of the block is read or written, other blocks are
+ *                                          unaffected.
+ * What is read.  split reads what the plain split reads and, one lane a wave, the element in front of the wave's first unit
+ * (elem single bytes inside the region): 2 bytes of traffic per tensor byte.  merge reads the planes TWICE, in the plain merge's
+ * aligned words: 3 bytes of traffic per tensor byte.
+ * Launches.  split is one launch, the plain split's with the subtraction and the fold in front of the transposition.  merge is
+ * three on the stream: the sum of the d's of every tile of SHAFA_PLANES_TILE elements (a tile at or behind d_n[b] is not read),
+ * one workgroup a block that turns the sums of the block's tiles into exclusive prefixes, and the plain merge with a prefix
+ * sum over the tile in element order on top of the tile's prefix.  In none of them does a workgroup wait for another: no
+ * tickets, no look-back, no flags.
+ * The device workspace is the plain entries', (20 + 8 elem) bytes per block plus 20, and for merge 8 bytes more per tile of the
+ * capacities; one that cannot be had is SHAFA_LACK_OF_MEMORY.  Enqueues only, as the plain entries.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), the plain entries' in the plain
+ * entries' order. */
+int shafa_hipd_split_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
+                                     const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                     const uint64_t *h_plane_off);
+int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
+                                     const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
+                                     const uint64_t *h_out_off);
+
 /* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
  * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
  * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every

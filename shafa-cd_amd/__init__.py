@@ -127,6 +127,8 @@ def lib():
                                       vp, vp, vp]
     L.shafa_hipd_split_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_split_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -189,7 +191,8 @@ def lib():
                  "shafa_hipd_sf_encoded_size_dev", "shafa_hipd_unpack_freq", "shafa_hipd_compare_dev", "shafa_hipd_crc32_dev",
                  "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev",
                  "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev",
-                 "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev"):
+                 "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev",
+                 "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -498,6 +501,23 @@ class Batch:
         po, ic, oo = _u64arr(plane_off), _u64arr(cap), _u64arr(out_off)
         _check(lib().shafa_hipd_merge_planes_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po), _p64(ic),
                                                  d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_dev")
+
+    def split_planes_diff_dev(self, stream, elem, d_in, in_off, cap, d_n, d_planes, plane_off):
+        """split_planes_dev of every element's difference to the element in front, zigzag-folded: with x[i] block b's elements as
+        unsigned integers, x[-1] = 0 (every block starts afresh), plane j is byte j of z[i], the fold of (x[i] - x[i-1]) mod
+        2^(8 elem).  split_planes_dev's arguments, and exactly its bytes written.  Enqueues only, one launch
+        (include/shafa_hip.h: "Byte planes of differences")."""
+        io, ic, po = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off)
+        _check(lib().shafa_hipd_split_planes_diff_dev(self.h, self._st(stream), len(io), elem, _addr(d_in), _p64(io), _p64(ic),
+                                                      d_n.data_ptr(), _addr(d_planes), _p64(po)), "hipd_split_planes_diff_dev")
+
+    def merge_planes_diff_dev(self, stream, elem, d_planes, plane_off, cap, d_n, d_out, out_off):
+        """split_planes_diff_dev's inverse: the prefix sums (mod 2^(8 elem)) of the differences unfolded from block b's planes
+        -> d_out + out_off[b].  merge_planes_dev's arguments, and exactly its bytes written.  Enqueues only: three launches, in
+        none of which a workgroup waits for another (include/shafa_hip.h: "Byte planes of differences")."""
+        oo, ic, po = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off)
+        _check(lib().shafa_hipd_merge_planes_diff_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po), _p64(ic),
+                                                      d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_diff_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -2826,6 +2846,16 @@ class CompressedDelta(CompressedTensor):
         return "CompressedDelta" + CompressedTensor.__repr__(self)[len("CompressedTensor"):-1] + f", base_crc={crc})"
 
 
+class CompressedSequence(CompressedTensor):
+    """A tensor compressed by byte plane as the differences of its flattened elements (compress_sequences): CompressedTensor's
+    fields, the planes being those of the zigzag-folded difference of every element, as an unsigned integer, to the element in
+    front.  Only decompress_sequences gives the tensor back."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "CompressedSequence" + CompressedTensor.__repr__(self)[len("CompressedTensor"):]
+
+
 def plane_files(entry):
     """The file arguments of decompress_files / decompress_many for one compressed plane of a CompressedTensor (compress_many's
     dict: with RLE the .rle.shaf decodes through both stages, without the .shaf is the plane)."""
@@ -2873,11 +2903,12 @@ def _base_side(bases, idx):
     return min(have), [PLANES_NO_BASE if bases[i] is None else bases[i].data_ptr() - min(have) for i in idx]
 
 
-def _split_into(bt, st, dev, ts, bases=None):
+def _split_into(bt, st, dev, ts, bases=None, diff=False):
     """one split_planes_dev per element size over ts (blocks addressed from the lowest tensor address: nothing is
     concatenated) -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  With `bases` (one entry per
     tensor: None or a tensor of the same dtype and numel) a size with a base among its tensors takes one split_planes_xor_dev
-    instead, the bases addressed from the lowest base address."""
+    instead, the bases addressed from the lowest base address.  With `diff` (and no bases) every size takes one
+    split_planes_diff_dev: one block a tensor, so the differences run over the flattened tensor."""
     import torch
     poff, pos = [], 0
     for t in ts:
@@ -2893,8 +2924,9 @@ def _split_into(bt, st, dev, ts, bases=None):
         base = min(ts[i].data_ptr() for i in idx)
         side = _base_side(bases, idx)
         if side is None:
-            bt.split_planes_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx],
-                                d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+            split = bt.split_planes_diff_dev if diff else bt.split_planes_dev
+            split(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx], d_n[at:at + len(idx)], buf,
+                  [o for i in idx for o in poff[i]])
         else:
             bt.split_planes_xor_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], side[0], side[1],
                                     [ts[i].numel() for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
@@ -2902,10 +2934,11 @@ def _split_into(bt, st, dev, ts, bases=None):
     return buf, poff
 
 
-def _merge_into(bt, st, dev, planes, outs, bases=None):
+def _merge_into(bt, st, dev, planes, outs, bases=None, diff=False):
     """one merge_planes_dev per element size: planes[i] (the 1-D uint8 plane tensors of tensor i, each of outs[i].numel()
     bytes) -> outs[i].  A plane that is not 16-aligned is copied first.  With `bases` (as _split_into's) a size with a base
-    among its tensors takes one merge_planes_xor_dev instead."""
+    among its tensors takes one merge_planes_xor_dev instead, and with `diff` (and no bases) every size one
+    merge_planes_diff_dev."""
     import torch
     groups = _by_elem([(o.element_size(), o.numel()) for o in outs])
     if not groups:
@@ -2918,9 +2951,9 @@ def _merge_into(bt, st, dev, planes, outs, bases=None):
         obase = min(outs[i].data_ptr() for i in idx)
         side = _base_side(bases, idx)
         if side is None:
-            bt.merge_planes_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]],
-                                [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
-                                [outs[i].data_ptr() - obase for i in idx])
+            merge = bt.merge_planes_diff_dev if diff else bt.merge_planes_dev
+            merge(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], [outs[i].numel() for i in idx],
+                  d_n[at:at + len(idx)], obase, [outs[i].data_ptr() - obase for i in idx])
         else:
             bt.merge_planes_xor_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], side[0], side[1],
                                     [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
@@ -3006,9 +3039,10 @@ def _back_to_back(buf, spans):
     return [buf[o:o + n] for o, n in spans], None
 
 
-def _plane_entries(what, ts, bases, block_size, stream):
-    """compress_tensors' chain over the checked tensors ts, or with `bases` (_split_into's) compress_deltas': the split, the
-    sizes, the file sets of the planes that shrink -> per tensor its plane entries, and their bytes"""
+def _plane_entries(what, ts, bases, block_size, stream, diff=False):
+    """compress_tensors' chain over the checked tensors ts, or with `bases` (_split_into's) compress_deltas', or with `diff`
+    compress_sequences': the split, the sizes, the file sets of the planes that shrink -> per tensor its plane entries, and
+    their bytes"""
     import torch
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
         raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
@@ -3019,7 +3053,7 @@ def _plane_entries(what, ts, bases, block_size, stream):
     with torch.cuda.stream(st):
         bt = Batch(len(ts), 1 << 20)
         try:
-            buf, poff = _split_into(bt, st, dev, ts, bases)
+            buf, poff = _split_into(bt, st, dev, ts, bases, diff)
             bt.finish(st, len(ts))
         finally:
             bt.close()
@@ -3061,6 +3095,23 @@ def compress_tensors(tensors, block_size=8 << 20, stream=None):
     ts = _plane_tensors("compress_tensors", tensors)
     entries, nbytes = _plane_entries("compress_tensors", ts, None, block_size, stream)
     return [CompressedTensor(t.dtype, t.shape, ps, nb) for t, ps, nb in zip(ts, entries, nbytes)]
+
+
+def compress_sequences(tensors, block_size=8 << 20, stream=None):
+    """compress_tensors of every tensor's differences along its flattened elements — document offsets, position ids, sorted
+    ids and COO / CSR indices, timestamps, sampled signals: data whose low bytes walk through all 256 values while the step
+    from one element to the next is small.  `tensors` and `block_size` as compress_tensors takes them, and its argument
+    ValueErrors; returns one CompressedSequence per tensor, which decompress_sequences gives back bit for bit, whatever the
+    dtype and the values: the elements are taken as unsigned integers of their width, the differences wrap, and their zigzag
+    fold (small differences of either sign become small values) is what the planes hold.
+
+    Chain: compress_tensors', with one split_planes_diff_dev per element size in place of the plain split — one block a
+    tensor, so a tensor's first element is kept as it is and no difference crosses from one tensor into the next; no temporary
+    of the differences exists -> compressed_sizes -> compress_many, as there.  Whether the differences code smaller than the
+    elements is the caller's to know: nothing is tried both ways."""
+    ts = _plane_tensors("compress_sequences", tensors)
+    entries, nbytes = _plane_entries("compress_sequences", ts, None, block_size, stream, diff=True)
+    return [CompressedSequence(t.dtype, t.shape, ps, nb) for t, ps, nb in zip(ts, entries, nbytes)]
 
 
 def _base_tensors(what, bases, metas):
@@ -3136,8 +3187,9 @@ def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=
             for t, b, ps, nb, c in zip(ts, bs, entries, nbytes, crcs)]
 
 
-def _merge_items(what, items, bases, check_base, stream):
-    """decompress_tensors' checks and chain over the list `items`, or with `bases` (one entry per item) decompress_deltas'"""
+def _merge_items(what, items, bases, check_base, stream, diff=False):
+    """decompress_tensors' checks and chain over the list `items`, or with `bases` (one entry per item) decompress_deltas', or
+    with `diff` decompress_sequences'"""
     import torch
     if bases is not None:
         for i, (it, b) in enumerate(zip(items, bases)):
@@ -3200,7 +3252,7 @@ def _merge_items(what, items, bases, check_base, stream):
         outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs, bases)
+            _merge_into(bt, st, dev, planes, outs, bases, diff)
             bt.finish(st, len(items))
         finally:
             bt.close()
@@ -3223,6 +3275,8 @@ def decompress_tensors(items, stream=None):
         raise ValueError("decompress_tensors: a CompressedTensor or a list of them")
     if any(isinstance(it, CompressedDelta) for it in items):
         raise ValueError("decompress_tensors: a CompressedDelta needs its base: decompress_deltas")
+    if any(isinstance(it, CompressedSequence) for it in items):
+        raise ValueError("decompress_tensors: a CompressedSequence holds differences: decompress_sequences")
     return _merge_items("decompress_tensors", items, None, False, stream)
 
 
@@ -3243,6 +3297,8 @@ def decompress_deltas(items, bases, check_base=True, stream=None):
         items = [items]
     if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedTensor) for it in items):
         raise ValueError("decompress_deltas: a CompressedDelta / CompressedTensor or a list of them")
+    if any(isinstance(it, CompressedSequence) for it in items):
+        raise ValueError("decompress_deltas: a CompressedSequence holds differences: decompress_sequences")
     if not isinstance(check_base, bool):
         raise ValueError("decompress_deltas: check_base is a bool")
     import torch
@@ -3251,3 +3307,18 @@ def decompress_deltas(items, bases, check_base=True, stream=None):
     if not isinstance(bases, (list, tuple)) or len(bases) != len(items):
         raise ValueError("decompress_deltas: bases is a list with one entry (a tensor or None) per item")
     return _merge_items("decompress_deltas", items, list(bases), check_base, stream)
+
+
+def decompress_sequences(items, stream=None):
+    """compress_sequences' inverse: `items` is a CompressedSequence or a list of them (their planes on one device) -> the list
+    of tensors, each equal to the original bit for bit.
+
+    Chain: decompress_tensors', with one merge_planes_diff_dev per element size in place of the plain merge: decompress_many
+    over all coded planes -> the prefix sums of the unfolded differences straight into fresh tensors.  An item that is not a
+    CompressedSequence — a plain CompressedTensor or a CompressedDelta, whose planes hold no differences — is refused with a
+    ValueError before any device work.  decompress_tensors' errors otherwise."""
+    if isinstance(items, CompressedTensor):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedSequence) for it in items):
+        raise ValueError("decompress_sequences: a CompressedSequence or a list of them (compress_sequences' items)")
+    return _merge_items("decompress_sequences", items, None, False, stream, diff=True)

@@ -549,8 +549,8 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
 }
 
 // the checks the plane transposes share (include/shafa_hip.h), then the launch: d_el is the element side; xr: the _xor entries,
-// with a base side
-static int planes_dev(bool merge, bool xr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_el,
+// with a base side; df: the _diff entries
+static int planes_dev(bool merge, bool xr, bool df, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_el,
                       const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
                       const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off)
 {
@@ -570,6 +570,9 @@ static int planes_dev(bool merge, bool xr, shafa_hipd_batch *b, void *stream, in
     for (size_t i = 0; i < (size_t)nblocks * elem; ++i)
         if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    if (df)
+        return planes_diff_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, merge, (u8 *)d_el, h_off, h_cap, d_n,
+                                      (u8 *)d_planes, h_plane_off);
     return planes_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
                              h_plane_off, xr ? d_base : nullptr, xr ? h_base_off : nullptr);
 }
@@ -578,28 +581,44 @@ int shafa_hipd_split_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, 
                                 const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                 const uint64_t *h_plane_off)
 {
-    return planes_dev(false, false, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
+    return planes_dev(false, false, false, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_merge_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
                                 const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                 const uint64_t *h_out_off)
 {
-    return planes_dev(true, false, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
+    return planes_dev(true, false, false, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_split_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
                                     const uint64_t *h_in_off, const uint8_t *d_base, const uint64_t *h_base_off,
                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes, const uint64_t *h_plane_off)
 {
-    return planes_dev(false, true, b, stream, nblocks, elem, d_in, h_in_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
+    return planes_dev(false, true, false, b, stream, nblocks, elem, d_in, h_in_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_merge_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
                                     const uint64_t *h_plane_off, const uint8_t *d_base, const uint64_t *h_base_off,
                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off)
 {
-    return planes_dev(true, true, b, stream, nblocks, elem, d_out, h_out_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
+    return planes_dev(true, true, false, b, stream, nblocks, elem, d_out, h_out_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
+}
+
+int shafa_hipd_split_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
+                                     const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                     const uint64_t *h_plane_off)
+{
+    return planes_dev(false, false, true, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                      h_plane_off);
+}
+
+int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
+                                     const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
+                                     const uint64_t *h_out_off)
+{
+    return planes_dev(true, false, true, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                      h_plane_off);
 }
 
 // span: a power of two, 256 .. 8192; flags: SHAFA_SEEK_SF / SHAFA_SEEK_RLE only

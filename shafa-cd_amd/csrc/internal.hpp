@@ -233,6 +233,10 @@ int find_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, cons
 // XORed with the element of the block's base region at d_base + h_base_off[b] (any alignment; SHAFA_PLANES_NO_BASE: none)
 int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
                       const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off);
+// the same transposes of the zigzag-folded differences to the element in front, every block starting afresh (planes.hip): split
+// is one launch, merge three (tile sums, the blocks' scans, the merge) with 8 bytes of workspace more per tile of the capacities
+int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off);
 // the checkpoints of blocks of SF-decoded bytes, every `span` symbols (seek.hip); the capacities' spans number fewer than 2^31
 int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                           const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,

@@ -34,6 +34,16 @@
 // pass where both regions are 16-aligned the base takes the coalesced path through LDS behind the element side — and merge onto
 // the rebuilt elements in front of the shift to the output's alignment.  3 bytes of traffic per tensor byte.  The plain entries
 // launch the XOR = false instantiations, from which every trace of the base is compiled out.
+//
+// Differences (template DIFF, the _diff_dev entries): the planes are those of z[i], the zigzag fold of
+// d[i] = x[i] - x[i-1] mod M, x the block's elements as unsigned little-endian integers, M = 2^(8 E), x[-1] = 0.  split subtracts
+// and folds on its element-ordered dwords in front of split_store; the element in front of a lane's unit is the last one of the
+// LDS word in front in the coalesced pass (the pass's first lane loads it), and elsewhere the lane in front's last one, by shuffle
+// (a wave's first lane loads it itself) — one launch, 2 bytes of traffic per tensor byte.
+// merge needs every element's prefix sum and no workgroup may wait for another, so it is three launches: the sum of the d's of
+// every tile (planes_diff_sums), each block's sums turned into exclusive prefixes (planes_diff_scan, one workgroup a block),
+// and the plain merge's structure with a scan over the tile in element order on top of the tile's prefix (planes_merge_diff) —
+// the planes are read twice, 3 bytes of traffic per tensor byte.
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -84,6 +94,179 @@ __device__ __forceinline__ u8 byte_of(const uint4 &v, int k)
 {
     const u32 x[4] = {v.x, v.y, v.z, v.w};
     return (u8)(x[k >> 2] >> (8 * (k & 3)));
+}
+
+// ---- differences: the arithmetic on element-ordered dwords, E bytes an element.  At E = 1 and 2 a dword holds 4 or 2 elements
+// and the operations are SWAR (H: every element's top bit, L: its low bit); sums are carried in DiffT<E>, whose low 8 E bits count.
+template <int E> struct DiffT { using T = u32; };
+template <> struct DiffT<8> { using T = u64; };
+template <int E> __device__ __forceinline__ constexpr u32 pk_h() { return E == 1 ? 0x80808080u : 0x80008000u; }
+template <int E> __device__ __forceinline__ constexpr u32 pk_l() { return E == 1 ? 0x01010101u : 0x00010001u; }
+typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
+typedef short i16x2_t __attribute__((ext_vector_type(2)));
+template <int E> __device__ __forceinline__ u32 pk_add(u32 a, u32 b)
+{
+    if (E == 2) return __builtin_bit_cast(u32, __builtin_bit_cast(u16x2_t, a) + __builtin_bit_cast(u16x2_t, b));     // v_pk_add_u16
+    return ((a & ~pk_h<E>()) + (b & ~pk_h<E>())) ^ ((a ^ b) & pk_h<E>());
+}
+template <int E> __device__ __forceinline__ u32 pk_sub(u32 a, u32 b)
+{
+    if (E == 2) return __builtin_bit_cast(u32, __builtin_bit_cast(u16x2_t, a) - __builtin_bit_cast(u16x2_t, b));     // v_pk_sub_u16
+    return ((a | pk_h<E>()) - (b & ~pk_h<E>())) ^ ((a ^ ~b) & pk_h<E>());
+}
+// c in every element of a dword; all ones in every element whose low bit is set in m (m has no other bit)
+template <int E> __device__ __forceinline__ u32 pk_all(u32 c) { return (c & (E == 1 ? 0xFFu : 0xFFFFu)) * pk_l<E>(); }
+template <int E> __device__ __forceinline__ u32 pk_ones(u32 m) { return m * (E == 1 ? 0xFFu : 0xFFFFu); }
+
+// z = (d << 1) XOR (all ones where d's top bit is set), and its inverse, on every element of the N dwords w
+template <int E, int N>
+__device__ __forceinline__ void zz_fold(u32 *w)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (E == 8) {
+            if (i & 1) {
+                const u64 d = (u64)w[i] << 32 | w[i - 1], z = (d << 1) ^ (u64)((long long)d >> 63);
+                w[i - 1] = (u32)z; w[i] = (u32)(z >> 32);
+            }
+        } else if (E == 4) w[i] = (w[i] << 1) ^ (u32)((int)w[i] >> 31);
+        else if (E == 2) {
+            const u16x2_t d = __builtin_bit_cast(u16x2_t, w[i]);
+            const i16x2_t m = __builtin_bit_cast(i16x2_t, w[i]) >> (i16x2_t)(15);
+            w[i] = __builtin_bit_cast(u32, (u16x2_t)(d << (u16x2_t)(1))) ^ __builtin_bit_cast(u32, m);
+        } else w[i] = ((w[i] & ~pk_h<E>()) << 1) ^ pk_ones<E>((w[i] >> (8 * E - 1)) & pk_l<E>());
+    }
+}
+template <int E, int N>
+__device__ __forceinline__ void zz_unfold(u32 *w)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (E == 8) {
+            if (i & 1) {
+                const u64 z = (u64)w[i] << 32 | w[i - 1], d = (z >> 1) ^ (0ull - (z & 1ull));
+                w[i - 1] = (u32)d; w[i] = (u32)(d >> 32);
+            }
+        } else if (E == 4) w[i] = (w[i] >> 1) ^ (0u - (w[i] & 1u));
+        else w[i] = ((w[i] >> 1) & ~pk_h<E>()) ^ pk_ones<E>(w[i] & pk_l<E>());
+    }
+}
+
+// the elements of the 16 in w -> the fold of their difference to the element in front, prev in front of the first
+template <int E>
+__device__ __forceinline__ void diff_fold(u32 (&w)[4 * E], typename DiffT<E>::T prev)
+{
+    if (E == 8) {
+        u64 p = prev;
+#pragma unroll
+        for (int i = 0; i < 4 * E; i += 2) {
+            const u64 x = (u64)w[i + 1] << 32 | w[i], d = x - p;
+            p = x;
+            w[i] = (u32)d; w[i + 1] = (u32)(d >> 32);
+        }
+    } else if (E == 4) {
+        u32 p = (u32)prev;
+#pragma unroll
+        for (int i = 0; i < 4 * E; ++i) {
+            const u32 x = w[i];
+            w[i] = x - p;
+            p = x;
+        }
+    } else {
+        u32 pv = (u32)prev << (32 - 8 * E);          // the dword in front: its last element is what counts
+#pragma unroll
+        for (int i = 0; i < 4 * E; ++i) {
+            const u32 x = w[i];
+            const u32 sh = E == 1 ? __builtin_amdgcn_alignbyte(x, pv, 3) : __builtin_amdgcn_alignbit(x, pv, 16);
+            pv = x;
+            w[i] = pk_sub<E>(x, sh);                 // every element minus the one in front of it
+        }
+    }
+    zz_fold<E, 4 * E>(w);
+}
+
+// the inclusive prefix sums of the elements of the N dwords w, in place; returns the last one, their total
+template <int E, int N>
+__device__ __forceinline__ typename DiffT<E>::T scan_incl(u32 *w)
+{
+    if (E == 8) {
+        u64 acc = 0;
+#pragma unroll
+        for (int i = 0; i < N; i += 2) {
+            acc += (u64)w[i + 1] << 32 | w[i];
+            w[i] = (u32)acc; w[i + 1] = (u32)(acc >> 32);
+        }
+        return (typename DiffT<E>::T)acc;
+    } else if (E == 4) {
+#pragma unroll
+        for (int i = 1; i < N; ++i) w[i] += w[i - 1];
+        return w[N - 1];
+    } else {
+        u32 carry = 0;                               // the total so far, in every element
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            u32 v = w[i];
+            v = pk_add<E>(v, v << (8 * E));
+            if (E == 1) v = pk_add<E>(v, v << 16);
+            v = pk_add<E>(v, carry);
+            w[i] = v;
+            carry = pk_all<E>(v >> (32 - 8 * E));
+        }
+        return w[N - 1] >> (32 - 8 * E);
+    }
+}
+
+// c onto every element of the N dwords w
+template <int E, int N>
+__device__ __forceinline__ void add_all(u32 *w, typename DiffT<E>::T c)
+{
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (E == 8) {
+            if (i & 1) {
+                const u64 v = ((u64)w[i] << 32 | w[i - 1]) + c;
+                w[i - 1] = (u32)v; w[i] = (u32)(v >> 32);
+            }
+        } else if (E == 4) w[i] += (u32)c;
+        else w[i] = pk_add<E>(w[i], pk_all<E>((u32)c));
+    }
+}
+
+// the sum of the elements of the N dwords w
+template <int E, int N>
+__device__ __forceinline__ typename DiffT<E>::T sum_of(const u32 *w)
+{
+    typename DiffT<E>::T s = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (E == 8) {
+            if (i & 1) s += (u64)w[i] << 32 | w[i - 1];
+        } else if (E == 4) s += w[i];
+        else if (E == 2) s += (w[i] & 0xFFFFu) + (w[i] >> 16);
+        else s = __builtin_amdgcn_udot4(w[i], 0x01010101u, (u32)s, false);
+    }
+    return s;
+}
+
+// element e - 1 of the region at src, any alignment: single bytes (one lane a wave asks)
+template <int E>
+__device__ __forceinline__ typename DiffT<E>::T elem_in_front(const u8 *src, u64 e)
+{
+    typename DiffT<E>::T v = 0;
+#pragma unroll
+    for (int k = 0; k < E; ++k) v |= (typename DiffT<E>::T)gload<u8>(src + (e - 1) * E + k) << (8 * k);
+    return v;
+}
+
+// the element in front of a lane's unit w once every lane of the wave in front of it holds its own unit: the last element of
+// the lane in front, and own0 (loaded by the caller, elem_in_front) for the wave's first lane
+template <int E>
+__device__ __forceinline__ typename DiffT<E>::T prev_of(const u32 (&w)[4 * E], typename DiffT<E>::T own0)
+{
+    typename DiffT<E>::T up;
+    if (E == 8) up = (u64)(u32)__shfl_up((int)w[4 * E - 1], 1, 64) << 32 | (u32)__shfl_up((int)w[4 * E - 2], 1, 64);
+    else up = (u32)__shfl_up((int)w[4 * E - 1], 1, 64) >> (32 - 8 * E);
+    return lane_id() == 0 ? own0 : up;
 }
 
 // the 16 elements w from element e0 < n -> one word of each plane; single bytes where the block ends inside the unit
@@ -153,10 +336,13 @@ __device__ __forceinline__ void xor_base(const u8 *bs, u64 nbytes, u64 p, u32 *w
 // An aligned word of the element side is read only where it holds a byte of the region; what such a word holds behind the
 // region ends up in plane bytes behind n, which are not stored.  bs (XOR: the block's base region, or NULL): the elements are
 // XORed with the base's in element order as soon as they are in place, so only one side's E + 1 words are live at a time.
-template <int E, int Q, bool XOR>
+// DIFF: the planes of the folded differences; the callers' active lanes are a wave's first ones, so the lane in front holds a unit.
+template <int E, int Q, bool XOR, bool DIFF>
 __device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, const u8 *bs, u8 *d_planes, const u64 *poff)
 {
     const u64 nbytes = n * E, p = e0 * E;
+    typename DiffT<E>::T own0 = 0;                   // asked for first: it is there when the unit's words are
+    if (DIFF && lane_id() == 0 && e0 != 0) own0 = elem_in_front<E>(src, e0);
     u32 w[4 * E];
     {
         uint4 a[E + 1];
@@ -164,6 +350,7 @@ __device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, 
         shift_into<E, Q, false>(a, r, w);
     }
     if (XOR && bs) xor_base<E>(bs, nbytes, p, w);    // (uniform)
+    if (DIFF) diff_fold<E>(w, prev_of<E>(w, own0));
     split_store<E>(w, n, e0, d_planes, poff);
 }
 
@@ -174,12 +361,21 @@ __device__ __forceinline__ void split_unit(const u8 *src, u64 n, u64 e0, u32 r, 
 // second round and is XORed onto the lane's words.  (XORing the two coalesced words in front of one round through LDS is
 // less LDS traffic and two barriers fewer, but keeps 2 E loads in flight a lane: 6 % slower at 4 bytes, no faster at 2.)
 constexpr int PL_LDS_SLOTS = TP_THREADS + TP_THREADS / 16;      // per byte of the element
-template <int E, bool XOR>
+template <int E, bool XOR, bool DIFF>
 __device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass, const u8 *bs, u8 *d_planes, const u64 *poff,
                                                uint4 *lds)
 {
     const u32 tid = threadIdx.x;
     const u8 *base = src + e0_pass * E;
+    // DIFF: the element in front of a lane's unit is the last one of the LDS word in front of its own; the pass's first lane
+    // loads it (one load: the region is 16-aligned), asked for first so that it is there when the pass's words are
+    typename DiffT<E>::T prev = 0;
+    if (DIFF && tid == 0 && e0_pass != 0) {
+        if (E == 8) prev = (typename DiffT<E>::T)gload<u64>(base - 8);
+        else if (E == 4) prev = gload<u32>(base - 4);
+        else if (E == 2) prev = gload<u16>(base - 2);
+        else prev = gload<u8>(base - 1);
+    }
 #pragma unroll
     for (int i = 0; i < E; ++i) {
         const u32 wd = (u32)i * TP_THREADS + tid;
@@ -192,6 +388,12 @@ __device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass
         const u32 wd = tid * E + (u32)i;
         const uint4 v = lds[wd + (wd >> 4)];
         w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    if (DIFF && tid != 0) {
+        const u32 wd = tid * E - 1;
+        const u32 *last = (const u32 *)&lds[wd + (wd >> 4)];
+        if (E == 8) prev = (typename DiffT<E>::T)((u64)last[3] << 32 | last[2]);
+        else prev = last[3] >> (32 - 8 * E);
     }
     lds_barrier();
     if (XOR && bs) {                                 // (uniform)
@@ -209,21 +411,22 @@ __device__ __forceinline__ void split_pass_lds(const u8 *src, u64 n, u64 e0_pass
         }
         lds_barrier();
     }
+    if (DIFF) diff_fold<E>(w, prev);
     split_store<E>(w, n, e0_pass + (u64)tid * PL_UNIT, d_planes, poff);
 }
 
-template <int E, int Q, bool XOR>
+template <int E, int Q, bool XOR, bool DIFF>
 __device__ __forceinline__ void split_tile(const TpWalk &wk, u32 r, const u8 *bs, u8 *d_planes, const u64 *poff, uint4 *lds)
 {
     const bool both16 = Q == 0 && r == 0 && (!XOR || ((uintptr_t)bs & 15u) == 0);     // a block without a base: bs is NULL
 #pragma nounroll
     for (int u = 0; u < PL_UNITS; ++u) {
         if (both16 && wk.pos0 + (u64)(u + 1) * PL_PASS <= wk.n) {                    // (uniform) the barriers are inside
-            split_pass_lds<E, XOR>(wk.in, wk.n, wk.pos0 + (u64)u * PL_PASS, bs, d_planes, poff, lds);
+            split_pass_lds<E, XOR, DIFF>(wk.in, wk.n, wk.pos0 + (u64)u * PL_PASS, bs, d_planes, poff, lds);
             continue;
         }
         const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 < wk.n) split_unit<E, Q, XOR>(wk.in, wk.n, e0, r, bs, d_planes, poff);
+        if (e0 < wk.n) split_unit<E, Q, XOR, DIFF>(wk.in, wk.n, e0, r, bs, d_planes, poff);
     }
 }
 
@@ -241,7 +444,30 @@ __device__ __forceinline__ void planes_errors(const u64 *__restrict__ cap, const
         if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
 }
 
-// XOR: the _xor entry's launch, block b's base region at d_base + d_boff[b]; the plain entry's passes neither
+// the split kernels' body.  XOR: block b's base region at d_base + d_boff[b]; DIFF: the folded differences
+template <int E, bool XOR, bool DIFF>
+__device__ __forceinline__ void split_blocks(const u8 *__restrict__ d_el, const u64 *__restrict__ off, const u64 *__restrict__ cap,
+                                             const u32 *__restrict__ tbase, int nblk, const u64 *__restrict__ d_n,
+                                             u8 *__restrict__ d_planes, const u64 *__restrict__ d_poff, int *__restrict__ err,
+                                             u32 n_tiles, u32 per_wg, const u8 *__restrict__ d_base,
+                                             const u64 *__restrict__ d_boff, uint4 *lds)
+{
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        const u8 *bs = XOR ? base_of(d_base, d_boff, wk.b) : nullptr;
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile<E, 0, XOR, DIFF>(wk, r, bs, d_planes, poff, lds); break;
+        case 1: split_tile<E, 1, XOR, DIFF>(wk, r, bs, d_planes, poff, lds); break;
+        case 2: split_tile<E, 2, XOR, DIFF>(wk, r, bs, d_planes, poff, lds); break;
+        default: split_tile<E, 3, XOR, DIFF>(wk, r, bs, d_planes, poff, lds); break;
+        }
+    }
+    planes_errors(cap, d_n, nblk, err);
+}
+
+// XOR: the _xor entry's launch; the plain entry's passes neither d_base nor d_boff
 template <int E, bool XOR>
 __global__ __launch_bounds__(TP_THREADS) void planes_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                            const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
@@ -251,19 +477,39 @@ __global__ __launch_bounds__(TP_THREADS) void planes_split(const u8 *__restrict_
                                                            const u64 *__restrict__ d_boff)
 {
     __shared__ uint4 lds[PL_LDS_SLOTS * E];
-    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
-        if (!wk.enter()) continue;
-        const u64 *poff = d_poff + (u64)wk.b * E;
-        const u8 *bs = XOR ? base_of(d_base, d_boff, wk.b) : nullptr;
-        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
-        switch (sh >> 2) {                           // uniform
-        case 0: split_tile<E, 0, XOR>(wk, r, bs, d_planes, poff, lds); break;
-        case 1: split_tile<E, 1, XOR>(wk, r, bs, d_planes, poff, lds); break;
-        case 2: split_tile<E, 2, XOR>(wk, r, bs, d_planes, poff, lds); break;
-        default: split_tile<E, 3, XOR>(wk, r, bs, d_planes, poff, lds); break;
-        }
+    split_blocks<E, XOR, false>(d_el, off, cap, tbase, nblk, d_n, d_planes, d_poff, err, n_tiles, per_wg, d_base, d_boff, lds);
+}
+
+// the _diff entry's launch
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_split_diff(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                int nblk, const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                                const u64 *__restrict__ d_poff, int *__restrict__ err, u32 n_tiles,
+                                                                u32 per_wg)
+{
+    __shared__ uint4 lds[PL_LDS_SLOTS * E];
+    split_blocks<E, false, true>(d_el, off, cap, tbase, nblk, d_n, d_planes, d_poff, err, n_tiles, per_wg, nullptr, nullptr, lds);
+}
+
+// The lanes' v -> their exclusive prefix sums over the workgroup, on top of carry; carry += the workgroup's total.  Every lane
+// of the workgroup calls.  wt: 2 x 4 words of LDS whose halves alternate between calls (turn), so one barrier a call is enough.
+template <typename T>
+__device__ __forceinline__ T wg_excl_scan(T v, T &carry, T *wt, u32 &turn)
+{
+    T *slot = wt + 4u * (turn & 1u);
+    ++turn;
+    const T incl = wave_incl_scan_add<T>(v);
+    if (lane_id() == 63) slot[wave_id()] = incl;
+    lds_barrier();
+    T pre = carry + incl - v;
+#pragma unroll
+    for (int q = 0; q < TP_THREADS / 64; ++q) {
+        const T t = slot[q];
+        if (q < wave_id()) pre += t;
+        carry += t;
     }
-    planes_errors(cap, d_n, nblk, err);
+    return pre;
 }
 
 // bytes 4 Q + r .. + 15 of the dwords at x (Q = 4: r = 0, the word behind)
@@ -278,9 +524,14 @@ __device__ __forceinline__ uint4 shift_at(const u32 *x, u32 r)
 // words.  Every lane of the wave calls (the shuffles); a lane with e0 >= n loads and stores nothing.  bs (XOR: the block's base
 // region, or NULL): the unit's bytes are XORed with the base's before they are shifted to dst's alignment, so what a lane hands
 // to the lane behind is finished; the tail a wave's first lane rebuilds takes the 16 base bytes in front of the unit.
-template <int E, int Q, bool XOR>
+// DIFF (launch 3 of the merge of differences): the planes are those of the folded differences, and the prefix sums come in
+// between.  Then EVERY lane of the workgroup calls (the barrier in wg_excl_scan); a lane with e0 >= n adds 0.  carry: the sum of
+// the d's in front of the pass, i.e. the element in front of it.  The scan runs in element order: the lane's 16 elements, the
+// lanes of the wave, the waves.  A lane's exclusive prefix IS the element in front of its unit, so a wave's first lane gets the
+// last 16 bytes of that unit from it: that unit's last d's, rebuilt from the planes, summed up and taken off.
+template <int E, int Q, bool XOR, bool DIFF>
 __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r, const u8 *bs, const u8 *d_planes,
-                                           const u64 *poff)
+                                           const u64 *poff, typename DiffT<E>::T *carry, typename DiffT<E>::T *wt, u32 *turn)
 {
     const bool active = e0 < n;
     // x: [the 16 bytes in front of the unit][the unit's 16 E bytes][zeros]
@@ -295,6 +546,13 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
 #pragma unroll
     for (int d = 0; d < 4 * E; ++d) x[4 + d] = merge_dword<E>(p, d);
     if (XOR && bs && active) xor_base<E>(bs, n * E, e0 * E, x + 4);
+    typename DiffT<E>::T pre = 0;
+    if (DIFF) {
+        zz_unfold<E, 4 * E>(x + 4);
+        const typename DiffT<E>::T tot = scan_incl<E, 4 * E>(x + 4);
+        pre = wg_excl_scan<typename DiffT<E>::T>(tot, *carry, wt, *turn);
+        add_all<E, 4 * E>(x + 4, pre);
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) x[k] = 0;
 #pragma unroll
@@ -312,6 +570,11 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
 #pragma unroll
             for (int k = 0; k < 4; ++k) x[k] = merge_dword<E>(pp, 4 * E - 4 + k);
             if (XOR && bs) xor_base<1>(bs, n * E, e0 * E - 16, x);
+            if (DIFF) {
+                zz_unfold<E, 4>(x);
+                const typename DiffT<E>::T tail = scan_incl<E, 4>(x);          // pre = the element in front of the tail + this
+                add_all<E, 4>(x, pre - tail);
+            }
         }
     }
     if (!active) return;
@@ -340,7 +603,8 @@ __device__ __forceinline__ void merge_tile(const TpWalk &wk, u32 sh, u32 r, cons
     for (int u = 0; u < PL_UNITS; ++u) {
         const u64 e0w = wk.pos0 + (u64)u * PL_PASS + (u64)(threadIdx.x & ~63u) * PL_UNIT;
         if (e0w >= wk.n) continue;                   // (wave uniform) no lane of the wave has an element
-        merge_unit<E, Q, XOR>((u8 *)wk.in, wk.n, e0w + (u64)lane_id() * PL_UNIT, sh, r, bs, d_planes, poff);
+        merge_unit<E, Q, XOR, false>((u8 *)wk.in, wk.n, e0w + (u64)lane_id() * PL_UNIT, sh, r, bs, d_planes, poff, nullptr,
+                                     nullptr, nullptr);
     }
 }
 
@@ -368,6 +632,110 @@ __global__ __launch_bounds__(TP_THREADS) void planes_merge(u8 *__restrict__ d_el
     planes_errors(cap, d_n, nblk, err);
 }
 
+// ---- merge of the differences: three launches, none of which waits for another workgroup
+// launch 1: sums[t] = the sum of the d's of global tile t (a tile at or behind its block's size is not read; what the words of
+// a block's last unit hold behind its size goes into the block's last sum, which nothing reads)
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_diff_sums(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
+                                                               const u64 *__restrict__ d_poff, u32 n_tiles, u32 per_wg,
+                                                               u64 *__restrict__ sums)
+{
+    using T = typename DiffT<E>::T;
+    __shared__ T wsum[TP_THREADS / 64];
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        T s = 0;
+#pragma unroll
+        for (int u = 0; u < PL_UNITS; ++u) {
+            const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+            if (e0 >= wk.n) continue;
+            u32 p[4 * E], z[4 * E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const uint4 v = gload_nt<uint4>(d_planes + poff[j] + e0);
+                p[4 * j] = v.x; p[4 * j + 1] = v.y; p[4 * j + 2] = v.z; p[4 * j + 3] = v.w;
+            }
+#pragma unroll
+            for (int d = 0; d < 4 * E; ++d) z[d] = merge_dword<E>(p, d);
+            zz_unfold<E, 4 * E>(z);
+            s += sum_of<E, 4 * E>(z);
+        }
+        s = wave_reduce_add<T>(s);
+        if (lane_id() == 0) wsum[wave_id()] = s;
+        lds_barrier();
+        if (threadIdx.x == 0) sums[wk.t] = (u64)(T)(wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+        lds_barrier();                               // the workgroup's next tile writes the wave sums
+    }
+}
+
+// launch 2: one workgroup a block (grid-stride): the sums of the block's ceil(d_n[b] / tile) tiles -> their exclusive prefixes,
+// in place, 256 at a time with a carried total; the next 256 are asked for before the scan of these
+__global__ __launch_bounds__(TP_THREADS) void planes_diff_scan(const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, u64 *__restrict__ sums)
+{
+    __shared__ u64 wt[2 * (TP_THREADS / 64)];
+    u32 turn = 0;
+    for (int b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const u64 n = d_n[b];
+        if (n > cap[b]) continue;                    // (uniform) past its capacity: its tiles are read by nobody
+        const u32 nt = (u32)((n + TP_TILE - 1) / TP_TILE);
+        u64 *s = sums + tbase[b];
+        u64 carry = 0;
+        u64 v = threadIdx.x < nt ? gload<u64>(s + threadIdx.x) : 0;
+        for (u32 at = 0; at < nt; at += TP_THREADS) {                          // (uniform)
+            const u32 i = at + threadIdx.x;
+            const u64 nx = i + TP_THREADS < nt ? gload<u64>(s + i + TP_THREADS) : 0;
+            const u64 pre = wg_excl_scan<u64>(v, carry, wt, turn);
+            if (i < nt) gstore<u64>(s + i, pre);
+            v = nx;
+        }
+    }
+}
+
+template <int E, int Q>
+__device__ __forceinline__ void merge_tile_diff(const TpWalk &wk, u32 sh, u32 r, const u8 *d_planes, const u64 *poff,
+                                                typename DiffT<E>::T carry, typename DiffT<E>::T *wt, u32 &turn)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0p = wk.pos0 + (u64)u * PL_PASS;
+        if (e0p >= wk.n) break;                      // (WORKGROUP uniform, unlike merge_tile's skip: a barrier is behind it)
+        merge_unit<E, Q, false, true>((u8 *)wk.in, wk.n, e0p + (u64)threadIdx.x * PL_UNIT, sh, r, nullptr, d_planes, poff, &carry,
+                                      wt, &turn);
+    }
+}
+
+// launch 3: sums[t] is by now the sum of the d's of the block's tiles in front of tile t
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_merge_diff(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                int nblk, const u64 *__restrict__ d_n,
+                                                                const u8 *__restrict__ d_planes, const u64 *__restrict__ d_poff,
+                                                                int *__restrict__ err, u32 n_tiles, u32 per_wg,
+                                                                const u64 *__restrict__ sums)
+{
+    using T = typename DiffT<E>::T;
+    __shared__ T wt[2 * (TP_THREADS / 64)];
+    u32 turn = 0;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        const T carry = (T)sums[wk.t];
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), m = (16u - sh) & 15u, r = m & 3u;
+        switch (sh == 0 ? 4u : m >> 2) {             // uniform
+        case 0: merge_tile_diff<E, 0>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
+        case 1: merge_tile_diff<E, 1>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
+        case 2: merge_tile_diff<E, 2>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
+        case 3: merge_tile_diff<E, 3>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
+        default: merge_tile_diff<E, 4>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
+        }
+    }
+    planes_errors(cap, d_n, nblk, err);
+}
+
 // d_boff non-NULL: the XOR kernels
 template <int E>
 void planes_launch(bool merge, u32 wgs, hipStream_t st, u8 *d_el, const u64 *off, const u64 *cap, const u32 *tbase, int nblk,
@@ -382,13 +750,38 @@ void planes_launch(bool merge, u32 wgs, hipStream_t st, u8 *d_el, const u64 *off
                            (const u8 *)d_el, off, cap, tbase, nblk, d_n, d_planes, poff, err, nt, per_wg, d_base, d_boff);
 }
 
+// what planes_upload leaves in the workspace for a launch
+struct PlanesWs {
+    const u64 *off, *cap, *poff, *boff;
+    const u32 *tbase;
+    u64 *sums;
+    u32 nt, per_wg, wgs;
+};
+
+template <int E>
+void planes_diff_launch(bool merge, const PlanesWs &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err)
+{
+    if (!merge) {
+        hipLaunchKernelGGL(planes_split_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, d_planes, a.poff, err, a.nt, a.per_wg);
+        return;
+    }
+    if (a.nt)
+        hipLaunchKernelGGL(planes_diff_sums<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, (const u8 *)d_planes, a.poff, a.nt, a.per_wg, a.sums);
+    const u32 bw = (u32)nblk < TP_MAX_BLOCK_WGS ? (u32)nblk : TP_MAX_BLOCK_WGS;
+    hipLaunchKernelGGL(planes_diff_scan, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblk, d_n, a.sums);
+    hipLaunchKernelGGL(planes_merge_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       (const u8 *)d_planes, a.poff, err, a.nt, a.per_wg, (const u64 *)a.sums);
+}
+
 }  // namespace
 
-// workspace, all of it uploaded by the host: [offsets][capacities][plane offsets: elem a block][base offsets: with h_base_off]
-// [tbase, zero padded to 16].  h_base_off (and d_base) non-NULL: the XOR kernels.  The caller has checked the arguments and that
-// the tiles number fewer than 2^31.
-int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
-                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off)
+// planes_upload: the launch arguments every entry shares, in the workspace: [offsets][capacities][plane offsets: elem a block][base offsets:
+// with h_base_off][tbase, zero padded to 16], all of it uploaded by the host, and behind it, with `sums`, 8 bytes per tile of the
+// capacities that the kernels fill.  The caller has checked the arguments and that the tiles number fewer than 2^31.
+static int planes_upload(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u64 *h_off, const u64 *h_cap,
+                         const u64 *h_plane_off, const u64 *h_base_off, bool sums, PlanesWs &a)
 {
     u64 ntiles = 0;
     for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_cap[b], TP_TILE);
@@ -397,7 +790,7 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
     const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_boff = u_poff + nb * elem * 8;
     const size_t u_base = u_boff + (h_base_off ? nb * 8 : 0);
     const size_t up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, up_bytes);
+    int rc = batch_reserve(bt, st, up_bytes + (sums ? (size_t)ntiles * 8 : 0));
     if (rc) return rc;
     u8 *ws = (u8 *)bt->d_ws;
     u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
@@ -415,16 +808,46 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
     hb[nblocks] = base;
     memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
     if ((rc = batch_upload(bt, st, ws, hs, up_bytes))) return rc;
-    const u64 *d_off = (const u64 *)(ws + u_off), *d_cap = (const u64 *)(ws + u_cap), *d_poff = (const u64 *)(ws + u_poff);
-    const u64 *d_bo = h_base_off ? (const u64 *)(ws + u_boff) : nullptr;
-    const u32 *d_tb = (const u32 *)(ws + u_base);
+    a.off = (const u64 *)(ws + u_off);
+    a.cap = (const u64 *)(ws + u_cap);
+    a.poff = (const u64 *)(ws + u_poff);
+    a.boff = h_base_off ? (const u64 *)(ws + u_boff) : nullptr;
+    a.tbase = (const u32 *)(ws + u_base);
+    a.sums = sums ? (u64 *)(ws + up_bytes) : nullptr;
     // without a tile one workgroup still looks for blocks past a capacity of 0
-    const u32 nt = (u32)ntiles, per_wg = nt ? (nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1, wgs = nt ? (nt + per_wg - 1) / per_wg : 1;
+    a.nt = (u32)ntiles;
+    a.per_wg = a.nt ? (a.nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1;
+    a.wgs = a.nt ? (a.nt + a.per_wg - 1) / a.per_wg : 1;
+    return SHAFA_SUCCESS;
+}
+
+// h_base_off (and d_base) non-NULL: the XOR kernels
+int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
+                      const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off)
+{
+    PlanesWs a;
+    if (int rc = planes_upload(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, h_base_off, false, a)) return rc;
     switch (elem) {
-    case 1: planes_launch<1>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
-    case 2: planes_launch<2>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
-    case 4: planes_launch<4>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
-    default: planes_launch<8>(merge, wgs, st, d_el, d_off, d_cap, d_tb, nblocks, d_n, d_planes, d_poff, bt->d_err, nt, per_wg, d_base, d_bo); break;
+    case 1: planes_launch<1>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
+    case 2: planes_launch<2>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
+    case 4: planes_launch<4>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
+    default: planes_launch<8>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
+// the _diff entries: split is one launch; merge is the tile sums (where there is a tile), the blocks' scans and the merge itself
+int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off)
+{
+    PlanesWs a;
+    if (int rc = planes_upload(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, nullptr, merge, a)) return rc;
+    switch (elem) {
+    case 1: planes_diff_launch<1>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 2: planes_diff_launch<2>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 4: planes_diff_launch<4>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    default: planes_diff_launch<8>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;

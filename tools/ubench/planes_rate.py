@@ -2,7 +2,7 @@
 next to what a user has without them and next to a plain copy.  Standalone; one process on one MI355X; HIP events around one
 enqueue on a stream (no batch set-up, no synchronisation inside), the median of --reps calls after --warmup untimed ones.
 
-  python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover] [--xor-only]
+  python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover] [--xor-only] [--diff-only]
 
 Legs, per dtype; the rate is (bytes read + bytes written) / time = 2 x the tensor's bytes / time:
   split_planes_dev   one block, the whole tensor
@@ -19,6 +19,16 @@ one byte behind that ("base+1"), each next to what a user has without them, time
 The rate of all four is the JOB's bytes, 3 x the tensor's, over the time, so that the two forms compare; `ratio` is the two-step
 time over the fused time.  torch XORs integers of the element's width where the base can be viewed as such, and bytes at
 base+1, where it cannot.  --xor-only leaves out the plain legs and the mover.
+The transposes of differences (split_planes_diff_dev / merge_planes_diff_dev), per dtype on the tensor's bits as int16 / int32,
+both sides 16-aligned, each next to what a user has without them, timed alternately with it in the same loop:
+  split_diff         one launch: planes of the folded differences                    2 x the tensor's bytes moved
+  diff_then_split    torch.diff into a temporary (its first element copied), then split_planes_dev          4 x
+  merge_diff         three launches: the prefix sums of the unfolded planes          3 x (the planes are read twice)
+  merge_then_cumsum  merge_planes_dev, then torch.cumsum(dtype = the signed dtype of that width)            4 x
+torch's side leaves the zigzag fold out, which favours it.  As with the XOR legs the rate of all four is 3 x the tensor's bytes
+over the time, and `ratio` the two-step time over the fused time.  `split_plain` / `merge_plain` are the plain entries timed
+alternately with the fused ones in a loop of their own, `vs_plain` the fused time over the plain time.  --diff-only leaves out
+everything else.
 and once: `mover`, the one-shot copy figure of tools/ubench/mover (a fraction of 8 TB/s, as a child process after everything
 timed here) when its binary is present.  Every answer is checked against the torch expression before it is timed.  --lib
 measures another build of the library (an experiment's).  Prints one JSON document."""
@@ -128,6 +138,61 @@ def xor_legs(torch, pkg, bt, st, args, x, dtype, k, n, d_n, planes, back, poff):
     return res
 
 
+def diff_legs(torch, pkg, bt, st, args, x, k, n, d_n, planes, back, poff):
+    """the four legs of the differences and the plain entries next to the fused ones"""
+    ity = {2: torch.int16, 4: torch.int32}[k]
+    xi, bi = x.view(ity), back.view(ity)
+    tmp, other = torch.empty_like(xi), torch.empty_like(xi)
+    split_d = lambda: bt.split_planes_diff_dev(st, k, x, [0], [n], d_n, planes, poff)
+    merge_d = lambda: bt.merge_planes_diff_dev(st, k, planes, poff, [n], d_n, back, [0])
+    split_p = lambda: bt.split_planes_dev(st, k, x, [0], [n], d_n, planes, poff)
+    merge_p = lambda: bt.merge_planes_dev(st, k, planes, poff, [n], d_n, back, [0])
+
+    def two_split():
+        tmp[:1].copy_(xi[:1])
+        torch.diff(xi, out=tmp[1:])
+        bt.split_planes_dev(st, k, tmp, [0], [n], d_n, planes, poff)
+
+    def two_merge():
+        bt.merge_planes_dev(st, k, planes, poff, [n], d_n, back, [0])
+        torch.cumsum(bi, 0, dtype=ity, out=other)
+
+    # the fused answer against torch's integer arithmetic (wrapping, as the signed dtypes do on the device)
+    d = torch.empty_like(xi)
+    d[:1].copy_(xi[:1])
+    torch.diff(xi, out=d[1:])
+    want = ((d << 1) ^ (d >> (8 * k - 1))).view(torch.uint8).reshape(-1, k).t().contiguous()
+    split_d()
+    bt.finish(st, 1)
+    ok = torch.equal(planes.view(k, n), want)
+    back.view(torch.uint8).zero_()
+    merge_d()
+    bt.finish(st, 1)
+    ok = ok and torch.equal(back.view(torch.uint8), x.view(torch.uint8))
+    del want
+    two_split()
+    bt.finish(st, 1)
+    ok = ok and torch.equal(planes.view(k, n), d.view(torch.uint8).reshape(-1, k).t().contiguous())
+    two_merge()
+    bt.finish(st, 1)
+    if not ok or not torch.equal(other.view(torch.uint8), x.view(torch.uint8)):
+        sys.exit("the legs of the differences differ from the torch expression")
+    del d
+    legs = {}
+    for fused, two, fa, fb in (("split_diff", "diff_then_split", split_d, two_split),
+                               ("merge_diff", "merge_then_cumsum", merge_d, two_merge)):
+        ma, mb = timed_pair(torch, st, fa, fb, args.reps, args.warmup)
+        legs[fused], legs[two] = leg(ma, 3 * n * k), leg(mb, 3 * n * k)
+        legs[fused]["ratio"] = round(statistics.median(mb) / statistics.median(ma), 3)
+    for fused, plain, fa, fb in (("split_diff", "split_plain", split_d, split_p), ("merge_diff", "merge_plain", merge_d, merge_p)):
+        ma, mb = timed_pair(torch, st, fa, fb, args.reps, args.warmup)
+        legs[plain] = leg(mb, 3 * n * k)
+        legs[plain]["fused_ms"] = leg(ma, 3 * n * k)["ms"]
+        legs[fused]["vs_plain"] = round(statistics.median(ma) / statistics.median(mb), 3)
+    bt.finish(st, 1)
+    return legs
+
+
 def mover_one_shot():
     exe = os.path.join(ROOT, "tools", "ubench", "mover")
     if not os.path.exists(exe):
@@ -145,6 +210,7 @@ def main():
     ap.add_argument("--lib", default=None)
     ap.add_argument("--no-mover", action="store_true")
     ap.add_argument("--xor-only", action="store_true")
+    ap.add_argument("--diff-only", action="store_true")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -181,19 +247,25 @@ def main():
             legs = {}
             for what, fn in (("split_planes_dev", split), ("merge_planes_dev", merge), ("torch_split", t_split),
                              ("torch_merge", t_merge), ("torch_copy", lambda: other.copy_(x))):
-                if not args.xor_only:
+                if not args.xor_only and not args.diff_only:
                     legs[what] = leg(timed(torch, st, fn, args.reps, args.warmup), 2 * n * k)
             bt.finish(st, 1)
             del want, other
             torch.cuda.empty_cache()
-            legs["xor"] = xor_legs(torch, pkg, bt, st, args, x, dtype, k, n, d_n, planes, back, poff)
+            if not args.diff_only:
+                legs["xor"] = xor_legs(torch, pkg, bt, st, args, x, dtype, k, n, d_n, planes, back, poff)
+            torch.cuda.empty_cache()
+            if not args.xor_only:
+                legs["diff"] = diff_legs(torch, pkg, bt, st, args, x, k, n, d_n, planes, back, poff)
             res["legs"][name] = legs
             del x, planes, back
             torch.cuda.empty_cache()
     bt.close()
-    res["done"] = not args.xor_only and all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
+    res["diff_done"] = not args.xor_only and all(res["legs"][d]["diff"][f]["ratio"] > 1 for d in res["legs"]
+                                                 for f in ("split_diff", "merge_diff"))
+    res["done"] = not args.xor_only and not args.diff_only and all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
                       for ours, theirs in (("split_planes_dev", "torch_split"), ("merge_planes_dev", "torch_merge")))
-    if not args.no_mover and not args.xor_only:
+    if not args.no_mover and not args.xor_only and not args.diff_only:
         torch.cuda.synchronize()
         fr = mover_one_shot()
         if fr is not None:
