@@ -12,6 +12,7 @@ There is NO CPU fallback: if the HIP library is missing, importing ``hip`` membe
 """
 import collections
 import ctypes as C
+import itertools
 import os
 
 import numpy as np
@@ -909,104 +910,42 @@ def _al16(x):
     return (x + 15) // 16 * 16
 
 
+def _stream(dev, stream):
+    """the stream a driver works on: the caller's, or a new one on dev"""
+    import torch
+    return stream if stream is not None else torch.cuda.Stream(device=dev)
+
+
+def _max_bytes(dev, max_bytes):
+    """a driver's working-memory budget: the caller's, or a quarter of what is free on dev"""
+    import torch
+    return torch.cuda.mem_get_info(dev)[0] // 4 if max_bytes is None else max_bytes
+
+
+def _aligned_blocks(bt, st, src, starts, sizes, d_sizes):
+    """The blocks of `src` at `starts` with these sizes (d_sizes: the sizes on the device) at 16-byte aligned addresses, the
+    device entries' rule: in place when they are, else gathered by one unpack_payloads -> (tensor, offsets)"""
+    import torch
+    if not src.data_ptr() % 16 and not any(o % 16 for o in starts):
+        return src, list(starts)
+    off, tot = _layout(sizes)
+    buf = torch.empty(tot + 16, dtype=torch.uint8, device=src.device)
+    bt.unpack_payloads(st, src, torch.tensor(starts, dtype=torch.int64, device=src.device), d_sizes, buf, off, sizes)
+    return buf, off
+
+
 def compress_files(d_in, block_size, force_rle=False, force_freq=False, stream=None):
     """The files the CLI's default run `shafa <file> -b <size> [-c r|f]` writes for the bytes of `d_in` (a contiguous uint8
-    CUDA tensor), made on the device: {".rle", ".rle.freq", ".freq", ".rle.cod", ".rle.shaf"} with RLE (".freq" only with
-    force_freq), {".freq", ".cod", ".shaf"} without.  Each value is a uint8 CUDA tensor holding exactly the file (a view of a
-    buffer sized by the pack bounds).
-
-    Block split and RLE rule of the C host (shafa_block_count; shafa_rle_worthwhile on block 0, f.c:250-258).  The choice is
-    settled first: the size pass (rle_encoded_size_dev) over every block -> one synchronisation that reads the sizes -> with
-    RLE, rle_encode_tiles into regions of exactly the measured sizes (hist256_tiles of the input only with force_freq);
-    without, hist256_tiles alone: no RLE launch, no RLE region -> sf_build_codes -> sf_encode_dev -> the packs -> one finish.
-    force_rle keeps the chain without a size pass: rle_encode_tiles into worst-case regions (2 n + 3, f.c:244), one
-    synchronisation in all.  Raises ShafaError(FILE_TOO_SMALL) below 1 KiB (f.c:220,366) and on any block's error."""
-    import torch
-    dev = d_in.device
-    total = int(d_in.numel())
-    bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
-    nb = int(host().shafa_block_count(total, C.byref(bs), C.byref(last)))
-    if total < 1024:
-        raise ShafaError(FILE_TOO_SMALL, "compress_files: fewer than 1024 bytes")
-    bs, last = bs.value, last.value
-    sizes = [bs] * (nb - 1) + [last]
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
-    # inputs at 16-byte aligned offsets (the device entries' rule): in place when the blocks already are
-    off = [b * bs for b in range(nb)]
-    src_in = d_in
-    if bs % 16 or d_in.data_ptr() % 16:
-        off = [b * _al16(bs) for b in range(nb)]
-        src_in = torch.zeros(off[-1] + _al16(last) + 16, dtype=torch.uint8, device=dev)
-        for b in range(nb):
-            src_in[off[b]:off[b] + sizes[b]].copy_(d_in[b * bs:b * bs + sizes[b]])
-    d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
-    bt = Batch(nb, 2 * max(sizes) + 64)
-    try:
-        # ---- the choice: forced, or the reference's decision on block 0's RLE size, measured with every other block's
-        if force_rle:
-            use_rle = True
-            rcap = [2 * n + 3 for n in sizes]                               # f.c:244
-        else:
-            d_rsize = torch.zeros(nb, dtype=torch.int64, device=dev)
-            bt.rle_encoded_size_dev(st, src_in, off, sizes, d_n_in, d_rsize)
-            bt.finish(st, nb)
-            rcap = _u64_host(d_rsize)                                       # exact: the encoder fills these regions
-            use_rle = bool(host().shafa_rle_worthwhile(sizes[0], rcap[0], False))
-        mode = b"R" if use_rle else b"N"
-        # ---- Module F: RLE of every block with its histogram and tile histograms, or the input's alone
-        if use_rle:
-            roff, pos = _layout(rcap)
-            d_rle = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-            d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-            d_freq_rle = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-            rtoff, pos = _layout([tile_hist_bytes(c) for c in rcap])
-            d_rth = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-            bt.rle_encode_tiles(st, src_in, off, sizes, d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff)
-        if force_freq or not use_rle:
-            d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-            itoff, pos = _layout([tile_hist_bytes(n) for n in sizes])
-            d_ith = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_ith, itoff)
-        # ---- Module T and Module C from what F left on the device
-        if use_rle:
-            e_src, e_off, e_cap, e_n, e_freq, e_th, e_toff = d_rle, roff, rcap, d_rle_n, d_freq_rle, d_rth, rtoff
-        else:
-            e_src, e_off, e_cap, e_n, e_freq, e_th, e_toff = src_in, off, sizes, d_n_in, d_freq_in, d_ith, itoff
-        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
-        bt.sf_build_codes(st, nb, e_freq, d_tab)
-        # Fano codes average under H + 1 <= 9 bits a symbol: 12 bits leave room (a block that does not fit is an error)
-        ocap = [c + c // 2 + 64 for c in e_cap]
-        ooff, pos = _layout(ocap)
-        d_enc = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        bt.sf_encode_dev(st, e_src, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, e_th, e_toff)
-        # ---- the files
-        jobs = []
-        lens = torch.zeros(8, dtype=torch.int64, device=dev)
-
-        def out(key, cap):
-            buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
-            jobs.append((key, buf))
-            return buf, lens[len(jobs) - 1:len(jobs)]
-
-        if use_rle:
-            buf, n = out(".rle", pack_payloads_max(rcap, FRAME_RAW))
-            bt.pack_payloads(st, FRAME_RAW, d_rle, roff, rcap, d_rle_n, buf, buf.numel(), n)
-            buf, n = out(".rle.freq", pack_freq_max(nb))
-            bt.pack_freq(st, nb, b"R", d_rle_n, d_freq_rle, buf, buf.numel(), n)
-        if not use_rle or force_freq:
-            buf, n = out(".freq", pack_freq_max(nb))
-            bt.pack_freq(st, nb, b"N", d_n_in, d_freq_in, buf, buf.numel(), n)
-        stem = ".rle" if use_rle else ""
-        buf, n = out(stem + ".cod", pack_cod_max(nb))
-        bt.pack_cod(st, nb, mode, e_n, d_tab, buf, buf.numel(), n)
-        buf, n = out(stem + ".shaf", pack_payloads_max(ocap, FRAME_SHAF))
-        bt.pack_payloads(st, FRAME_SHAF, d_enc, ooff, ocap, d_enc_n, buf, buf.numel(), n)
-        bt.finish(st, nb)
-        got = lens.cpu().tolist()
-        return {key: buf[:got[i]] for i, (key, buf) in enumerate(jobs)}
-    finally:
-        bt.close()
+    CUDA tensor, any alignment), made on the device: {".rle", ".rle.freq", ".freq", ".rle.cod", ".rle.shaf"} with RLE (".freq"
+    only with force_freq), {".freq", ".cod", ".shaf"} without.  Each value is a uint8 CUDA tensor holding exactly the file.
+    This is compress_many's chain on one file (one group, whatever its block count): see there.  Raises
+    ShafaError(FILE_TOO_SMALL) below 1 KiB before any device work, else the file's first error in block order, an error of
+    the size pass in front of a later stage's."""
+    entry, = _per_group("compress_files", d_in, [int(d_in.numel())], block_size, stream,
+                        lambda g: _compress_group(g, force_rle, force_freq))
+    if isinstance(entry, ShafaError):
+        raise entry
+    return entry
 
 
 MANY_GROUP_BLOCKS = 16384      # compress_many: blocks per device batch (the F / T / C launches put blocks on the grid's y)
@@ -1017,7 +956,7 @@ def _many_files(name, d_in, sizes, block_size):
     the C host's split (shafa_block_count) for the files of 1 KiB or more, groups of those files): a group holds at most
     MANY_GROUP_BLOCKS blocks, and (its largest block's 8 KiB tiles) x (its blocks) stays within RLE_GRID_TILES, which bounds
     the grid of rle_encode_tiles' emit pass — (pairs of 4 KiB tiles of the largest block) x (blocks) workgroups of 256 lanes —
-    below 2^32 lanes however many small blocks join a large one."""
+    below 2^32 lanes however many small blocks join a large one.  A file alone is one group whatever its block count."""
     import torch
     if isinstance(d_in, (list, tuple)):
         if sizes is None:
@@ -1056,30 +995,39 @@ def _many_files(name, d_in, sizes, block_size):
     return d_in, sizes, start, split, groups
 
 
+def _per_group(name, d_in, sizes, block_size, stream, body):
+    """The compress drivers' prelude: the arguments checked, split and grouped (_many_files), then body(group) -> the
+    entries of that group's files, for each group on its own batch -> one entry per file, for a file under 1 KiB a
+    ShafaError(FILE_TOO_SMALL) instance, settled before any device work (f.c:220,366)."""
+    d_in, sizes, start, split, groups = _many_files(name, d_in, sizes, block_size)
+    results = [None if f in split else ShafaError(FILE_TOO_SMALL, f"{name}: fewer than 1024 bytes")
+               for f in range(len(sizes))]
+    st = _stream(d_in.device, stream) if groups else None
+    for group in groups:
+        with _GroupBlocks(name, d_in, start, split, group, st) as g:
+            entries = body(g)
+            for f, entry in zip(g.files, entries):                         # g.files: as the body left them (rle_first)
+                results[f] = entry
+    return results
+
+
 def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_freq=False, stream=None):
     """compress_files for many files in one device batch.  `d_in` holds the files back to back (a contiguous uint8 CUDA tensor;
     a list of such tensors is concatenated), `sizes` their lengths (for a list: None = the tensors' lengths).  Returns one entry
     per file: the dict compress_files returns for that file alone, byte for byte, or a ShafaError instance (not raised) for a
     file that failed — FILE_TOO_SMALL below 1 KiB, else the first error in the file's block order.  Other files are unaffected.
 
-    Chain per batch of files, its length independent of the file count: block split (shafa_block_count) -> one unpack_payloads
-    gather into 16-aligned regions when some block start is not aligned -> the size pass (rle_encoded_size_dev) over all
-    blocks -> one synchronisation reading every block's RLE size; each file's choice is shafa_rle_worthwhile on its block 0 ->
-    rle_encode_tiles over the blocks of the files that take RLE only, into regions of exactly the measured sizes, and
-    hist256_tiles over the blocks of the plain files only (over all of them with force_freq) -> sf_build_codes + sf_encode_dev
-    over all blocks, RLE and plain files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena)
-    -> the segmented packs, one call per kind of file -> one finish.  Two synchronisations per batch.  force_rle keeps the
-    chain without a size pass: rle_encode_tiles over all blocks into worst-case regions (2 n + 3), one synchronisation per
-    batch.  Files are batched by MANY_GROUP_BLOCKS blocks and by the RLE encoder's grid (_many_files)."""
-    import torch
-    d_in, sizes, start, split, groups = _many_files("compress_many", d_in, sizes, block_size)
-    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
-    # a file under 1 KiB is refused before any device work (f.c:220,366)
-    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "compress_many: fewer than 1024 bytes")
-               for f in range(len(sizes))]
-    for group in groups:
-        _compress_group(d_in, start, split, group, force_rle, force_freq, st, results)
-    return results
+    Chain per batch of files (_compress_group, the one copy: compress_files runs it on one file), its length independent of
+    the file count: block split (shafa_block_count) -> one unpack_payloads gather into 16-aligned regions when some block
+    start is not aligned -> the size pass (rle_encoded_size_dev) over all blocks -> one synchronisation reading every
+    block's RLE size; each file's choice is shafa_rle_worthwhile on its block 0 (f.c:250-258) -> rle_encode_tiles over the
+    blocks of the files that take RLE only, into regions of exactly the measured sizes, and hist256_tiles over the blocks of
+    the plain files only (over all of them with force_freq) -> sf_build_codes + sf_encode_dev over all blocks, RLE and plain
+    files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena) -> the segmented packs, one
+    call per kind of file (the single-file packs for a batch of one file) -> one finish.  Two synchronisations per batch.  force_rle keeps the chain without a size pass:
+    rle_encode_tiles over all blocks into worst-case regions (2 n + 3, f.c:244), one synchronisation per batch.  Files are
+    batched by MANY_GROUP_BLOCKS blocks and by the RLE encoder's grid (_many_files)."""
+    return _per_group("compress_many", d_in, sizes, block_size, stream, lambda g: _compress_group(g, force_rle, force_freq))
 
 
 def rle_encoded_sizes(d_in, sizes=None, block_size=65536, stream=None):
@@ -1088,25 +1036,11 @@ def rle_encoded_sizes(d_in, sizes=None, block_size=65536, stream=None):
     .rle.freq would name — or a ShafaError instance (FILE_TOO_SMALL) for a file under 1 KiB.  One read of the data by the
     size pass (rle_encoded_size_dev) and one synchronisation per batch of files; nothing is encoded, and beyond the sizes
     nothing is allocated (block starts that are not 16-aligned are first gathered into aligned regions, as in compress_many)."""
-    import torch
-    d_in, sizes, start, split, groups = _many_files("rle_encoded_sizes", d_in, sizes, block_size)
-    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
-    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "rle_encoded_sizes: fewer than 1024 bytes")
-               for f in range(len(sizes))]
-    for group in groups:
-        g = _GroupBlocks(start, split, group)
-        bt = Batch(g.nb, 2 * max(g.sizes) + 64)
-        try:
-            src_in, off = g.aligned(bt, st, d_in)
-            r, errs = _rle_encoded(bt, st, src_in, off, g.sizes, g.d_n_in(d_in.device))
-        finally:
-            bt.close()
-        for i, f in enumerate(group):
-            lo, hi = g.first[i], g.first[i] + g.count[i]
-            b, e = _first_error(errs[lo:hi])
-            results[f] = ShafaError(e, f"rle_encoded_sizes: block {b}") if e else \
-                (bool(host().shafa_rle_worthwhile(g.sizes[lo], r[lo], False)), r[lo:hi])
-    return results
+    def body(g):
+        r = g.rle_sizes()
+        return g.entries(g.errs0, [(u, r[g.first[i]:g.first[i] + g.count[i]]) for i, u in enumerate(g.use_rle(r))])
+
+    return _per_group("rle_encoded_sizes", d_in, sizes, block_size, stream, body)
 
 
 def shaf_file_bytes(block_sizes):
@@ -1128,261 +1062,252 @@ def compressed_sizes(d_in, sizes=None, block_size=65536, force_rle=False, force_
     writing them measures them) -> one finish.  ".rle" is the sum of the file's RLE sizes, ".shaf" shaf_file_bytes of its
     Shannon-Fano sizes.  Two synchronisations per batch, one with force_rle, as compress_many; the same batches
     (_many_files)."""
+    return _per_group("compressed_sizes", d_in, sizes, block_size, stream, lambda g: _sizes_group(g, force_rle, force_freq))
+
+
+def _sizes_group(g, force_rle, force_freq):
     import torch
-    d_in, sizes, start, split, groups = _many_files("compressed_sizes", d_in, sizes, block_size)
-    st = stream if stream is not None else torch.cuda.Stream(device=d_in.device)
-    results = [None if f in split else ShafaError(FILE_TOO_SMALL, "compressed_sizes: fewer than 1024 bytes")
-               for f in range(len(sizes))]
-    for group in groups:
-        _sizes_group(d_in, start, split, group, force_rle, force_freq, st, results)
-    return results
-
-
-def _sizes_group(d_in, start, split, files, force_rle, force_freq, st, results):
-    import torch
-    dev = d_in.device
-    nf = len(files)
-    g = _GroupBlocks(start, split, files)
-    nb = g.nb
-    bt = Batch(nb, 2 * max(g.sizes) + 64)
-    try:
-        src_in, off = g.aligned(bt, st, d_in)
-        d_n_in = g.d_n_in(dev)
-        # ---- Module F's two histograms of every block, without an RLE stream: the choice needs the RLE sizes on the host,
-        # and a histogram of the input that ran before it costs no synchronisation of its own
-        d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        d_freq_rle = torch.empty(nb * 256, dtype=torch.int64, device=dev)
-        d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-        bt.rle_encoded_hist_dev(st, src_in, off, g.sizes, d_n_in, d_rle_n, d_freq_rle)
-        errs0 = [SUCCESS] * nb
-        if force_rle:
-            use = [True] * nf
-        else:
-            bt.hist256(st, src_in, off, g.sizes, d_freq_in)
-            _, errs0 = bt.finish(st, nb, raise_on_error=False)
-            rsize = _u64_host(d_rle_n)
-            use = [bool(host().shafa_rle_worthwhile(g.sizes[g.first[i]], rsize[g.first[i]], False)) for i in range(nf)]
-        if force_rle and force_freq:
-            bt.hist256(st, src_in, off, g.sizes, d_freq_in)
-        # ---- per block: the RLE histogram and size, or the input's
-        if all(use):
-            e_n, e_freq = d_rle_n, d_freq_rle
-        elif not any(use):
-            e_n, e_freq = d_n_in, d_freq_in
-        else:
-            pick = torch.tensor([u for i, u in enumerate(use) for _ in range(g.count[i])], dtype=torch.bool, device=dev)
-            with torch.cuda.stream(st):
-                e_n = torch.where(pick, d_rle_n, d_n_in)
-                e_freq = torch.where(pick.repeat_interleave(256), d_freq_rle, d_freq_in)
-        # ---- Module T, and Module C's sizes
-        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
-        bt.sf_build_codes(st, nb, e_freq, d_tab)
-        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        bt.sf_encoded_size_dev(st, nb, e_freq, d_tab, d_enc_n)
-        # ---- the texts, for their lengths
-        lens = torch.zeros(3 * nf, dtype=torch.int64, device=dev)
-        kinds = []                                                          # per pack call: (its files, their keys)
-
-        def pack(call, sel, keys, cap, args):
-            fs = [i for i in range(nf) if sel[i]]
-            if not fs:
-                return
-            caps = [cap(g.count[i]) for i in fs]
-            doff, dtot = _layout(caps)
-            buf = torch.empty(dtot + 16, dtype=torch.uint8, device=dev)
-            n = lens[len(kinds) * nf:(len(kinds) + 1) * nf]
-            call(st, [g.first[i] for i in fs], [g.count[i] for i in fs], *args(fs), buf, doff, caps, n)
-            kinds.append((fs, [keys(i) for i in fs]))
-
-        modes = [b"R" if u else b"N" for u in use]
-        stem = lambda i: ".rle" if use[i] else ""                           # noqa: E731
-        pack(bt.pack_freq_files, [True] * nf, lambda i: stem(i) + ".freq", pack_freq_max,
-             lambda fs: ([modes[i] for i in fs], e_n, e_freq))
+    bt, st, dev, nb, nf, d_n_in = g.bt, g.st, g.dev, g.nb, g.nf, g.d_n_in
+    # ---- Module F's two histograms of every block, without an RLE stream: the choice needs the RLE sizes on the host,
+    # and a histogram of the input that ran before it costs no synchronisation of its own
+    d_rle_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+    d_freq_rle = torch.empty(nb * 256, dtype=torch.int64, device=dev)
+    d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+    bt.rle_encoded_hist_dev(st, g.src_in, g.off, g.sizes, d_n_in, d_rle_n, d_freq_rle)
+    if force_rle:
+        use = [True] * nf
         if force_freq:
-            pack(bt.pack_freq_files, use, lambda i: ".freq", pack_freq_max,
-                 lambda fs: ([b"N"] * len(fs), d_n_in, d_freq_in))
-        pack(bt.pack_cod_files, [True] * nf, lambda i: stem(i) + ".cod", pack_cod_max,
-             lambda fs: ([modes[i] for i in fs], e_n, d_tab))
-        _, errs = bt.finish(st, nb, raise_on_error=False)
-        got = lens.cpu().tolist()
-        rsize, esize = _u64_host(d_rle_n), _u64_host(d_enc_n)
-        out = [{} for _ in range(nf)]
-        for i in range(nf):
-            lo, hi = g.first[i], g.first[i] + g.count[i]
-            if use[i]:
-                out[i][".rle"] = int(sum(rsize[lo:hi]))
-            out[i][stem(i) + ".shaf"] = shaf_file_bytes(esize[lo:hi])
-        for k, (fs, keys) in enumerate(kinds):
-            for j, i in enumerate(fs):
-                out[i][keys[j]] = int(got[k * nf + j])
-        for i, f in enumerate(files):
-            lo, hi = g.first[i], g.first[i] + g.count[i]
-            b, e = _first_error(errs0[lo:hi])
-            if not e:
-                b, e = _first_error(errs[lo:hi])
-            results[f] = ShafaError(e, f"compressed_sizes: block {b}") if e else out[i]
-    finally:
-        bt.close()
+            bt.hist256(st, g.src_in, g.off, g.sizes, d_freq_in)
+    else:
+        bt.hist256(st, g.src_in, g.off, g.sizes, d_freq_in)
+        g.errs0 = g.finish()
+        use = g.use_rle(_u64_host(d_rle_n))
+    # ---- per block: the RLE histogram and size, or the input's
+    if all(use):
+        e_n, e_freq = d_rle_n, d_freq_rle
+    elif not any(use):
+        e_n, e_freq = d_n_in, d_freq_in
+    else:
+        pick = torch.tensor([u for i, u in enumerate(use) for _ in range(g.count[i])], dtype=torch.bool, device=dev)
+        with torch.cuda.stream(st):
+            e_n = torch.where(pick, d_rle_n, d_n_in)
+            e_freq = torch.where(pick.repeat_interleave(256), d_freq_rle, d_freq_in)
+    # ---- Module T, and Module C's sizes
+    d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+    bt.sf_build_codes(st, nb, e_freq, d_tab)
+    d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+    bt.sf_encoded_size_dev(st, nb, e_freq, d_tab, d_enc_n)
+    # ---- the texts, for their lengths
+    modes = [b"R" if u else b"N" for u in use]
+    stem = lambda i: ".rle" if use[i] else ""                               # noqa: E731
+    g.pack_text("freq", [True] * nf, lambda i: stem(i) + ".freq", modes, e_n, e_freq)
+    if force_freq:
+        g.pack_text("freq", use, lambda i: ".freq", [b"N"] * nf, d_n_in, d_freq_in)
+    g.pack_text("cod", [True] * nf, lambda i: stem(i) + ".cod", modes, e_n, d_tab)
+    errs = g.finish()
+    rsize, esize = _u64_host(d_rle_n), _u64_host(d_enc_n)
+    out = [{key: int(text.numel()) for key, text in files.items()} for files in g.packed()]
+    for i in range(nf):
+        lo, hi = g.first[i], g.first[i] + g.count[i]
+        if use[i]:
+            out[i][".rle"] = int(sum(rsize[lo:hi]))
+        out[i][stem(i) + ".shaf"] = shaf_file_bytes(esize[lo:hi])
+    return g.entries(errs, out)
 
 
 class _GroupBlocks:
-    """the blocks of a group of files, file after file: per block its size and start in d_in, per file its first block and
-    block count"""
+    """One group of files on its device batch (a context manager: leaving it closes the Batch).  The blocks of the files, file
+    after file: per block its size (`sizes`; on the device `d_n_in`) and its 16-aligned place (`src_in`, `off`), per file
+    (`files`: its index in the call) its first block and block count.  Beside them what every compress driver keeps per
+    group: the codes of the size pass (`errs0`), each file's RLE choice, the segmented packs' lengths, keys and buffers, and
+    the rule that turns per-block codes into each file's entry."""
 
-    def __init__(self, start, split, files):
-        self.sizes, self.first, self.count, self.src = [], [], [], []
+    def __init__(self, name, d_in, start, split, files, st):
+        import torch
+        self.name, self.st, self.dev, self.files, self.nf = name, st, d_in.device, list(files), len(files)
+        self.sizes, self.first, self.count, src = [], [], [], []
         for f in files:
             self.first.append(len(self.sizes))
             self.count.append(len(split[f]))
             o = start[f]
             for n in split[f]:
-                self.src.append(o)
+                src.append(o)
                 self.sizes.append(n)
                 o += n
         self.nb = len(self.sizes)
-        self._d_n = None
+        self.errs0 = [SUCCESS] * self.nb
+        self.lens, self.kinds = None, []                                    # per pack call: (its files, their keys, buffer, offsets)
+        self.d_n_in = torch.tensor(self.sizes, dtype=torch.int64, device=self.dev)
+        self.bt = Batch(self.nb, 2 * max(self.sizes) + 64)
+        self.src_in, self.off = _aligned_blocks(self.bt, st, d_in, src, self.sizes, self.d_n_in)
 
-    def d_n_in(self, dev):
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.bt.close()
+
+    def blocks(self, i):
+        return range(self.first[i], self.first[i] + self.count[i])
+
+    def finish(self):
+        """one synchronisation -> the per-block codes"""
+        return self.bt.finish(self.st, self.nb, raise_on_error=False)[1]
+
+    def rle_sizes(self):
+        """The size pass (rle_encoded_size_dev) over every block and its synchronisation, which reads the sizes back -> the RLE
+        sizes; its codes stay in errs0"""
         import torch
-        if self._d_n is None:
-            self._d_n = torch.tensor(self.sizes, dtype=torch.int64, device=dev)
-        return self._d_n
+        d_size = torch.zeros(self.nb, dtype=torch.int64, device=self.dev)
+        self.bt.rle_encoded_size_dev(self.st, self.src_in, self.off, self.sizes, self.d_n_in, d_size)
+        self.errs0 = self.finish()
+        return _u64_host(d_size)
 
-    def aligned(self, bt, st, d_in):
-        """the inputs at 16-byte aligned addresses: in place, or gathered by one unpack_payloads -> (tensor, offsets)"""
+    def use_rle(self, rsize):
+        """per file: the reference's decision on its block 0's RLE size (shafa_rle_worthwhile, f.c:250-258)"""
+        return [bool(host().shafa_rle_worthwhile(self.sizes[b], rsize[b], False)) for b in self.first]
+
+    def rle_first(self, use, rcap):
+        """Put the files that take RLE in front of the plain ones: the blocks of either kind become one range, so each stage
+        runs over its range only and a block's error word is the same in every call -> (use, rcap) in the new order"""
         import torch
-        if d_in.data_ptr() % 16 or any(o % 16 for o in self.src):
-            d_so = torch.tensor(self.src, dtype=torch.int64, device=d_in.device)
-            off, tot = _layout(self.sizes)
-            src_in = torch.empty(tot + 16, dtype=torch.uint8, device=d_in.device)
-            bt.unpack_payloads(st, d_in, d_so, self.d_n_in(d_in.device), src_in, off, self.sizes)
-            return src_in, off
-        return d_in, list(self.src)
+        order = [i for i in range(self.nf) if use[i]] + [i for i in range(self.nf) if not use[i]]
+        if order == list(range(self.nf)):
+            return use, rcap
+        perm = [b for i in order for b in self.blocks(i)]
+        self.files, self.count = [self.files[i] for i in order], [self.count[i] for i in order]
+        self.first = [0] + list(itertools.accumulate(self.count))[:-1]
+        self.sizes, self.off, self.errs0 = ([v[b] for b in perm] for v in (self.sizes, self.off, self.errs0))
+        self.d_n_in = torch.tensor(self.sizes, dtype=torch.int64, device=self.dev)
+        return [use[i] for i in order], [rcap[b] for b in perm]
 
+    def _regions(self, sel, keys, bound):
+        """For one pack, over the files i with sel[i] under the keys keys(i): a buffer with a 16-aligned region of bound(i)
+        bytes per file, and that pack's length words -> (files, buffer, offsets, capacities, lengths), or None without files"""
+        import torch
+        fs = [i for i in range(self.nf) if sel[i]]
+        if not fs:
+            return None
+        if self.lens is None:                                               # at most five packs: .rle, two .freq, .cod, .shaf
+            self.lens = torch.zeros(5 * self.nf, dtype=torch.int64, device=self.dev)
+        dcap = [bound(i) for i in fs]
+        doff, dtot = _layout(dcap)
+        buf = torch.empty(dtot + 16, dtype=torch.uint8, device=self.dev)
+        n = self.lens[len(self.kinds) * self.nf:(len(self.kinds) + 1) * self.nf]
+        self.kinds.append((fs, [keys(i) for i in fs], buf, doff))
+        return fs, buf, doff, dcap, n
 
-def _rle_encoded(bt, st, d_in, in_off, in_n, d_in_n):
-    """The size pass (rle_encoded_size_dev) over these input blocks and its synchronisation, which reads the sizes back
-    -> (RLE sizes, per-block codes)"""
-    import torch
-    d_size = torch.zeros(len(in_n), dtype=torch.int64, device=d_in_n.device)
-    bt.rle_encoded_size_dev(st, d_in, in_off, in_n, d_in_n, d_size)
-    _, errs = bt.finish(st, len(in_n), raise_on_error=False)
-    return _u64_host(d_size), errs
-
-
-def _compress_group(d_in, start, split, files, force_rle, force_freq, st, results):
-    import torch
-    dev = d_in.device
-    nf = len(files)
-    g = _GroupBlocks(start, split, files)
-    nb = g.nb
-    bt = Batch(nb, 2 * max(g.sizes) + 64)
-    try:
-        src_in, off = g.aligned(bt, st, d_in)
-        # ---- the choice per file: forced, or the reference's decision on its block 0's RLE size
-        errs0 = [SUCCESS] * nb
-        if force_rle:
-            use = [True] * nf
-            rcap = [2 * n + 3 for n in g.sizes]                             # f.c:244
+    # The packs: segmented, one call per kind of file.  A group of one file takes the single-file pack, which writes the same
+    # bytes with one launch and one upload fewer (compress_files pays its fixed cost per call).
+    def pack_payloads(self, sel, keys, framing, d_src, src_off, src_cap, d_src_n):
+        """the blocks' payloads as .rle (FRAME_RAW) or .shaf (FRAME_SHAF) files, each region sized by pack_payloads_max"""
+        r = self._regions(sel, keys, lambda i: pack_payloads_max([src_cap[b] for b in self.blocks(i)], framing))
+        if not r:
+            return
+        fs, buf, doff, dcap, n = r
+        if self.nf == 1:
+            self.bt.pack_payloads(self.st, framing, d_src, src_off, src_cap, d_src_n, buf, dcap[0], n)
         else:
-            rcap, errs0 = _rle_encoded(bt, st, src_in, off, g.sizes, g.d_n_in(dev))
-            use = [bool(host().shafa_rle_worthwhile(g.sizes[g.first[i]], rcap[g.first[i]], False)) for i in range(nf)]
-        # ---- the files that take RLE first, the plain ones behind them: the blocks of either kind are one range, so each
-        # stage runs over its range only and a block's error word is the same in every call
-        order = [i for i in range(nf) if use[i]] + [i for i in range(nf) if not use[i]]
-        perm = [b for i in order for b in range(g.first[i], g.first[i] + g.count[i])]
-        files = [files[i] for i in order]
-        use = [use[i] for i in order]
-        count = [g.count[i] for i in order]
-        first, pos = [], 0
-        for c in count:
-            first.append(pos)
-            pos += c
-        sizes, off, errs0 = [g.sizes[b] for b in perm], [off[b] for b in perm], [errs0[b] for b in perm]
-        rcap = [rcap[b] for b in perm]
-        nr = sum(c for u, c in zip(use, count) if u)                        # blocks [0, nr) take RLE, [nr, nb) are plain
-        d_n_in = torch.tensor(sizes, dtype=torch.int64, device=dev)
-        in_lo = 0 if force_freq else nr                                     # the input's histogram: blocks [in_lo, nb)
-        # tile histograms: the RLE outputs' then the inputs', in one arena
-        th_off, th_tot = _layout([tile_hist_bytes(c) for c in rcap[:nr]] + [tile_hist_bytes(n) for n in sizes[in_lo:]])
-        rtoff, itoff = th_off[:nr], [None] * in_lo + th_off[nr:]
-        d_th = torch.empty(th_tot + 16, dtype=torch.uint8, device=dev)
-        # ---- Module F: RLE over the blocks that take it, into exact regions (worst-case ones with force_rle); the input's
-        # histogram over the others
-        roff, rtot = _layout(rcap[:nr])
-        d_rle = torch.empty(rtot + 16, dtype=torch.uint8, device=dev)
-        e_n = d_n_in.clone()                                                # per block: RLE size | input size
-        e_freq = torch.zeros(nb * 256, dtype=torch.int64, device=dev)       # per block: RLE histogram | input histogram
-        if nr:
-            bt.rle_encode_tiles(st, src_in, off[:nr], sizes[:nr], d_rle, roff, rcap[:nr], e_n, e_freq, d_th, rtoff)
-        d_freq_in = e_freq
-        if in_lo < nb:
-            if in_lo < nr:                                                  # force_freq: the RLE files' inputs as well
-                d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
-                bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_th, itoff)
-                with torch.cuda.stream(st):
-                    e_freq[nr * 256:].copy_(d_freq_in[nr * 256:])
-            else:
-                bt.hist256_tiles(st, src_in, off[nr:], sizes[nr:], e_freq[nr * 256:], d_th, itoff[nr:])
-        # ---- Module T and Module C once over all blocks: each block's source and tile histograms by its file
-        lo = d_rle if d_rle.data_ptr() < src_in.data_ptr() else src_in      # one base for inputs and RLE outputs
-        a_in, a_rle = src_in.data_ptr() - lo.data_ptr(), d_rle.data_ptr() - lo.data_ptr()
-        e_off = [a_rle + o for o in roff] + [a_in + o for o in off[nr:]]
-        e_cap = rcap[:nr] + sizes[nr:]
-        e_toff = rtoff + itoff[nr:]
-        d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
-        bt.sf_build_codes(st, nb, e_freq, d_tab)
-        ocap = [c + c // 2 + 64 for c in e_cap]                             # compress_files' bound
-        ooff, otot = _layout(ocap)
-        d_enc = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
-        d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
-        bt.sf_encode_dev(st, lo, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, d_th, e_toff)
-        # ---- the files: one segmented pack per kind, each file's region sized by the single-file bound
-        lens = torch.zeros(5 * nf, dtype=torch.int64, device=dev)
-        kinds = []                                                          # per pack call: (its files, their keys, buffer, offsets)
+            self.bt.pack_payloads_files(self.st, [self.first[i] for i in fs], [self.count[i] for i in fs], framing, d_src,
+                                        src_off, src_cap, d_src_n, buf, doff, dcap, n)
 
-        def pack(call, sel, keys, caps, args):
-            fs = [i for i in range(nf) if sel[i]]
-            if not fs:
-                return
-            doff, dtot = _layout([caps(i) for i in fs])
-            buf = torch.empty(dtot + 16, dtype=torch.uint8, device=dev)
-            n = lens[len(kinds) * nf:(len(kinds) + 1) * nf]
-            call(st, [first[i] for i in fs], [count[i] for i in fs], *args(fs), buf, doff, [caps(i) for i in fs], n)
-            kinds.append((fs, [keys(i) for i in fs], buf, doff))
+    def pack_text(self, kind, sel, keys, modes, d_sizes, d_body):
+        """.cod (kind "cod", d_body: the code tables) or .freq (kind "freq", d_body: the histograms) files in the files' modes,
+        each region sized by pack_cod_max / pack_freq_max"""
+        bound = pack_cod_max if kind == "cod" else pack_freq_max
+        r = self._regions(sel, keys, lambda i: bound(self.count[i]))
+        if not r:
+            return
+        fs, buf, doff, dcap, n = r
+        if self.nf == 1:
+            getattr(self.bt, "pack_" + kind)(self.st, self.nb, modes[0], d_sizes, d_body, buf, dcap[0], n)
+        else:
+            getattr(self.bt, f"pack_{kind}_files")(self.st, [self.first[i] for i in fs], [self.count[i] for i in fs],
+                                                   [modes[i] for i in fs], d_sizes, d_body, buf, doff, dcap, n)
 
-        def blocks(i):
-            return range(first[i], first[i] + count[i])
-
-        modes = [b"R" if u else b"N" for u in use]
-        pack(bt.pack_payloads_files, use, lambda i: ".rle", lambda i: pack_payloads_max([rcap[b] for b in blocks(i)],
-                                                                                        FRAME_RAW),
-             lambda fs: (FRAME_RAW, d_rle, roff + [0] * (nb - nr), rcap, e_n))
-        pack(bt.pack_freq_files, [True] * nf, lambda i: ".rle.freq" if use[i] else ".freq", lambda i: pack_freq_max(count[i]),
-             lambda fs: ([modes[i] for i in fs], e_n, e_freq))
-        if force_freq:
-            pack(bt.pack_freq_files, use, lambda i: ".freq", lambda i: pack_freq_max(count[i]),
-                 lambda fs: ([b"N"] * len(fs), d_n_in, d_freq_in))
-        stem = lambda i: ".rle" if use[i] else ""                           # noqa: E731
-        pack(bt.pack_cod_files, [True] * nf, lambda i: stem(i) + ".cod", lambda i: pack_cod_max(count[i]),
-             lambda fs: ([modes[i] for i in fs], e_n, d_tab))
-        pack(bt.pack_payloads_files, [True] * nf, lambda i: stem(i) + ".shaf",
-             lambda i: pack_payloads_max([ocap[b] for b in blocks(i)], FRAME_SHAF),
-             lambda fs: (FRAME_SHAF, d_enc, ooff, ocap, d_enc_n))
-        _, errs = bt.finish(st, nb, raise_on_error=False)
-        got = lens.cpu().tolist()
-        out = [{} for _ in range(nf)]
-        for k, (fs, keys, buf, doff) in enumerate(kinds):
+    def packed(self):
+        """after the finish behind the packs, one read of all lengths -> per file {key: the file, a view of its pack's buffer}"""
+        got = self.lens.cpu().tolist()
+        out = [{} for _ in range(self.nf)]
+        for k, (fs, keys, buf, doff) in enumerate(self.kinds):
             for j, i in enumerate(fs):
-                n = got[k * nf + j]
-                out[i][keys[j]] = buf[doff[j]:doff[j] + n]
-        for i, f in enumerate(files):                                       # compress_files raises at its first finish
-            b, e = _first_error(errs0[first[i]:first[i] + count[i]])
+                out[i][keys[j]] = buf[doff[j]:doff[j] + got[k * self.nf + j]]
+        return out
+
+    def entries(self, errs, out):
+        """per file: a ShafaError for its first error in block order, the size pass's (errs0) in front of a later stage's
+        (errs), or out[i]"""
+        res = []
+        for i in range(self.nf):
+            lo, hi = self.first[i], self.first[i] + self.count[i]
+            b, e = _first_error(self.errs0[lo:hi])
             if not e:
-                b, e = _first_error(errs[first[i]:first[i] + count[i]])
-            results[f] = ShafaError(e, f"compress_many: block {b}") if e else out[i]
-    finally:
-        bt.close()
+                b, e = _first_error(errs[lo:hi])
+            res.append(ShafaError(e, f"{self.name}: block {b}") if e else out[i])
+        return res
+
+
+def _compress_group(g, force_rle, force_freq):
+    """compress_many's chain over one group -> its files' entries"""
+    import torch
+    bt, st, dev, nb, nf = g.bt, g.st, g.dev, g.nb, g.nf
+    # ---- the choice per file: forced, or the reference's decision on its block 0's RLE size, measured with every other
+    # block's (exact: the encoder fills these regions)
+    if force_rle:
+        use, rcap = [True] * nf, [2 * n + 3 for n in g.sizes]               # f.c:244
+    else:
+        rcap = g.rle_sizes()
+        use = g.use_rle(rcap)
+    use, rcap = g.rle_first(use, rcap)
+    src_in, off, sizes, d_n_in = g.src_in, g.off, g.sizes, g.d_n_in
+    nr = sum(c for u, c in zip(use, g.count) if u)                            # blocks [0, nr) take RLE, [nr, nb) are plain
+    in_lo = 0 if force_freq else nr                                         # the input's histogram: blocks [in_lo, nb)
+    # tile histograms: the RLE outputs' then the inputs', in one arena
+    th_off, th_tot = _layout([tile_hist_bytes(c) for c in rcap[:nr]] + [tile_hist_bytes(n) for n in sizes[in_lo:]])
+    rtoff, itoff = th_off[:nr], [None] * in_lo + th_off[nr:]
+    d_th = torch.empty(th_tot + 16, dtype=torch.uint8, device=dev)
+    # ---- Module F: RLE over the blocks that take it, into exact regions (worst-case ones with force_rle); the input's
+    # histogram over the others
+    roff, rtot = _layout(rcap[:nr])
+    d_rle = torch.empty(rtot + 16, dtype=torch.uint8, device=dev)
+    e_n = d_n_in.clone() if nr else d_n_in                                  # per block: RLE size | input size
+    e_freq = torch.zeros(nb * 256, dtype=torch.int64, device=dev)           # per block: RLE histogram | input histogram
+    if nr:
+        bt.rle_encode_tiles(st, src_in, off[:nr], sizes[:nr], d_rle, roff, rcap[:nr], e_n, e_freq, d_th, rtoff)
+    d_freq_in = e_freq
+    if in_lo < nb:
+        if in_lo < nr:                                                      # force_freq: the RLE files' inputs as well
+            d_freq_in = torch.zeros(nb * 256, dtype=torch.int64, device=dev)
+            bt.hist256_tiles(st, src_in, off, sizes, d_freq_in, d_th, itoff)
+            with torch.cuda.stream(st):
+                e_freq[nr * 256:].copy_(d_freq_in[nr * 256:])
+        else:
+            bt.hist256_tiles(st, src_in, off[nr:], sizes[nr:], e_freq[nr * 256:], d_th, itoff[nr:])
+    # ---- Module T and Module C once over all blocks: each block's source and tile histograms by its file
+    lo = d_rle if d_rle.data_ptr() < src_in.data_ptr() else src_in          # one base for inputs and RLE outputs
+    a_in, a_rle = src_in.data_ptr() - lo.data_ptr(), d_rle.data_ptr() - lo.data_ptr()
+    e_off = [a_rle + o for o in roff] + [a_in + o for o in off[nr:]]
+    e_cap = rcap[:nr] + sizes[nr:]
+    e_toff = rtoff + itoff[nr:]
+    d_tab = torch.empty(nb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+    bt.sf_build_codes(st, nb, e_freq, d_tab)
+    # Fano codes average under H + 1 <= 9 bits a symbol: 12 bits leave room (a block that does not fit is an error)
+    ocap = [c + c // 2 + 64 for c in e_cap]
+    ooff, otot = _layout(ocap)
+    d_enc = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+    d_enc_n = torch.zeros(nb, dtype=torch.int64, device=dev)
+    bt.sf_encode_dev(st, lo, e_off, e_cap, e_n, d_tab, d_enc, ooff, ocap, d_enc_n, d_th, e_toff)
+    # ---- the files: one pack per kind
+    modes = [b"R" if u else b"N" for u in use]
+    stem = lambda i: ".rle" if use[i] else ""                               # noqa: E731
+    g.pack_payloads(use, lambda i: ".rle", FRAME_RAW, d_rle, roff + [0] * (nb - nr), rcap, e_n)
+    g.pack_text("freq", [True] * nf, lambda i: stem(i) + ".freq", modes, e_n, e_freq)
+    if force_freq:
+        g.pack_text("freq", use, lambda i: ".freq", [b"N"] * nf, d_n_in, d_freq_in)
+    g.pack_text("cod", [True] * nf, lambda i: stem(i) + ".cod", modes, e_n, d_tab)
+    g.pack_payloads([True] * nf, lambda i: stem(i) + ".shaf", FRAME_SHAF, d_enc, ooff, ocap, d_enc_n)
+    errs = g.finish()
+    return g.entries(errs, g.packed())
 
 
 # ------------------------------------------------------------------ files in device memory -> the decoded bytes
@@ -1506,9 +1431,8 @@ class _Parse:
 
 def _open_files(shaf, cod, rle, freq, stream, what):
     """the argument checks, the stream and the batch of a single-file-set call -> (sf, files, stream, slots, batch)"""
-    import torch
     sf, files = _decode_args(shaf, cod, rle, freq, what)
-    st = stream if stream is not None else torch.cuda.Stream(device=files[0].device)
+    st = _stream(files[0].device, stream)
     mb = unpack_max_blocks(files[1].numel(), "cod" if sf else "freq")
     if mb > 0x7FFFFFFF:
         raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
@@ -1659,8 +1583,7 @@ def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, 
     sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
         dev = files[0].device
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
         if p.fb == 0:
             return torch.empty(0, dtype=torch.uint8, device=dev)
@@ -1717,8 +1640,7 @@ def decompress_range(offset, length, shaf=None, cod=None, rle=None, freq=None, s
     sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
         dev = files[0].device
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
         out, lo, hi = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
         if p.fb:
@@ -1779,8 +1701,7 @@ def verify_files(d_in, shaf=None, cod=None, rle=None, freq=None, decode_rle=True
             raise ValueError(f"{what}: d_in is a contiguous uint8 CUDA tensor on the files' device")
         d_in = d_in.reshape(-1)
         ref_len = d_in.numel()
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
         sizes, first = [], []
         if p.fb and sf and not (p.mode == "R" and decode_rle):
@@ -1882,7 +1803,7 @@ def crc32(d_in, sizes=None, stream=None, _piece=None):
     out = [0] * len(segs)
     if off:
         dev = d_in.device
-        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        st = _stream(dev, stream)
         bt = Batch(max(len(off), len(segs)), piece)
         try:
             d_n = torch.tensor(cap, dtype=torch.int64).to(dev)
@@ -1921,8 +1842,7 @@ def checksum_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, st
     sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
         dev = files[0].device
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
         if p.fb == 0:
             return Checksum(0, 0)
@@ -2017,7 +1937,7 @@ def find(d_in, pattern, sizes=None, max_hits=65536, stream=None, _piece=None):
     counts, kept, hoff, h = [0] * len(segs), [0] * len(segs), [0] * len(segs), np.empty(0, dtype=np.int64)
     if off:
         dev = d_in.device
-        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        st = _stream(dev, stream)
         bt = Batch(len(off), piece)
         try:
             d_n = torch.tensor(cap, dtype=torch.int64).to(dev)
@@ -2073,8 +1993,7 @@ def find_files(pattern, shaf=None, cod=None, rle=None, freq=None, decode_rle=Tru
     sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
         dev = files[0].device
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
         if p.fb == 0:
             return Found(0, np.empty(0, dtype=np.int64), 0)
@@ -2217,8 +2136,7 @@ def build_index(shaf=None, cod=None, rle=None, freq=None, span=1024, stream=None
     sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
     try:
         dev = files[0].device
-        if max_bytes is None:
-            max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+        max_bytes = _max_bytes(dev, max_bytes)
         p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
         mode = p.mode if sf else "rle"
         is_rle = mode != "N"
@@ -2320,7 +2238,7 @@ def read_ranges(index, ranges, shaf=None, cod=None, rle=None, freq=None, stream=
     out = torch.empty(offsets[-1], dtype=torch.uint8, device=dev)
     items, other = _seek_items(index, spans)
     if items:
-        st = stream if stream is not None else torch.cuda.Stream(device=dev)
+        st = _stream(dev, stream)
         mb = unpack_max_blocks(files[1].numel(), "cod") if sf else 1
         bt = Batch(max(mb, len(index.blocks), len(items)), 1 << 20)
         try:
@@ -2387,16 +2305,14 @@ def decompress_many(entries, stream=None, max_bytes=None):
     blocks on the grid's y): a group with more repeats the chain after synchronisation 1.  Per file the error is decompress_files':
     a bad header, the mode rule, a parse fault on block 0, SF errors before the first parse fault, RLE errors there, then the
     parse fault."""
-    import torch
     if not isinstance(entries, (list, tuple)) or not entries:
         raise ValueError("decompress_many: no entries")
     parsed = [_many_entry(e) for e in entries]
     dev = parsed[0][1][0].device
     if any(t.device != dev for _, fs, _ in parsed for t in fs):
         raise ValueError("decompress_many: files on more than one device")
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
-    if max_bytes is None:
-        max_bytes = torch.cuda.mem_get_info(dev)[0] // 4
+    st = _stream(dev, stream)
+    max_bytes = _max_bytes(dev, max_bytes)
     results = [None] * len(parsed)
     slots = {}
     for i, (sf, fs, _) in enumerate(parsed):
@@ -2679,7 +2595,7 @@ def build_cod(freq, stream=None):
     what = "build_cod"
     f, = _file_tensors(what, freq=freq)
     dev = f.device
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    st = _stream(dev, stream)
     mb = unpack_max_blocks(f.numel(), "counts")
     if mb > 0x7FFFFFFF:
         raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
@@ -2734,12 +2650,11 @@ def encode_files(d_in, cod, stream=None):
     FILE_STREAM_FAILED, also over a table error of the same block; a text that fails shafa_cod_parse, or a data symbol
     without a code, is FILE_UNRECOGNIZABLE.  A header count of 0 gives "@0".  More than GRID_BLOCKS blocks in one file are
     LACK_OF_MEMORY (one launch takes the file's blocks)."""
-    import itertools
     import torch
     what = "encode_files"
     src, text = _file_tensors(what, d_in=d_in, cod=cod)
     dev = src.device
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    st = _stream(dev, stream)
     mb = unpack_max_blocks(text.numel(), "cod")
     if mb > 0x7FFFFFFF:
         raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
@@ -2774,15 +2689,7 @@ def encode_files(d_in, cod, stream=None):
         if fb == 0:
             raise ShafaError(perr, f"{what}: block 0")
         sizes = sizes[:fb]
-        start = [0] + list(itertools.accumulate(sizes))[:-1]
-        if src.data_ptr() % 16 or any(o % 16 for o in start):
-            off, pos = _layout(sizes)
-            buf = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-            d_start = torch.tensor(start, dtype=torch.int64, device=dev)
-            bt.unpack_payloads(st, src, d_start, d_n[:fb], buf, off, sizes)
-            src = buf
-        else:
-            off = start
+        src, off = _aligned_blocks(bt, st, src, [0] + list(itertools.accumulate(sizes))[:-1], sizes, d_n[:fb])
         d_freq = torch.zeros(fb * 256, dtype=torch.int64, device=dev)
         toff, pos = _layout([tile_hist_bytes(n) for n in sizes])
         d_th = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
@@ -2884,7 +2791,7 @@ def _plane_tensors(what, ts):
 def _plane_stream(dev, stream):
     """the stream a driver works on, ordered behind the caller's current one (which produced the arguments)"""
     import torch
-    st = stream if stream is not None else torch.cuda.Stream(device=dev)
+    st = _stream(dev, stream)
     st.wait_stream(torch.cuda.current_stream(dev))
     return st
 

@@ -3,7 +3,11 @@ csrc/pack.hip) and shafa.compress_many, which chains F -> T -> C -> those packs 
 
 1. compress_many reproduces every golden session whose first command runs Module F, one call per block size and -c flag;
 2. on a mixed corpus (edge sizes, RLE and plain content, a file under 1 KiB, files at odd offsets) every file equals
-   compress_files on that file alone, under each flag setting, and decodes back to its input;
+   compress_files on that file alone, under each flag setting, and decodes back to its input; both run one chain, so
+   every file the reference binary writes for that file alone is compared with compress_files' as well;
+2a. compress_files on a tensor at an odd address (the gather into aligned regions) equals the aligned copy's files, and a
+   block size that is no multiple of 16 round-trips at either alignment; a block's error raises the code compress_many's
+   entry carries, the size pass's first, then the first in block order;
 3. its files decode with our CLI and with the reference binary;
 4. each file of a segmented pack equals the host's framing / formatter of its blocks (random partitions, overlaps, gaps,
    per-file modes, 0-byte payloads, all-empty tables);
@@ -12,6 +16,7 @@ csrc/pack.hip) and shafa.compress_many, which chains F -> T -> C -> those packs 
 7. one pack over more than 65 536 blocks (the bulk grid in slices) is exact."""
 import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -115,26 +120,141 @@ def _same_files(got, want, what):
         assert got[k].cpu().numpy().tobytes() == want[k].cpu().numpy().tobytes(), (what, k)
 
 
+def _spelled(flag, value):
+    """[flag, value] as a golden session's command line spells it"""
+    for case in F_CASES:
+        argv = _manifest(case)["cmds"][0]["argv"]
+        if _opt(argv, flag) == value:
+            return argv[argv.index(flag):argv.index(flag) + 2]
+    raise AssertionError(f"no golden session runs {flag} {value}")
+
+
+def _reference_files(work, data, args):
+    """the files the reference binary writes for `data` as the file "f" in `work`, run with `args`: {".rle": bytes, ...}"""
+    import oracle_lib
+    for name in os.listdir(work):
+        os.remove(os.path.join(work, name))
+    data.tofile(os.path.join(work, "f"))
+    r = subprocess.run([oracle_lib.REF_BIN, "f"] + args, cwd=work, capture_output=True, timeout=300)
+    assert r.returncode == 0, (args, r.returncode, r.stderr[-2000:])
+    out = {}
+    for name in sorted(os.listdir(work)):
+        if name != "f":
+            assert name.startswith("f."), name
+            with open(os.path.join(work, name), "rb") as f:
+                out[name[1:]] = f.read()
+    return out
+
+
 @pytest.mark.parametrize("flags", [(False, False), (True, False), (False, True)], ids=["default", "c_r", "c_f"])
-def test_compress_many_equals_compress_files_per_file(shafa, flags):
+def test_compress_many_equals_compress_files_per_file(shafa, flags, tmp_path):
+    import oracle_lib
     import torch
     force_rle, force_freq = flags
     sizes, datas = _corpus()
     d_in = _packed_at_odd_offsets(datas)
     res = shafa.compress_many(d_in, sizes, K, force_rle=force_rle, force_freq=force_freq)
     assert len(res) == len(sizes)
-    modes = set()
+    modes, wants = set(), {}
     for i, (n, data) in enumerate(zip(sizes, datas)):
         one = torch.from_numpy(data).to(_dev())
         if n < 1024:
             assert isinstance(res[i], shafa.ShafaError) and res[i].code == shafa.FILE_TOO_SMALL, res[i]
             continue
-        want = shafa.compress_files(one, K, force_rle=force_rle, force_freq=force_freq)
+        want = wants[i] = shafa.compress_files(one, K, force_rle=force_rle, force_freq=force_freq)
         assert isinstance(res[i], dict), (i, res[i])
         _same_files(res[i], want, f"file {i} ({n} bytes)")
         modes.add(".rle.cod" in want)
     if not force_rle:
         assert modes == {True, False}, "the corpus should hold RLE and plain files"
+    # the two drivers run one chain: the anchor outside it is the reference binary on each file alone
+    if not os.path.exists(oracle_lib.REF_BIN):
+        pytest.skip("reference binary not built (oracle/_ref/shafa)")
+    args = _spelled("-b", "K") + (_spelled("-c", "r") if force_rle else _spelled("-c", "f") if force_freq else [])
+    assert len(wants) == 9
+    for i, want in wants.items():
+        ref = _reference_files(str(tmp_path), datas[i], args)
+        assert sorted(ref) == sorted(want), (i, sorted(ref), sorted(want))
+        for k in ref:
+            assert want[k].cpu().numpy().tobytes() == ref[k], f"file {i} ({sizes[i]} bytes): {k} differs from the reference's"
+
+
+# ---------------------------------------------------------------- compress_files: alignment, block sizes, errors
+@pytest.mark.parametrize("i", [6, 5], ids=["runs_3K+17", "uniform_K+1023"])
+def test_compress_files_at_an_odd_address_equals_the_aligned_copy(shafa, i):
+    import torch
+    sizes, datas = _corpus()
+    assert sizes[i] == (3 * K + 17, K + 1023)[i == 5]
+    aligned = torch.from_numpy(datas[i]).to(_dev())
+    odd = _packed_at_odd_offsets([datas[i]])
+    assert aligned.data_ptr() % 16 == 0 and odd.data_ptr() % 16 == 3 and torch.equal(odd, aligned)
+    want = shafa.compress_files(aligned, K)
+    assert (".rle.shaf" in want) == (i == 6), sorted(want)
+    _same_files(shafa.compress_files(odd, K), want, f"file {i} at an odd address")
+
+
+def test_compress_files_block_size_no_multiple_of_16_round_trips(shafa):
+    import torch
+    import golden.make_golden as mg
+    n, bs = 200_000, 65537
+    data = np.ascontiguousarray(mg.zipf_table(1.2)[mg.gen_bytes(77, 2 * n).view(np.uint16)[:n]], dtype=np.uint8)
+    aligned = torch.from_numpy(data).to(_dev())
+    odd = _packed_at_odd_offsets([data])
+    assert aligned.data_ptr() % 16 == 0 and odd.data_ptr() % 16 == 3
+    got = []
+    for what, d_in in (("aligned", aligned), ("odd", odd)):
+        files = shafa.compress_files(d_in, bs)
+        if ".rle.shaf" in files:
+            back = shafa.decompress_files(shaf=files[".rle.shaf"], cod=files[".rle.cod"])
+        else:
+            back = shafa.decompress_files(shaf=files[".shaf"], cod=files[".cod"], decode_rle=False)
+        assert back.cpu().numpy().tobytes() == data.tobytes(), what
+        stem = ".rle" if ".rle.shaf" in files else ""
+        assert files[stem + ".shaf"].cpu().numpy().tobytes().startswith(b"@4@"), what      # 3 x 65 537 bytes and 3 389
+        got.append(files)
+    _same_files(got[1], got[0], "odd against aligned")
+
+
+ERROR_CASES = {       # {finish call: {block: the code it reports}} -> the file's code
+    "size_pass": ({1: {1: 2}}, 2),
+    "packs": ({2: {1: 5}}, 5),
+    "size_pass_before_packs": ({1: {2: 1}, 2: {0: 2}}, 1),
+    "first_in_block_order": ({2: {2: 2, 1: 4}}, 4),
+}
+
+
+@pytest.mark.parametrize("name", list(ERROR_CASES))
+def test_compress_files_raises_the_code_compress_many_carries(shafa, monkeypatch, name):
+    """No input reaches a block error in the compress chain by itself (the size pass and the packs cannot fail on sizes the
+    driver computed, and the encoder's region holds 12 bits a symbol), so Batch.finish reports chosen codes for chosen
+    blocks of a three-block file."""
+    import torch
+    import golden.make_golden as mg
+    inject, code = ERROR_CASES[name]
+    assert (shafa.OUTSIDE_MODULE, shafa.LACK_OF_MEMORY, shafa.FILE_UNRECOGNIZABLE, shafa.FILE_STREAM_FAILED) == (1, 2, 4, 5)
+    d_in = torch.from_numpy(mg.runs_stream(41, 65536 * 2 + 7777, mg.zipf_table(1.2))).to(_dev())
+    real = shafa.Batch.finish
+    calls = []
+
+    def finish(self, stream, nblocks, raise_on_error=True):
+        rc, errs = real(self, stream, nblocks, raise_on_error=False)
+        calls.append(nblocks)
+        assert rc == 0 and nblocks == 3
+        for b, e in inject.get(len(calls), {}).items():
+            errs[b] = e
+        rc = next((e for e in errs if e), 0)
+        if raise_on_error and rc:
+            raise shafa.ShafaError(rc, "finish")
+        return rc, errs
+
+    monkeypatch.setattr(shafa.Batch, "finish", finish)
+    many = shafa.compress_many(d_in, [d_in.numel()], 65536)[0]
+    assert len(calls) == 2
+    assert isinstance(many, shafa.ShafaError) and many.code == code, many
+    calls.clear()
+    with pytest.raises(shafa.ShafaError) as e:
+        shafa.compress_files(d_in, 65536)
+    assert e.value.code == many.code
 
 
 def test_compress_many_takes_a_list_and_round_trips(shafa):

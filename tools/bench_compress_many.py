@@ -11,7 +11,10 @@ Workloads (inputs generated on the device, files back to back in one tensor):
   M128:         one 8 GiB Zipf(1.2) file at -b M (128 x 64 MiB blocks)
 Run-heavy: Zipf(1.2) symbols repeated 1..12 times (RLE is worthwhile).  Per workload: ms per call of both forms (median
 [min - max] over the repetitions), the loop's ms per file, the ratio loop / many, and whether every file of compress_many
-equals compress_files' byte for byte.  Prints one JSON document.
+equals compress_files' byte for byte.  compress_files is compress_many's chain on one file, so that column compares one
+file alone (a batch of one, which takes the single-file packs) against the same file among many (the grouping, the
+RLE-first order and the segmented packs), not two implementations of the chain; the reference's files anchor both (tests/test_gpu_pack.py, tests/test_gpu_pack_files.py).  Prints one JSON
+document.
 """
 import argparse
 import json
