@@ -547,6 +547,50 @@ int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblo
                                      const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                      const uint64_t *h_out_off);
 
+/* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
+ * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
+ * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block
+ * b is d_n[b] (<= h_cap[b], device resident) RECORDS of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes.
+ *   record side    the block's width * d_n[b] bytes at d_in (d_out) + h_in_off[b] (h_out_off[b]); the offsets are 64-bit and
+ *                  need NO alignment: records are transposed where they lie.
+ *   column side    column j of block b = byte j of every record: d_n[b] bytes at d_planes + h_plane_off[b * width + j].
+ *                  d_planes and every column offset are multiples of 16 (the caller allocates this side).
+ * shafa_hipd_split_records_dev reads the record side and writes the columns; shafa_hipd_merge_records_dev is its inverse.  At
+ * width 1, 2, 4, 8 the result is byte for byte the plain plane entries' with elem = width.
+ * What is read.  split reads the record side in aligned 16-byte words that each hold at least one byte of the region; no other
+ * byte is touched, nothing is copied, and bytes outside the region never influence the result.  merge reads a column in aligned
+ * 16-byte words that each hold at least one of its d_n[b] bytes.
+ * What is written.  split writes the d_n[b] bytes of each column and nothing behind them (whole 16-byte words, single bytes
+ * in the last one).  merge writes the width * d_n[b] bytes of the region and nothing else: aligned 16-byte words that lie
+ * wholly inside the bytes of one pass (below), single bytes where an unaligned region puts a word across the border of two
+ * passes or across an end of the region; the up to 15 bytes on either side of an unaligned region are untouched.
+ * Per-block codes through shafa_hipd_finish:
+ *   d_n[b] > h_cap[b]                      SHAFA_OUTSIDE_MODULE; no byte of the block is read or written, other blocks are
+ *                                          unaffected.
+ * One launch for all blocks, in which no workgroup waits for another: tiles of SHAFA_RECORDS_TILE records, numbered from the
+ * capacities; a workgroup takes its tile through LDS in passes of SHAFA_RECORDS_PASS(width) records (at most 32 KiB), both
+ * directions moving the record side in coalesced aligned words and a column in words of 16 records; a tile at or behind d_n[b]
+ * exits.  The only atomic is the error word above.  The device workspace is (20 + 8 width) bytes per block plus 20.  Enqueues
+ * only: d_n is never read on the host, no device-to-host copy is issued and nothing is synchronised; the one exception is the
+ * batch's growth, from nblocks.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), in the plain entries' order:
+ * NULL b (first), d_in / d_out, d_planes or d_n, a width outside 1 .. SHAFA_RECORDS_MAX_WIDTH: SHAFA_OUTSIDE_MODULE; then
+ * nblocks <= 0: success (the host arrays may be NULL); nblocks > the batch's max_blocks: SHAFA_LACK_OF_MEMORY; NULL h_cap:
+ * SHAFA_OUTSIDE_MODULE; a width * h_cap[b] or their sum past 64 bits, or 2^31 tiles of SHAFA_RECORDS_TILE records or more in
+ * the capacities: SHAFA_LACK_OF_MEMORY; NULL h_in_off / h_out_off or h_plane_off, a d_planes or an h_plane_off[b * width + j]
+ * that is no multiple of 16: SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_RECORDS_MAX_WIDTH 64
+#define SHAFA_RECORDS_TILE 8192 /* records; = SHAFA_PLANES_TILE */
+/* the records a workgroup takes through LDS at a time: the largest power of two with PASS * width <= 32768, 8192 at the most;
+ * a multiple of 16 that divides the tile */
+#define SHAFA_RECORDS_PASS(width) ((width) <= 4 ? 8192 : (width) <= 8 ? 4096 : (width) <= 16 ? 2048 : (width) <= 32 ? 1024 : 512)
+int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,
+                                 const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                 const uint64_t *h_plane_off);
+int shafa_hipd_merge_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_planes,
+                                 const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
+                                 const uint64_t *h_out_off);
+
 /* ---- Seek index: byte ranges of a file set without decoding whole blocks -------------------------------------------------
  * A .shaf has no sync markers and an RLE triple may straddle any boundary, so a decoder can only start where it is told the
  * bit offset, the RLE state and the decoded offset.  A seek index tells it: one CHECKPOINT every `span` symbols of every

@@ -128,6 +128,8 @@ def lib():
                                       vp, vp, vp]
     L.shafa_hipd_split_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_split_records_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_records_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
@@ -193,7 +195,8 @@ def lib():
                  "shafa_hipd_crc32_combine_dev", "shafa_hipd_seek_index_dev", "shafa_hipd_read_spans_dev",
                  "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev",
                  "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev",
-                 "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev"):
+                 "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev",
+                 "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -543,6 +546,25 @@ class Batch:
         _check(lib().shafa_hipd_merge_planes_xor_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po),
                                                      _addr(d_base), _p64(bo), _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)),
                "hipd_merge_planes_xor_dev")
+
+    def split_records_dev(self, stream, width, d_in, in_off, cap, d_n, d_planes, plane_off):
+        """Block b's d_n[b] (int64, device; <= cap[b]) RECORDS of `width` = 1 .. RECORDS_MAX_WIDTH bytes at d_in + in_off[b]
+        (bytes, any alignment, read in place) -> their byte columns: column j (byte j of every record) is d_n[b] bytes at
+        d_planes + plane_off[b * width + j].  d_planes and every column offset are multiples of 16; nothing behind a column's
+        d_n[b] bytes is written.  At width 1, 2, 4, 8 the bytes are split_planes_dev's.  d_in and d_planes are tensors or device
+        addresses (int).  Enqueues only (include/shafa_hip.h: "Byte columns of fixed-width records")."""
+        io, ic, po = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off)
+        _check(lib().shafa_hipd_split_records_dev(self.h, self._st(stream), len(io), width, _addr(d_in), _p64(io), _p64(ic),
+                                                  d_n.data_ptr(), _addr(d_planes), _p64(po)), "hipd_split_records_dev")
+
+    def merge_records_dev(self, stream, width, d_planes, plane_off, cap, d_n, d_out, out_off):
+        """split_records_dev's inverse: block b's columns (d_n[b] bytes each at d_planes + plane_off[b * width + j], multiples
+        of 16) -> its width * d_n[b] bytes at d_out + out_off[b] (any alignment); no other byte of d_out is written, the up to
+        15 bytes on either side of an unaligned region included.  d_planes and d_out are tensors or device addresses (int).
+        Enqueues only (include/shafa_hip.h: "Byte columns of fixed-width records")."""
+        po, ic, oo = _u64arr(plane_off), _u64arr(cap), _u64arr(out_off)
+        _check(lib().shafa_hipd_merge_records_dev(self.h, self._st(stream), len(oo), width, _addr(d_planes), _p64(po), _p64(ic),
+                                                  d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_records_dev")
 
     def seek_index_dev(self, stream, d_in, in_off, in_cap, d_in_n, d_tables, span, flags, ckpt_first, d_ckpt, d_status, d_out_n):
         """The checkpoints, every `span` symbols, of blocks of SF-decoded bytes: block b's d_in_n[b] (int64, device; <=
@@ -2721,6 +2743,8 @@ def encode_files(d_in, cod, stream=None):
 PLANES_TILE = 8192              # SHAFA_PLANES_TILE: the elements of one tile of split_planes_dev / merge_planes_dev
 PLANES_ELEM = (1, 2, 4, 8)      # the element sizes they take
 PLANES_NO_BASE = (1 << 64) - 1  # SHAFA_PLANES_NO_BASE: the base offset of a block without a base (the _xor_dev entries)
+RECORDS_MAX_WIDTH = 64          # SHAFA_RECORDS_MAX_WIDTH: split_records_dev / merge_records_dev take records of 1 .. 64 bytes
+RECORDS_TILE = 8192             # SHAFA_RECORDS_TILE: the records of one tile of theirs
 
 
 class CompressedTensor:
@@ -3229,3 +3253,8 @@ def decompress_sequences(items, stream=None):
     if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedSequence) for it in items):
         raise ValueError("decompress_sequences: a CompressedSequence or a list of them (compress_sequences' items)")
     return _merge_items("decompress_sequences", items, None, False, stream, diff=True)
+
+
+# ------------------------------------------------------------------ fixed-width records, one file set per byte column
+from .records import (CompressedRecords, compress_records, decompress_records, merge_records, records_pass,  # noqa: E402,F401
+                      split_records)

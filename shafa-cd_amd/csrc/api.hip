@@ -621,6 +621,46 @@ int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblo
                       h_plane_off);
 }
 
+// the checks of the record transposes (include/shafa_hip.h): the plain plane entries', in their order, with a width of
+// 1 .. SHAFA_RECORDS_MAX_WIDTH in place of the element size; d_rec is the record side
+static int records_dev(bool merge, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_rec,
+                       const uint64_t *h_off, const uint64_t *h_cap, const uint64_t *d_n, const uint8_t *d_planes,
+                       const uint64_t *h_plane_off)
+{
+    if (!b || !d_rec || !d_planes || !d_n) return SHAFA_OUTSIDE_MODULE;
+    if (width < 1 || width > SHAFA_RECORDS_MAX_WIDTH) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_cap) return SHAFA_OUTSIDE_MODULE;
+    u64 ntiles = 0, bytes = 0;                       // tiles of SHAFA_RECORDS_TILE records (records.hip numbers them in 31 bits)
+    for (int i = 0; i < nblocks; ++i) {
+        if (h_cap[i] > ~0ull / width || bytes + h_cap[i] * width < bytes) return SHAFA_LACK_OF_MEMORY;
+        bytes += h_cap[i] * width;
+        if ((ntiles += h_cap[i] / SHAFA_RECORDS_TILE + (h_cap[i] % SHAFA_RECORDS_TILE != 0)) > 0x7FFFFFFFull)
+            return SHAFA_LACK_OF_MEMORY;
+    }
+    if (!h_off || !h_plane_off || ((uintptr_t)d_planes & 15)) return SHAFA_OUTSIDE_MODULE;
+    for (size_t i = 0; i < (size_t)nblocks * width; ++i)
+        if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, width, merge, (u8 *)d_rec, h_off, h_cap, d_n, (u8 *)d_planes,
+                              h_plane_off);
+}
+
+int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,
+                                 const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                 const uint64_t *h_plane_off)
+{
+    return records_dev(false, b, stream, nblocks, width, d_in, h_in_off, h_cap, d_n, d_planes, h_plane_off);
+}
+
+int shafa_hipd_merge_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_planes,
+                                 const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
+                                 const uint64_t *h_out_off)
+{
+    return records_dev(true, b, stream, nblocks, width, d_out, h_out_off, h_cap, d_n, d_planes, h_plane_off);
+}
+
 // span: a power of two, 256 .. 8192; flags: SHAFA_SEEK_SF / SHAFA_SEEK_RLE only
 static bool seek_shape_ok(uint32_t span, int flags)
 {

@@ -237,6 +237,11 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
 // is one launch, merge three (tile sums, the blocks' scans, the merge) with 8 bytes of workspace more per tile of the capacities
 int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off);
+// block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
+// byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
+// (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31
+int records_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 width, bool merge, u8 *d_rec, const u64 *h_off, const u64 *h_cap,
+                       const u64 *d_n, u8 *d_planes, const u64 *h_plane_off);
 // the checkpoints of blocks of SF-decoded bytes, every `span` symbols (seek.hip); the capacities' spans number fewer than 2^31
 int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                           const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,

@@ -13,7 +13,8 @@ constexpr int REPS = 2048;
 
 enum Mode {
     RD32_4K, RD32_1K, RD32_256B, RDU8_1K, RDU8_256B, BPERM, RD32_ROWS, RD2_ROWS, RD64_ROWS2, RD64_8K, RD64_4K,
-    OR_ALL, OR_THIRD, WR_ALL, WR_THIRD, OR_LINEAR, WR_LINEAR, RD32_LINEAR, RD32_4K_HALF, RD32_4K_QUARTER, N_MODES
+    OR_ALL, OR_THIRD, WR_ALL, WR_THIRD, OR_LINEAR, WR_LINEAR, RD32_LINEAR, RD32_4K_HALF, RD32_4K_QUARTER,
+    RDU8_REC, RDU8_REC_NOPAD, WR8_REC, WR8_REC_NOPAD, WR8_LINEAR, N_MODES
 };
 
 template <int MODE>
@@ -42,6 +43,10 @@ __global__ __launch_bounds__(256) void k_tp(u32 *out, const u32 *rnd, u32 seed)
         case RD64_4K: ad[j] = sb + ((rv >> 3) % 512u) * 8; break;
         case OR_ALL: case OR_THIRD: case WR_ALL: case WR_THIRD: ad[j] = sb + ((tid * 39 + prog) & ~3u); break;
         case OR_LINEAR: case WR_LINEAR: case RD32_LINEAR: ad[j] = sb + (tid + 256 * j) * 4; break;
+        // records.hip's column walk at width 8: lane l's bytes are 8 apart, its neighbour's 16 * 8 (+ 4 of padding) further on
+        case RDU8_REC: case WR8_REC: ad[j] = sb + tid * 132 + j * 8; break;
+        case RDU8_REC_NOPAD: case WR8_REC_NOPAD: ad[j] = sb + tid * 128 + j * 8; break;
+        case WR8_LINEAR: ad[j] = sb + tid + 256 * j; break;
         }
         bool a = true;
         if (MODE == OR_THIRD || MODE == WR_THIRD) a = (rv >> 20) % 10u < 3u;
@@ -57,7 +62,7 @@ __global__ __launch_bounds__(256) void k_tp(u32 *out, const u32 *rnd, u32 seed)
                 switch (MODE) {
                 case RD32_4K: case RD32_1K: case RD32_256B: case RD32_ROWS: case RD32_LINEAR: case RD32_4K_HALF: case RD32_4K_QUARTER:
                     { u32 v; asm volatile("ds_read_b32 %0, %1" : "=v"(v) : "v"(ad[j])); asm volatile("" :: "v"(v)); } break;
-                case RDU8_1K: case RDU8_256B:
+                case RDU8_1K: case RDU8_256B: case RDU8_REC: case RDU8_REC_NOPAD:
                     { u32 v; asm volatile("ds_read_u8 %0, %1" : "=v"(v) : "v"(ad[j])); asm volatile("" :: "v"(v)); } break;
                 case BPERM:
                     { u32 v; asm volatile("ds_bpermute_b32 %0, %1, %2" : "=v"(v) : "v"(ad[j]), "v"(seed)); asm volatile("" :: "v"(v)); } break;
@@ -69,6 +74,8 @@ __global__ __launch_bounds__(256) void k_tp(u32 *out, const u32 *rnd, u32 seed)
                     asm volatile("ds_or_b32 %0, %1" :: "v"(ad[j]), "v"(seed) : "memory"); break;
                 case WR_ALL: case WR_THIRD: case WR_LINEAR:
                     asm volatile("ds_write_b32 %0, %1" :: "v"(ad[j]), "v"(seed) : "memory"); break;
+                case WR8_REC: case WR8_REC_NOPAD: case WR8_LINEAR:
+                    asm volatile("ds_write_b8 %0, %1" :: "v"(ad[j]), "v"(seed) : "memory"); break;
                 }
             }
         }
@@ -146,6 +153,11 @@ int main()
         RUNL(WR_ALL, "ds_write_b32 runs 39 bytes apart, all lanes")
         RUNL(OR_ALL, "ds_or_b32 runs 39 bytes apart, all lanes")
         RUNL(WR_THIRD, "ds_write_b32 runs 39 bytes apart, 30 % of the lanes")
+        RUNL(RDU8_REC, "ds_read_u8 lanes 132 bytes apart (records, padded)")
+        RUNL(RDU8_REC_NOPAD, "ds_read_u8 lanes 128 bytes apart (records, no pad)")
+        RUNL(WR8_REC, "ds_write_b8 lanes 132 bytes apart (records, padded)")
+        RUNL(WR8_REC_NOPAD, "ds_write_b8 lanes 128 bytes apart (records, no pad)")
+        RUNL(WR8_LINEAR, "ds_write_b8 lane-linear")
         RUNL(OR_THIRD, "ds_or_b32 runs 39 bytes apart, 30 % of the lanes")
     }
     printf("latency, one wave per SIMD (cycles per dependent look-up, includes the address arithmetic)\n");

@@ -3,6 +3,7 @@ next to what a user has without them and next to a plain copy.  Standalone; one 
 enqueue on a stream (no batch set-up, no synchronisation inside), the median of --reps calls after --warmup untimed ones.
 
   python tools/ubench/planes_rate.py [--reps 20] [--warmup 3] [--mib 1024] [--lib PATH] [--no-mover] [--xor-only] [--diff-only]
+                                      [--records-only]
 
 Legs, per dtype; the rate is (bytes read + bytes written) / time = 2 x the tensor's bytes / time:
   split_planes_dev   one block, the whole tensor
@@ -29,6 +30,13 @@ torch's side leaves the zigzag fold out, which favours it.  As with the XOR legs
 over the time, and `ratio` the two-step time over the fused time.  `split_plain` / `merge_plain` are the plain entries timed
 alternately with the fused ones in a loop of their own, `vs_plain` the fused time over the plain time.  --diff-only leaves out
 everything else.
+The record transposes (split_records_dev / merge_records_dev; csrc/records.hip) on uint8 buffers of --mib MiB (rounded down to
+whole groups of 16 records), both sides 16-aligned, per width:
+  3, 12, 16, 32      split_records_dev / merge_records_dev next to torch_split = x.view(n, w).t().contiguous() and torch_merge,
+                     its inverse; `records_done`: ours is the faster one in all eight comparisons
+  2, 4, 8            next to split_planes_dev / merge_planes_dev, timed alternately in one loop; `vs_planes` is the record
+                     entry's time over the plane entry's
+The rate is 2 x the buffer's bytes / time.  --records-only leaves out everything else but the mover.
 and once: `mover`, the one-shot copy figure of tools/ubench/mover (a fraction of 8 TB/s, as a child process after everything
 timed here) when its binary is present.  Every answer is checked against the torch expression before it is timed.  --lib
 measures another build of the library (an experiment's).  Prints one JSON document."""
@@ -193,6 +201,46 @@ def diff_legs(torch, pkg, bt, st, args, x, k, n, d_n, planes, back, poff):
     return legs
 
 
+def record_legs(torch, bt, st, args, dev, nbytes):
+    """the record entries at widths 3, 12, 16, 32 next to torch's strided copy, and at 2, 4, 8 next to the plane entries"""
+    res = {}
+    for w in (3, 12, 16, 32, 2, 4, 8):
+        n = nbytes // (16 * w) * 16
+        x = torch.randint(0, 256, (n * w,), dtype=torch.uint8, device=dev)
+        d_n = torch.tensor([n], dtype=torch.int64, device=dev)
+        cols = torch.empty(w * n, dtype=torch.uint8, device=dev)
+        back = torch.empty_like(x)
+        poff = [j * n for j in range(w)]
+        split = lambda: bt.split_records_dev(st, w, x, [0], [n], d_n, cols, poff)
+        merge = lambda: bt.merge_records_dev(st, w, cols, poff, [n], d_n, back, [0])
+        t_split = lambda: x.view(n, w).t().contiguous()
+        want = t_split()
+        t_merge = lambda: want.t().contiguous()
+        split()
+        merge()
+        bt.finish(st, 1)
+        if not torch.equal(cols.view(w, n), want) or not torch.equal(back, x) or not torch.equal(t_merge().view(-1), x):
+            sys.exit(f"width {w}: the columns differ from the torch expression")
+        legs = {"records": n}
+        if w in (2, 4, 8):
+            p_split = lambda: bt.split_planes_dev(st, w, x, [0], [n], d_n, cols, poff)
+            p_merge = lambda: bt.merge_planes_dev(st, w, cols, poff, [n], d_n, back, [0])
+            for ours, theirs, fa, fb in (("split_records_dev", "split_planes_dev", split, p_split),
+                                         ("merge_records_dev", "merge_planes_dev", merge, p_merge)):
+                ma, mb = timed_pair(torch, st, fa, fb, args.reps, args.warmup)
+                legs[ours], legs[theirs] = leg(ma, 2 * n * w), leg(mb, 2 * n * w)
+                legs[ours]["vs_planes"] = round(statistics.median(ma) / statistics.median(mb), 3)
+        else:
+            for what, fn in (("split_records_dev", split), ("merge_records_dev", merge), ("torch_split", t_split),
+                             ("torch_merge", t_merge)):
+                legs[what] = leg(timed(torch, st, fn, args.reps, args.warmup), 2 * n * w)
+        bt.finish(st, 1)
+        res[str(w)] = legs
+        del x, cols, back, want
+        torch.cuda.empty_cache()
+    return res
+
+
 def mover_one_shot():
     exe = os.path.join(ROOT, "tools", "ubench", "mover")
     if not os.path.exists(exe):
@@ -211,6 +259,7 @@ def main():
     ap.add_argument("--no-mover", action="store_true")
     ap.add_argument("--xor-only", action="store_true")
     ap.add_argument("--diff-only", action="store_true")
+    ap.add_argument("--records-only", action="store_true")
     args = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -224,7 +273,7 @@ def main():
     res = {"bytes": nbytes, "reps": args.reps, "warmup": args.warmup, "lib": pkg.LIB_PATH, "legs": {}}
     bt = pkg.Batch(1, 1 << 20)
     with torch.cuda.stream(st):
-        for name, dtype in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
+        for name, dtype in (() if args.records_only else (("bf16", torch.bfloat16), ("fp32", torch.float32))):
             k = torch.empty((), dtype=dtype).element_size()
             n = nbytes // k
             x = torch.empty(n, dtype=torch.float32, device=dev).normal_(0, 0.02).to(dtype)
@@ -260,10 +309,14 @@ def main():
             res["legs"][name] = legs
             del x, planes, back
             torch.cuda.empty_cache()
+        if args.records_only or not (args.xor_only or args.diff_only):
+            res["records"] = record_legs(torch, bt, st, args, dev, nbytes)
+            res["records_done"] = all(res["records"][w][ours]["GB_s"] > res["records"][w][theirs]["GB_s"] for w in ("3", "12", "16", "32")
+                                      for ours, theirs in (("split_records_dev", "torch_split"), ("merge_records_dev", "torch_merge")))
     bt.close()
-    res["diff_done"] = not args.xor_only and all(res["legs"][d]["diff"][f]["ratio"] > 1 for d in res["legs"]
+    res["diff_done"] = not args.xor_only and not args.records_only and all(res["legs"][d]["diff"][f]["ratio"] > 1 for d in res["legs"]
                                                  for f in ("split_diff", "merge_diff"))
-    res["done"] = not args.xor_only and not args.diff_only and all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
+    res["done"] = not args.xor_only and not args.diff_only and not args.records_only and all(res["legs"][d][ours]["GB_s"] >= res["legs"][d][theirs]["GB_s"] for d in res["legs"]
                       for ours, theirs in (("split_planes_dev", "torch_split"), ("merge_planes_dev", "torch_merge")))
     if not args.no_mover and not args.xor_only and not args.diff_only:
         torch.cuda.synchronize()
