@@ -2820,9 +2820,17 @@ def _plane_stream(dev, stream):
     return st
 
 
-def _by_elem(sizes):
-    """indices of the non-empty tensors, grouped by element size -> [(elem, [index, ...])]"""
-    return [(k, idx) for k in PLANES_ELEM for idx in [[i for i, (e, n) in enumerate(sizes) if e == k and n]] if idx]
+# The drivers below serve four variants of one chain.  A tensor is `units` = (count, width): its count of units of `width` bytes,
+# an element's 1, 2, 4 or 8 or a record's 1 .. RECORDS_MAX_WIDTH; column j of a unit is a plane.  The variant `kind` names the
+# pair of Batch methods, split_<kind>_dev / merge_<kind>_dev: "planes", "planes_xor" (with `bases`), "planes_diff" or "records".
+def _by_width(units):
+    """indices of the non-empty tensors, grouped by unit width -> [(width, [index, ...])]"""
+    return [(w, [i for i, (n, x) in enumerate(units) if x == w and n]) for w in sorted({x for n, x in units if n})]
+
+
+def _elements(ts):
+    """the units of tensors taken by element"""
+    return [(t.numel(), t.element_size()) for t in ts]
 
 
 def _base_side(bases, idx):
@@ -2834,62 +2842,73 @@ def _base_side(bases, idx):
     return min(have), [PLANES_NO_BASE if bases[i] is None else bases[i].data_ptr() - min(have) for i in idx]
 
 
-def _split_into(bt, st, dev, ts, bases=None, diff=False):
-    """one split_planes_dev per element size over ts (blocks addressed from the lowest tensor address: nothing is
-    concatenated) -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  With `bases` (one entry per
-    tensor: None or a tensor of the same dtype and numel) a size with a base among its tensors takes one split_planes_xor_dev
-    instead, the bases addressed from the lowest base address.  With `diff` (and no bases) every size takes one
-    split_planes_diff_dev: one block a tensor, so the differences run over the flattened tensor."""
+def _transpose(bt, way, kind, side):
+    """bt's `way` ("split" / "merge") method of the variant; a "planes_xor" launch none of whose tensors has a base (side is
+    None) is the plain one"""
+    return getattr(bt, f"{way}_{'planes' if kind == 'planes_xor' and side is None else kind}_dev")
+
+
+def _split_into(bt, st, dev, ts, units, kind, bases=None):
+    """one split launch per distinct width over ts (blocks addressed from the lowest tensor address: nothing is concatenated)
+    -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  "planes_xor" with `bases` (one entry per
+    tensor: None or a tensor of the same dtype and numel): a width with a base among its tensors takes split_planes_xor_dev, the
+    bases addressed from the lowest base address.  "planes_diff": one block a tensor, so the differences run over the
+    flattened tensor."""
     import torch
     poff, pos = [], 0
-    for t in ts:
-        step = _al16(t.numel())
-        poff.append([pos + j * step for j in range(t.element_size())])
-        pos += t.element_size() * step
+    for n, w in units:
+        step = _al16(n)
+        poff.append([pos + j * step for j in range(w)])
+        pos += w * step
     buf = torch.empty(pos + 16, dtype=torch.uint8, device=dev)
-    groups = _by_elem([(t.element_size(), t.numel()) for t in ts])
+    groups = _by_width(units)
     if groups:
-        d_n = torch.tensor([ts[i].numel() for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+        d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
     at = 0
-    for k, idx in groups:
+    for w, idx in groups:
         base = min(ts[i].data_ptr() for i in idx)
         side = _base_side(bases, idx)
-        if side is None:
-            split = bt.split_planes_diff_dev if diff else bt.split_planes_dev
-            split(st, k, base, [ts[i].data_ptr() - base for i in idx], [ts[i].numel() for i in idx], d_n[at:at + len(idx)], buf,
-                  [o for i in idx for o in poff[i]])
-        else:
-            bt.split_planes_xor_dev(st, k, base, [ts[i].data_ptr() - base for i in idx], side[0], side[1],
-                                    [ts[i].numel() for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+        _transpose(bt, "split", kind, side)(st, w, base, [ts[i].data_ptr() - base for i in idx], *(side or ()),
+                                            [units[i][0] for i in idx], d_n[at:at + len(idx)], buf,
+                                            [o for i in idx for o in poff[i]])
         at += len(idx)
     return buf, poff
 
 
-def _merge_into(bt, st, dev, planes, outs, bases=None, diff=False):
-    """one merge_planes_dev per element size: planes[i] (the 1-D uint8 plane tensors of tensor i, each of outs[i].numel()
-    bytes) -> outs[i].  A plane that is not 16-aligned is copied first.  With `bases` (as _split_into's) a size with a base
-    among its tensors takes one merge_planes_xor_dev instead, and with `diff` (and no bases) every size one
-    merge_planes_diff_dev."""
+def _merge_into(bt, st, dev, planes, outs, units, kind, bases=None):
+    """one merge launch per distinct width: planes[i] (the 1-D uint8 plane tensors of tensor i, each of units[i]'s count of
+    bytes) -> outs[i].  A plane that is not 16-aligned is copied first.  `kind` and `bases` as _split_into takes them."""
     import torch
-    groups = _by_elem([(o.element_size(), o.numel()) for o in outs])
+    groups = _by_width(units)
     if not groups:
         return
     planes = [[p if p.data_ptr() % 16 == 0 else p.clone() for p in ps] for ps in planes]
-    d_n = torch.tensor([outs[i].numel() for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+    d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
     at = 0
-    for k, idx in groups:
+    for w, idx in groups:
         pbase = min(p.data_ptr() for i in idx for p in planes[i])
         obase = min(outs[i].data_ptr() for i in idx)
         side = _base_side(bases, idx)
-        if side is None:
-            merge = bt.merge_planes_diff_dev if diff else bt.merge_planes_dev
-            merge(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], [outs[i].numel() for i in idx],
-                  d_n[at:at + len(idx)], obase, [outs[i].data_ptr() - obase for i in idx])
-        else:
-            bt.merge_planes_xor_dev(st, k, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], side[0], side[1],
-                                    [outs[i].numel() for i in idx], d_n[at:at + len(idx)], obase,
-                                    [outs[i].data_ptr() - obase for i in idx])
+        _transpose(bt, "merge", kind, side)(st, w, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], *(side or ()),
+                                            [units[i][0] for i in idx], d_n[at:at + len(idx)], obase,
+                                            [outs[i].data_ptr() - obase for i in idx])
         at += len(idx)
+
+
+def _split_one(kind, t, n, w, stream):
+    """split_planes' / split_records' work on the checked tensor t of n units of w bytes: one launch, one synchronisation"""
+    import torch
+    dev = t.device
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        bt = Batch(1, 1 << 20)
+        try:
+            buf, _ = _split_into(bt, st, dev, [t], [(n, w)], kind)
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return buf[:w * _al16(n)].view(w, _al16(n))[:, :n]
 
 
 def split_planes(t, stream=None):
@@ -2900,17 +2919,7 @@ def split_planes(t, stream=None):
     if not isinstance(t, torch.Tensor):
         raise ValueError("split_planes: a contiguous CUDA tensor")
     t = _plane_tensors("split_planes", t)[0]
-    dev, k, n = t.device, t.element_size(), t.numel()
-    st = _plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        bt = Batch(1, 1 << 20)
-        try:
-            buf, _ = _split_into(bt, st, dev, [t])
-            bt.finish(st, 1)
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return buf[:k * _al16(n)].view(k, _al16(n))[:, :n]
+    return _split_one("planes", t, t.numel(), t.element_size(), stream)
 
 
 def _numel(shape):
@@ -2920,21 +2929,58 @@ def _numel(shape):
     return n
 
 
-def _plane_dtype(what, dtype, shape):
-    """dtype and shape of a tensor to be put together from planes, checked -> (element size, shape, numel)"""
+def _elem_size(what, dtype):
     import torch
     if not isinstance(dtype, torch.dtype):
         raise ValueError(f"{what}: dtype is a torch.dtype")
-    k = torch.empty((), dtype=dtype).element_size()
-    if k not in PLANES_ELEM:
-        raise ValueError(f"{what}: {dtype} has elements of {k} bytes, not 1, 2, 4 or 8")
+    return torch.empty((), dtype=dtype).element_size()
+
+
+def _shape(what, shape):
     try:
         shape = tuple(int(d) for d in shape)
     except TypeError:
         raise ValueError(f"{what}: shape is a sequence of ints") from None
     if any(d < 0 for d in shape):
         raise ValueError(f"{what}: negative dimension")
+    return shape
+
+
+def _plane_dtype(what, dtype, shape):
+    """dtype and shape of a tensor to be put together from planes, checked -> (element size, shape, numel)"""
+    k = _elem_size(what, dtype)
+    if k not in PLANES_ELEM:
+        raise ValueError(f"{what}: {dtype} has elements of {k} bytes, not 1, 2, 4 or 8")
+    shape = _shape(what, shape)
     return k, shape, _numel(shape)
+
+
+def _record_dtype(what, dtype, shape, width):
+    """dtype, shape and width of a tensor to be put together from columns, checked -> (width, shape, records)"""
+    k = _elem_size(what, dtype)
+    shape = _shape(what, shape)
+    nbytes = _numel(shape) * k
+    if nbytes % records._width(what, width):
+        raise ValueError(f"{what}: a width of {width} does not divide the tensor's {nbytes} bytes")
+    return width, shape, nbytes // width
+
+
+def _merge_one(kind, planes, dtype, shape, stream):
+    """merge_planes' / merge_records' work on the checked planes [w, n] -> the tensor: one launch, one synchronisation"""
+    import torch
+    w, n = int(planes.shape[0]), int(planes.shape[1])
+    dev = planes.device
+    st = _plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        bt = Batch(1, 1 << 20)
+        try:
+            _merge_into(bt, st, dev, [[planes[j].contiguous() for j in range(w)]], [out], [(n, w)], kind)
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return out
 
 
 def merge_planes(planes, dtype, shape, stream=None):
@@ -2948,18 +2994,7 @@ def merge_planes(planes, dtype, shape, stream=None):
         raise ValueError("merge_planes: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
     if tuple(planes.shape) != (k, n):
         raise ValueError(f"merge_planes: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
-    dev = planes.device
-    st = _plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        out = torch.empty(shape, dtype=dtype, device=dev)
-        bt = Batch(1, 1 << 20)
-        try:
-            _merge_into(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out])
-            bt.finish(st, 1)
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return out
+    return _merge_one("planes", planes, dtype, shape, stream)
 
 
 def _back_to_back(buf, spans):
@@ -2970,10 +3005,10 @@ def _back_to_back(buf, spans):
     return [buf[o:o + n] for o, n in spans], None
 
 
-def _plane_entries(what, ts, bases, block_size, stream, diff=False):
-    """compress_tensors' chain over the checked tensors ts, or with `bases` (_split_into's) compress_deltas', or with `diff`
-    compress_sequences': the split, the sizes, the file sets of the planes that shrink -> per tensor its plane entries, and
-    their bytes"""
+def _plane_entries(what, ts, units, kind, bases, block_size, stream):
+    """compress_tensors' chain over the checked tensors ts of `units`, and in its other variants compress_deltas' (with `bases`,
+    _split_into's), compress_sequences' and compress_records': the split, the sizes, the file sets of the planes that shrink ->
+    per tensor its plane entries, and their bytes"""
     import torch
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
         raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
@@ -2984,21 +3019,21 @@ def _plane_entries(what, ts, bases, block_size, stream, diff=False):
     with torch.cuda.stream(st):
         bt = Batch(len(ts), 1 << 20)
         try:
-            buf, poff = _split_into(bt, st, dev, ts, bases, diff)
+            buf, poff = _split_into(bt, st, dev, ts, units, kind, bases)
             bt.finish(st, len(ts))
         finally:
             bt.close()
-        entries = [[buf[o:o + t.numel()] for o in poff[i]] for i, t in enumerate(ts)]
-        cand = [(i, j) for i, t in enumerate(ts) if t.numel() >= 1024 for j in range(t.element_size())]
+        entries = [[buf[o:o + n] for o in poff[i]] for i, (n, _) in enumerate(units)]
+        cand = [(i, j) for i, (n, w) in enumerate(units) if n >= 1024 for j in range(w)]
         if cand:
-            spans = [(poff[i][j], ts[i].numel()) for i, j in cand]
+            spans = [(poff[i][j], units[i][0]) for i, j in cand]
             d_in, sizes = _back_to_back(buf, spans)
             sized = compressed_sizes(d_in, sizes, block_size=block_size, stream=st)
-            keep = [c for c, e in zip(cand, sized) if isinstance(e, dict) and sum(e.values()) < ts[c[0]].numel()]
+            keep = [c for c, e in zip(cand, sized) if isinstance(e, dict) and sum(e.values()) < units[c[0]][0]]
         else:
             keep = []
         if keep:
-            d_in, sizes = _back_to_back(buf, [(poff[i][j], ts[i].numel()) for i, j in keep])
+            d_in, sizes = _back_to_back(buf, [(poff[i][j], units[i][0]) for i, j in keep])
             for (i, j), e in zip(keep, compress_many(d_in, sizes, block_size=block_size, stream=st)):
                 if isinstance(e, ShafaError):
                     raise e
@@ -3024,7 +3059,7 @@ def compress_tensors(tensors, block_size=8 << 20, stream=None):
     (every numel a multiple of 16, none skipped), and otherwise a list of views, which they concatenate — one copy of those
     planes.  `block_size` is theirs (the C host's split of a plane into blocks)."""
     ts = _plane_tensors("compress_tensors", tensors)
-    entries, nbytes = _plane_entries("compress_tensors", ts, None, block_size, stream)
+    entries, nbytes = _plane_entries("compress_tensors", ts, _elements(ts), "planes", None, block_size, stream)
     return [CompressedTensor(t.dtype, t.shape, ps, nb) for t, ps, nb in zip(ts, entries, nbytes)]
 
 
@@ -3041,7 +3076,7 @@ def compress_sequences(tensors, block_size=8 << 20, stream=None):
     of the differences exists -> compressed_sizes -> compress_many, as there.  Whether the differences code smaller than the
     elements is the caller's to know: nothing is tried both ways."""
     ts = _plane_tensors("compress_sequences", tensors)
-    entries, nbytes = _plane_entries("compress_sequences", ts, None, block_size, stream, diff=True)
+    entries, nbytes = _plane_entries("compress_sequences", ts, _elements(ts), "planes_diff", None, block_size, stream)
     return [CompressedSequence(t.dtype, t.shape, ps, nb) for t, ps, nb in zip(ts, entries, nbytes)]
 
 
@@ -3113,15 +3148,16 @@ def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=
     if not isinstance(check_base, bool):
         raise ValueError("compress_deltas: check_base is a bool")
     crcs = _base_crcs(bs, stream) if check_base and ts else [None] * len(ts)
-    entries, nbytes = _plane_entries("compress_deltas", ts, bs, block_size, stream)
+    entries, nbytes = _plane_entries("compress_deltas", ts, _elements(ts), "planes_xor", bs, block_size, stream)
     return [CompressedTensor(t.dtype, t.shape, ps, nb) if b is None else CompressedDelta(t.dtype, t.shape, ps, nb, c)
             for t, b, ps, nb, c in zip(ts, bs, entries, nbytes, crcs)]
 
 
-def _merge_items(what, items, bases, check_base, stream, diff=False):
-    """decompress_tensors' checks and chain over the list `items`, or with `bases` (one entry per item) decompress_deltas', or
-    with `diff` decompress_sequences'"""
+def _merge_items(what, items, kind, bases, check_base, stream):
+    """decompress_tensors' checks and chain over the list `items`, and in its other variants decompress_deltas' (with `bases`,
+    one entry per item), decompress_sequences' and decompress_records' (whose messages say "column" for a plane)"""
     import torch
+    noun, length = ("column", "record count") if kind == "records" else ("plane", "tensor's numel")
     if bases is not None:
         for i, (it, b) in enumerate(zip(items, bases)):
             if isinstance(it, CompressedDelta) and b is None:
@@ -3131,27 +3167,32 @@ def _merge_items(what, items, bases, check_base, stream, diff=False):
         bases = _base_tensors(what, bases, [(it.dtype, _plane_dtype(what, it.dtype, it.shape)[2], None) for it in items])
     metas, dev = [], None
     for it in items:
-        k, shape, n = _plane_dtype(what, it.dtype, it.shape)
+        if kind == "records":
+            k, shape, n = _record_dtype(what, it.dtype, it.shape, it.width)
+            count = f"records of {k} bytes have {k} columns"
+        else:
+            k, shape, n = _plane_dtype(what, it.dtype, it.shape)
+            count = f"{it.dtype} has {k} planes"
         if not isinstance(it.planes, (list, tuple)) or len(it.planes) != k:
-            raise ValueError(f"{what}: {it.dtype} has {k} planes")
+            raise ValueError(f"{what}: {count}")
         for p in it.planes:
             if isinstance(p, ShafaError):
                 continue
             if isinstance(p, dict):
                 fs = [f for f in p.values() if isinstance(f, torch.Tensor)]
                 if not ({".shaf", ".cod"} <= set(p) or {".rle.shaf", ".rle.cod"} <= set(p)) or len(fs) != len(p):
-                    raise ValueError(f"{what}: a compressed plane is compress_many's dict of files")
+                    raise ValueError(f"{what}: a compressed {noun} is compress_many's dict of files")
             elif isinstance(p, torch.Tensor) and p.dtype == torch.uint8 and p.dim() == 1 and p.is_contiguous():
                 fs = [p]
             else:
-                raise ValueError(f"{what}: a plane is a dict of files or a contiguous 1-D uint8 tensor")
+                raise ValueError(f"{what}: a {noun} is a dict of files or a contiguous 1-D uint8 tensor")
             for f in fs:
                 if not f.is_cuda:
-                    raise ValueError(f"{what}: planes are CUDA tensors")
+                    raise ValueError(f"{what}: {noun}s are CUDA tensors")
                 if dev is not None and f.device != dev:
-                    raise ValueError(f"{what}: the planes are on one device")
+                    raise ValueError(f"{what}: the {noun}s are on one device")
                 dev = f.device
-        metas.append((shape, n))
+        metas.append((shape, n, k))
     for it in items:
         for p in it.planes:
             if isinstance(p, ShafaError):
@@ -3177,13 +3218,13 @@ def _merge_items(what, items, bases, check_base, stream, diff=False):
                 if isinstance(r, ShafaError):
                     raise r
                 planes[i][j] = r
-        for (_, n), ps in zip(metas, planes):
+        for (_, n, _), ps in zip(metas, planes):
             if any(int(p.numel()) != n for p in ps):
-                raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: a plane's length is not the tensor's numel")
-        outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _) in zip(items, metas)]
+                raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: a {noun}'s length is not the {length}")
+        outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs, bases, diff)
+            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, bases)
             bt.finish(st, len(items))
         finally:
             bt.close()
@@ -3208,7 +3249,7 @@ def decompress_tensors(items, stream=None):
         raise ValueError("decompress_tensors: a CompressedDelta needs its base: decompress_deltas")
     if any(isinstance(it, CompressedSequence) for it in items):
         raise ValueError("decompress_tensors: a CompressedSequence holds differences: decompress_sequences")
-    return _merge_items("decompress_tensors", items, None, False, stream)
+    return _merge_items("decompress_tensors", items, "planes", None, False, stream)
 
 
 def decompress_deltas(items, bases, check_base=True, stream=None):
@@ -3237,7 +3278,7 @@ def decompress_deltas(items, bases, check_base=True, stream=None):
         bases = [bases]
     if not isinstance(bases, (list, tuple)) or len(bases) != len(items):
         raise ValueError("decompress_deltas: bases is a list with one entry (a tensor or None) per item")
-    return _merge_items("decompress_deltas", items, list(bases), check_base, stream)
+    return _merge_items("decompress_deltas", items, "planes_xor", list(bases), check_base, stream)
 
 
 def decompress_sequences(items, stream=None):
@@ -3252,9 +3293,10 @@ def decompress_sequences(items, stream=None):
         items = [items]
     if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedSequence) for it in items):
         raise ValueError("decompress_sequences: a CompressedSequence or a list of them (compress_sequences' items)")
-    return _merge_items("decompress_sequences", items, None, False, stream, diff=True)
+    return _merge_items("decompress_sequences", items, "planes_diff", None, False, stream)
 
 
 # ------------------------------------------------------------------ fixed-width records, one file set per byte column
+from . import records  # noqa: E402  (_record_dtype asks it for a width's check)
 from .records import (CompressedRecords, compress_records, decompress_records, merge_records, records_pass,  # noqa: E402,F401
                       split_records)

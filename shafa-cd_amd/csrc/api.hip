@@ -206,6 +206,63 @@ void batch_stage_retire(Batch *b, hipStream_t st)
     if (segs.empty()) b->stage_used = 0;
 }
 
+int tile_count(int nblocks, const u64 *h_cap, u64 unit, u64 *ntiles)
+{
+    u64 n = 0;
+    for (int b = 0; b < nblocks; ++b)
+        if ((n += h_cap[b] / unit + (h_cap[b] % unit != 0)) > 0x7FFFFFFFull) return b;
+    if (ntiles) *ntiles = n;
+    return nblocks;
+}
+
+// such a part: h's bytes (NULL: zeros), zero padded to the next part
+static void put16(u8 *dst, const void *h, size_t bytes)
+{
+    if (h) memcpy(dst, h, bytes);
+    else memset(dst, 0, bytes);
+    memset(dst + bytes, 0, (0 - bytes) & 15);
+}
+
+// the layout is described once, in internal.hpp
+int tile_setup(Batch *bt, hipStream_t st, int nblocks, const u64 *h_off, const u64 *h_cap, u32 unit, const TileExtra *extras,
+               int nextras, size_t scratch_per_tile, size_t scratch_fixed, TileSetup *s)
+{
+    u64 ntiles = 0;
+    if (tile_count(nblocks, h_cap, unit, &ntiles) < nblocks) return SHAFA_LACK_OF_MEMORY;
+    const size_t nb = (size_t)nblocks;
+    size_t o_up = 0, up_bytes = 0, u_extra[TILE_EXTRAS] = {};
+    take16(o_up, (size_t)ntiles * scratch_per_tile + scratch_fixed);
+    const size_t u_off = take16(up_bytes, nb * 8), u_cap = take16(up_bytes, nb * 8);
+    for (int i = 0; i < nextras; ++i) u_extra[i] = take16(up_bytes, extras[i].bytes);
+    const size_t u_base = take16(up_bytes, (nb + 1) * 4);
+    int rc = batch_reserve(bt, st, o_up + up_bytes);
+    if (rc) return rc;
+    u8 *up = (u8 *)bt->d_ws + o_up;
+    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
+    if (!hs) return SHAFA_LACK_OF_MEMORY;
+    put16(hs + u_off, h_off, nb * 8);
+    put16(hs + u_cap, h_cap, nb * 8);
+    for (int i = 0; i < nextras; ++i) put16(hs + u_extra[i], extras[i].h, extras[i].bytes);
+    u32 *hb = (u32 *)(hs + u_base);
+    u32 base = 0;
+    for (int b = 0; b < nblocks; ++b) {
+        hb[b] = base;
+        base += (u32)(h_cap[b] / unit + (h_cap[b] % unit != 0));
+    }
+    hb[nblocks] = base;
+    memset(hb + nb + 1, 0, (0 - (nb + 1) * 4) & 15);
+    if ((rc = batch_upload(bt, st, up, hs, up_bytes))) return rc;
+    s->off = (const u64 *)(up + u_off);
+    s->cap = (const u64 *)(up + u_cap);
+    for (int i = 0; i < TILE_EXTRAS; ++i) s->extra[i] = i < nextras ? up + u_extra[i] : nullptr;
+    s->tbase = (const u32 *)(up + u_base);
+    s->scratch = (u8 *)bt->d_ws;
+    s->nt = (u32)ntiles;
+    s->per_wg = s->nt ? (s->nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1;
+    s->wgs = (s->nt + s->per_wg - 1) / s->per_wg;
+    return SHAFA_SUCCESS;
+}
+
 // the argument checks of the size entries (shafa_hipd_rle_decoded_size_dev, shafa_hipd_rle_encoded_size_dev,
 // shafa_hipd_rle_encoded_hist_dev), of shafa_hipd_compare_dev's side a and of shafa_hipd_crc32_dev (whose regions need no
 // alignment: aligned = false), before HIP is touched: true = go on, false = the call returns *rc
@@ -492,9 +549,7 @@ int shafa_hipd_compare_dev(shafa_hipd_batch *b, void *stream, int nblocks, const
     int rc;
     if (!size_pass_check((Batch *)b, nblocks, h_a_off, h_a_cap, d_a_n, d_first, &rc)) return rc;
     if (!h_ref_off || !h_ref_n) return SHAFA_OUTSIDE_MODULE;
-    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (compare.hip numbers them in 31 bits)
-    for (int i = 0; i < nblocks; ++i)
-        if ((ntiles += h_a_cap[i] / 8192 + (h_a_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if (tile_count(nblocks, h_a_cap, 8192) < nblocks) return SHAFA_LACK_OF_MEMORY;      // 8 KiB tiles of the capacities
     if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
     return compare_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_a, h_a_off, h_a_cap, d_a_n, d_ref, h_ref_off, h_ref_n,
                               d_first);
@@ -506,9 +561,7 @@ int shafa_hipd_crc32_dev(shafa_hipd_batch *b, void *stream, int nblocks, const u
     if (!b || !d_in) return SHAFA_OUTSIDE_MODULE;
     int rc;
     if (!size_pass_check((Batch *)b, nblocks, h_in_off, h_in_cap, d_in_n, d_crc, &rc, false)) return rc;
-    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (tile_pass.hpp numbers them in 31 bits)
-    for (int i = 0; i < nblocks; ++i)
-        if ((ntiles += h_in_cap[i] / 8192 + (h_in_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if (tile_count(nblocks, h_in_cap, 8192) < nblocks) return SHAFA_LACK_OF_MEMORY;     // 8 KiB tiles of the capacities
     if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
     return crc32_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_crc);
 }
@@ -536,9 +589,7 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_in_cap) return SHAFA_OUTSIDE_MODULE;
-    u64 ntiles = 0;                                  // 8 KiB tiles of the capacities (tile_pass.hpp numbers them in 31 bits)
-    for (int i = 0; i < nblocks; ++i)
-        if ((ntiles += h_in_cap[i] / 8192 + (h_in_cap[i] % 8192 != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
+    if (tile_count(nblocks, h_in_cap, 8192) < nblocks) return SHAFA_LACK_OF_MEMORY;     // 8 KiB tiles of the capacities
     if (!h_in_off || !h_pos) return SHAFA_OUTSIDE_MODULE;
     for (int i = 0; h_flags && i < nblocks; ++i)
         if (h_flags[i] & ~(SHAFA_FIND_NEXT | SHAFA_FIND_CONTEXT)) return SHAFA_OUTSIDE_MODULE;
@@ -548,32 +599,40 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
                            pat_n, max_hits, d_hits, d_count, d_total);
 }
 
-// the checks the plane transposes share (include/shafa_hip.h), then the launch: d_el is the element side; xr: the _xor entries,
-// with a base side; df: the _diff entries
-static int planes_dev(bool merge, bool xr, bool df, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_el,
-                      const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
-                      const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off)
+// the checks the plane and the record transposes share (include/shafa_hip.h), in one order, then the launch.  d_el is the element
+// or record side; `unit` the bytes of an element (1, 2, 4 or 8) or, TR_RECORDS, of a record (1 .. SHAFA_RECORDS_MAX_WIDTH);
+// TR_XOR: the _xor entries, with a base side; TR_DIFF: the _diff entries
+enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_RECORDS };
+static_assert(SHAFA_RECORDS_TILE == SHAFA_PLANES_TILE, "one tile for the plane and the record entries");
+
+static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
+                         const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
+                         const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off)
 {
+    const bool xr = tr == TR_XOR;
     if (!b || !d_el || !d_planes || !d_n || (xr && !d_base)) return SHAFA_OUTSIDE_MODULE;
-    if (elem != 1 && elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
+    if (tr == TR_RECORDS ? unit < 1 || unit > SHAFA_RECORDS_MAX_WIDTH : unit != 1 && unit != 2 && unit != 4 && unit != 8)
+        return SHAFA_OUTSIDE_MODULE;
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_cap) return SHAFA_OUTSIDE_MODULE;
-    u64 ntiles = 0, bytes = 0;                       // tiles of SHAFA_PLANES_TILE elements (planes.hip numbers them in 31 bits)
+    u64 bytes = 0;
     for (int i = 0; i < nblocks; ++i) {
-        if (h_cap[i] > ~0ull / elem || bytes + h_cap[i] * elem < bytes) return SHAFA_LACK_OF_MEMORY;
-        bytes += h_cap[i] * elem;
-        if ((ntiles += h_cap[i] / SHAFA_PLANES_TILE + (h_cap[i] % SHAFA_PLANES_TILE != 0)) > 0x7FFFFFFFull)
-            return SHAFA_LACK_OF_MEMORY;
+        if (h_cap[i] > ~0ull / unit || bytes + h_cap[i] * unit < bytes) return SHAFA_LACK_OF_MEMORY;
+        bytes += h_cap[i] * unit;
     }
+    if (tile_count(nblocks, h_cap, SHAFA_PLANES_TILE) < nblocks) return SHAFA_LACK_OF_MEMORY;    // tiles of elements or records
     if (!h_off || !h_plane_off || (xr && !h_base_off) || ((uintptr_t)d_planes & 15)) return SHAFA_OUTSIDE_MODULE;
-    for (size_t i = 0; i < (size_t)nblocks * elem; ++i)
+    for (size_t i = 0; i < (size_t)nblocks * unit; ++i)
         if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
-    if (df)
-        return planes_diff_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, merge, (u8 *)d_el, h_off, h_cap, d_n,
+    if (tr == TR_RECORDS)
+        return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
+                                  h_plane_off);
+    if (tr == TR_DIFF)
+        return planes_diff_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
                                       (u8 *)d_planes, h_plane_off);
-    return planes_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
+    return planes_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
                              h_plane_off, xr ? d_base : nullptr, xr ? h_base_off : nullptr);
 }
 
@@ -581,84 +640,60 @@ int shafa_hipd_split_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, 
                                 const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                 const uint64_t *h_plane_off)
 {
-    return planes_dev(false, false, false, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(false, TR_PLANES, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_merge_planes_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
                                 const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                 const uint64_t *h_out_off)
 {
-    return planes_dev(true, false, false, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(true, TR_PLANES, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_split_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
                                     const uint64_t *h_in_off, const uint8_t *d_base, const uint64_t *h_base_off,
                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes, const uint64_t *h_plane_off)
 {
-    return planes_dev(false, true, false, b, stream, nblocks, elem, d_in, h_in_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(false, TR_XOR, b, stream, nblocks, elem, d_in, h_in_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_merge_planes_xor_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
                                     const uint64_t *h_plane_off, const uint8_t *d_base, const uint64_t *h_base_off,
                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off)
 {
-    return planes_dev(true, true, false, b, stream, nblocks, elem, d_out, h_out_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(true, TR_XOR, b, stream, nblocks, elem, d_out, h_out_off, d_base, h_base_off, h_cap, d_n, d_planes, h_plane_off);
 }
 
 int shafa_hipd_split_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
                                      const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                      const uint64_t *h_plane_off)
 {
-    return planes_dev(false, false, true, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
-                      h_plane_off);
+    return transpose_dev(false, TR_DIFF, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off);
 }
 
 int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_planes,
                                      const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                      const uint64_t *h_out_off)
 {
-    return planes_dev(true, false, true, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
-                      h_plane_off);
-}
-
-// the checks of the record transposes (include/shafa_hip.h): the plain plane entries', in their order, with a width of
-// 1 .. SHAFA_RECORDS_MAX_WIDTH in place of the element size; d_rec is the record side
-static int records_dev(bool merge, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_rec,
-                       const uint64_t *h_off, const uint64_t *h_cap, const uint64_t *d_n, const uint8_t *d_planes,
-                       const uint64_t *h_plane_off)
-{
-    if (!b || !d_rec || !d_planes || !d_n) return SHAFA_OUTSIDE_MODULE;
-    if (width < 1 || width > SHAFA_RECORDS_MAX_WIDTH) return SHAFA_OUTSIDE_MODULE;
-    if (nblocks <= 0) return SHAFA_SUCCESS;
-    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
-    if (!h_cap) return SHAFA_OUTSIDE_MODULE;
-    u64 ntiles = 0, bytes = 0;                       // tiles of SHAFA_RECORDS_TILE records (records.hip numbers them in 31 bits)
-    for (int i = 0; i < nblocks; ++i) {
-        if (h_cap[i] > ~0ull / width || bytes + h_cap[i] * width < bytes) return SHAFA_LACK_OF_MEMORY;
-        bytes += h_cap[i] * width;
-        if ((ntiles += h_cap[i] / SHAFA_RECORDS_TILE + (h_cap[i] % SHAFA_RECORDS_TILE != 0)) > 0x7FFFFFFFull)
-            return SHAFA_LACK_OF_MEMORY;
-    }
-    if (!h_off || !h_plane_off || ((uintptr_t)d_planes & 15)) return SHAFA_OUTSIDE_MODULE;
-    for (size_t i = 0; i < (size_t)nblocks * width; ++i)
-        if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
-    return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, width, merge, (u8 *)d_rec, h_off, h_cap, d_n, (u8 *)d_planes,
-                              h_plane_off);
+    return transpose_dev(true, TR_DIFF, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off);
 }
 
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,
                                  const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                  const uint64_t *h_plane_off)
 {
-    return records_dev(false, b, stream, nblocks, width, d_in, h_in_off, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(false, TR_RECORDS, b, stream, nblocks, width, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off);
 }
 
 int shafa_hipd_merge_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_planes,
                                  const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                  const uint64_t *h_out_off)
 {
-    return records_dev(true, b, stream, nblocks, width, d_out, h_out_off, h_cap, d_n, d_planes, h_plane_off);
+    return transpose_dev(true, TR_RECORDS, b, stream, nblocks, width, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off);
 }
 
 // span: a power of two, 256 .. 8192; flags: SHAFA_SEEK_SF / SHAFA_SEEK_RLE only
@@ -676,11 +711,10 @@ int shafa_hipd_seek_index_dev(shafa_hipd_batch *b, void *stream, int nblocks, co
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_in_off || !h_in_cap || !h_ckpt_first || ((uintptr_t)d_in & 15)) return SHAFA_OUTSIDE_MODULE;
-    u64 nspans = 0;
-    for (int i = 0; i < nblocks; ++i) {
+    const int fit = tile_count(nblocks, h_in_cap, span);       // block by block: the offset, then the spans so far
+    for (int i = 0; i < nblocks && i <= fit; ++i)
         if (h_in_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-        if ((nspans += h_in_cap[i] / span + (h_in_cap[i] % span != 0)) > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
-    }
+    if (fit < nblocks) return SHAFA_LACK_OF_MEMORY;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
     return seek_index_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, d_in, h_in_off, h_in_cap, d_in_n,
                                  (flags & SHAFA_SEEK_SF) ? d_tables : nullptr, span, flags, h_ckpt_first, d_ckpt, d_status, d_out_n);

@@ -170,42 +170,20 @@ __global__ __launch_bounds__(TP_THREADS) void compare_blocks(const u64 *__restri
 
 }  // namespace
 
-// workspace: [records: 16 B per tile of a's capacities][a_off][a_cap][ref_off][ref_n][tbase, zero padded to 16]; the last
-// five are what the host uploads.  The caller has checked that the tiles number fewer than 2^31.
+// workspace: tile_setup's with two extras, ref_off and ref_n; scratch: the records, 16 B per tile of a's capacities
 int compare_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_a, const u64 *h_a_off, const u64 *h_a_cap,
                        const u64 *d_a_n, const u8 *d_ref, const u64 *h_ref_off, const u64 *h_ref_n, u64 *d_first)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_a_cap[b], TP_TILE);
-    const size_t nb = (size_t)nblocks;
-    const size_t o_up = (size_t)ntiles * 16, u_base = 4 * nb * 8, up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, o_up + up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    const u64 *h_arr[4] = {h_a_off, h_a_cap, h_ref_off, h_ref_n};
-    for (int i = 0; i < 4; ++i) memcpy(hs + (size_t)i * nb * 8, h_arr[i], nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_a_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
-    if ((rc = batch_upload(bt, st, ws + o_up, hs, up_bytes))) return rc;
-    const u64 *d_arr = (const u64 *)(ws + o_up);
-    const u64 *d_off = d_arr, *d_cap = d_arr + nb, *d_roff = d_arr + 2 * nb, *d_rn = d_arr + 3 * nb;
-    const u32 *d_base = (const u32 *)(ws + o_up + u_base);
-    if (ntiles) {
-        const u32 nt = (u32)ntiles, per_wg = (nt + TP_MAX_WGS - 1) / TP_MAX_WGS, wgs = (nt + per_wg - 1) / per_wg;
-        hipLaunchKernelGGL(compare_tiles, dim3(wgs), dim3(TP_THREADS), 0, st, d_a, d_off, d_cap, d_base, nblocks, d_a_n, d_ref,
-                           d_roff, d_rn, (u32 *)ws, nt, per_wg);
-    }
+    const TileExtra x[2] = {{h_ref_off, (size_t)nblocks * 8}, {h_ref_n, (size_t)nblocks * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_a_off, h_a_cap, TP_TILE, x, 2, 16, 0, &a)) return rc;
+    const u64 *d_roff = (const u64 *)a.extra[0], *d_rn = (const u64 *)a.extra[1];
+    if (a.nt)
+        hipLaunchKernelGGL(compare_tiles, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_a, a.off, a.cap, a.tbase, nblocks, d_a_n, d_ref,
+                           d_roff, d_rn, (u32 *)a.scratch, a.nt, a.per_wg);
     const u32 bw = (u32)nblocks < TP_MAX_BLOCK_WGS ? (u32)nblocks : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(compare_blocks, dim3(bw), dim3(TP_THREADS), 0, st, d_cap, d_base, nblocks, d_a_n, d_rn,
-                       (const uint4 *)ws, d_first, bt->d_err);
+    hipLaunchKernelGGL(compare_blocks, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblocks, d_a_n, d_rn,
+                       (const uint4 *)a.scratch, d_first, bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

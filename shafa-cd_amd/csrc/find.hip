@@ -299,58 +299,35 @@ __global__ __launch_bounds__(TP_THREADS) void find_emit(const u8 *__restrict__ d
 
 }  // namespace
 
-// workspace: [records: 16 B per tile of the capacities][block bases: 8 B a block][seam masks: 32 B a block], then what the
-// host uploads: [offsets][capacities][positions][tbase][flags, zero padded to 16][pattern, zero padded to 256].  The caller
-// has checked the arguments and that the tiles number fewer than 2^31.
+// workspace: tile_setup's with three extras — the positions, the flags (a byte a block) and the pattern, zero padded to
+// FIND_MAX; scratch: [records: 16 B per tile of the capacities][block bases: 8 B a block][seam masks: 32 B a block].  The caller
+// has checked the arguments.
 int find_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                     const u64 *d_in_n, const u8 *h_flags, const u64 *h_pos, const u8 *h_pat, u32 pat_n, u64 max_hits, u64 *d_hits,
                     u64 *d_count, u64 *d_total)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_in_cap[b], TP_TILE);
-    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
     const size_t nb = (size_t)nblocks;
-    const size_t o_base = (size_t)ntiles * 16, o_seam = o_base + nb * 8, o_up = (o_seam + nb * 32 + 15) & ~(size_t)15;
-    const size_t u_off = 0, u_cap = nb * 8, u_pos = 2 * nb * 8, u_base = 3 * nb * 8, u_flags = u_base + (nb + 1) * 4;
-    const size_t u_pat = (u_flags + nb + 15) & ~(size_t)15, up_bytes = u_pat + FIND_MAX;
-    int rc = batch_reserve(bt, st, o_up + up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memcpy(hs + u_off, h_in_off, nb * 8);
-    memcpy(hs + u_cap, h_in_cap, nb * 8);
-    memcpy(hs + u_pos, h_pos, nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_in_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_flags, 0, up_bytes - u_flags);
-    if (h_flags) memcpy(hs + u_flags, h_flags, nb);
-    memcpy(hs + u_pat, h_pat, pat_n);
+    u8 pat[FIND_MAX] = {};
+    memcpy(pat, h_pat, pat_n);
     u32 pat4 = 0;
     for (u32 i = 0; i < 4 && i < pat_n; ++i) pat4 |= (u32)h_pat[i] << (8 * i);
-    if ((rc = batch_upload(bt, st, ws + o_up, hs, up_bytes))) return rc;
-    const u64 *d_off = (const u64 *)(ws + o_up + u_off), *d_cap = (const u64 *)(ws + o_up + u_cap);
-    const u64 *d_pos = (const u64 *)(ws + o_up + u_pos);
-    const u32 *d_base = (const u32 *)(ws + o_up + u_base);
-    const u8 *d_flags = ws + o_up + u_flags, *d_pat = ws + o_up + u_pat;
-    u64 *rec = (u64 *)ws, *blk_base = (u64 *)(ws + o_base), *seam = (u64 *)(ws + o_seam);
-    const u32 nt = (u32)ntiles, per_wg = (nt + TP_MAX_WGS - 1) / TP_MAX_WGS, wgs = nt ? (nt + per_wg - 1) / per_wg : 0;
-    if (nt)
-        hipLaunchKernelGGL(find_tiles, dim3(wgs), dim3(TP_THREADS), 0, st, d_in, d_off, d_cap, d_base, nblocks, d_in_n, d_flags,
-                           d_pat, pat_n, pat4, rec, nt, per_wg);
+    const TileExtra x[3] = {{h_pos, nb * 8}, {h_flags, nb}, {pat, FIND_MAX}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_in_off, h_in_cap, TP_TILE, x, 3, 16, nb * 40, &a)) return rc;
+    const u64 *d_pos = (const u64 *)a.extra[0];
+    const u8 *d_flags = a.extra[1], *d_pat = a.extra[2];
+    u64 *rec = (u64 *)a.scratch, *blk_base = rec + 2 * (size_t)a.nt, *seam = blk_base + nb;
+    if (a.nt)
+        hipLaunchKernelGGL(find_tiles, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_in, a.off, a.cap, a.tbase, nblocks, d_in_n, d_flags,
+                           d_pat, pat_n, pat4, rec, a.nt, a.per_wg);
     const u32 bw = (u32)nblocks < TP_MAX_BLOCK_WGS ? (u32)nblocks : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(find_blocks, dim3(bw), dim3(TP_THREADS), 0, st, d_in, d_off, d_cap, d_base, nblocks, d_in_n, d_flags,
+    hipLaunchKernelGGL(find_blocks, dim3(bw), dim3(TP_THREADS), 0, st, d_in, a.off, a.cap, a.tbase, nblocks, d_in_n, d_flags,
                        d_pat, pat_n, rec, seam, d_count, bt->d_err);
     hipLaunchKernelGGL(find_order, dim3(1), dim3(TP_THREADS), 0, st, (const u64 *)d_count, nblocks, blk_base, d_total);
-    if (max_hits && nt)                              // a match needs a byte, a byte a tile
-        hipLaunchKernelGGL(find_emit, dim3(wgs), dim3(TP_THREADS), 0, st, d_in, d_off, d_cap, d_base, nblocks, d_in_n, d_flags,
+    if (max_hits && a.nt)                            // a match needs a byte, a byte a tile
+        hipLaunchKernelGGL(find_emit, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_in, a.off, a.cap, a.tbase, nblocks, d_in_n, d_flags,
                            d_pos, d_pat, pat_n, pat4, (const u64 *)rec, (const u64 *)seam, (const u64 *)blk_base,
-                           (const u64 *)d_count, max_hits, d_hits, nt, per_wg);
+                           (const u64 *)d_count, max_hits, d_hits, a.nt, a.per_wg);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

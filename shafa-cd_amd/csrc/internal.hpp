@@ -102,6 +102,45 @@ struct ParamsScope {
     ParamsScope &operator=(const ParamsScope &) = delete;
 };
 
+// the offset of the next `bytes` of an upload whose parts start at multiples of 16
+inline size_t take16(size_t &pos, size_t bytes)
+{
+    const size_t at = pos;
+    pos = (pos + bytes + 15) & ~(size_t)15;
+    return at;
+}
+
+// ---- the host set-up of a tile-walk launch (api.hip) -------------------------------------------
+// A launcher whose kernels walk the tiles of the blocks' capacities (tile_pass.hpp's TpWalk, seek.hip's spans) gets from
+// tile_setup, in the batch's workspace,
+//     [scratch: scratch_per_tile bytes per tile + scratch_fixed, for the kernels][offsets][capacities][extras ...][tbase]
+// every part at a multiple of 16 bytes and zero padded to the next; all but the scratch is put together in pinned staging and
+// uploaded in ONE batch_upload on `st`.  tbase[b] is the number of block b's first tile among the tiles of all blocks, nblocks + 1
+// entries of 32 bits; `unit` is the tile: TP_TILE bytes, elements or records, or the span.  An extra is a host array of the
+// caller's that its kernels read behind the capacities (NULL: zeros).
+// Returns SHAFA_LACK_OF_MEMORY for 2^31 tiles or more (tile_count) before anything is touched, then what batch_reserve,
+// batch_stage (SHAFA_LACK_OF_MEMORY) and batch_upload return.
+constexpr u32 TP_MAX_WGS = 16384;                  // a tile walk's workgroups per launch (64 a CU, 8 of them resident at a time)
+constexpr int TILE_EXTRAS = 3;
+struct TileExtra {
+    const void *h;
+    size_t bytes;
+};
+struct TileSetup {
+    const u64 *off, *cap;          // device pointers into the workspace
+    const u32 *tbase;
+    const u8 *extra[TILE_EXTRAS];
+    u8 *scratch;
+    u32 nt;                        // the tiles of all blocks
+    u32 per_wg, wgs;               // equal runs of tiles over at most TP_MAX_WGS workgroups (per_wg >= 1; no tile: no workgroup);
+                                   //   a launcher with a grid rule of its own takes nt alone
+};
+int tile_setup(Batch *bt, hipStream_t st, int nblocks, const u64 *h_off, const u64 *h_cap, u32 unit, const TileExtra *extras,
+               int nextras, size_t scratch_per_tile, size_t scratch_fixed, TileSetup *s);
+// the first block at which the capacities' tiles of `unit` number 2^31 or more (the kernels number them in 31 bits), nblocks
+// where they stay below; *ntiles (where asked for) is then their number
+int tile_count(int nblocks, const u64 *h_cap, u64 unit, u64 *ntiles = nullptr);
+
 // ---- per-op parameter records (device arrays) --------------------------------------------------
 struct EncBlk {
     const u8 *in;

@@ -90,12 +90,6 @@ __device__ __forceinline__ u32 merge_dword(const u32 (&p)[4 * E], int d)
     return pick4(p, s[0], s[1], s[2], s[3]);
 }
 
-__device__ __forceinline__ u8 byte_of(const uint4 &v, int k)
-{
-    const u32 x[4] = {v.x, v.y, v.z, v.w};
-    return (u8)(x[k >> 2] >> (8 * (k & 3)));
-}
-
 // ---- differences: the arithmetic on element-ordered dwords, E bytes an element.  At E = 1 and 2 a dword holds 4 or 2 elements
 // and the operations are SWAR (H: every element's top bit, L: its low bit); sums are carried in DiffT<E>, whose low 8 E bits count.
 template <int E> struct DiffT { using T = u32; };
@@ -282,7 +276,7 @@ __device__ __forceinline__ void split_store(const u32 (&w)[4 * E], u64 n, u64 e0
         else {
 #pragma unroll
             for (int k = 0; k < PL_UNIT; ++k)
-                if ((u32)k < c) gstore<u8>(dst + k, byte_of(o, k));
+                if ((u32)k < c) gstore<u8>(dst + k, tp_byte_of(o, k));
         }
     }
 }
@@ -437,13 +431,6 @@ __device__ __forceinline__ const u8 *base_of(const u8 *d_base, const u64 *d_boff
     return o == SHAFA_PLANES_NO_BASE ? nullptr : d_base + o;
 }
 
-// a block whose size is past its capacity: the walk has skipped its tiles (a capacity of 0 has none), this reports it
-__device__ __forceinline__ void planes_errors(const u64 *__restrict__ cap, const u64 *__restrict__ d_n, int nblk, int *__restrict__ err)
-{
-    for (u64 b = (u64)blockIdx.x * TP_THREADS + threadIdx.x; b < (u64)nblk; b += (u64)gridDim.x * TP_THREADS)
-        if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
-}
-
 // the split kernels' body.  XOR: block b's base region at d_base + d_boff[b]; DIFF: the folded differences
 template <int E, bool XOR, bool DIFF>
 __device__ __forceinline__ void split_blocks(const u8 *__restrict__ d_el, const u64 *__restrict__ off, const u64 *__restrict__ cap,
@@ -464,7 +451,7 @@ __device__ __forceinline__ void split_blocks(const u8 *__restrict__ d_el, const 
         default: split_tile<E, 3, XOR, DIFF>(wk, r, bs, d_planes, poff, lds); break;
         }
     }
-    planes_errors(cap, d_n, nblk, err);
+    tp_size_errors(cap, d_n, nblk, err);
 }
 
 // XOR: the _xor entry's launch; the plain entry's passes neither d_base nor d_boff
@@ -591,7 +578,7 @@ __device__ __forceinline__ void merge_unit(u8 *dst, u64 n, u64 e0, u32 sh, u32 r
         else {
 #pragma unroll
             for (int k = 0; k < 16; ++k)
-                if (ub + lo + k >= 0 && lo + k < cb) gstore<u8>(dst + (ub + lo + k), byte_of(o, k));
+                if (ub + lo + k >= 0 && lo + k < cb) gstore<u8>(dst + (ub + lo + k), tp_byte_of(o, k));
         }
     }
 }
@@ -629,7 +616,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_merge(u8 *__restrict__ d_el
         default: merge_tile<E, 4, XOR>(wk, sh, r, bs, d_planes, poff); break;
         }
     }
-    planes_errors(cap, d_n, nblk, err);
+    tp_size_errors(cap, d_n, nblk, err);
 }
 
 // ---- merge of the differences: three launches, none of which waits for another workgroup
@@ -733,91 +720,54 @@ __global__ __launch_bounds__(TP_THREADS) void planes_merge_diff(u8 *__restrict__
         default: merge_tile_diff<E, 4>(wk, sh, r, d_planes, poff, carry, wt, turn); break;
         }
     }
-    planes_errors(cap, d_n, nblk, err);
+    tp_size_errors(cap, d_n, nblk, err);
 }
 
-// d_boff non-NULL: the XOR kernels
+// the launches read tile_setup's workspace: extra 0 the plane offsets, extra 1 (the XOR kernels: non-NULL) the base offsets,
+// the scratch (the merge of differences) the tile sums
 template <int E>
-void planes_launch(bool merge, u32 wgs, hipStream_t st, u8 *d_el, const u64 *off, const u64 *cap, const u32 *tbase, int nblk,
-                   const u64 *d_n, u8 *d_planes, const u64 *poff, int *err, u32 nt, u32 per_wg, const u8 *d_base,
-                   const u64 *d_boff)
+void planes_launch(bool merge, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err,
+                   const u8 *d_base)
 {
+    const u64 *poff = (const u64 *)a.extra[0], *boff = (const u64 *)a.extra[1];
     if (merge)
-        hipLaunchKernelGGL((d_boff ? planes_merge<E, true> : planes_merge<E, false>), dim3(wgs), dim3(TP_THREADS), 0, st, d_el, off,
-                           cap, tbase, nblk, d_n, (const u8 *)d_planes, poff, err, nt, per_wg, d_base, d_boff);
+        hipLaunchKernelGGL((boff ? planes_merge<E, true> : planes_merge<E, false>), dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off,
+                           a.cap, a.tbase, nblk, d_n, (const u8 *)d_planes, poff, err, a.nt, a.per_wg, d_base, boff);
     else
-        hipLaunchKernelGGL((d_boff ? planes_split<E, true> : planes_split<E, false>), dim3(wgs), dim3(TP_THREADS), 0, st,
-                           (const u8 *)d_el, off, cap, tbase, nblk, d_n, d_planes, poff, err, nt, per_wg, d_base, d_boff);
+        hipLaunchKernelGGL((boff ? planes_split<E, true> : planes_split<E, false>), dim3(a.wgs), dim3(TP_THREADS), 0, st,
+                           (const u8 *)d_el, a.off, a.cap, a.tbase, nblk, d_n, d_planes, poff, err, a.nt, a.per_wg, d_base, boff);
 }
 
-// what planes_upload leaves in the workspace for a launch
-struct PlanesWs {
-    const u64 *off, *cap, *poff, *boff;
-    const u32 *tbase;
-    u64 *sums;
-    u32 nt, per_wg, wgs;
-};
-
 template <int E>
-void planes_diff_launch(bool merge, const PlanesWs &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err)
+void planes_diff_launch(bool merge, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err)
 {
+    const u64 *poff = (const u64 *)a.extra[0];
+    u64 *sums = (u64 *)a.scratch;
     if (!merge) {
         hipLaunchKernelGGL(planes_split_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
-                           d_n, d_planes, a.poff, err, a.nt, a.per_wg);
+                           d_n, d_planes, poff, err, a.nt, a.per_wg);
         return;
     }
     if (a.nt)
         hipLaunchKernelGGL(planes_diff_sums<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
-                           d_n, (const u8 *)d_planes, a.poff, a.nt, a.per_wg, a.sums);
+                           d_n, (const u8 *)d_planes, poff, a.nt, a.per_wg, sums);
     const u32 bw = (u32)nblk < TP_MAX_BLOCK_WGS ? (u32)nblk : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(planes_diff_scan, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblk, d_n, a.sums);
+    hipLaunchKernelGGL(planes_diff_scan, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblk, d_n, sums);
     hipLaunchKernelGGL(planes_merge_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
-                       (const u8 *)d_planes, a.poff, err, a.nt, a.per_wg, (const u64 *)a.sums);
+                       (const u8 *)d_planes, poff, err, a.nt, a.per_wg, (const u64 *)sums);
 }
 
 }  // namespace
 
-// planes_upload: the launch arguments every entry shares, in the workspace: [offsets][capacities][plane offsets: elem a block][base offsets:
-// with h_base_off][tbase, zero padded to 16], all of it uploaded by the host, and behind it, with `sums`, 8 bytes per tile of the
-// capacities that the kernels fill.  The caller has checked the arguments and that the tiles number fewer than 2^31.
-static int planes_upload(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u64 *h_off, const u64 *h_cap,
-                         const u64 *h_plane_off, const u64 *h_base_off, bool sums, PlanesWs &a)
+// the launch arguments every entry shares.  workspace: tile_setup's with the plane offsets (elem a block) and, with h_base_off,
+// the base offsets as extras; scratch, with `sums`: 8 bytes per tile of the capacities that the kernels fill.  The caller has
+// checked the arguments.
+static int planes_setup(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u64 *h_off, const u64 *h_cap,
+                        const u64 *h_plane_off, const u64 *h_base_off, bool sums, TileSetup &a)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_cap[b], TP_TILE);
-    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
-    const size_t nb = (size_t)nblocks;
-    const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_boff = u_poff + nb * elem * 8;
-    const size_t u_base = u_boff + (h_base_off ? nb * 8 : 0);
-    const size_t up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, up_bytes + (sums ? (size_t)ntiles * 8 : 0));
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memcpy(hs + u_off, h_off, nb * 8);
-    memcpy(hs + u_cap, h_cap, nb * 8);
-    memcpy(hs + u_poff, h_plane_off, nb * elem * 8);
-    if (h_base_off) memcpy(hs + u_boff, h_base_off, nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
-    if ((rc = batch_upload(bt, st, ws, hs, up_bytes))) return rc;
-    a.off = (const u64 *)(ws + u_off);
-    a.cap = (const u64 *)(ws + u_cap);
-    a.poff = (const u64 *)(ws + u_poff);
-    a.boff = h_base_off ? (const u64 *)(ws + u_boff) : nullptr;
-    a.tbase = (const u32 *)(ws + u_base);
-    a.sums = sums ? (u64 *)(ws + up_bytes) : nullptr;
-    // without a tile one workgroup still looks for blocks past a capacity of 0
-    a.nt = (u32)ntiles;
-    a.per_wg = a.nt ? (a.nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1;
-    a.wgs = a.nt ? (a.nt + a.per_wg - 1) / a.per_wg : 1;
+    const TileExtra x[2] = {{h_plane_off, (size_t)nblocks * elem * 8}, {h_base_off, (size_t)nblocks * 8}};
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, h_base_off ? 2 : 1, sums ? 8 : 0, 0, &a)) return rc;
+    if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
     return SHAFA_SUCCESS;
 }
 
@@ -825,13 +775,13 @@ static int planes_upload(Batch *bt, hipStream_t st, int nblocks, u32 elem, const
 int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off, const u64 *h_cap,
                       const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u8 *d_base, const u64 *h_base_off)
 {
-    PlanesWs a;
-    if (int rc = planes_upload(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, h_base_off, false, a)) return rc;
+    TileSetup a;
+    if (int rc = planes_setup(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, h_base_off, false, a)) return rc;
     switch (elem) {
-    case 1: planes_launch<1>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
-    case 2: planes_launch<2>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
-    case 4: planes_launch<4>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
-    default: planes_launch<8>(merge, a.wgs, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes, a.poff, bt->d_err, a.nt, a.per_wg, d_base, a.boff); break;
+    case 1: planes_launch<1>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err, d_base); break;
+    case 2: planes_launch<2>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err, d_base); break;
+    case 4: planes_launch<4>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err, d_base); break;
+    default: planes_launch<8>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err, d_base); break;
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
@@ -841,8 +791,8 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
 int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off)
 {
-    PlanesWs a;
-    if (int rc = planes_upload(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, nullptr, merge, a)) return rc;
+    TileSetup a;
+    if (int rc = planes_setup(bt, st, nblocks, elem, h_off, h_cap, h_plane_off, nullptr, merge, a)) return rc;
     switch (elem) {
     case 1: planes_diff_launch<1>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     case 2: planes_diff_launch<2>(merge, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;

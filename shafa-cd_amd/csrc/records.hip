@@ -82,19 +82,6 @@ struct RcPass {
     }
 };
 
-// a block whose size is past its capacity: the walk has skipped its tiles (a capacity of 0 has none), this reports it
-__device__ __forceinline__ void records_errors(const u64 *__restrict__ cap, const u64 *__restrict__ d_n, int nblk, int *__restrict__ err)
-{
-    for (u64 b = (u64)blockIdx.x * TP_THREADS + threadIdx.x; b < (u64)nblk; b += (u64)gridDim.x * TP_THREADS)
-        if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
-}
-
-__device__ __forceinline__ u8 rc_byte_of(const uint4 &v, int k)
-{
-    const u32 x[4] = {v.x, v.y, v.z, v.w};
-    return (u8)(x[k >> 2] >> (8 * (k & 3)));
-}
-
 // the LDS bytes of a unit's 16 record bytes: unit u of the pass = column j, group g; byte i is image byte sh + (16 g + i) W + j,
 // which lies in image row g or, from t = sh + j + i W >= 16 W on, in row g + 1 (t < 32 W)
 struct RcUnit {
@@ -162,13 +149,13 @@ __global__ __launch_bounds__(TP_THREADS) void records_split(const u8 *__restrict
                     const u32 c = (u32)(tile_end - r0);
 #pragma unroll
                     for (int k = 0; k < 16; ++k)
-                        if ((u32)k < c) gstore<u8>(dst + k, rc_byte_of(ov, k));
+                        if ((u32)k < c) gstore<u8>(dst + k, tp_byte_of(ov, k));
                 }
             }
             lds_barrier();                                                 // the next pass writes the image
         }
     }
-    records_errors(cap, d_n, nblk, err);
+    tp_size_errors(cap, d_n, nblk, err);
 }
 
 __global__ __launch_bounds__(TP_THREADS) void records_merge(u8 *__restrict__ d_rec, const u64 *__restrict__ off,
@@ -195,7 +182,7 @@ __global__ __launch_bounds__(TP_THREADS) void records_merge(u8 *__restrict__ d_r
                 const RcUnit un(u, ps, mg, w);
                 const uint4 v = gload_nt<uint4>(d_planes + poff[un.j] + e0 + 16ull * un.g);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) lds8[un.at(i, w)] = rc_byte_of(v, i);
+                for (int i = 0; i < 16; ++i) lds8[un.at(i, w)] = tp_byte_of(v, i);
             }
             lds_barrier();
 #pragma nounroll
@@ -208,55 +195,33 @@ __global__ __launch_bounds__(TP_THREADS) void records_merge(u8 *__restrict__ d_r
                 else {
 #pragma unroll
                     for (int i = 0; i < 16; ++i)
-                        if (lo + i >= 0 && (u32)(lo + i) < ps.nbytes) gstore<u8>(dst + i, rc_byte_of(v, i));
+                        if (lo + i >= 0 && (u32)(lo + i) < ps.nbytes) gstore<u8>(dst + i, tp_byte_of(v, i));
                 }
             }
             lds_barrier();                                                 // the next pass writes the image
         }
     }
-    records_errors(cap, d_n, nblk, err);
+    tp_size_errors(cap, d_n, nblk, err);
 }
 
 }  // namespace
 
-// The launch arguments in the workspace: [offsets][capacities][column offsets: width a block][tbase, zero padded to 16], all of
-// it uploaded by the host.  The caller has checked the arguments and that the tiles number fewer than 2^31.
+// workspace: tile_setup's with one extra, the column offsets (width a block), and no scratch.  The caller has checked the
+// arguments.
 int records_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 width, bool merge, u8 *d_rec, const u64 *h_off, const u64 *h_cap,
                        const u64 *d_n, u8 *d_planes, const u64 *h_plane_off)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_cap[b], TP_TILE);
-    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
-    const size_t nb = (size_t)nblocks;
-    const size_t u_off = 0, u_cap = nb * 8, u_poff = 2 * nb * 8, u_base = u_poff + nb * width * 8;
-    const size_t up_bytes = (u_base + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memcpy(hs + u_off, h_off, nb * 8);
-    memcpy(hs + u_cap, h_cap, nb * 8);
-    memcpy(hs + u_poff, h_plane_off, nb * width * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
-    if ((rc = batch_upload(bt, st, ws, hs, up_bytes))) return rc;
-    const u64 *off = (const u64 *)(ws + u_off), *cap = (const u64 *)(ws + u_cap), *poff = (const u64 *)(ws + u_poff);
-    const u32 *tbase = (const u32 *)(ws + u_base);
-    // without a tile one workgroup still looks for blocks past a capacity of 0
-    const u32 nt = (u32)ntiles, per_wg = nt ? (nt + TP_MAX_WGS - 1) / TP_MAX_WGS : 1, wgs = nt ? (nt + per_wg - 1) / per_wg : 1;
+    const TileExtra x = {h_plane_off, (size_t)nblocks * width * 8};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, &x, 1, 0, 0, &a)) return rc;
+    const u64 *poff = (const u64 *)a.extra[0];
+    const u32 wgs = a.wgs ? a.wgs : 1;               // without a tile one workgroup still looks for blocks past a capacity of 0
     if (merge)
-        hipLaunchKernelGGL(records_merge, dim3(wgs), dim3(TP_THREADS), 0, st, d_rec, off, cap, tbase, nblocks, d_n,
-                           (const u8 *)d_planes, poff, bt->d_err, nt, per_wg, width);
+        hipLaunchKernelGGL(records_merge, dim3(wgs), dim3(TP_THREADS), 0, st, d_rec, a.off, a.cap, a.tbase, nblocks, d_n,
+                           (const u8 *)d_planes, poff, bt->d_err, a.nt, a.per_wg, width);
     else
-        hipLaunchKernelGGL(records_split, dim3(wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_rec, off, cap, tbase, nblocks, d_n,
-                           d_planes, poff, bt->d_err, nt, per_wg, width);
+        hipLaunchKernelGGL(records_split, dim3(wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_rec, a.off, a.cap, a.tbase, nblocks, d_n,
+                           d_planes, poff, bt->d_err, a.nt, a.per_wg, width);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

@@ -314,48 +314,26 @@ __global__ __launch_bounds__(TP_THREADS) void rle_ehist_blocks(const u64 *__rest
 
 }  // namespace
 
-// tp_launch's layout and uploads (tile_pass.hpp) with the counts: they are zeroed first, the tiles kernel adds to them.
-// A workgroup takes at least a few tiles where the call has many, so that clearing and summing its 32 KiB of bins is paid
-// once per several tiles.
+// workspace: tp_launch's (tile_pass.hpp), with the counts: they are zeroed first, the tiles kernel adds to them.  The grid is
+// this launcher's own: a workgroup takes at least a few tiles where the call has many, so that clearing and summing its 32 KiB
+// of bins is paid once per several tiles.
 int rleehist_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                         const u64 *d_in_n, u64 *d_out_n, u64 *d_freq)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_in_cap[b], TP_TILE);
-    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
-    const size_t nb = (size_t)nblocks;
-    const size_t o_rec = 0, o_up = (size_t)ntiles * 16;
-    const size_t u_off = 0, u_cap = nb * 8, u_base = 2 * nb * 8, up_bytes = (2 * nb * 8 + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, o_up + up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memcpy(hs + u_off, h_in_off, nb * 8);
-    memcpy(hs + u_cap, h_in_cap, nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_in_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
-    if ((rc = batch_upload(bt, st, ws + o_up, hs, up_bytes))) return rc;
-    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * 256 * sizeof(u64), st));
-    const u64 *d_off = (const u64 *)(ws + o_up + u_off), *d_cap = (const u64 *)(ws + o_up + u_cap);
-    const u32 *d_base = (const u32 *)(ws + o_up + u_base);
-    if (ntiles) {
-        const u32 nt = (u32)ntiles, few = (nt + 4095u) / 4096u;
-        u32 per_wg = (nt + TP_MAX_WGS - 1) / TP_MAX_WGS;
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_in_off, h_in_cap, TP_TILE, nullptr, 0, 16, 0, &a)) return rc;
+    HIP_TRY(hipMemsetAsync(d_freq, 0, (size_t)nblocks * 256 * sizeof(u64), st));
+    if (a.nt) {
+        const u32 nt = a.nt, few = (nt + 4095u) / 4096u;
+        u32 per_wg = a.per_wg;
         if (per_wg < 8u) per_wg = few < 8u ? (few > per_wg ? few : per_wg) : 8u;
         const u32 wgs = (nt + per_wg - 1) / per_wg;
-        hipLaunchKernelGGL(rle_ehist_tiles, dim3(wgs), dim3(TP_THREADS), 0, st, d_in, d_off, d_cap, d_base, nblocks, d_in_n,
-                           (uint4 *)(ws + o_rec), nt, per_wg, d_freq);
+        hipLaunchKernelGGL(rle_ehist_tiles, dim3(wgs), dim3(TP_THREADS), 0, st, d_in, a.off, a.cap, a.tbase, nblocks, d_in_n,
+                           (uint4 *)a.scratch, nt, per_wg, d_freq);
     }
     const u32 bw = (u32)nblocks < TP_MAX_BLOCK_WGS ? (u32)nblocks : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(rle_ehist_blocks, dim3(bw), dim3(TP_THREADS), 0, st, d_cap, d_base, nblocks, d_in_n,
-                       (const uint4 *)(ws + o_rec), d_out_n, d_freq, bt->d_err);
+    hipLaunchKernelGGL(rle_ehist_blocks, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblocks, d_in_n,
+                       (const uint4 *)a.scratch, d_out_n, d_freq, bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

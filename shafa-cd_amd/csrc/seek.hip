@@ -473,55 +473,25 @@ __global__ __launch_bounds__(RS_LANES) void read_spans(const u8 *__restrict__ d_
     }
 }
 
-// the offset of the next `bytes` of an upload whose parts start at multiples of 16
-inline size_t take(size_t &pos, size_t bytes)
-{
-    const size_t at = pos;
-    pos = (pos + bytes + 15) & ~(size_t)15;
-    return at;
-}
-
 }  // namespace
 
-// workspace: [records: 16 B per span of the capacities][offsets][capacities][first checkpoints][sbase, padded to 16]; the last
-// four are what the host uploads.  The caller has checked that the spans number fewer than 2^31.
+// workspace: tile_setup's with the span as the tile and one extra, the first checkpoints; scratch: the records, 16 B per span
+// of the capacities.  The grids are SK_*'s.
 int seek_index_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                           const u64 *d_in_n, const shafa_code_table *d_tables, u32 span, int flags, const u64 *h_ckpt_first,
                           u64 *d_ckpt, u32 *d_status, u64 *d_out_n)
 {
-    u64 nspans = 0;
-    for (int b = 0; b < nblocks; ++b) nspans += ceil_div_u64(h_in_cap[b], span);
-    const size_t nb = (size_t)nblocks, o_up = (size_t)nspans * 16;
-    size_t up_bytes = 0;
-    const size_t u_off = take(up_bytes, nb * 8), u_cap = take(up_bytes, nb * 8), u_ck = take(up_bytes, nb * 8);
-    const size_t u_base = take(up_bytes, (nb + 1) * 4);
-    int rc = batch_reserve(bt, st, o_up + up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memset(hs, 0, up_bytes);
-    memcpy(hs + u_off, h_in_off, nb * 8);
-    memcpy(hs + u_cap, h_in_cap, nb * 8);
-    memcpy(hs + u_ck, h_ckpt_first, nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_in_cap[b], span);
-    }
-    hb[nblocks] = base;
-    if ((rc = batch_upload(bt, st, ws + o_up, hs, up_bytes))) return rc;
-    const u64 *d_off = (const u64 *)(ws + o_up + u_off), *d_cap = (const u64 *)(ws + o_up + u_cap);
-    const u64 *d_ck = (const u64 *)(ws + o_up + u_ck);
-    const u32 *d_base = (const u32 *)(ws + o_up + u_base);
-    if (nspans) {
-        const u64 want = ceil_div_u64(nspans, SK_THREADS / 64);
-        hipLaunchKernelGGL(seek_spans, dim3((u32)(want < SK_MAX_WGS ? want : SK_MAX_WGS)), dim3(SK_THREADS), 0, st, d_in, d_off,
-                           d_cap, d_base, nblocks, d_in_n, d_tables, span, flags, (uint4 *)ws, (u32)nspans);
+    const TileExtra x = {h_ckpt_first, (size_t)nblocks * 8};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_in_off, h_in_cap, span, &x, 1, 16, 0, &a)) return rc;
+    const u64 *d_ck = (const u64 *)a.extra[0];
+    if (a.nt) {
+        const u64 want = ceil_div_u64(a.nt, SK_THREADS / 64);
+        hipLaunchKernelGGL(seek_spans, dim3((u32)(want < SK_MAX_WGS ? want : SK_MAX_WGS)), dim3(SK_THREADS), 0, st, d_in, a.off,
+                           a.cap, a.tbase, nblocks, d_in_n, d_tables, span, flags, (uint4 *)a.scratch, a.nt);
     }
     hipLaunchKernelGGL(seek_blocks, dim3((u32)nblocks < SK_MAX_WGS ? (u32)nblocks : SK_MAX_WGS), dim3(SK_THREADS), 0, st, d_in,
-                       d_off, d_cap, d_base, nblocks, d_in_n, d_tables, span, flags, (const uint4 *)ws, d_ck, d_ckpt, d_status,
+                       a.off, a.cap, a.tbase, nblocks, d_in_n, d_tables, span, flags, (const uint4 *)a.scratch, d_ck, d_ckpt, d_status,
                        d_out_n, bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
@@ -551,9 +521,9 @@ int read_spans_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_fi
     if (slots_max > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
     const size_t nb = (size_t)nblocks, ni = (size_t)nitems;
     size_t up_bytes = 0;
-    const size_t u_off = take(up_bytes, nb * 8), u_n = take(up_bytes, nb * 8), u_sym = take(up_bytes, nb * 8);
-    const size_t u_ck = take(up_bytes, nb * 8), u_items = take(up_bytes, ni * sizeof(RsItem));
-    const size_t u_tasks = take(up_bytes, (size_t)((slots_max + RS_LANES - 1) / RS_LANES * RS_LANES) * 8);
+    const size_t u_off = take16(up_bytes, nb * 8), u_n = take16(up_bytes, nb * 8), u_sym = take16(up_bytes, nb * 8);
+    const size_t u_ck = take16(up_bytes, nb * 8), u_items = take16(up_bytes, ni * sizeof(RsItem));
+    const size_t u_tasks = take16(up_bytes, (size_t)((slots_max + RS_LANES - 1) / RS_LANES * RS_LANES) * 8);
     int rc = batch_reserve(bt, st, up_bytes);
     if (rc) return rc;
     u8 *ws = (u8 *)bt->d_ws;

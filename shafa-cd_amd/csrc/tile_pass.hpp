@@ -8,9 +8,9 @@
 //   tp_lane_load    the lane's 32 bytes of a tile
 //   tp_wave_reduce  an ordered reduction of summaries across the wave
 //   tp_blocks       the blocks kernel's body over a summary trait
-//   tp_launch       the host launcher: workspace, upload, both launches
-// The tiles of all blocks are numbered consecutively (from the capacities, on the host) and dealt to the workgroups in equal
-// runs, so the grid is the call's tile count (at most TP_MAX_WGS workgroups) whatever the mix of block sizes.
+//   tp_launch       the host launcher: both launches, on the workspace that tile_setup (internal.hpp) lays out and uploads
+// The tiles of all blocks are numbered consecutively (from the capacities, on the host: tile_setup) and dealt to the workgroups
+// in equal runs, so the grid is the call's tile count (at most TP_MAX_WGS workgroups) whatever the mix of block sizes.
 #pragma once
 
 #include "common.hpp"
@@ -21,7 +21,7 @@ namespace {
 constexpr int TP_THREADS = 256;
 constexpr int TP_BPL = 32;                         // bytes per lane
 constexpr int TP_TILE = TP_THREADS * TP_BPL;
-constexpr u32 TP_MAX_WGS = 16384;                  // tiles kernel: workgroups per launch (64 a CU, 8 of them resident at a time)
+// (TP_MAX_WGS, the tiles kernel's workgroups per launch, is internal.hpp's: tile_setup deals the tiles out)
 constexpr u32 TP_MAX_BLOCK_WGS = 1u << 20;         // blocks kernel: workgroups per launch (grid-stride over the blocks)
 
 // the block of global tile t: the largest b with tbase[b] <= t (tbase is non-decreasing, tbase[0] = 0, tbase[nblk] > t);
@@ -112,6 +112,21 @@ __device__ __forceinline__ u32 tp_lane_load(const u8 *in, u64 pos0, u64 n, u32 (
     return nvalid;
 }
 
+// byte k of a 16-byte word
+__device__ __forceinline__ u8 tp_byte_of(const uint4 &v, int k)
+{
+    const u32 x[4] = {v.x, v.y, v.z, v.w};
+    return (u8)(x[k >> 2] >> (8 * (k & 3)));
+}
+
+// for a pass without a blocks kernel (planes.hip, records.hip): a block whose size is past its capacity — the walk has skipped
+// its tiles (a capacity of 0 has none), this reports it
+__device__ __forceinline__ void tp_size_errors(const u64 *__restrict__ cap, const u64 *__restrict__ d_n, int nblk, int *__restrict__ err)
+{
+    for (u64 b = (u64)blockIdx.x * TP_THREADS + threadIdx.x; b < (u64)nblk; b += (u64)gridDim.x * TP_THREADS)
+        if (d_n[b] > cap[b]) set_error(err + b, SHAFA_OUTSIDE_MODULE);
+}
+
 // A summary trait S: Agg (the summary of a piece), then(a, b) (associative: a's piece, then b's) and from_lane(a, d) (lane
 // l + d's a).  After the step of distance d lane l holds lanes [l, l + 2 d) of the wave: lane 0 ends with the wave's.
 template <typename S>
@@ -169,42 +184,17 @@ __device__ __forceinline__ void tp_blocks(const u64 *__restrict__ in_cap, const 
 using TpTilesKernel = void (*)(const u8 *, const u64 *, const u64 *, const u32 *, int, const u64 *, uint4 *, u32, u32);
 using TpBlocksKernel = void (*)(const u64 *, const u32 *, int, const u64 *, const uint4 *, u64 *, int *);
 
-// workspace: [records: 16 B per tile of the capacities][offsets][capacities][tbase, zero padded to 16]; the last three are
-// what the host uploads
+// workspace: tile_setup's with no extra; scratch: the records, 16 B per tile of the capacities
 inline int tp_launch(TpTilesKernel tiles, TpBlocksKernel blocks, Batch *bt, hipStream_t st, int nblocks, const u8 *d_in,
                      const u64 *h_in_off, const u64 *h_in_cap, const u64 *d_in_n, u64 *d_out_n)
 {
-    u64 ntiles = 0;
-    for (int b = 0; b < nblocks; ++b) ntiles += ceil_div_u64(h_in_cap[b], TP_TILE);
-    if (ntiles > 0x7FFFFFFFull) return SHAFA_LACK_OF_MEMORY;
-    const size_t nb = (size_t)nblocks;
-    const size_t o_rec = 0, o_up = (size_t)ntiles * 16;
-    const size_t u_off = 0, u_cap = nb * 8, u_base = 2 * nb * 8, up_bytes = (2 * nb * 8 + (nb + 1) * 4 + 15) & ~(size_t)15;
-    int rc = batch_reserve(bt, st, o_up + up_bytes);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    memcpy(hs + u_off, h_in_off, nb * 8);
-    memcpy(hs + u_cap, h_in_cap, nb * 8);
-    u32 *hb = (u32 *)(hs + u_base);
-    u32 base = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        hb[b] = base;
-        base += (u32)ceil_div_u64(h_in_cap[b], TP_TILE);
-    }
-    hb[nblocks] = base;
-    memset(hs + u_base + (nb + 1) * 4, 0, up_bytes - (u_base + (nb + 1) * 4));
-    if ((rc = batch_upload(bt, st, ws + o_up, hs, up_bytes))) return rc;
-    const u64 *d_off = (const u64 *)(ws + o_up + u_off), *d_cap = (const u64 *)(ws + o_up + u_cap);
-    const u32 *d_base = (const u32 *)(ws + o_up + u_base);
-    if (ntiles) {
-        const u32 nt = (u32)ntiles, per_wg = (nt + TP_MAX_WGS - 1) / TP_MAX_WGS, wgs = (nt + per_wg - 1) / per_wg;
-        hipLaunchKernelGGL(tiles, dim3(wgs), dim3(TP_THREADS), 0, st, d_in, d_off, d_cap, d_base, nblocks, d_in_n,
-                           (uint4 *)(ws + o_rec), nt, per_wg);
-    }
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_in_off, h_in_cap, TP_TILE, nullptr, 0, 16, 0, &a)) return rc;
+    if (a.nt)
+        hipLaunchKernelGGL(tiles, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_in, a.off, a.cap, a.tbase, nblocks, d_in_n,
+                           (uint4 *)a.scratch, a.nt, a.per_wg);
     const u32 bw = (u32)nblocks < TP_MAX_BLOCK_WGS ? (u32)nblocks : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(blocks, dim3(bw), dim3(TP_THREADS), 0, st, d_cap, d_base, nblocks, d_in_n, (const uint4 *)(ws + o_rec),
+    hipLaunchKernelGGL(blocks, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblocks, d_in_n, (const uint4 *)a.scratch,
                        d_out_n, bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
