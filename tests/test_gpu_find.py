@@ -7,7 +7,8 @@ The shapes are the smallest at which the kernels can go wrong: a lane is 32 byte
 most 255.  Every region lies at one of the alignments 0, 1, 15, 16, 17 in a buffer whose guard and slack bytes are copies of
 the pattern, so a read in front of a region or behind d_in_n shows up as a wrong count.  The background is seeded random bytes
 over four symbols, the patterns are drawn from the same four: prefixes of the pattern occur often and the filter on the first
-four bytes passes many false candidates."""
+four bytes passes many false candidates.  The full range of alignments, 0 .. 15 at every region size, is
+test_gpu_every_alignment.py's."""
 import bisect
 
 import numpy as np
@@ -50,13 +51,14 @@ def _oracle(regions, flags, pat):
     return counts, hits
 
 
-def _place(regions, pat, slack):
+def _place(regions, pat, slack, aligns=ALIGN):
     """The regions in one host buffer made of copies of the pattern, a copy ending right in front of each region and one
-    starting right behind its bytes (its slack, then its guard); region i at alignment ALIGN[i % 5] -> (buffer, offsets, caps)"""
+    starting right behind its bytes (its slack, then its guard); region i at alignment aligns[i % len(aligns)] (ALIGN[i % 5]
+    unless the caller brings its own) -> (buffer, offsets, caps)"""
     m = len(pat)
     off, cap, pos = [], [], 0
     for i, r in enumerate(regions):
-        pos = (pos + m + 32 + 255) // 256 * 256 + 32 * (i % 3) + ALIGN[i % len(ALIGN)]
+        pos = (pos + m + 32 + 255) // 256 * 256 + 32 * (i % 3) + aligns[i % len(aligns)]
         off.append(pos)
         cap.append(len(r) + (slack[i] if slack else 0))
         pos += cap[-1]
@@ -70,11 +72,13 @@ def _place(regions, pat, slack):
 
 
 class _Run:
-    """one find_dev call on real regions -> counts, total, hits (the whole array, guard values behind), per-block codes"""
+    """one find_dev call on real regions -> counts, total, hits (the whole array, guard values behind), per-block codes;
+    `addr`: the device address of every region"""
 
-    def __init__(self, shafa, regions, flags, pat, max_hits=None, slack=None, over=(), pos=None, append=None, null_hits=False):
+    def __init__(self, shafa, regions, flags, pat, max_hits=None, slack=None, over=(), pos=None, append=None, null_hits=False,
+                 aligns=ALIGN):
         nb = len(regions)
-        buf, self.off, self.cap = _place(regions, pat, slack)
+        buf, self.off, self.cap = _place(regions, pat, slack, aligns)
         self.pos = pos if pos is not None else [(i << 34) + 7 * i for i in range(nb)]
         sizes = [c + 1 + i if i in over else len(r) for i, (r, c) in enumerate(zip(regions, self.cap))]
         self.regions = [b"" if i in over else r for i, r in enumerate(regions)]      # what the call may look at
@@ -92,6 +96,7 @@ class _Run:
         import torch
         nb, max_hits = len(sizes), self.max_hits
         d_in = torch.from_numpy(buf.copy()).to(_dev())
+        self.addr = [d_in.data_ptr() + o for o in self.off]
         d_n = torch.tensor(sizes, dtype=torch.int64).to(_dev())
         if append is None:
             self.d_hits = torch.full((max_hits + 8,), GUARD, dtype=torch.int64, device=_dev())

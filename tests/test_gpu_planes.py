@@ -6,7 +6,7 @@ The shapes are the smallest at which the kernels can go wrong: a lane transposes
 elements, the element side lies at the byte alignments 0, 1, 3, 8, 15.  Every buffer is 0xA5 where no data lies and is compared
 whole, so a byte written in front of a region, behind a plane's d_n bytes or into a guard shows up.  The tiles are numbered
 from the capacities: a capacity of 2^28 elements with few real ones gives every workgroup a run of several tiles without the
-memory.
+memory.  The full range of alignments, 0 .. 15 against every end of the region mod 16, is test_gpu_every_alignment.py's.
 
 A compressed plane is compress_many's dict with the files' names as keys; shafa.plane_files(entry) names the two of them that
 decompress_files takes (the issue's `decompress_files(**entry)` with the keyword names filled in)."""

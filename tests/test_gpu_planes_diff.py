@@ -6,7 +6,8 @@ expectation is np.cumsum of the unfolded z.  Nothing is compared with device cod
 The shapes are the borders of the kernels: a lane has 16 elements, a wave 1024, a pass of the workgroup 4096, a tile
 T = PLANES_TILE, and merge's scan kernel takes a block's tiles 256 at a time.  The data is uniformly random bit patterns whose
 first element is M / 2 or more: every difference wraps, and one wrong carry spoils everything behind it.  Every buffer holds 0xA5
-where no data lies, every region has 16 guard bytes or more around it, and every comparison is of whole images."""
+where no data lies, every region has 16 guard bytes or more around it, and every comparison is of whole images.  The full
+range of alignments, 0 .. 15 against every end of the region mod 16, is test_gpu_every_alignment.py's."""
 import numpy as np
 import pytest
 
@@ -70,9 +71,9 @@ def _data(kind, n, k, rng):
 class _Layout:
     """blocks (n elements of `kind`, element side at alignment a) of k-byte elements in two host images: `el` the element side
     and `pl` numpy's planes of the folded differences, both FILL where no data lies; 16 guard bytes or more around every
-    region"""
+    region.  raw: the blocks' bytes, where the caller brings data of its own instead of a kind's."""
 
-    def __init__(self, k, blocks, seed, a_out=None):
+    def __init__(self, k, blocks, seed, a_out=None, raw=None):
         rng = np.random.default_rng(seed)
         self.k, self.n = k, [b[0] for b in blocks]
         self.off, self.poff = [], []
@@ -84,7 +85,8 @@ class _Layout:
             for _ in range(k):
                 self.poff.append(ppos)
                 ppos += _al16(n) + 32
-        self.raw = [_data(b[2] if len(b) > 2 else "random", b[0], k, rng) for b in blocks]
+        self.raw = [_data(b[2] if len(b) > 2 else "random", b[0], k, rng) for b in blocks] if raw is None else list(raw)
+        assert [len(r) for r in self.raw] == [n * k for n in self.n]
         self.el = np.full(pos + 80, FILL, np.uint8)
         self.pl = np.full(ppos + 16, FILL, np.uint8)
         for b, n in enumerate(self.n):

@@ -6,7 +6,8 @@ The shapes are test_gpu_planes.py's, the smallest at which the kernels can go wr
 T = PLANES_TILE elements, and here the element side and the base side each lie at a byte alignment of their own — (0, 0) with
 4096 elements or more takes the coalesced pass through LDS, every other pair the direct loads with the base's shift picked apart
 from the element side's.  Three host images (element side, base side, plane side) are 0xA5 where no data lies, every region
-has 16 guard bytes or more around it, and every comparison is of whole images."""
+has 16 guard bytes or more around it, and every comparison is of whole images.  All 256 (element, base) alignment pairs are
+test_gpu_every_alignment.py's."""
 import numpy as np
 import pytest
 
