@@ -935,7 +935,10 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_ends(const DecBlk *__restrict
 // The stream sits in LDS one row per chunk (8 words + the next row's first: rows 9 words apart, conflict free), LSB
 // first (bytes bit-reversed): the window at LDS bit address q is alignbit(W[(q>>5)+1], W[q>>5], q), no bit buffer,
 // and the 30 bits it delivers serve two or three look-ups.
-// dynamic LDS: rows | sym3 (tab_bytes) | long table (LONG) | image (cap bytes) | wsum[4], next
+// A launch without escapes whose tables all say so (DecBlk::one, sym1_pays) takes sfd_wstage<0, false, true>, which walks with
+// ws_walk1 instead: one symbol per look-up from sym1 (half of sym3's bytes), whole words of the lane's own symbols stored
+// plainly, ORs at the two ends of its run only.
+// dynamic LDS: rows | sym3 or sym1 (tab_bytes) | long table (LONG) | image (cap bytes) | wsum[4], next
 // The host sizes the image for the launch's average symbols per tile plus a margin (LDS is what limits the waves per
 // CU); a tile with more symbols than it holds goes in several rounds of consecutive lanes.
 // A workgroup runs up to 16 tiles and asks for the next tile's rows in front of a tile's walk; the image's stores are
@@ -958,8 +961,115 @@ typedef unsigned int u32x3_t __attribute__((ext_vector_type(3)));
 constexpr u32 WS_NST = 4, WS_DROP = 0x7FFFFFF0u;
 constexpr int WS_RSRC_FLAGS = 0x00020000, WS_AUX_NT = 2;
 
+// The walk of a block whose codes all fit a window of at most 10 bits (DecBlk::one): ONE symbol per look-up, from sym1
+// (sym | len << 8 by the K1-bit window, LSB first), three look-ups per fetch.  With a fixed count per look-up, symbol k of a lane is byte k & 3 of the
+// lane's word k >> 2 at compile time: no shift, no count and no carry per look-up, and a word is finished at known points of
+// the unrolled body.  q2: the lane's LDS bit position minus 1 (the window times two is its entry's byte offset); xa: the LDS
+// address of the lane's first image byte.
+// by_pos: whole fetches while the fetch starts in front of q2end, tested before every fetch.  A group is the four fetches
+// after which the phase repeats: 12 symbols, 3 words.  A finished lane word L[j] and the one
+// before it give the image word E[j] = alignbyte(L[j], L[j - 1], s), s = (4 - x & 3) & 3, at P + 4 j, P = the word of byte
+// x - 1: it holds the symbols 4 j - 4 + s .. 4 j - 1 + s (x & 3 == 0: L[j - 1] itself, a word late).  E[j] is finished inside
+// the fetch of symbol 4 j + 3, whose first symbol, 3 * (that fetch), starts in front of the end, so is the lane's own — and with
+// it all of E[j], which leaves as a plain store, in all cases but two: E[0] holds bytes of the lane in front (ORed; the first
+// group is peeled for it), and the group's last word ends with the fetch's last symbol and may hold its second,
+// 4 j + 2: it is kept until the test in front of the next fetch has passed (then symbol 4 j + 4 is the lane's own), or ORed
+// when it has not.  At the end the word being gathered and the bytes behind it are ORed: these and E[0] are the only words a
+// neighbour's OR meets, and the up to two symbols of the next chunk in them are the ones the next lane places there.
+__device__ __forceinline__ void ws_walk1(const u32 tab_off, const u32 mask2, const u32 xa, u32 q2, const u32 q2end, u32 want,
+                                         const bool by_pos)
+{
+    auto window2 = [&]() -> u32 {
+        const lds_u32 *pa = (const lds_u32 *)(size_t)((q2 >> 3) & ~3u);
+        return __builtin_amdgcn_alignbit(pa[1], pa[0], q2);
+    };
+    auto look = [&](const u32 w) -> u32 { return *(const lds_u16 *)(size_t)(tab_off + (w & mask2)); };
+    auto image_or = [](const u32 at, const u32 v) {
+        __hip_atomic_fetch_or((lds_u32 *)(size_t)at, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    if (by_pos) {
+        constexpr u32 N = 3, F = 4, WPG = F * N / 4;    // look-ups per fetch; fetches and words per group
+        const u32 s = (0u - xa) & 3u;
+        u32 ptr = ((xa + 3u) & ~3u) - 4u;               // P; from the second group on, P + 4 * (words of the groups before)
+        u32 L = 0, Lp = 0, Ep = 0;                      // the word being gathered, the finished one before it, the word kept
+        auto group = [&](auto first_group) -> bool {
+            constexpr bool FIRST = decltype(first_group)::value;
+            u32 x0 = 0, x1 = 0, ub = 0;                 // the stream at an even fetch's position, and the bits that fetch used
+#pragma unroll
+            for (u32 f = 0; f < F; ++f) {
+                if (!((int)q2 < (int)q2end)) {          // the end: OR what has not left
+                    if (f == 0) {
+                        if (!FIRST) {
+                            image_or(ptr + 4u * (WPG - 1u), Ep);
+                            image_or(ptr + 4u * WPG, __builtin_amdgcn_alignbyte(0u, Lp, s));
+                        }
+                    } else {
+                        const u32 at = ptr + 4u * (f * N >> 2);
+                        image_or(at, __builtin_amdgcn_alignbyte(L, Lp, s));
+                        image_or(at + 4u, __builtin_amdgcn_alignbyte(0u, L, s));
+                    }
+                    return false;
+                }
+                if (f == 0 && !FIRST) {
+                    *(lds_u32 *)(size_t)(ptr + 4u * (WPG - 1u)) = Ep;
+                    ptr += 4u * WPG;
+                }
+                // Two fetches share one read of the stream: the 96 bits around the position, shifted down to it as two words,
+                // hold the second fetch's window too (a fetch uses at most 30 bits) — one more alignbit, no second address
+                // and no second wait.  (The third word may lie behind the row's look-ahead words; a fetch that starts in
+                // front of the end reads no bit of it there.)
+                u32 w;
+                if ((f & 1u) == 0) {
+                    const lds_u32 *pa = (const lds_u32 *)(size_t)((q2 >> 3) & ~3u);
+                    const u32 w0 = pa[0], w1 = pa[1], w2 = pa[2];
+                    w = x0 = __builtin_amdgcn_alignbit(w1, w0, q2);
+                    x1 = __builtin_amdgcn_alignbit(w2, w1, q2);
+                } else
+                    w = __builtin_amdgcn_alignbit(x1, x0, ub);
+                u32 ua = 0;
+#pragma unroll
+                for (u32 i = 0; i < N; ++i) {
+                    const u32 k = f * N + i, b = k & 3u;
+                    const u32 e = look(w >> ua);
+                    ua += e >> 8;
+                    // the symbol becomes byte b of L; the bytes above it are cleared (b == 0 starts a new word)
+                    L = __builtin_amdgcn_perm(e, L, b == 0 ? 0x0C0C0C04u : b == 1 ? 0x0C0C0400u : b == 2 ? 0x0C040100u : 0x04020100u);
+                    if (b == 3u) {
+                        const u32 E = __builtin_amdgcn_alignbyte(L, Lp, s), at = ptr + 4u * (k >> 2);
+                        Lp = L;
+                        if (FIRST && k == 3u) image_or(at, E);
+                        else if (k == F * N - 1u) Ep = E;
+                        else *(lds_u32 *)(size_t)at = E;
+                    }
+                }
+                q2 += ua;
+                ub = ua;
+            }
+            return true;
+        };
+        if (group(std::true_type{}))
+            while (group(std::false_type{})) {}
+        return;
+    }
+    // counted: a step is one symbol, gathered at its byte of the image word and ORed when the word is full
+    u32 wp = xa & ~3u, nb = 8u * (xa & 3u), acc = 0;
+    for (; want; --want) {
+        const u32 e = look(window2());
+        q2 += e >> 8;
+        acc |= (e & 0xFFu) << nb;
+        nb += 8u;
+        if (nb == 32u) {
+            image_or(wp, acc);
+            wp += 4u;
+            acc = nb = 0;
+        }
+    }
+    if (nb) image_or(wp, acc);
+}
+
 // ESC: some code of the launch may be longer than its block's sym3 window (then a look-up can return no symbol)
-template <int LONG, bool ESC>
+// ONE: every block of the launch is walked one code per look-up (DecBlk::one): sym1 in sym3's place, ws_walk1
+template <int LONG, bool ESC, bool ONE = false>
 __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restrict__ blks, const u8 *__restrict__ chunk_entry,
                                                           const u16 *__restrict__ chunk_cnt, const u64 *__restrict__ tile_off,
                                                           u32 tpw, u32 tab_bytes, u32 cap, u32 long_bytes)
@@ -982,7 +1092,9 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
     const u32 tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const u32 K1 = blk.K1, K3 = sym3_window(K1);
     const u32 sh = 32 - K1;
-    fill_lds16(smem + tab_off, (const void *)blk.sym3, 4u << K3);
+    static_assert(!ONE || (LONG == 0 && !ESC), "the one-code walk has no escapes");
+    constexpr bool one = ONE;
+    fill_lds16(smem + tab_off, (const void *)blk.sym3, (one ? 2u : 4u) << K3);
     if (LONG) {
         const u16 *src = LONG == 1 ? blk.longtab : blk.long32;
         if (src) fill_lds16((void *)lt, src, LONGB);
@@ -993,8 +1105,9 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
     // LDS addresses as literals: the kernel has no static LDS, so its dynamic segment starts at 0 (checked), and a
     // literal goes into the ds offset field where "smem + offset" leaves an add per look-up
     if (lds_addr(smem) != 0) __builtin_trap();
-    const u32 q2row = 8u * (16u + 4u * (WS_ROW * tid + (ESC ? 0u : tid >> 4))) - 2u;     // LDS bit address of the lane's row, minus 2 (see step)
-    const u32 mask4 = ((1u << K3) - 1u) << 2;
+    // LDS bit address of the lane's row, minus 2 (see step; sym1's entries are two bytes: minus 1)
+    const u32 q2row = 8u * (16u + 4u * (WS_ROW * tid + (ESC ? 0u : tid >> 4))) - (one ? 1u : 2u);
+    const u32 mask4 = ((1u << K3) - 1u) << (one ? 1 : 2);
     // 16 stream bytes at `off` (zeros past the end)
     auto fetch16 = [&](const u64 off) -> uint4 {
         if (off + 16 <= blk.in_n) return gload_nt<uint4>(blk.in + off);
@@ -1133,7 +1246,10 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_wstage(const DecBlk *__restri
                 nxt = (u32)__builtin_amdgcn_readfirstlane((int)*next);
                 lds_barrier();
             }
-            if (want && pre >= done && pre + want <= nxt) {
+            const bool mine = want && pre >= done && pre + want <= nxt;       // the lane's symbols go in this round
+            if constexpr (ONE) {
+                if (mine) ws_walk1(tab_off, mask4, img_off + mis + (pre - done), q2, q2end, want, by_pos);
+            } else if (mine) {
                 const u32 x = mis + (pre - done);
                 // LDS addresses are absolute from here on (the dynamic segment's base folded into the constants): an
                 // address that is "base + variable" costs an add per look-up that the ds instructions cannot absorb
@@ -1434,9 +1550,10 @@ static u32 sfd_tpw(u32 most, u32 max_tiles, int nblocks)
 // the exact kernels of `form`; sfd_offsets; the symbol pass sfd_wstage (with escapes when `esc`).  long_used: bytes of the
 // table of long codes the blocks fill (long_all, mid32), else 0.  all_spec: every block speculates, so the exact kernels are
 // fall-backs that normally return at once: fat workgroups (256 tiles each) make that a launch of a few thousand workgroups
-// instead of a few hundred thousand.  ws_tab, ws_cap: sfd_wstage's three-codes table and symbol image, bytes.
+// instead of a few hundred thousand.  ws_tab, ws_cap: sfd_wstage's three-codes table and symbol image, bytes; one: every
+// block has DecBlk::one set (no escapes): the symbol pass with the one-code walk.
 static void sfd_launch_packed(hipStream_t st, const DecBlk *dblk, int nblocks, u32 max_tiles, SfdForm form, bool esc, bool spec,
-                              u32 tabb, u32 long_used, bool all_spec, u32 ws_tab, u32 ws_cap, const SfdArrays &a)
+                              u32 tabb, u32 long_used, bool all_spec, u32 ws_tab, u32 ws_cap, const SfdArrays &a, bool one = false)
 {
     // the kernels of each form in the order of SfdForm, which is also the order the code object holds them in
     static decltype(&sfd_scan<0>) const scans[3] = {sfd_scan<2>, sfd_scan<1>, sfd_scan<0>};
@@ -1470,11 +1587,11 @@ static void sfd_launch_packed(hipStream_t st, const DecBlk *dblk, int nblocks, u
     hipLaunchKernelGGL(sfd_offsets, grid_b, wg, 0, st, dblk, (const u32 *)a.tcnt, a.toff);
     // the staged symbol pass takes 16 tiles per workgroup (table fill, image zeroing and the prefetch pipeline's start are
     // paid once per workgroup: 7.8 -> 7.7 ms on the headline data against 4; 32: the same)
-    static decltype(&sfd_wstage<0, false>) const wstages[4] = {sfd_wstage<2, true>, sfd_wstage<1, true>, sfd_wstage<0, true>,
-                                                               sfd_wstage<0, false>};
+    static decltype(&sfd_wstage<0, false>) const wstages[5] = {sfd_wstage<2, true>, sfd_wstage<1, true>, sfd_wstage<0, true>,
+                                                               sfd_wstage<0, false>, sfd_wstage<0, false, true>};
     const u32 tpw_ws = sfd_tpw(16, max_tiles, nblocks);
     const size_t lds_ws = (size_t)ws_rows_bytes(esc) + ws_tab + ws_cap + WS_MISC + long_used;
-    hipLaunchKernelGGL(wstages[f == 2 && !esc ? 3 : f], dim3((u32)ceil_div_u64(max_tiles, tpw_ws), (u32)nblocks), wg, lds_ws, st,
+    hipLaunchKernelGGL(wstages[one ? 4 : f == 2 && !esc ? 3 : f], dim3((u32)ceil_div_u64(max_tiles, tpw_ws), (u32)nblocks), wg, lds_ws, st,
                        dblk, (const u8 *)a.cent, (const u16 *)a.ccnt, (const u64 *)a.toff, tpw_ws, ws_tab, ws_cap, long_used);
 }
 
@@ -1564,6 +1681,10 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     const bool long_all = R == 16 && !pair_all && c16_all && lmax_all > (u32)LEN_MAXK;
     const bool packed = R == 16 && ((pair_all && lmax_all <= (u32)LEN_MAXK) || long_all);
     const bool mid32 = !packed && R == 32 && c32_all;
+    const bool ws_esc = mid32 || long_all || lmax_all > (u32)SYM3_MAXK;                   // sfd_wstage with escapes
+    bool ws_one = !ws_esc;                             // ... or with the one-code walk: when it pays for every table of the launch
+    for (int b = 0; b < nblocks; ++b)
+        if (ntiles[b] && !tabs[b].one) ws_one = false;
     if (!packed && !mid32 && R < 32) R = 32;           // the byte-map kernels keep 32 entries per chunk at least
 
     // workspace layout
@@ -1653,6 +1774,7 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
         e.K1 = h.K1;
         e.KW = hblk_kw[b];
         e.lmax = h.lmax;
+        e.one = ws_one;
         e.n_states = (u32)(h.trie.size() / 2);
         tab_pos[b] = tpos;                                  // where this block's tables start in the staging arena
         e.lut2 = (const u16 *)(dpar + tpos);
@@ -1719,17 +1841,16 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
     }
     const SfdForm form = mid32 ? SFD_MID32 : long_all ? SFD_LONG_ALL : k1_all == 12 ? SFD_PACKED12 : k1_all == 13 ? SFD_PACKED13
                                                                                                           : SFD_PACKED;
-    u32 ws_tab = 16;                                   // sym3 bytes of the widest table of the launch
+    u32 ws_tab = 16;                                   // bytes of the launch's widest sym3 table (sym1: half of that)
     for (int b = 0; b < nblocks; ++b) {
-        const u32 k3 = sym3_window(tabs[b].K1);
-        if ((4u << k3) > ws_tab) ws_tab = 4u << k3;
+        const u32 k3 = sym3_window(tabs[b].K1), tb = (ws_one ? 2u : 4u) << k3;
+        if (tb > ws_tab) ws_tab = tb;
     }
     // image: the densest block's average symbols per tile + 1/8 + 1 KiB, 4 .. 40 KiB — unless a smaller margin (1/32 +
     // 256 bytes; a tile that exceeds the image goes in rounds) lets more workgroups share a CU: the symbol pass loses time
     // almost in proportion to the waves it loses, and a CU's LDS is handed out as two halves of 80 KiB (8 workgroups up to
     // 20 KiB each, 6 up to 26.25, 4 up to 40, 2 above: DESIGN.md §3.2).  Codes of up to 12 bits on run-heavy data: 41.7 KB
     // with the wide margin = 2 workgroups per CU, 40 KB with the narrow one = 4.
-    const bool ws_esc = mid32 || long_all || lmax_all > (u32)SYM3_MAXK;                   // sfd_wstage with escapes
     u32 ws_cap = 4096, ws_tight = 4096;
     for (int b = 0; b < nblocks; ++b) {
         if (!ntiles[b]) continue;
@@ -1753,7 +1874,7 @@ int sfdec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u
         }
     }
     ws_cap &= ~15u;
-    sfd_launch_packed(st, dblk, nblocks, max_tiles, form, ws_esc, any_spec, 2u << k1_max, long_used, all_spec, ws_tab, ws_cap, arr);
+    sfd_launch_packed(st, dblk, nblocks, max_tiles, form, ws_esc, any_spec, 2u << k1_max, long_used, all_spec, ws_tab, ws_cap, arr, ws_one);
     HIP_TRY(hipGetLastError());
     return pscope.done();
 }

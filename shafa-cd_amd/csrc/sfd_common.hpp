@@ -40,6 +40,7 @@ struct DecBlk {
     u16 *cnt3;             // sfd_scan's tables, 2^KW bytes each: [total bits | codes << 5 of the whole codes (at most 7) in a
                            // window] then [length of the window's first code]
     u32 *sym3;             // 2^K3 entries: sym0 | sym1 << 8 | sym2 << 16 | total bits << 24 (6 bits) | n << 30
+                           //   (`one`: sym1 in its place, 2^K3 u16: sym | len << 8)
     u8 *pairlut;           // 2^(K1+1) entries: (len(p)-1) | (len(p+1)-1) << 4 from a K1+1-bit window (complete codes)
     const u16 *lut13;      // 2^K1 entries: sym | len << 8, single level (only when Lmax <= 13), else NULL
     const u32 *trie;       // pairs {child0, child1}: 0x80000000|sym = leaf, 0xFFFFFFFF = missing
@@ -56,6 +57,7 @@ struct DecBlk {
     const u8 *lenlut32;    // 2^13 entries: len <= 13, or 128 + k = internal node root13[k] of long32 (16 < Lmax <= 32 launches)
     const u16 *long32;     // LONG32_BYTES: sorted 12-bit prefixes of the codes of 13..32 bits + their sub-tries
     const u16 *longtab;    // LONG_BYTES: sorted 12-bit prefixes of the codes of 13..16 bits + 16 entries sym | len << 8 each
+    u32 one;               // the launch's symbol pass walks one code per look-up (sfd_wstage<0, false, true>): sym1 in sym3's place
     u32 *run_dp;           // speculative launches: *run_dp != 0 <=> the block needs the exact (DP) kernels: it was not
                            //   tried speculatively or did not verify; NULL: no speculation, the DP kernels always run
 };
@@ -67,6 +69,26 @@ __host__ __device__ __forceinline__ u32 sym3_window(u32 K1)
 {
     const u32 k = K1 < (u32)SYM3_MINW ? (u32)SYM3_MINW : K1;
     return k < (u32)SYM3_MAXK ? k : (u32)SYM3_MAXK;
+}
+// Does sfd_wstage's walk of ONE code per look-up (ws_walk1, table sym1) pay for a table whose codes all fit the window?  It
+// delivers exactly as many symbols per fetch as look-ups fit the fetch's 30 bits, at about two thirds of the cost per fetch;
+// the three-codes table delivers that number times the whole codes per window.  So: three look-ups per fetch (K1 <= 10), and
+// at most 1.4 whole codes (of up to three) per K1-bit window on average over all windows, which is the average over data that
+// the code fits (Zipf(1.2) mod 256: 1.27, and 3 % faster; 8/9-bit codes of uniform bytes: 1.0; the 12-bit tables of run-heavy
+// data and of text: 2.1, two look-ups per fetch, and 19 % slower).  lenlut: 2^K1 code lengths by the window, MSB first.
+__host__ __forceinline__ bool sym1_pays(const u8 *lenlut, u32 K1)
+{
+    if (K1 > 10) return false;
+    const u32 mask = (1u << K1) - 1u;
+    u32 n = 0;
+    for (u32 i = 0; i <= mask; ++i)
+        for (u32 pos = 0, c = 0; c < 3; ++c) {
+            const u32 L = lenlut[(i << pos) & mask];
+            if (L == 0 || L > K1 - pos) break;
+            pos += L;
+            ++n;
+        }
+    return 5u * n <= (7u << K1);
 }
 // window of sfd_scan's counting tables for one block.  A 13-bit table in a launch with the table of long codes (which holds
 // every code of more than 12 bits, by 12-bit prefix) may count with 12-bit windows: the 13-bit codes become escapes like the

@@ -316,6 +316,7 @@ __global__ __launch_bounds__(256) void sfd_plan_dev(const SdvHost *__restrict__ 
     e.lmax = lmax;
     e.n_states = nodes;
     e.n_tiles = (u32)((in_n + DTILE - 1) / DTILE);
+    e.one = 0;                                          // (the launch's kernels are chosen before the tables are known)
     if (packed) {
         u8 *tb = po.tabs + (size_t)b * SDV_TABS;
         e.cnt3 = (u16 *)tb;

@@ -119,10 +119,12 @@ __device__ __forceinline__ void fill_lds16(void *dst, const void *src, u32 bytes
 // sfd_tables: one workgroup per block expands the host tables (complete codes, Lmax <= 13) into
 //   pairlut: the two-positions-per-lookup length table of the DP, and
 //   cnt3 / sym3: up to three whole codes per K1-bit window for the symbol passes.
+// (a block with `one` set, which sfd_wstage<0, false> walks one code per look-up: sym1 in sym3's place)
 __global__ __launch_bounds__(DEC_THREADS) void sfd_tables(const DecBlk *__restrict__ blks)
 {
     const DecBlk blk = blks[blockIdx.x];
     if (!blk.n_tiles) return;
+    const bool one = blk.one != 0;
     // gridDim.y workgroups share a block's tables (an entry is a chain of up to fifteen dependent look-ups in global
     // memory: one workgroup per block took 45 us for 12-bit tables, as long as the symbol pass of a small launch)
     const u32 T0 = threadIdx.x + blockIdx.y * DEC_THREADS, TS = DEC_THREADS * gridDim.y;
@@ -144,7 +146,12 @@ __global__ __launch_bounds__(DEC_THREADS) void sfd_tables(const DecBlk *__restri
         ((u8 *)blk.cnt3)[j] = (u8)(pos | (n << 5));              // bits in the low five: the sum of a fetch's entries is the next look-up's shift
         ((u8 *)blk.cnt3)[(1u << KW) + j] = (u8)l0;
     }
-    for (u32 i = T0; i < (1u << K3); i += TS) {   // K3-bit window; n = 0: first code is longer
+    // sym1, in sym3's place: the window's first code alone, sym | len << 8 (lut13's entry; every code fits the window here)
+    for (u32 i = T0; one && i < (1u << K3); i += TS) {
+        const u32 e = blk.lut13[i];
+        ((u16 *)blk.sym3)[__builtin_bitreverse32(i) >> (32 - K3)] = (u16)(e >> 8 ? e : 1u << 8);   // (a length of 0 would stop the walk)
+    }
+    for (u32 i = T0; !one && i < (1u << K3); i += TS) {   // K3-bit window; n = 0: first code is longer
         u32 pos = 0, n = 0, syms = 0;
         for (; n < 3; ++n) {
             const u32 e = blk.lut13[K3 >= K1 ? (((i << pos) & ((1u << K3) - 1u)) >> (K3 - K1)) : (((i << (K1 - K3)) << pos) & mask)];

@@ -12,6 +12,7 @@ struct HostTab {
     std::vector<u8> lenlut32;  // lenlut with escape ids 128 + k for the 13-bit prefixes of longer codes (with long32)
     u32 K, K1, lmax;
     bool ok, empty, complete, complete16, complete32;
+    bool one;                  // complete, Lmax <= 12 and sym1_pays: sfd_wstage may walk it one code per look-up
 };
 
 void build_host_tab(const shafa_code_table &t, HostTab &h)
@@ -21,6 +22,7 @@ void build_host_tab(const shafa_code_table &t, HostTab &h)
     h.complete = false;
     h.complete16 = false;
     h.complete32 = false;
+    h.one = false;
     h.lmax = 0;
     for (int s = 0; s < 256; ++s) h.lmax = t.len[s] > h.lmax ? t.len[s] : h.lmax;
     h.empty = h.lmax == 0;
@@ -70,6 +72,7 @@ void build_host_tab(const shafa_code_table &t, HostTab &h)
     if (!h.ok) return;
     h.complete = h.lmax <= (u32)LEN_MAXK;               // every K1-bit window starts a code: pair table usable
     for (size_t i = 0; h.complete && i < ((size_t)1 << h.K1); ++i) h.complete = h.lenlut[i] != 0;
+    h.one = h.complete && h.lmax <= (u32)SYM3_MAXK && sym1_pays(h.lenlut.data(), h.K1);
     if (h.lmax <= 16) {                                 // prefix-free (checked above) + Kraft sum 1 = complete tree
         u64 kraft = 0;
         for (int s = 0; s < 256; ++s) if (t.len[s]) kraft += 1ull << (16 - t.len[s]);
