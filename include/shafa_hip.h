@@ -547,6 +547,54 @@ int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblo
                                      const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out,
                                      const uint64_t *h_out_off);
 
+/* ---- Byte planes of lagged differences: the difference to the element h_lag[b] in front ------------------------------------
+ * Data that runs along an axis is seldom stored along it: a [T, C] sensor log runs along T with the channels interleaved, an
+ * [H, W, 3] image along W at distance 3 and along H at distance 3 W, a [steps, params] stack of checkpoints along steps.  The
+ * difference to the flat neighbour subtracts one channel from another; the difference to the element one axis stride in front
+ * is the small one.  With M = 2^(8 elem), x[i] element i of the block as an unsigned little-endian integer, L = h_lag[b] >= 1
+ * (a host array with ONE LAG PER BLOCK, so one launch per element size serves any mix of shapes) and x[i] = 0 for i < 0 —
+ * every block starts afresh:
+ *   d[i] = (x[i] - x[i-L]) mod M,   z[i] = the zigzag fold of d[i] (above),   plane j of the block = byte j of z[i]
+ * and back: d[i] unfolded, x[i] = (x[i-L] + d[i]) mod M — the block seen as rows of L columns, a prefix sum down every column.
+ * It is a bijection on any input.  With L >= d_n[b] the planes are those of the fold of x itself; any L up to 2^64 - 1 is
+ * legal.  With L = 1 both entries produce byte for byte what the _diff_dev entries produce.
+ * shafa_hipd_split_planes_lag_dev writes the planes of z; shafa_hipd_merge_planes_lag_dev is its inverse.
+ * Everything said above of the plain entries holds — the blocks, the plane side at multiples of 16, elem = 1, 2, 4 or 8, the
+ * capacities on the host and the sizes device resident, what is written: exactly the plain entries' bytes and nothing outside
+ * them, the per-block code (d_n[b] > h_cap[b]: SHAFA_OUTSIDE_MODULE, no byte of the block read or written) — with ONE
+ * exception, which is deliberate:
+ *   element side   d_in / d_out and every h_in_off[b] / h_out_off[b] are MULTIPLES OF elem.  A tensor's elements always lie at
+ *                  multiples of their size; bytes at odd addresses are what the record entries are for.
+ * Launches.  split is one launch: the plain split's units, each with the unit L elements in front of it read from the block's
+ * own region as a base (mostly from L2 where L is small): 2 bytes of traffic per tensor byte.  merge is up to three on the
+ * stream.  A block is cut into chunks of G rows by strips of W columns, one column a lane:
+ *   L >= SHAFA_PLANES_LAG_STRIP   W = SHAFA_PLANES_LAG_STRIP, S = 1
+ *   L <  SHAFA_PLANES_LAG_STRIP   W = L, and the workgroup's lanes are S = SHAFA_PLANES_LAG_STRIP / L (rounded down) segments of
+ *                                 rows, so a round of rows is a contiguous run of the block
+ *   G = SHAFA_PLANES_LAG_ROWS * S * m, m = max(1, items / SHAFA_PLANES_LAG_ITEMS rounded down), items = the chunk-strips that
+ *   h_cap[b] would have at m = 1
+ * all from h_cap[b] and h_lag[b], which the host has.  Launch 1 writes the column sums (mod M, elem bytes each) of every chunk
+ * that has a chunk behind it, launch 2 turns them into exclusive prefixes down each column, launch 3 rebuilds the elements
+ * chunk by chunk on top of its prefix (in a strip of SHAFA_PLANES_LAG_STRIP columns a lane takes four columns next to each
+ * other and a quarter of the rows, so the planes are read a dword and the elements written four at a time); where no block
+ * of the call has more than one chunk, launches 1 and 2 are not made.  No workgroup ever waits for another: no tickets, no
+ * look-back, no flags; the only atomic is the error word.  The planes are read twice: 3 bytes of traffic per tensor byte.
+ * The device workspace is (28 + 8 elem) bytes per block plus 20 and, for a merge with a block of more than one chunk,
+ * elem * SHAFA_PLANES_TILE / 8 bytes per tile of the capacities: at most 1/8 of the capacities' bytes plus elem KiB per block.
+ * One that cannot be had is SHAFA_LACK_OF_MEMORY.  Enqueues only, as the plain entries.
+ * Argument errors return from the call with nothing enqueued (checked before HIP is touched), the plain entries' in the plain
+ * entries' order, and with the host arrays (behind the plane offsets' alignment), each SHAFA_OUTSIDE_MODULE: NULL h_lag or an
+ * h_lag[b] of 0; a d_in / d_out or an h_in_off[b] / h_out_off[b] that is no multiple of elem. */
+#define SHAFA_PLANES_LAG_STRIP 256  /* columns of a strip; below it a block's rows are taken whole */
+#define SHAFA_PLANES_LAG_ROWS 32    /* rows a lane takes at a time */
+#define SHAFA_PLANES_LAG_ITEMS 4096 /* chunk-strips of a block beyond which its chunks grow */
+int shafa_hipd_split_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint64_t *h_lag,
+                                    const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                    uint8_t *d_planes, const uint64_t *h_plane_off);
+int shafa_hipd_merge_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint64_t *h_lag,
+                                    const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_cap,
+                                    const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

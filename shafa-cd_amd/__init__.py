@@ -132,6 +132,8 @@ def lib():
     L.shafa_hipd_merge_records_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_split_planes_lag_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_planes_lag_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -196,6 +198,7 @@ def lib():
                  "shafa_hipd_find_dev", "shafa_hipd_split_planes_dev", "shafa_hipd_merge_planes_dev",
                  "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev",
                  "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev",
+                 "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
                  "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -522,6 +525,28 @@ class Batch:
         oo, ic, po = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off)
         _check(lib().shafa_hipd_merge_planes_diff_dev(self.h, self._st(stream), len(oo), elem, _addr(d_planes), _p64(po), _p64(ic),
                                                       d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_diff_dev")
+
+    def split_planes_lag_dev(self, stream, elem, lag, d_in, in_off, cap, d_n, d_planes, plane_off):
+        """split_planes_dev of every element's difference to the element lag[b] >= 1 in front of it in block b (one lag a block;
+        none in front: the element itself), zigzag-folded; lag 1 is split_planes_diff_dev byte for byte.  split_planes_dev's
+        arguments, and exactly its bytes written, but the element side lies at multiples of elem: d_in and every in_off[b].
+        Enqueues only, one launch (include/shafa_hip.h: "Byte planes of lagged differences")."""
+        io, ic, po, lg = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off), _u64arr(lag)
+        if len(lg) != len(io):
+            raise ValueError("split_planes_lag_dev: one lag per block")
+        _check(lib().shafa_hipd_split_planes_lag_dev(self.h, self._st(stream), len(io), elem, _p64(lg), _addr(d_in), _p64(io),
+                                                     _p64(ic), d_n.data_ptr(), _addr(d_planes), _p64(po)), "hipd_split_planes_lag_dev")
+
+    def merge_planes_lag_dev(self, stream, elem, lag, d_planes, plane_off, cap, d_n, d_out, out_off):
+        """split_planes_lag_dev's inverse: the prefix sums (mod 2^(8 elem)) down the lag[b] columns of the differences unfolded
+        from block b's planes -> d_out + out_off[b], multiples of elem.  merge_planes_dev's arguments otherwise, and exactly its
+        bytes written.  Enqueues only: up to three launches, in none of which a workgroup waits for another
+        (include/shafa_hip.h: "Byte planes of lagged differences")."""
+        oo, ic, po, lg = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off), _u64arr(lag)
+        if len(lg) != len(oo):
+            raise ValueError("merge_planes_lag_dev: one lag per block")
+        _check(lib().shafa_hipd_merge_planes_lag_dev(self.h, self._st(stream), len(oo), elem, _p64(lg), _addr(d_planes), _p64(po),
+                                                     _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_lag_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -2743,6 +2768,9 @@ def encode_files(d_in, cod, stream=None):
 PLANES_TILE = 8192              # SHAFA_PLANES_TILE: the elements of one tile of split_planes_dev / merge_planes_dev
 PLANES_ELEM = (1, 2, 4, 8)      # the element sizes they take
 PLANES_NO_BASE = (1 << 64) - 1  # SHAFA_PLANES_NO_BASE: the base offset of a block without a base (the _xor_dev entries)
+PLANES_LAG_STRIP = 256          # SHAFA_PLANES_LAG_STRIP, _ROWS, _ITEMS: the form merge_planes_lag_dev gives a block
+PLANES_LAG_ROWS = 32
+PLANES_LAG_ITEMS = 4096
 RECORDS_MAX_WIDTH = 64          # SHAFA_RECORDS_MAX_WIDTH: split_records_dev / merge_records_dev take records of 1 .. 64 bytes
 RECORDS_TILE = 8192             # SHAFA_RECORDS_TILE: the records of one tile of theirs
 
@@ -2820,9 +2848,10 @@ def _plane_stream(dev, stream):
     return st
 
 
-# The drivers below serve four variants of one chain.  A tensor is `units` = (count, width): its count of units of `width` bytes,
+# The drivers below serve five variants of one chain.  A tensor is `units` = (count, width): its count of units of `width` bytes,
 # an element's 1, 2, 4 or 8 or a record's 1 .. RECORDS_MAX_WIDTH; column j of a unit is a plane.  The variant `kind` names the
-# pair of Batch methods, split_<kind>_dev / merge_<kind>_dev: "planes", "planes_xor" (with `bases`), "planes_diff" or "records".
+# pair of Batch methods, split_<kind>_dev / merge_<kind>_dev: "planes", "planes_xor" (with `bases`), "planes_diff", "planes_lag"
+# (`bases` holds the tensors' lags) or "records".
 def _by_width(units):
     """indices of the non-empty tensors, grouped by unit width -> [(width, [index, ...])]"""
     return [(w, [i for i, (n, x) in enumerate(units) if x == w and n]) for w in sorted({x for n, x in units if n})]
@@ -2848,12 +2877,18 @@ def _transpose(bt, way, kind, side):
     return getattr(bt, f"{way}_{'planes' if kind == 'planes_xor' and side is None else kind}_dev")
 
 
+def _lag_side(kind, lags, idx):
+    """the lag argument of a split_planes_lag_dev / merge_planes_lag_dev launch over the tensors idx, behind the width: a tuple
+    to be spliced in, empty for every other variant"""
+    return ([int(lags[i]) for i in idx],) if kind == "planes_lag" else ()
+
+
 def _split_into(bt, st, dev, ts, units, kind, bases=None):
     """one split launch per distinct width over ts (blocks addressed from the lowest tensor address: nothing is concatenated)
     -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  "planes_xor" with `bases` (one entry per
     tensor: None or a tensor of the same dtype and numel): a width with a base among its tensors takes split_planes_xor_dev, the
     bases addressed from the lowest base address.  "planes_diff": one block a tensor, so the differences run over the
-    flattened tensor."""
+    flattened tensor.  "planes_lag": the same at the distance bases[i], an int, for tensor i."""
     import torch
     poff, pos = [], 0
     for n, w in units:
@@ -2867,8 +2902,9 @@ def _split_into(bt, st, dev, ts, units, kind, bases=None):
     at = 0
     for w, idx in groups:
         base = min(ts[i].data_ptr() for i in idx)
-        side = _base_side(bases, idx)
-        _transpose(bt, "split", kind, side)(st, w, base, [ts[i].data_ptr() - base for i in idx], *(side or ()),
+        side = _base_side(bases, idx) if kind == "planes_xor" else None
+        _transpose(bt, "split", kind, side)(st, w, *_lag_side(kind, bases, idx), base, [ts[i].data_ptr() - base for i in idx],
+                                            *(side or ()),
                                             [units[i][0] for i in idx], d_n[at:at + len(idx)], buf,
                                             [o for i in idx for o in poff[i]])
         at += len(idx)
@@ -2888,22 +2924,24 @@ def _merge_into(bt, st, dev, planes, outs, units, kind, bases=None):
     for w, idx in groups:
         pbase = min(p.data_ptr() for i in idx for p in planes[i])
         obase = min(outs[i].data_ptr() for i in idx)
-        side = _base_side(bases, idx)
-        _transpose(bt, "merge", kind, side)(st, w, pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]], *(side or ()),
+        side = _base_side(bases, idx) if kind == "planes_xor" else None
+        _transpose(bt, "merge", kind, side)(st, w, *_lag_side(kind, bases, idx), pbase,
+                                            [p.data_ptr() - pbase for i in idx for p in planes[i]], *(side or ()),
                                             [units[i][0] for i in idx], d_n[at:at + len(idx)], obase,
                                             [outs[i].data_ptr() - obase for i in idx])
         at += len(idx)
 
 
-def _split_one(kind, t, n, w, stream):
-    """split_planes' / split_records' work on the checked tensor t of n units of w bytes: one launch, one synchronisation"""
+def _split_one(kind, t, n, w, stream, bases=None):
+    """split_planes' / split_records' / split_strided's work on the checked tensor t of n units of w bytes (bases: _split_into's):
+    one launch, one synchronisation"""
     import torch
     dev = t.device
     st = _plane_stream(dev, stream)
     with torch.cuda.stream(st):
         bt = Batch(1, 1 << 20)
         try:
-            buf, _ = _split_into(bt, st, dev, [t], [(n, w)], kind)
+            buf, _ = _split_into(bt, st, dev, [t], [(n, w)], kind, bases)
             bt.finish(st, 1)
         finally:
             bt.close()
@@ -2965,8 +3003,9 @@ def _record_dtype(what, dtype, shape, width):
     return width, shape, nbytes // width
 
 
-def _merge_one(kind, planes, dtype, shape, stream):
-    """merge_planes' / merge_records' work on the checked planes [w, n] -> the tensor: one launch, one synchronisation"""
+def _merge_one(kind, planes, dtype, shape, stream, bases=None):
+    """merge_planes' / merge_records' / merge_strided's work on the checked planes [w, n] -> the tensor (bases: _merge_into's): one
+    launch, one synchronisation"""
     import torch
     w, n = int(planes.shape[0]), int(planes.shape[1])
     dev = planes.device
@@ -2975,7 +3014,7 @@ def _merge_one(kind, planes, dtype, shape, stream):
         out = torch.empty(shape, dtype=dtype, device=dev)
         bt = Batch(1, 1 << 20)
         try:
-            _merge_into(bt, st, dev, [[planes[j].contiguous() for j in range(w)]], [out], [(n, w)], kind)
+            _merge_into(bt, st, dev, [[planes[j].contiguous() for j in range(w)]], [out], [(n, w)], kind, bases)
             bt.finish(st, 1)
         finally:
             bt.close()
@@ -3007,8 +3046,8 @@ def _back_to_back(buf, spans):
 
 def _plane_entries(what, ts, units, kind, bases, block_size, stream):
     """compress_tensors' chain over the checked tensors ts of `units`, and in its other variants compress_deltas' (with `bases`,
-    _split_into's), compress_sequences' and compress_records': the split, the sizes, the file sets of the planes that shrink ->
-    per tensor its plane entries, and their bytes"""
+    _split_into's), compress_sequences', compress_strided's (`bases` the lags) and compress_records': the split, the sizes, the
+    file sets of the planes that shrink -> per tensor its plane entries, and their bytes"""
     import torch
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
         raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
@@ -3155,9 +3194,13 @@ def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=
 
 def _merge_items(what, items, kind, bases, check_base, stream):
     """decompress_tensors' checks and chain over the list `items`, and in its other variants decompress_deltas' (with `bases`,
-    one entry per item), decompress_sequences' and decompress_records' (whose messages say "column" for a plane)"""
+    one entry per item), decompress_sequences', decompress_strided's (`bases` the items' lags) and decompress_records' (whose
+    messages say "column" for a plane)"""
     import torch
     noun, length = ("column", "record count") if kind == "records" else ("plane", "tensor's numel")
+    lags = bases if kind == "planes_lag" else None   # that variant's `bases` are ints, one per item
+    if kind != "planes_xor":
+        bases = None                                 # only this one has base tensors to check
     if bases is not None:
         for i, (it, b) in enumerate(zip(items, bases)):
             if isinstance(it, CompressedDelta) and b is None:
@@ -3224,7 +3267,7 @@ def _merge_items(what, items, kind, bases, check_base, stream):
         outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, bases)
+            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, lags if kind == "planes_lag" else bases)
             bt.finish(st, len(items))
         finally:
             bt.close()
@@ -3300,3 +3343,8 @@ def decompress_sequences(items, stream=None):
 from . import records  # noqa: E402  (_record_dtype asks it for a width's check)
 from .records import (CompressedRecords, compress_records, decompress_records, merge_records, records_pass,  # noqa: E402,F401
                       split_records)
+
+
+# ------------------------------------------------------------------ differences along an axis, one file set per byte plane
+from . import strided  # noqa: E402
+from .strided import (CompressedStrided, compress_strided, decompress_strided, merge_strided, split_strided)  # noqa: E402,F401

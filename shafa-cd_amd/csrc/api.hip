@@ -601,13 +601,14 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
 
 // the checks the plane and the record transposes share (include/shafa_hip.h), in one order, then the launch.  d_el is the element
 // or record side; `unit` the bytes of an element (1, 2, 4 or 8) or, TR_RECORDS, of a record (1 .. SHAFA_RECORDS_MAX_WIDTH);
-// TR_XOR: the _xor entries, with a base side; TR_DIFF: the _diff entries
-enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_RECORDS };
+// TR_XOR: the _xor entries, with a base side; TR_DIFF: the _diff entries; TR_LAG: the _lag entries, with a lag a block (h_lag) and
+// the element side at multiples of the element
+enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_LAG, TR_RECORDS };
 static_assert(SHAFA_RECORDS_TILE == SHAFA_PLANES_TILE, "one tile for the plane and the record entries");
 
 static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
                          const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
-                         const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off)
+                         const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr)
 {
     const bool xr = tr == TR_XOR;
     if (!b || !d_el || !d_planes || !d_n || (xr && !d_base)) return SHAFA_OUTSIDE_MODULE;
@@ -625,7 +626,15 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
     if (!h_off || !h_plane_off || (xr && !h_base_off) || ((uintptr_t)d_planes & 15)) return SHAFA_OUTSIDE_MODULE;
     for (size_t i = 0; i < (size_t)nblocks * unit; ++i)
         if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
+    if (tr == TR_LAG) {
+        if (!h_lag || (uintptr_t)d_el % unit) return SHAFA_OUTSIDE_MODULE;
+        for (int i = 0; i < nblocks; ++i)
+            if (!h_lag[i] || h_off[i] % unit) return SHAFA_OUTSIDE_MODULE;
+    }
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    if (tr == TR_LAG)
+        return planes_lag_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
+                                     (u8 *)d_planes, h_plane_off, h_lag);
     if (tr == TR_RECORDS)
         return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
                                   h_plane_off);
@@ -678,6 +687,22 @@ int shafa_hipd_merge_planes_diff_dev(shafa_hipd_batch *b, void *stream, int nblo
 {
     return transpose_dev(true, TR_DIFF, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
                          h_plane_off);
+}
+
+int shafa_hipd_split_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint64_t *h_lag,
+                                    const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                    uint8_t *d_planes, const uint64_t *h_plane_off)
+{
+    return transpose_dev(false, TR_LAG, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lag);
+}
+
+int shafa_hipd_merge_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint64_t *h_lag,
+                                    const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_cap,
+                                    const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off)
+{
+    return transpose_dev(true, TR_LAG, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lag);
 }
 
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,

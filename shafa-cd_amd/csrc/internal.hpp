@@ -276,6 +276,11 @@ int planes_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool mer
 // is one launch, merge three (tile sums, the blocks' scans, the merge) with 8 bytes of workspace more per tile of the capacities
 int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off);
+// the same with block b's differences taken to the element h_lag[b] >= 1 in front, the element side at multiples of elem
+// (planes_lag.hip): split is one launch, merge up to three (column sums of the chunks, their scans, the merge) with elem bytes of
+// workspace more per 8 elements of the capacities' tiles where a block has more than one chunk
+int planes_lag_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                          const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u64 *h_lag);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

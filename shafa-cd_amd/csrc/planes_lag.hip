@@ -1,0 +1,524 @@
+// planes_lag.hip — byte planes of LAGGED differences (shafa_hipd_split_planes_lag_dev, shafa_hipd_merge_planes_lag_dev, DESIGN
+// 7.26): planes.hip's differences with a distance in them.  Block b is d_n[b] (<= cap[b]) elements of E = 1, 2, 4 or 8 bytes,
+// x[i] as unsigned little-endian integers, L = lag[b] >= 1 its lag (one a block, from the host):
+//     d[i] = x[i] - x[i - L] mod 2^(8 E)   (x[i] = 0 for i < 0),   plane j = byte j of the zigzag fold of d[i]
+// and back x[i] = x[i - L] + d[i]: the block seen as rows of L columns, a prefix sum down every column.  ELEMENT SIDE at multiples
+// of E (the entries refuse anything else), PLANE SIDE at multiples of 16, as everywhere.  The host clamps L to the block's
+// capacity: a lag at or past d_n[b] subtracts nothing, whatever its value.
+//
+// split: one launch over tile_pass.hpp's tiles, the plain split's direct path (16 elements a lane: E aligned words shifted into
+// place, v_perm_b32, one word of each plane).  The "base" of a unit is the unit L elements in front of it in the block's own
+// region, read the same way at an alignment of its own (lag_base: the region moved up by L elements), elements in front of the
+// block zeroed; subtract, fold, store.  2 bytes of traffic per tensor byte, the second read of the region from L2 where L is
+// small.
+//
+// merge: a chunk is G rows of a strip of W columns, one column a lane (LagGeom):
+//     L >= 256   W = 256: a row of a strip is 256 consecutive elements, a lane walks its column down the chunk's rows;
+//     L < 256    W = L, and the workgroup's 256 lanes are S = 256 / L segments of 32 rows each, so a round of 32 S rows is a
+//                contiguous run of 32 S L (4097 .. 8192) elements; the segments' totals go through LDS.
+// A chunk is m rounds of 32 S rows; m grows with the block so that it has about SHAFA_PLANES_LAG_ITEMS chunk-strips (items) and
+// the column sums stay few.  Three launches at the most, the stream their only order, no workgroup ever waits for another:
+//     planes_lag_sums    the column sums of every chunk but the one the block ends in, mod 2^(8 E), E bytes each
+//     planes_lag_scan    exclusive prefixes down each column of the sums, a workgroup a run of 32 columns, 8 chunks a lane a round
+//     planes_lag_merge   the elements, chunk by chunk on top of its prefix; in a strip of 256 columns a lane takes four columns
+//                        and eight of a round's rows (lag_merge_wide): a dword of each plane, four elements a store
+// A block whose rows fit one chunk has no sums, and where no block has any the first two launches are not made.  All three walk
+// the tiles of the capacities (TpWalk) and deal a block's items (or column runs) to its tiles in equal runs, so the grid is the
+// plain entries' whatever the lags.  The planes are read twice: 3 bytes of traffic per tensor byte.  The sums of block b lie at
+// LAG_SUMS_TILE elements per tile of the capacities in front of it: NC L <= (cap / 16)(1 + 1 / 32) once there are two chunks.
+#include "common.hpp"
+#include "internal.hpp"
+#include "tile_pass.hpp"
+#include "planes_arith.hpp"
+
+#include <vector>
+
+namespace {
+
+constexpr u32 LAG_STRIP = SHAFA_PLANES_LAG_STRIP;               // columns of a strip: one a lane
+constexpr u32 LAG_ROWS = SHAFA_PLANES_LAG_ROWS;                 // rows a lane holds in registers at a time
+constexpr u32 LAG_ITEMS = SHAFA_PLANES_LAG_ITEMS;               // items a block is cut into before its chunks grow
+constexpr u32 LAG_SUMS_TILE = SHAFA_PLANES_TILE / 8;            // column sums per tile of the capacities
+constexpr u32 LAG_SCAN_COLS = 32, LAG_SCAN_PER = 8;             // the scan: columns of a run, chunks a lane a round
+static_assert(LAG_STRIP == TP_THREADS && LAG_ROWS * LAG_STRIP == TP_TILE, "a round of a strip is a tile");
+
+template <int E> struct ElT { using T = u32; };
+template <> struct ElT<1> { using T = u8; };
+template <> struct ElT<2> { using T = u16; };
+template <> struct ElT<8> { using T = u64; };
+
+// the form of a block of capacity cap >= 1 and lag 1 <= L <= cap (all uniform)
+struct LagGeom {
+    u64 L;
+    u32 W, S;          // a strip's columns; the segments of rows the lanes are cut into (L >= 256: 1)
+    u32 m;             // rounds of LAG_ROWS S rows a chunk
+    u64 NS, G, NC, NI; // strips; rows of a chunk; chunks of the capacity; items = NS NC, item w = chunk w / NS, strip w % NS
+    __host__ __device__ LagGeom(u64 cap, u64 lag) : L(lag)
+    {
+        W = L < LAG_STRIP ? (u32)L : LAG_STRIP;
+        S = LAG_STRIP / W;
+        NS = (L + W - 1) / W;
+        const u64 g0 = (u64)LAG_ROWS * S, rows = (cap + L - 1) / L, i0 = NS * ((rows + g0 - 1) / g0);
+        m = i0 / LAG_ITEMS > 1 ? (u32)(i0 / LAG_ITEMS) : 1u;
+        G = g0 * m;
+        NC = (rows + G - 1) / G;
+        NI = NS * NC;
+    }
+};
+
+// ---- split
+template <int E>
+__device__ __forceinline__ void sub_words(u32 (&w)[4 * E], const u32 (&b)[4 * E])
+{
+#pragma unroll
+    for (int i = 0; i < 4 * E; ++i) {
+        if (E == 8) {
+            if (i & 1) {
+                const u64 v = ((u64)w[i] << 32 | w[i - 1]) - ((u64)b[i] << 32 | b[i - 1]);
+                w[i - 1] = (u32)v; w[i] = (u32)(v >> 32);
+            }
+        } else if (E == 4) w[i] -= b[i];
+        else w[i] = pk_sub<E>(w[i], b[i]);
+    }
+}
+
+// wb = elements e0 - L .. e0 - L + 15 of the region of n elements at src, zero where the index is negative (e0 + 16 > L: at
+// least one is not).  The region moved up by L elements is a region at an alignment of its own whose unit e0 these are; an
+// aligned word is read only where it holds a byte of the real region in front of byte n E.
+template <int E>
+__device__ __forceinline__ void lag_base(const u8 *src, u64 n, u64 L, u64 e0, u32 (&wb)[4 * E])
+{
+    const u64 moved = (u64)(uintptr_t)src - L * E;
+    const u32 sh = (u32)(moved & 15u), r = sh & 3u;
+    const long long p = (long long)(e0 * E), first = (long long)(L * E), end = (long long)(n * E);
+    const u8 *s16 = (const u8 *)(uintptr_t)((moved + (u64)p) & ~(u64)15);
+    uint4 a[E + 1];
+#pragma unroll
+    for (int i = 0; i <= E; ++i) {
+        a[i] = make_uint4(0, 0, 0, 0);
+        const long long lo = p + 16 * i - (long long)sh;
+        if (lo + 16 > first && lo < end && (i < E || sh != 0)) a[i] = gload<uint4>(s16 + 16 * i);
+    }
+    switch (sh >> 2) {                               // uniform
+    case 0: shift_into<E, 0, false>(a, r, wb); break;
+    case 1: shift_into<E, 1, false>(a, r, wb); break;
+    case 2: shift_into<E, 2, false>(a, r, wb); break;
+    default: shift_into<E, 3, false>(a, r, wb); break;
+    }
+    if (L > e0) {                                    // the unit the block's first L elements end in
+        const u32 zb = (u32)(L - e0) * E;            // its bytes in front of element L
+#pragma unroll
+        for (int i = 0; i < 4 * E; ++i) {
+            if (4u * i + 4u <= zb) wb[i] = 0;
+            else if (4u * i < zb) wb[i] &= ~0u << (8u * (zb - 4u * i));
+        }
+    }
+}
+
+template <int E, int Q>
+__device__ __forceinline__ void split_tile_lag(const TpWalk &wk, u32 r, u64 L, u8 *d_planes, const u64 *poff)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+        if (e0 + PL_UNIT > L) {
+            u32 wb[4 * E];
+            lag_base<E>(wk.in, wk.n, L, e0, wb);
+            sub_words<E>(w, wb);
+        }
+        zz_fold<E, 4 * E>(w);
+        split_store<E>(w, wk.n, e0, d_planes, poff);
+    }
+}
+
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_lag_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                               const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                               int *__restrict__ err, u32 n_tiles, u32 per_wg)
+{
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        const u64 L = d_lag[wk.b];
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile_lag<E, 0>(wk, r, L, d_planes, poff); break;
+        case 1: split_tile_lag<E, 1>(wk, r, L, d_planes, poff); break;
+        case 2: split_tile_lag<E, 2>(wk, r, L, d_planes, poff); break;
+        default: split_tile_lag<E, 3>(wk, r, L, d_planes, poff); break;
+        }
+    }
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// ---- merge
+// d[i], unfolded from byte i of the E planes at pl[0 .. E - 1]
+template <int E>
+__device__ __forceinline__ typename ElT<E>::T lag_d(const u8 *const (&pl)[E], u64 i)
+{
+    using T = typename ElT<E>::T;
+    T z = 0;
+#pragma unroll
+    for (int j = 0; j < E; ++j) z = (T)(z | (T)((T)gload<u8>(pl[j] + i) << (8 * j)));
+    return (T)((T)(z >> 1) ^ (T)(0 - (z & 1)));
+}
+
+// The walk all three launches share: every tile of the capacities is entered (the skips are by item, not by tile), and tile k of
+// a block's nt takes the run [k count / nt, (k + 1) count / nt) of the block's `count` items or column runs.
+struct LagRun {
+    u64 lo, hi;
+    __device__ __forceinline__ LagRun(const TpWalk &wk, u64 count)
+    {
+        // floor(k count / nt) without the product k count, which passes 64 bits for a lag and a capacity of 2^43 elements
+        // or more: per k <= count, and rest k < nt^2 < 2^62
+        const u64 nt = wk.tnext - wk.tb, per = count / nt, rest = count % nt;
+        lo = per * wk.k + rest * wk.k / nt;
+        hi = per * (wk.k + 1ull) + rest * (wk.k + 1ull) / nt;
+    }
+};
+
+// launch 1: sums[chunk L + column] for every chunk with a chunk behind it in the block's d_n[b] elements (all its rows are whole)
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                              const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                              const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
+                                                              const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                              u32 n_tiles, u32 per_wg, u8 *__restrict__ sums_all)
+{
+    using T = typename ElT<E>::T;
+    __shared__ T seg[TP_THREADS];
+    const u32 tid = threadIdx.x;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        wk.enter();
+        if (!wk.n) continue;                         // (uniform) empty, or past its capacity
+        const LagGeom g(cap[wk.b], d_lag[wk.b]);
+        if (g.NC < 2) continue;                      // (uniform)
+        const u64 rows = (wk.n + g.L - 1) / g.L;
+        const LagRun run(wk, g.NI);
+        T *sums = (T *)sums_all + (u64)wk.tb * LAG_SUMS_TILE;
+        const u8 *pl[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) pl[j] = d_planes + d_poff[(u64)wk.b * E + j];
+        const u32 s = tid / g.W, c = tid - s * g.W;
+        for (u64 w = run.lo; w < run.hi; ++w) {
+            const u64 ch = w / g.NS, col = (w - ch * g.NS) * g.W + c, row0 = ch * g.G;
+            if (row0 + g.G >= rows) break;           // (uniform) the chunk the block ends in, or one behind it
+            const bool act = s < g.S && col < g.L;
+            T t = 0;
+            if (act) {
+                for (u32 q = 0; q < g.m; ++q) {
+                    u64 i = (row0 + (u64)q * LAG_ROWS * g.S + (u64)s * LAG_ROWS) * g.L + col;
+#pragma unroll 8
+                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) t = (T)(t + lag_d<E>(pl, i));
+                }
+            }
+            if (g.S > 1) {                           // (uniform)
+                seg[tid] = t;
+                lds_barrier();
+                if (s == 0 && act) {
+                    t = 0;
+                    for (u32 s2 = 0; s2 < g.S; ++s2) t = (T)(t + seg[s2 * g.W + c]);
+                }
+            }
+            if (s == 0 && act) gstore<T>(sums + ch * g.L + col, t);
+            if (g.S > 1) lds_barrier();              // the next item writes the segments' totals
+        }
+    }
+}
+
+// launch 2: down each column, the sums of the chunks in front of every chunk that holds a row of the block
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_lag_scan(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                              const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                              const u64 *__restrict__ d_n, const u64 *__restrict__ d_lag,
+                                                              u32 n_tiles, u32 per_wg, u8 *__restrict__ sums_all)
+{
+    using T = typename ElT<E>::T;
+    __shared__ T seg[TP_THREADS];
+    const u32 tid = threadIdx.x;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        wk.enter();
+        if (!wk.n) continue;                         // (uniform)
+        const LagGeom g(cap[wk.b], d_lag[wk.b]);
+        if (g.NC < 2) continue;                      // (uniform)
+        const u64 rows = (wk.n + g.L - 1) / g.L, nc = (rows + g.G - 1) / g.G;      // the chunks that hold a row
+        if (nc < 2) continue;                        // (uniform) the merge reads no prefix
+        const u32 w2 = g.L < LAG_SCAN_COLS ? (u32)g.L : LAG_SCAN_COLS, gs_n = TP_THREADS / w2;
+        const LagRun run(wk, (g.L + w2 - 1) / w2);
+        T *sums = (T *)sums_all + (u64)wk.tb * LAG_SUMS_TILE;
+        const u32 gs = tid / w2, c = tid - gs * w2;
+        for (u64 cr = run.lo; cr < run.hi; ++cr) {
+            const u64 col = cr * w2 + c;
+            const bool act = gs < gs_n && col < g.L;
+            T carry = 0;
+            for (u64 at = 0; at < nc; at += (u64)gs_n * LAG_SCAN_PER) {         // (uniform)
+                const u64 ch0 = at + (u64)gs * LAG_SCAN_PER;
+                T v[LAG_SCAN_PER], t = 0;
+#pragma unroll
+                for (u32 q = 0; q < LAG_SCAN_PER; ++q) v[q] = act && ch0 + q + 1 < nc ? gload<T>(sums + (ch0 + q) * g.L + col) : (T)0;
+#pragma unroll
+                for (u32 q = 0; q < LAG_SCAN_PER; ++q) {
+                    const T x = v[q];
+                    v[q] = t;
+                    t = (T)(t + x);
+                }
+                seg[tid] = t;
+                lds_barrier();
+                T pre = carry, tot = 0;
+                for (u32 g2 = 0; g2 < gs_n; ++g2) {
+                    const T x = seg[g2 * w2 + c];
+                    if (g2 < gs) pre = (T)(pre + x);
+                    tot = (T)(tot + x);
+                }
+                lds_barrier();                       // the next round writes the lanes' totals
+                carry = (T)(carry + tot);
+#pragma unroll
+                for (u32 q = 0; q < LAG_SCAN_PER; ++q)
+                    if (act && ch0 + q < nc) gstore<T>(sums + (ch0 + q) * g.L + col, (T)(pre + v[q]));
+            }
+        }
+    }
+}
+
+// ---- the strips of 256 columns (L >= LAG_STRIP) in launch 3: a lane takes FOUR columns next to each other and LAG_ROWS / 4 rows
+// of the round's LAG_ROWS, so a plane is read a dword a lane (a wave: 256 contiguous bytes of one row, at any alignment) and the
+// elements leave four at a time; the four groups of rows are chained through LDS as the segments of the narrow form are.
+constexpr u32 LAG_VEC = 4, LAG_VROWS = LAG_ROWS / LAG_VEC;
+typedef u32 u32_any_t __attribute__((aligned(1)));
+typedef u32x2_t u32x2_any_t __attribute__((aligned(2)));
+typedef u32x4_t u32x4_any_t __attribute__((aligned(4)));
+
+// four elements next to each other to p, a multiple of E: one store (two at 8 bytes) at the element's alignment
+template <int E>
+__device__ __forceinline__ void lag_store4(u8 *p, const typename ElT<E>::T (&v)[LAG_VEC])
+{
+    const unsigned long long a = (unsigned long long)p;
+    if (E == 1) *(GLOBAL_AS u32_any_t *)a = (u32)v[0] | (u32)v[1] << 8 | (u32)v[2] << 16 | (u32)v[3] << 24;
+    else if (E == 2) {
+        u32x2_t x;
+        x.x = (u32)v[0] | (u32)v[1] << 16; x.y = (u32)v[2] | (u32)v[3] << 16;
+        *(GLOBAL_AS u32x2_any_t *)a = x;
+    } else if (E == 4) {
+        u32x4_t x;
+        x.x = (u32)v[0]; x.y = (u32)v[1]; x.z = (u32)v[2]; x.w = (u32)v[3];
+        *(GLOBAL_AS u32x4_any_t *)a = x;
+    } else {
+        u32x4_t x, y;
+        x.x = (u32)v[0]; x.y = (u32)((u64)v[0] >> 32); x.z = (u32)v[1]; x.w = (u32)((u64)v[1] >> 32);
+        y.x = (u32)v[2]; y.y = (u32)((u64)v[2] >> 32); y.z = (u32)v[3]; y.w = (u32)((u64)v[3] >> 32);
+        *(GLOBAL_AS u32x4_any_t *)a = x;
+        *(GLOBAL_AS u32x4_any_t *)(a + 16) = y;
+    }
+}
+
+// d[i .. i + 3] (all four inside the block and the row) from one dword of each plane
+template <int E>
+__device__ __forceinline__ void lag_d4(const u8 *const (&pl)[E], u64 i, typename ElT<E>::T (&d)[LAG_VEC])
+{
+    using T = typename ElT<E>::T;
+    u32 w[E];
+#pragma unroll
+    for (int j = 0; j < E; ++j) w[j] = *(const GLOBAL_AS u32_any_t *)(unsigned long long)(pl[j] + i);
+#pragma unroll
+    for (u32 c = 0; c < LAG_VEC; ++c) {
+        T z = 0;
+#pragma unroll
+        for (int j = 0; j < E; ++j) z = (T)(z | (T)((T)((w[j] >> (8 * c)) & 0xFFu) << (8 * j)));
+        d[c] = (T)((T)(z >> 1) ^ (T)(0 - (z & 1)));
+    }
+}
+
+// one chunk of a strip of 256 columns from row row0 on: every lane of the workgroup calls (the barriers); m, rows, n uniform
+template <int E>
+__device__ __forceinline__ void lag_merge_wide(const u8 *const (&pl)[E], u8 *dst, u64 n, u64 L, u64 rows, u64 row0, u32 m, u64 strip0,
+                                               const typename ElT<E>::T *prefix, typename ElT<E>::T *seg)
+{
+    using T = typename ElT<E>::T;
+    const u32 tid = threadIdx.x, rg = tid >> 6, cl = tid & 63u;
+    const u64 col0 = strip0 + (u64)cl * LAG_VEC;
+    const bool whole = col0 + LAG_VEC <= L;          // the lane's four columns are all the row's
+    T acc[LAG_VEC];
+#pragma unroll
+    for (u32 c = 0; c < LAG_VEC; ++c) acc[c] = prefix && col0 + c < L ? gload<T>(prefix + col0 + c) : (T)0;
+    for (u32 q = 0; q < m; ++q) {
+        const u64 rq = row0 + (u64)q * LAG_ROWS;
+        if (rq >= rows) break;                       // (uniform)
+        const u64 i0 = (rq + (u64)rg * LAG_VROWS) * L + col0;
+        T d[LAG_VROWS][LAG_VEC];
+        {
+            u64 i = i0;
+#pragma unroll
+            for (u32 k = 0; k < LAG_VROWS; ++k, i += L) {
+                if (whole && i + LAG_VEC <= n) lag_d4<E>(pl, i, d[k]);
+                else {
+#pragma unroll
+                    for (u32 c = 0; c < LAG_VEC; ++c) d[k][c] = col0 + c < L && i + c < n ? lag_d<E>(pl, i + c) : (T)0;
+                }
+            }
+        }
+#pragma unroll
+        for (u32 k = 1; k < LAG_VROWS; ++k)
+#pragma unroll
+            for (u32 c = 0; c < LAG_VEC; ++c) d[k][c] = (T)(d[k][c] + d[k - 1][c]);
+#pragma unroll
+        for (u32 c = 0; c < LAG_VEC; ++c) seg[tid * LAG_VEC + c] = d[LAG_VROWS - 1][c];
+        lds_barrier();
+        T pre[LAG_VEC];
+#pragma unroll
+        for (u32 c = 0; c < LAG_VEC; ++c) {
+            pre[c] = acc[c];
+#pragma unroll
+            for (u32 g2 = 0; g2 < LAG_VEC; ++g2) {
+                const T x = seg[(g2 * 64u + cl) * LAG_VEC + c];
+                if (g2 < rg) pre[c] = (T)(pre[c] + x);
+                acc[c] = (T)(acc[c] + x);
+            }
+        }
+        lds_barrier();                               // the next round writes the groups' totals
+        {
+            u64 i = i0;
+#pragma unroll
+            for (u32 k = 0; k < LAG_VROWS; ++k, i += L) {
+                if (whole && i + LAG_VEC <= n) {
+                    T o[LAG_VEC];
+#pragma unroll
+                    for (u32 c = 0; c < LAG_VEC; ++c) o[c] = (T)(pre[c] + d[k][c]);
+                    lag_store4<E>(dst + i * E, o);
+                } else {
+#pragma unroll
+                    for (u32 c = 0; c < LAG_VEC; ++c)
+                        if (col0 + c < L && i + c < n) gstore<T>(dst + (i + c) * E, (T)(pre[c] + d[k][c]));
+                }
+            }
+        }
+    }
+}
+
+// launch 3: sums[chunk L + column] is by now the sum of the column's d's in front of the chunk (have_sums: launches 1 and 2 ran)
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
+                                                               const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                               int *__restrict__ err, u32 n_tiles, u32 per_wg,
+                                                               const u8 *__restrict__ sums_all)
+{
+    using T = typename ElT<E>::T;
+    __shared__ T seg[TP_THREADS * LAG_VEC];
+    const u32 tid = threadIdx.x;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        wk.enter();
+        const u64 n = wk.n;
+        if (!n) continue;                            // (uniform) empty, or past its capacity: no byte of it is touched
+        const LagGeom g(cap[wk.b], d_lag[wk.b]);
+        const u64 rows = (n + g.L - 1) / g.L;
+        const bool chained = (rows + g.G - 1) / g.G > 1;                         // (uniform) planes_lag_scan's condition
+        const LagRun run(wk, g.NI);
+        const T *sums = (const T *)sums_all + (u64)wk.tb * LAG_SUMS_TILE;
+        u8 *dst = (u8 *)wk.in;
+        const u8 *pl[E];
+#pragma unroll
+        for (int j = 0; j < E; ++j) pl[j] = d_planes + d_poff[(u64)wk.b * E + j];
+        const u32 s = tid / g.W, c = tid - s * g.W;
+        for (u64 w = run.lo; w < run.hi; ++w) {
+            const u64 ch = w / g.NS, col = (w - ch * g.NS) * g.W + c, row0 = ch * g.G;
+            if (row0 >= rows) break;                 // (uniform) behind the block's last row
+            if (g.W == LAG_STRIP) {                  // (uniform) four columns a lane
+                lag_merge_wide<E>(pl, dst, n, g.L, rows, row0, g.m, (w - ch * g.NS) * g.W, chained ? sums + ch * g.L : nullptr, seg);
+                continue;
+            }
+            const bool act = s < g.S && col < g.L;
+            T acc = chained && act ? gload<T>(sums + ch * g.L + col) : (T)0;     // the element above the round's first row
+            for (u32 q = 0; q < g.m; ++q) {
+                const u64 rq = row0 + (u64)q * LAG_ROWS * g.S;
+                if (rq >= rows) break;               // (uniform)
+                const u64 i0 = (rq + (u64)s * LAG_ROWS) * g.L + col;
+                T d[LAG_ROWS];
+                {
+                    u64 i = i0;
+#pragma unroll
+                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) d[k] = act && i < n ? lag_d<E>(pl, i) : (T)0;
+                }
+#pragma unroll
+                for (u32 k = 1; k < LAG_ROWS; ++k) d[k] = (T)(d[k] + d[k - 1]);
+                T pre = acc;
+                if (g.S > 1) {                       // (uniform) the segments above this one in the round
+                    seg[tid] = d[LAG_ROWS - 1];
+                    lds_barrier();
+                    T tot = 0;
+                    for (u32 s2 = 0; s2 < g.S; ++s2) {
+                        const T x = seg[s2 * g.W + c];
+                        if (s2 < s) pre = (T)(pre + x);
+                        tot = (T)(tot + x);
+                    }
+                    lds_barrier();                   // the next round writes the segments' totals
+                    acc = (T)(acc + tot);
+                } else acc = (T)(acc + d[LAG_ROWS - 1]);
+                {
+                    u64 i = i0;
+#pragma unroll
+                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L)
+                        if (act && i < n) gstore<T>(dst + i * E, (T)(pre + d[k]));
+                }
+            }
+        }
+    }
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// the launches read tile_setup's workspace: extra 0 the plane offsets, extra 1 the clamped lags, the scratch the column sums
+template <int E>
+void planes_lag_launch(bool merge, bool sums, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes,
+                       int *err)
+{
+    const u64 *poff = (const u64 *)a.extra[0], *lag = (const u64 *)a.extra[1];
+    if (!merge) {
+        hipLaunchKernelGGL(planes_lag_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, d_planes, poff, lag, err, a.nt, a.per_wg);
+        return;
+    }
+    if (sums) {
+        hipLaunchKernelGGL(planes_lag_sums<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, (const u8 *)d_planes, poff, lag, a.nt, a.per_wg, a.scratch);
+        hipLaunchKernelGGL(planes_lag_scan<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, lag, a.nt, a.per_wg, a.scratch);
+    }
+    hipLaunchKernelGGL(planes_lag_merge<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       (const u8 *)d_planes, poff, lag, err, a.nt, a.per_wg, (const u8 *)a.scratch);
+}
+
+}  // namespace
+
+// the _lag entries: split is one launch; merge is the column sums and their scan (where a block has more than one chunk) and the
+// merge itself.  The caller has checked the arguments (every h_lag[b] >= 1).
+int planes_lag_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                          const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u64 *h_lag)
+{
+    std::vector<u64> lag((size_t)nblocks);
+    bool sums = false;
+    for (int b = 0; b < nblocks; ++b) {
+        lag[b] = h_lag[b] < h_cap[b] ? h_lag[b] : h_cap[b] ? h_cap[b] : 1;       // at or past the capacity: no element has a base
+        if (merge && h_cap[b] && LagGeom(h_cap[b], lag[b]).NC > 1) sums = true;
+    }
+    const TileExtra x[2] = {{h_plane_off, (size_t)nblocks * elem * 8}, {lag.data(), (size_t)nblocks * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, sums ? (size_t)LAG_SUMS_TILE * elem : 0, 0, &a)) return rc;
+    if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
+    switch (elem) {
+    case 1: planes_lag_launch<1>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 2: planes_lag_launch<2>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 4: planes_lag_launch<4>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    default: planes_lag_launch<8>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
