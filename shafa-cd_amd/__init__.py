@@ -1421,14 +1421,14 @@ def _rle_groups(sizes, in_n, max_bytes):
     return _groups([_al16(s) for s in sizes], max_bytes, [max(1, -(-n // 8192)) for n in in_n])
 
 
-def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes):
+def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes, groups=None):
     """rle_decode_dev of these blocks into regions of exactly their decoded sizes (_rle_measure's), group after group
-    (_rle_groups) into one buffer sized for the largest group.  Yields (first, end, buffer, offsets, device sizes) once a
-    group's decode is enqueued; what the caller enqueues then reads the buffer before the next group's decode overwrites
-    it.  Groups that decode to nothing are left out.  Enqueues only."""
+    (`groups`, or _rle_groups) into one buffer sized for the largest group.  Yields (first, end, buffer, offsets, device
+    sizes) once a group's decode is enqueued; what the caller enqueues then reads the buffer before the next group's decode
+    overwrites it.  Groups that decode to nothing are left out.  Enqueues only."""
     import torch
     dev = d_in.device
-    groups = _rle_groups(sizes, in_n, max_bytes)
+    groups = groups or _rle_groups(sizes, in_n, max_bytes)
     biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
     d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
     d_out_n = torch.zeros(len(sizes), dtype=torch.int64, device=dev)
@@ -1471,141 +1471,248 @@ def _decode_args(shaf, cod, rle, freq, what):
     return sf, files
 
 
-class _Parse:
-    """one file set after the parse's synchronisation: mode, the blocks in front of the first parse fault (fb) with their
-    payload sizes (pn) and symbol counts (nsym, .cod only), that fault (perr), and the device arrays of the parse"""
+def _accepted_modes(sf, decode_rle):
+    """The modes a decode takes from the .cod or .freq.  decode_rle True asks for RLE bytes to decode: mode R only; False, and
+    None ("as the .cod's mode says"), take a .shaf + .cod of either mode."""
+    return "RN" if sf and not decode_rle else "R"
 
 
-def _open_files(shaf, cod, rle, freq, stream, what):
-    """the argument checks, the stream and the batch of a single-file-set call -> (sf, files, stream, slots, batch)"""
-    sf, files = _decode_args(shaf, cod, rle, freq, what)
-    st = _stream(files[0].device, stream)
-    mb = unpack_max_blocks(files[1].numel(), "cod" if sf else "freq")
-    if mb > 0x7FFFFFFF:
-        raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
-    return sf, files, st, mb, Batch(mb, 1 << 20)
+def _no_rle_stage(sf, mode, decode_rle):
+    """whether the decoded bytes are the SF decoder's output: a mode-N pair, or a mode-R pair read as its .rle bytes"""
+    return sf and (mode == "N" or decode_rle is False)
 
 
-def _parse_files(bt, st, sf, files, mb, modes, what):
-    """unpack_cod + unpack_shaf (or unpack_rle_freq), one synchronisation, 16 bytes a block read back -> _Parse.  Raises a
-    bad header, a mode outside `modes` and a parse fault on block 0; fb == 0 without one is the empty file."""
-    import torch
-    dev = files[0].device
-    p = _Parse()
-    d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
-    p.d_off = torch.zeros(mb, dtype=torch.int64, device=dev)
-    p.d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
-    if sf:
-        p.d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
-        p.d_tab = torch.empty(mb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
-        bt.unpack_cod(st, mb, files[1], d_info, p.d_nsym, p.d_tab)
-        bt.unpack_shaf(st, mb, files[0], d_info[INFO_INDEXED:INFO_INDEXED + 1], p.d_off, p.d_n)
-    else:
-        bt.unpack_rle_freq(st, mb, files[1], files[0].numel(), d_info, p.d_off, p.d_n)
-    _, errs = bt.finish(st, mb, raise_on_error=False)                        # the parse's one synchronisation
-    info = _u64_host(d_info)
+def _parse_rules(what, info, errs, pn, nsym, sf, modes):
+    """The rules behind the parse's synchronisation, for one file, on plain lists: its info words, and from its first slot
+    on the per-block codes, payload sizes and (sf) symbol counts -> (mode, fb, perr): the blocks in front of the first parse
+    fault, and that fault.  Raises a bad header, a mode outside `modes` and a fault on block 0; fb == 0 without one is the
+    empty file.  A symbol count above 8 x the payload's bytes is a fault of that block (decompress_files)."""
     if info[INFO_STATUS]:
         raise ShafaError(FILE_STREAM_FAILED, f"{what}: bad header")
-    p.mode = chr(info[INFO_MODE])
-    if p.mode not in modes:
-        raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: mode {p.mode!r}")
+    mode = chr(info[INFO_MODE])
+    if mode not in modes:
+        raise ShafaError(FILE_UNRECOGNIZABLE, f"{what}: mode {mode!r}")
     nidx = info[INFO_INDEXED]
-    pn = _u64_host(p.d_n)[:nidx]
     errs = errs[:nidx]
-    nsym = None
     if sf:
-        nsym = _u64_host(p.d_nsym)[:nidx]
         errs = [e if e or nsym[b] <= 8 * pn[b] else FILE_UNRECOGNIZABLE for b, e in enumerate(errs)]
-    p.fb, p.perr = _first_error(errs)
-    if not p.perr and info[INFO_COUNT] > nidx:                               # cannot happen: max_blocks covers any count
-        p.perr = FILE_STREAM_FAILED
-    if p.fb == 0 and p.perr:
-        raise ShafaError(p.perr, f"{what}: block 0")
-    p.pn, p.nsym = pn[:p.fb], nsym[:p.fb] if sf else None
-    return p
+    fb, perr = _first_error(errs)
+    if not perr and info[INFO_COUNT] > nidx:                                 # cannot happen: max_blocks covers any count
+        perr = FILE_STREAM_FAILED
+    if fb == 0 and perr:
+        raise ShafaError(perr, f"{what}: block 0")
+    return mode, fb, perr
 
 
-def _gather_payloads(bt, st, d_file, p, b0, b1):
-    """unpack_payloads of blocks [b0, b1) into exact aligned regions -> (buffer, offsets, sizes, device sizes)"""
-    import torch
-    pn = p.pn[b0:b1]
-    poff, ptot = _layout(pn)
-    d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=d_file.device)
-    bt.unpack_payloads(st, d_file, p.d_off[b0:b1], p.d_n[b0:b1], d_pay, poff, pn)
-    return d_pay, poff, pn, p.d_n[b0:b1]
-
-
-def _sf_decode_blocks(bt, st, d_shaf, p, b0, b1, pack, what, then=None):
-    """Blocks [b0, b1) of a parsed .shaf / .cod pair: unpack_payloads -> sf_decode_dev (-> pack_payloads(RAW) when `pack`;
-    -> then(buffer, offsets, sizes, device sizes), which enqueues a reader of the decoded regions, when given) -> one
-    synchronisation; a block whose codes take the decoder's single slot for 33..64-bit codes from another is decoded
-    again on its own (and the pack and `then` run again).  The first SF error in block order raises.
-    -> (buffer, offsets, sizes, device sizes) of the decoded blocks, and the packed tensor (None without `pack`)"""
-    import torch
-    dev = d_shaf.device
+def _sf_decode_again(bt, st, args, errs, lo, hi, again, width):
+    """While the first error of blocks [lo, hi) of an sf_decode_dev call (`args`: what followed its stream; errs: its codes) is
+    LACK_OF_MEMORY at a block not yet in `again` — the decoder's one slot for 33..64-bit codes was taken by another block —
+    that block is decoded again on its own: one synchronisation each, over `width` error words; its code in errs is replaced
+    and it joins `again`.  -> the span's first error now, as (block - lo, code)"""
+    d_pay, poff, pn, d_n, d_tab, d_nsym, d_sfo, ooff, nsym = args
     tsz = C.sizeof(CodeTable)
-    d_pay, poff, pn, d_n = _gather_payloads(bt, st, d_shaf, p, b0, b1)
-    nsym, d_nsym, d_tab = p.nsym[b0:b1], p.d_nsym[b0:b1], p.d_tab[b0 * tsz:b1 * tsz]
-    ooff, otot = _layout(nsym)
-    d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
-    bt.sf_decode_dev(st, d_pay, poff, pn, d_n, d_tab, d_nsym, d_sfo, ooff, nsym)
-    out = None
-    if pack:
-        total = sum(nsym)
-        out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
-        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
-        bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
-    if then:
-        then(d_sfo, ooff, nsym, d_nsym)
-    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-    errs = errs[:b1 - b0]
-    again = set()
-    b, e = _first_error(errs)
-    while e == LACK_OF_MEMORY and b not in again:                            # the one slot for 33..64-bit codes was taken
-        bt.sf_decode_dev(st, d_pay, poff[b:b + 1], pn[b:b + 1], d_n[b:b + 1], d_tab[b * tsz:(b + 1) * tsz],
-                         d_nsym[b:b + 1], d_sfo, ooff[b:b + 1], nsym[b:b + 1])
-        _, one = bt.finish(st, bt.max_blocks, raise_on_error=False)
-        errs[b] = one[0]
-        again.add(b)
+    b, e = _first_error(errs[lo:hi])
+    while e == LACK_OF_MEMORY and lo + b not in again:
+        g = lo + b
+        bt.sf_decode_dev(st, d_pay, poff[g:g + 1], pn[g:g + 1], d_n[g:g + 1], d_tab[g * tsz:(g + 1) * tsz], d_nsym[g:g + 1],
+                         d_sfo, ooff[g:g + 1], nsym[g:g + 1])
+        _, one = bt.finish(st, width, raise_on_error=False)
+        errs[g] = one[0]
+        again.add(g)
+        b, e = _first_error(errs[lo:hi])
+    return b, e
+
+
+class _ParsedSet:
+    """One file set on its batch, for the single-set decode drivers (the decode side's _GroupBlocks).  Making it checks the
+    file arguments (decompress_files') and takes the stream; entering it opens the Batch — closed on leaving — and parses:
+    unpack_cod + unpack_shaf (or unpack_rle_freq), one synchronisation, 16 bytes a block read back, _parse_rules.  Then it
+    holds mode; fb, the blocks in front of the first parse fault, with their payload sizes (pn) and symbol counts (nsym, .cod
+    only); perr, that fault, which fault() raises at the driver's place for it; plain, whether the decoded bytes are the SF
+    decoder's output (_no_rle_stage); the device arrays of the parse; max_bytes (default: a quarter of the free device
+    memory).  decode_rle: the caller's True or False, or None for "as the .cod's mode says"."""
+
+    def __init__(self, what, shaf, cod, rle, freq, stream, max_bytes=None, decode_rle=None):
+        self.what, self.max_bytes = what, max_bytes
+        self.decode_rle = decode_rle if decode_rle is None else bool(decode_rle)
+        self.sf, self.files = _decode_args(shaf, cod, rle, freq, what)
+        self.dev = self.files[0].device
+        self.st = _stream(self.dev, stream)
+        self.mb = unpack_max_blocks(self.files[1].numel(), "cod" if self.sf else "freq")
+        if self.mb > 0x7FFFFFFF:
+            raise ShafaError(LACK_OF_MEMORY, f"{what}: text too long")
+
+    def __enter__(self):
+        self.bt = Batch(self.mb, 1 << 20)
+        try:
+            self.max_bytes = _max_bytes(self.dev, self.max_bytes)
+            self._parse()
+        except BaseException:
+            self.bt.close()
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        self.bt.close()
+
+    def _parse(self):
+        import torch
+        bt, st, sf, files, mb, dev = self.bt, self.st, self.sf, self.files, self.mb, self.dev
+        d_info = torch.zeros(UNPACK_INFO_WORDS, dtype=torch.int64, device=dev)
+        self.d_off = torch.zeros(mb, dtype=torch.int64, device=dev)
+        self.d_n = torch.zeros(mb, dtype=torch.int64, device=dev)
+        if sf:
+            self.d_nsym = torch.zeros(mb, dtype=torch.int64, device=dev)
+            self.d_tab = torch.empty(mb * C.sizeof(CodeTable), dtype=torch.uint8, device=dev)
+            bt.unpack_cod(st, mb, files[1], d_info, self.d_nsym, self.d_tab)
+            bt.unpack_shaf(st, mb, files[0], d_info[INFO_INDEXED:INFO_INDEXED + 1], self.d_off, self.d_n)
+        else:
+            bt.unpack_rle_freq(st, mb, files[1], files[0].numel(), d_info, self.d_off, self.d_n)
+        _, errs = bt.finish(st, mb, raise_on_error=False)                    # the parse's one synchronisation
+        info = _u64_host(d_info)
+        pn = _u64_host(self.d_n)[:info[INFO_INDEXED]]
+        nsym = _u64_host(self.d_nsym)[:info[INFO_INDEXED]] if sf else None
+        self.mode, self.fb, self.perr = _parse_rules(self.what, info, errs, pn, nsym, sf, _accepted_modes(sf, self.decode_rle))
+        self.pn, self.nsym = pn[:self.fb], nsym[:self.fb] if sf else None
+        self.plain = _no_rle_stage(sf, self.mode, self.decode_rle)
+
+    def fault(self):
+        """raises the parse fault, if there is one: each driver calls this where that fault comes in its order of errors"""
+        if self.perr:
+            raise ShafaError(self.perr, f"{self.what}: block {self.fb}")
+
+    def check(self, errs, b0=0):
+        """raises the first of these per-block codes, of blocks b0 on, in block order"""
         b, e = _first_error(errs)
-    if e:
-        raise ShafaError(e, f"{what}: block {b0 + b}")
-    if again and (pack or then):
+        if e:
+            raise ShafaError(e, f"{self.what}: block {b0 + b}")
+
+    def finish_rle(self):
+        """the synchronisation behind rle_decode_dev of measured blocks, with the late rule: the size pass accepted every
+        block, so an error now is the device's and names no block"""
+        _, errs = self.bt.finish(self.st, self.bt.max_blocks, raise_on_error=False)
+        _, e = _first_error(errs)
+        if e:
+            raise ShafaError(e, f"{self.what}: RLE decoding")
+
+    def gather(self, b0, b1):
+        """unpack_payloads of blocks [b0, b1) into exact aligned regions -> (buffer, offsets, sizes, device sizes)"""
+        import torch
+        pn = self.pn[b0:b1]
+        poff, ptot = _layout(pn)
+        d_pay = torch.empty(ptot + 16, dtype=torch.uint8, device=self.dev)
+        self.bt.unpack_payloads(self.st, self.files[0], self.d_off[b0:b1], self.d_n[b0:b1], d_pay, poff, pn)
+        return d_pay, poff, pn, self.d_n[b0:b1]
+
+    def sf_decode(self, b0, b1, pack, then=None):
+        """Blocks [b0, b1) of a .shaf / .cod pair: unpack_payloads -> sf_decode_dev (-> pack_payloads(RAW) when `pack`; ->
+        then(buffer, offsets, sizes, device sizes), which enqueues a reader of the decoded regions, when given) -> one
+        synchronisation; a block whose codes take the decoder's single slot for 33..64-bit codes from another is decoded
+        again on its own (_sf_decode_again; the pack and `then` run again).  The first SF error in block order raises.
+        -> (buffer, offsets, sizes, device sizes) of the decoded blocks, and the packed tensor (None without `pack`)"""
+        import torch
+        bt, st, dev = self.bt, self.st, self.dev
+        tsz = C.sizeof(CodeTable)
+        d_pay, poff, pn, d_n = self.gather(b0, b1)
+        nsym, d_nsym = self.nsym[b0:b1], self.d_nsym[b0:b1]
+        ooff, otot = _layout(nsym)
+        d_sfo = torch.empty(otot + 16, dtype=torch.uint8, device=dev)
+        args = (d_pay, poff, pn, d_n, self.d_tab[b0 * tsz:b1 * tsz], d_nsym, d_sfo, ooff, nsym)
+        bt.sf_decode_dev(st, *args)
+        out = None
         if pack:
+            total = sum(nsym)
+            out = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            d_len = torch.zeros(1, dtype=torch.int64, device=dev)
             bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
         if then:
             then(d_sfo, ooff, nsym, d_nsym)
-        bt.finish(st, bt.max_blocks)
-    return (d_sfo, ooff, nsym, d_nsym), (out[:total] if pack else None)
+        _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+        errs = errs[:b1 - b0]
+        again = set()
+        _sf_decode_again(bt, st, args, errs, 0, b1 - b0, again, bt.max_blocks)
+        self.check(errs, b0)
+        if again and (pack or then):
+            if pack:
+                bt.pack_payloads(st, FRAME_RAW, d_sfo, ooff, nsym, d_nsym, out, total, d_len)
+            if then:
+                then(d_sfo, ooff, nsym, d_nsym)
+            bt.finish(st, bt.max_blocks)
+        return (d_sfo, ooff, nsym, d_nsym), (out[:total] if pack else None)
 
+    def measure(self):
+        """The decoded size of every block in front of the first parse fault (fb > 0), and the RLE decoder's inputs (buffer,
+        offsets, sizes, device sizes; None for a plain set, whose sizes are the .cod's).  An RLE set goes through
+        unpack_payloads (and sf_decode_dev for .shaf + .cod) and the size pass; the first SF error, then the first RLE error
+        in block order raise."""
+        if self.plain:
+            return list(self.nsym), None
+        rin = self.sf_decode(0, self.fb, False)[0] if self.sf else self.gather(0, self.fb)
+        sizes, errs = _rle_measure(self.bt, self.st, *rin, self.bt.max_blocks)
+        self.check(errs)
+        return sizes, rin
 
-def _measure_set(bt, st, sf, files, p, what):
-    """The decoded size of every block in front of the first parse fault of a parsed set (fb > 0), and the RLE decoder's
-    inputs (buffer, offsets, sizes, device sizes; None for mode N, whose sizes are the .cod's).  An RLE set goes through
-    unpack_payloads (and sf_decode_dev for .shaf + .cod) and the size pass; the first SF error, then the first RLE error in
-    block order raise."""
-    if sf and p.mode == "N":
-        return list(p.nsym), None
-    if sf:
-        rin, _ = _sf_decode_blocks(bt, st, files[0], p, 0, p.fb, False, what)
-    else:
-        rin = _gather_payloads(bt, st, files[0], p, 0, p.fb)
-    sizes, errs = _rle_measure(bt, st, *rin, bt.max_blocks)
-    b, e = _first_error(errs)
-    if e:
-        raise ShafaError(e, f"{what}: block {b}")
-    return sizes, rin
+    def rle_range(self, rin, sizes, b0, b1):
+        """blocks [b0, b1) of a measured RLE set, decoded and packed -> their bytes; synchronised"""
+        d_in, in_off, in_n, d_in_n = rin
+        out = _rle_decode_exact(self.bt, self.st, d_in, in_off[b0:b1], in_n[b0:b1], d_in_n[b0:b1], sizes[b0:b1], self.max_bytes)
+        self.finish_rle()
+        return out
 
+    def plan(self, measured=True):
+        """What walk goes by (fb > 0), settled before anything of the groups is enqueued: `sizes` of the regions a reader is
+        given, block by block, `starts` (their prefix sums) and `groups`, [(first, end)] within max_bytes.
+          a plain set                      the .cod's symbol counts; groups by _al16(symbols) + _al16(payload)
+          an RLE form, measured            measure(), then the parse fault; the decoded sizes; _rle_groups
+          an RLE form, measured=False      its RLE bytes as they leave the SF decoder (or lie in the .rle), grouped as a plain
+                                           set (.rle: by _al16(payload)): build_index, whose entry measures them itself"""
+        import itertools
+        self.rin = None
+        if self.plain or not measured:
+            self.sizes = list(self.nsym if self.sf else self.pn)
+            cost = [_al16(s) + _al16(n) for s, n in zip(self.sizes, self.pn)] if self.sf else [_al16(n) for n in self.pn]
+            self.groups = _groups(cost, self.max_bytes)
+        else:
+            self.sizes, self.rin = self.measure()
+            self.fault()
+            self.groups = _rle_groups(self.sizes, self.rin[2], self.max_bytes)
+        self.starts = list(itertools.accumulate(self.sizes, initial=0))
 
-def _rle_decode_range(bt, st, rin, sizes, b0, b1, max_bytes, what):
-    """blocks [b0, b1) of a measured RLE set, decoded and packed -> their bytes; synchronised"""
-    d_in, in_off, in_n, d_in_n = rin
-    out = _rle_decode_exact(bt, st, d_in, in_off[b0:b1], in_n[b0:b1], d_in_n[b0:b1], sizes[b0:b1], max_bytes)
-    _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-    _, e = _first_error(errs)
-    if e:                                                                    # the size pass accepted every block: the device
-        raise ShafaError(e, f"{what}: RLE decoding")
-    return out
+    def walk(self, reader, before_last=None):
+        """The blocks of a planned set, group by group: reader(a, z, buffer, offsets, sizes, device sizes) enqueues what reads
+        the regions of blocks [a, z), which hold until the next group is decoded.  A reader may be called a second time for
+        the same group — a block of it was decoded again (sf_decode) — and must then leave what a single call would have left;
+        that is all the walk promises about calls.  before_last() is enqueued behind the last group's reader, in front of the
+        last synchronisation.
+          a plain set            sf_decode -> reader, one synchronisation a group, which raises the group's SF faults; the parse
+                                 fault behind the last group
+          an unmeasured RLE form sf_decode and its synchronisation (.rle: unpack_payloads) -> reader -> one synchronisation a
+                                 group; the reader's per-block codes wait for the SF faults of the groups behind, then raise in
+                                 block order; then the parse fault
+          a measured RLE form    rle_decode_dev -> reader, the groups back to back on the stream through one reused buffer
+                                 (_rle_decode_groups; groups that decode to nothing are left out), one synchronisation
+                                 (finish_rle)"""
+        bt, st = self.bt, self.st
+        if self.rin is not None:
+            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *self.rin, self.sizes, self.max_bytes, self.groups):
+                reader(a, z, d_a, a_off, self.sizes[a:z], d_a_n)
+            if before_last:
+                before_last()
+            return self.finish_rle()
+        codes = []
+        for a, z in self.groups:
+            def then(*regions):
+                reader(a, z, *regions)
+                if before_last and z == self.fb:
+                    before_last()
+            if self.plain:                                                   # no fault of its own: within the group's one synchronisation
+                self.sf_decode(a, z, False, then)
+                continue
+            then(*(self.sf_decode(a, z, False)[0] if self.sf else self.gather(a, z)))
+            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
+            codes += errs[:z - a]
+        self.check(codes)
+        self.fault()
 
 
 def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, stream=None, max_bytes=None):
@@ -1626,25 +1733,16 @@ def decompress_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, 
     decoding (every code of a table the decoder accepts has >= 1 bit, so the host's decoder runs out of input).  A block whose
     codes take the decoder's single slot for 33..64-bit codes from another is decoded again on its own."""
     import torch
-    what = "decompress_files"
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
-        if p.fb == 0:
-            return torch.empty(0, dtype=torch.uint8, device=dev)
-        if sf and not (p.mode == "R" and decode_rle):
-            _, out = _sf_decode_blocks(bt, st, files[0], p, 0, p.fb, not p.perr, what)
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
+    with _ParsedSet("decompress_files", shaf, cod, rle, freq, stream, max_bytes, decode_rle) as s:
+        if s.fb == 0:
+            return torch.empty(0, dtype=torch.uint8, device=s.dev)
+        if s.plain:
+            _, out = s.sf_decode(0, s.fb, not s.perr)
+            s.fault()
             return out
-        sizes, rin = _measure_set(bt, st, sf, files, p, what)
-        if p.perr:
-            raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        return _rle_decode_range(bt, st, rin, sizes, 0, p.fb, max_bytes, what)
-    finally:
-        bt.close()
+        sizes, rin = s.measure()
+        s.fault()
+        return s.rle_range(rin, sizes, 0, s.fb)
 
 
 def decoded_sizes(shaf=None, cod=None, rle=None, freq=None, stream=None):
@@ -1656,16 +1754,10 @@ def decoded_sizes(shaf=None, cod=None, rle=None, freq=None, stream=None):
       shaf + cod, mode R   unpack_payloads, sf_decode_dev, then the size pass on the RLE bytes; no RLE output is allocated
     Raises what decompress_files raises for faults in what the call looked at, with its precedence: header, mode, parse
     faults, and for the two RLE forms the SF and RLE faults of every block."""
-    what = "decoded_sizes"
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
-        sizes = _measure_set(bt, st, sf, files, p, what)[0] if p.fb else []
-        if p.perr:
-            raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        return [int(s) for s in sizes]
-    finally:
-        bt.close()
+    with _ParsedSet("decoded_sizes", shaf, cod, rle, freq, stream, 0) as s:  # no working memory to bound: nothing is asked
+        sizes = s.measure()[0] if s.fb else []
+        s.fault()
+        return [int(n) for n in sizes]
 
 
 def decompress_range(offset, length, shaf=None, cod=None, rle=None, freq=None, stream=None, max_bytes=None):
@@ -1684,29 +1776,19 @@ def decompress_range(offset, length, shaf=None, cod=None, rle=None, freq=None, s
     what = "decompress_range"
     if offset < 0 or length < 0:
         raise ValueError(f"{what}: negative offset or length")
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
-        out, lo, hi = torch.empty(0, dtype=torch.uint8, device=dev), 0, 0
-        if p.fb:
-            sizes, rin = _measure_set(bt, st, sf, files, p, what)
+    with _ParsedSet(what, shaf, cod, rle, freq, stream, max_bytes) as s:
+        out, lo, hi = torch.empty(0, dtype=torch.uint8, device=s.dev), 0, 0
+        if s.fb:
+            sizes, rin = s.measure()
             ends = list(itertools.accumulate(sizes))                         # block b is bytes [ends[b] - sizes[b], ends[b])
             lo, hi = min(offset, ends[-1]), min(offset + length, ends[-1])
             if lo < hi:
                 b0, b1 = bisect.bisect_right(ends, lo), bisect.bisect_left(ends, hi) + 1
-                if rin is None:
-                    _, out = _sf_decode_blocks(bt, st, files[0], p, b0, b1, True, what)
-                else:
-                    out = _rle_decode_range(bt, st, rin, sizes, b0, b1, max_bytes, what)
+                out = s.sf_decode(b0, b1, True)[1] if rin is None else s.rle_range(rin, sizes, b0, b1)
                 first = ends[b0] - sizes[b0]
                 lo, hi = lo - first, hi - first
-        if p.perr:
-            raise ShafaError(p.perr, f"{what}: block {p.fb}")
+        s.fault()
         return out[lo:hi]
-    finally:
-        bt.close()
 
 
 Verify = collections.namedtuple("Verify", "equal first_diff decoded_size")
@@ -1733,57 +1815,40 @@ def verify_files(d_in, shaf=None, cod=None, rle=None, freq=None, decode_rle=True
     wherever it lies.
     Neither the decoded file nor a copy of d_in ever exists: blocks are decoded in groups that fit max_bytes (default: a
     quarter of the free device memory) into exact aligned regions, which compare_dev reads against d_in in place.
+    The chain is _ParsedSet.walk's with compare_dev as the reader:
       shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload); each runs unpack_payloads ->
-                                  sf_decode_dev -> compare_dev -> one synchronisation, which also reads its results
-      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files (a mode-R set keeps its .rle bytes resident),
+                                  sf_decode_dev -> compare_dev -> one synchronisation
+      rle + freq; shaf + cod, mode R          the measure as in decompress_files (a mode-R set keeps its .rle bytes resident),
                                   then per group of _rle_groups rle_decode_dev -> compare_dev into one reused buffer, back to
-                                  back on the stream; one synchronisation ends the call and the results are read once
-    No pack_payloads(RAW) runs.  A mode-R .cod with decode_rle=False is compared as the .rle bytes, group by group as mode N."""
+                                  back on the stream; one synchronisation ends the call
+    The results are read once, behind the last synchronisation.  No pack_payloads(RAW) runs.  A mode-R .cod with
+    decode_rle=False is compared as the .rle bytes, group by group as mode N."""
     import torch
     what = "verify_files"
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        if not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_contiguous() or d_in.device != dev:
-            raise ValueError(f"{what}: d_in is a contiguous uint8 CUDA tensor on the files' device")
-        d_in = d_in.reshape(-1)
-        ref_len = d_in.numel()
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
-        sizes, first = [], []
-        if p.fb and sf and not (p.mode == "R" and decode_rle):
-            sizes = list(p.nsym)
+    s = _ParsedSet(what, shaf, cod, rle, freq, stream, max_bytes, decode_rle)
+    if not isinstance(d_in, torch.Tensor) or d_in.dtype != torch.uint8 or not d_in.is_contiguous() or d_in.device != s.dev:
+        raise ValueError(f"{what}: d_in is a contiguous uint8 CUDA tensor on the files' device")
+    d_in = d_in.reshape(-1)
+    ref_len = d_in.numel()
+    with s:
+        sizes, ref_n, first = [], [], []
+        if s.fb:
+            s.plan()
+            sizes = s.sizes
             ref_off, ref_n = _ref_spans(sizes, ref_len)
-            d_first = torch.zeros(p.fb, dtype=torch.int64, device=dev)
-            for a, z in _groups([_al16(s) + _al16(n) for s, n in zip(sizes, p.pn)], max_bytes):
-                def compare(d_a, a_off, a_cap, d_a_n):
-                    bt.compare_dev(st, d_a, a_off, a_cap, d_a_n, d_in if ref_len else d_a, ref_off[a:z], ref_n[a:z], d_first[a:z])
-                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=compare)
-                first += _u64_host(d_first[a:z])
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        elif p.fb:
-            sizes, rin = _measure_set(bt, st, sf, files, p, what)
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-            ref_off, ref_n = _ref_spans(sizes, ref_len)
-            d_first = torch.zeros(p.fb, dtype=torch.int64, device=dev)
-            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
-                bt.compare_dev(st, d_a, a_off, sizes[a:z], d_a_n, d_in if ref_len else d_a, ref_off[a:z], ref_n[a:z], d_first[a:z])
-            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-            _, e = _first_error(errs)
-            if e:                                                                # the size pass accepted every block: the device
-                raise ShafaError(e, f"{what}: RLE decoding")
+            d_first = torch.zeros(s.fb, dtype=torch.int64, device=s.dev)
+
+            def compare(a, z, d_a, a_off, a_cap, d_a_n):
+                s.bt.compare_dev(s.st, d_a, a_off, a_cap, d_a_n, d_in if ref_len else d_a, ref_off[a:z], ref_n[a:z], d_first[a:z])
+            s.walk(compare)
             first = _u64_host(d_first)
         # the first block that is not its span of d_in; behind the last one d_in may go on
         pos = 0
-        for s, r, f in zip(sizes, ref_n if sizes else [], first):
-            if f < s or r != s:
+        for n, r, f in zip(sizes, ref_n, first):
+            if f < n or r != n:
                 return Verify(False, pos + f, sum(sizes))
-            pos += s
+            pos += n
         return Verify(ref_len == pos, None if ref_len == pos else pos, pos)
-    finally:
-        bt.close()
 
 
 # ------------------------------------------------------------------ CRC-32 (DESIGN.md 7.17)
@@ -1875,54 +1940,32 @@ def checksum_files(shaf=None, cod=None, rle=None, freq=None, decode_rle=True, st
     out.numel(), crc32 = zlib.crc32 of out's bytes; raises what that call raises — every block is decoded, so a fault is
     reported whichever group it lies in.  The original need not exist any more: a digest taken from it (shafa.crc32, or
     zlib.crc32 on any host) is what the answer is checked against.
-    The decoded file never exists, nor a tensor of its size: verify_files' structure with crc32_dev where compare_dev is.
-      shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload) that fit max_bytes (default: a quarter
-                                  of the free device memory); each runs unpack_payloads -> sf_decode_dev -> crc32_dev -> one
-                                  synchronisation; the last group's also covers the combine
-      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files, then per group of _rle_groups rle_decode_dev
-                                  -> crc32_dev out of one reused buffer, back to back on the stream, the combine, and one
-                                  synchronisation
+    The decoded file never exists, nor a tensor of its size: verify_files' chain (_ParsedSet.walk, groups that fit max_bytes,
+    default a quarter of the free device memory) with crc32_dev where compare_dev is; the combine goes in front of the last
+    synchronisation — the last group's for mode N (decode_rle=False), the one that ends the call for the two RLE forms.
     The blocks' CRCs (4 bytes a block) and their device-resident decoded sizes gather on the device; one crc32_combine_dev
     over all blocks ends the call.  No pack_payloads(RAW) runs; the synchronisations are verify_files'."""
     import torch
-    what = "checksum_files"
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
-        if p.fb == 0:
+    with _ParsedSet("checksum_files", shaf, cod, rle, freq, stream, max_bytes, decode_rle) as s:
+        if s.fb == 0:
             return Checksum(0, 0)
-        d_crc = torch.zeros(p.fb, dtype=torch.int32, device=dev)
+        bt, st, dev = s.bt, s.st, s.dev
+        s.plan()
+        d_crc = torch.zeros(s.fb, dtype=torch.int32, device=dev)
         d_file_crc = torch.zeros(1, dtype=torch.int32, device=dev)
         d_file_n = torch.zeros(1, dtype=torch.int64, device=dev)
-        if sf and not (p.mode == "R" and decode_rle):
-            d_n = p.d_nsym[:p.fb]
-            for a, z in _groups([_al16(s) + _al16(n) for s, n in zip(p.nsym, p.pn)], max_bytes):
-                def digest(d_a, a_off, a_cap, d_a_n):
-                    bt.crc32_dev(st, d_a, a_off, a_cap, d_a_n, d_crc[a:z])
-                    if z == p.fb:                                            # the earlier groups' CRCs are in front on the stream
-                        bt.crc32_combine_dev(st, [0], [p.fb], d_crc, d_n, d_file_crc, d_file_n)
-                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=digest)
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        else:
-            sizes, rin = _measure_set(bt, st, sf, files, p, what)
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-            d_n = torch.zeros(p.fb, dtype=torch.int64, device=dev)
-            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
-                bt.crc32_dev(st, d_a, a_off, sizes[a:z], d_a_n, d_crc[a:z])
+        # the decoded sizes on the device: the .cod's, or the RLE decoder's own, gathered group by group
+        d_n = s.d_nsym[:s.fb] if s.plain else torch.zeros(s.fb, dtype=torch.int64, device=dev)
+
+        def digest(a, z, d_a, a_off, a_cap, d_a_n):
+            bt.crc32_dev(st, d_a, a_off, a_cap, d_a_n, d_crc[a:z])
+            if not s.plain:
                 with torch.cuda.stream(st):
-                    d_n[a:z].copy_(d_a_n)                                    # the decoder's own sizes, device to device
-            bt.crc32_combine_dev(st, [0], [p.fb], d_crc, d_n, d_file_crc, d_file_n)
-            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-            _, e = _first_error(errs)
-            if e:                                                                # the size pass accepted every block: the device
-                raise ShafaError(e, f"{what}: RLE decoding")
+                    d_n[a:z].copy_(d_a_n)
+
+        # the combine: behind every group's CRCs on the stream
+        s.walk(digest, lambda: bt.crc32_combine_dev(st, [0], [s.fb], d_crc, d_n, d_file_crc, d_file_n))
         return Checksum(int(d_file_crc.cpu()[0]) & 0xFFFFFFFF, int(d_file_n.cpu()[0]))
-    finally:
-        bt.close()
 
 
 # ------------------------------------------------------------------ pattern search (DESIGN.md 7.19)
@@ -2019,121 +2062,93 @@ def find_files(pattern, shaf=None, cod=None, rle=None, freq=None, decode_rle=Tru
     find(out, pattern, max_hits=max_hits), size = out.numel(); raises what that call raises — every block is decoded, so a
     fault is reported whichever group it lies in.  Together with build_index / read_ranges this is the complete "locate, then
     fetch" pair: the positions found here are the ranges read there, and the decoded file never exists for either.
-    Neither the decoded file nor a tensor of its size ever exists: verify_files' structure with find_dev where compare_dev is.
-      shaf + cod, mode N (decode_rle=False)   groups by _al16(symbols) + _al16(payload) that fit max_bytes (default: a quarter
-                                  of the free device memory); each runs unpack_payloads -> sf_decode_dev -> find_dev -> one
-                                  synchronisation
-      rle + freq; shaf + cod, mode R          _measure_set as in decompress_files, then per group of _rle_groups rle_decode_dev
-                                  -> find_dev out of one reused buffer, back to back on the stream, and one synchronisation
+    Neither the decoded file nor a tensor of its size ever exists: verify_files' chain (_ParsedSet.walk, groups that fit
+    max_bytes, default a quarter of the free device memory) with find_dev where compare_dev is.
     A group's blocks are one chain (FIND_NEXT), each reported at its offset in the decoded file.  Occurrences over a GROUP
     seam: behind a group's find_dev the last len(pattern) - 1 bytes of the stream so far are copied to a carry (stream
     ordered, before the buffer is used again); in front of the next group's find_dev a seam tensor of that carry and the
     group's first len(pattern) - 1 bytes is searched as two regions, {FIND_NEXT} and {FIND_CONTEXT}.  All calls append into
     one array and one total on the device, so the positions come out ascending without a sort and without a
-    synchronisation of their own; behind the last synchronisation the total is read, then the positions kept.  No
-    pack_payloads(RAW) runs; the synchronisations are verify_files'."""
-    import itertools
+    synchronisation of their own; behind the last synchronisation the total is read, then the positions kept.  A group
+    searched a second time, because a block of it was decoded again, starts from the total (saved on the device) and the
+    carry in front of it.  No pack_payloads(RAW) runs; the synchronisations are verify_files'."""
     import torch
     what = "find_files"
     pat, max_hits = _find_args(pattern, max_hits, what)
     m = len(pat)
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf and not decode_rle else "R", what)
-        if p.fb == 0:
+    with _ParsedSet(what, shaf, cod, rle, freq, stream, max_bytes, decode_rle) as s:
+        if s.fb == 0:
             return Found(0, np.empty(0, dtype=np.int64), 0)
+        bt, st, dev = s.bt, s.st, s.dev
         res = torch.empty(1 + max_hits, dtype=torch.int64, device=dev)           # the total, then the positions
         d_total, d_hits = res[:1], res[1:] if max_hits else None
         d_total.zero_()
         d_save = torch.zeros(1, dtype=torch.int64, device=dev)
-        d_count = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+        d_count = torch.zeros(s.fb, dtype=torch.int64, device=dev)
         d_count2 = torch.zeros(2, dtype=torch.int64, device=dev)
         carry = [torch.empty(m, dtype=torch.uint8, device=dev) for _ in range(2)]
         d_seam = torch.empty(2 * m + 16, dtype=torch.uint8, device=dev)
         st.wait_stream(torch.cuda.current_stream(dev))                           # the zeroing above, in front of the stream's work
-
-        def seam_sizes(groups):
-            """per group: the carry's and the head's lengths, on the device (from the host's sizes)"""
-            t = [[min(m - 1, starts[a]), min(m - 1, starts[z] - starts[a])] for a, z in groups]
-            return {a: d for (a, _), d in zip(groups, torch.tensor(t, dtype=torch.int64).reshape(-1, 2).to(dev))}
+        s.plan()
+        starts = s.starts
+        # per group: the carry's and the head's lengths, on the device (from the host's sizes)
+        t = [[min(m - 1, starts[a]), min(m - 1, starts[z] - starts[a])] for a, z in s.groups]
+        d_seam_n = {a: d for (a, _), d in zip(s.groups, torch.tensor(t, dtype=torch.int64).reshape(-1, 2).to(dev))}
 
         def search(a, d_a, a_off, a_n, d_a_n, cin):
             """enqueue, for the group of blocks from a on: the seam's search, the group's own, the copy of the new carry
             -> the carry behind the group (which of the two buffers, its length)"""
             ci, cl = cin
             nb, total = len(a_n), sum(a_n)
-            with torch.cuda.stream(st):
-                if m > 1 and cl and total:
-                    d_seam[:cl].copy_(carry[ci][:cl])
-                    hl = 0
-                    for o, n in zip(a_off, a_n):                             # the head may span several short blocks
-                        take = min(n, m - 1 - hl)
-                        if take:
-                            d_seam[cl + hl:cl + hl + take].copy_(d_a[o:o + take])
-                            hl += take
-                        if hl == m - 1:
-                            break
-                    bt.find_dev(st, d_seam, [0, cl], [cl, hl], d_seam_n[a], [FIND_NEXT, FIND_CONTEXT],
-                                [starts[a] - cl, starts[a]], pat, max_hits, d_hits, d_count2, d_total)
-                bt.find_dev(st, d_a, a_off, a_n, d_a_n, [FIND_NEXT] * (nb - 1) + [0], starts[a:a + nb], pat, max_hits, d_hits,
-                            d_count[a:a + nb], d_total)
-                if m == 1:
-                    return cin
-                tail, have = [], 0
-                for o, n in zip(reversed(a_off), reversed(a_n)):
-                    take = min(n, m - 1 - have)
+            if m > 1 and cl and total:
+                d_seam[:cl].copy_(carry[ci][:cl])
+                hl = 0
+                for o, n in zip(a_off, a_n):                                 # the head may span several short blocks
+                    take = min(n, m - 1 - hl)
                     if take:
-                        tail.append((o + n - take, take))
-                        have += take
-                    if have == m - 1:
+                        d_seam[cl + hl:cl + hl + take].copy_(d_a[o:o + take])
+                        hl += take
+                    if hl == m - 1:
                         break
-                old = min(cl, m - 1 - have)                                  # a group shorter than the carry keeps some of it
-                nxt = carry[1 - ci]
-                if old:
-                    nxt[:old].copy_(carry[ci][cl - old:cl])
-                for o, t in reversed(tail):
-                    nxt[old:old + t].copy_(d_a[o:o + t])
-                    old += t
-                return 1 - ci, old
+                bt.find_dev(st, d_seam, [0, cl], [cl, hl], d_seam_n[a], [FIND_NEXT, FIND_CONTEXT],
+                            [starts[a] - cl, starts[a]], pat, max_hits, d_hits, d_count2, d_total)
+            bt.find_dev(st, d_a, a_off, a_n, d_a_n, [FIND_NEXT] * (nb - 1) + [0], starts[a:a + nb], pat, max_hits, d_hits,
+                        d_count[a:a + nb], d_total)
+            if m == 1:
+                return cin
+            tail, have = [], 0
+            for o, n in zip(reversed(a_off), reversed(a_n)):
+                take = min(n, m - 1 - have)
+                if take:
+                    tail.append((o + n - take, take))
+                    have += take
+                if have == m - 1:
+                    break
+            old = min(cl, m - 1 - have)                                      # a group shorter than the carry keeps some of it
+            nxt = carry[1 - ci]
+            if old:
+                nxt[:old].copy_(carry[ci][cl - old:cl])
+            for o, t in reversed(tail):
+                nxt[old:old + t].copy_(d_a[o:o + t])
+                old += t
+            return 1 - ci, old
 
-        cur = (0, 0)
-        if sf and not (p.mode == "R" and decode_rle):
-            sizes = list(p.nsym)
-            starts = list(itertools.accumulate(sizes, initial=0))
-            groups = _groups([_al16(s) + _al16(n) for s, n in zip(sizes, p.pn)], max_bytes)
-            d_seam_n = seam_sizes(groups)
-            for a, z in groups:
-                nxt = []
+        cin, cur = {}, (0, 0)                                                    # the carry in front of each group searched; the last one
 
-                def then(d_a, a_off, a_n, d_a_n):
-                    with torch.cuda.stream(st):
-                        d_total.copy_(d_save)                                # a group decoded again is searched again
-                    nxt.append(search(a, d_a, a_off, a_n, d_a_n, cur))
-                with torch.cuda.stream(st):
+        def reader(a, z, d_a, a_off, a_n, d_a_n):
+            nonlocal cur
+            with torch.cuda.stream(st):
+                if a in cin:                                                     # decoded again: searched again, from the total
+                    d_total.copy_(d_save)                                        # and the carry in front of the group
+                else:
                     d_save.copy_(d_total)
-                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=then)
-                cur = nxt[-1]
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        else:
-            sizes, rin = _measure_set(bt, st, sf, files, p, what)
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block {p.fb}")
-            starts = list(itertools.accumulate(sizes, initial=0))
-            d_seam_n = seam_sizes(_rle_groups(sizes, rin[2], max_bytes))
-            for a, z, d_a, a_off, d_a_n in _rle_decode_groups(bt, st, *rin, sizes, max_bytes):
-                cur = search(a, d_a, a_off, sizes[a:z], d_a_n, cur)
-            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-            _, e = _first_error(errs)
-            if e:                                                                # the size pass accepted every block: the device
-                raise ShafaError(e, f"{what}: RLE decoding")
+                    cin[a] = cur
+                cur = search(a, d_a, a_off, a_n, d_a_n, cin[a])
+
+        s.walk(reader)
         total = int(res[:1].cpu()[0])
         kept = min(total, max_hits)
         return Found(total, res[1:1 + kept].cpu().numpy().copy() if kept else np.empty(0, dtype=np.int64), starts[-1])
-    finally:
-        bt.close()
 
 
 # ------------------------------------------------------------------ seek index (DESIGN.md 7.18)
@@ -2180,55 +2195,35 @@ def build_index(shaf=None, cod=None, rle=None, freq=None, span=1024, stream=None
     import torch
     what = "build_index"
     _seek_span(span, what)
-    sf, files, st, mb, bt = _open_files(shaf, cod, rle, freq, stream, what)
-    try:
-        dev = files[0].device
-        max_bytes = _max_bytes(dev, max_bytes)
-        p = _parse_files(bt, st, sf, files, mb, "RN" if sf else "R", what)
-        mode = p.mode if sf else "rle"
+    with _ParsedSet(what, shaf, cod, rle, freq, stream, max_bytes) as s:
+        bt, st, dev, sf = s.bt, s.st, s.dev, s.sf
+        mode = s.mode if sf else "rle"
         is_rle = mode != "N"
         flags = (SEEK_SF if sf else 0) | (SEEK_RLE if is_rle else 0)
-        lengths = (files[0].numel(), files[1].numel())
-        if p.fb == 0:
-            if p.perr:
-                raise ShafaError(p.perr, f"{what}: block 0")
+        lengths = (s.files[0].numel(), s.files[1].numel())
+        if s.fb == 0:
             return SeekIndex(torch.zeros(0, dtype=torch.int64, device=dev), [], span, mode, lengths,
                              np.zeros(0, dtype=np.int64) if is_rle else None)
-        nsym = list(p.nsym if sf else p.pn)
+        s.plan(measured=False)                                               # the RLE forms: seek_index_dev measures them itself
+        nsym = s.sizes
         nck = [max(1, -(-n // span)) for n in nsym]
         first = [0]
         for c in nck:
             first.append(first[-1] + c)
         d_ckpt = torch.zeros(2 * first[-1], dtype=torch.int64, device=dev)
-        d_status = torch.zeros(p.fb, dtype=torch.int32, device=dev)
-        d_size = torch.zeros(p.fb, dtype=torch.int64, device=dev)
+        d_status = torch.zeros(s.fb, dtype=torch.int32, device=dev)
+        d_size = torch.zeros(s.fb, dtype=torch.int64, device=dev)
         tsz = C.sizeof(CodeTable)
-        cost = [_al16(s) + _al16(n) for s, n in zip(nsym, p.pn)] if sf else [_al16(n) for n in p.pn]
-        rle_errs = []
-        for a, z in _groups(cost, max_bytes):
-            def index(d_a, a_off, a_cap, d_a_n):
-                bt.seek_index_dev(st, d_a, a_off, a_cap, d_a_n, p.d_tab[a * tsz:z * tsz] if sf else None, span, flags,
-                                  first[a:z], d_ckpt, d_status[a:z], d_size[a:z])
-            if not is_rle:                                                   # no fault of its own: within the group's one synchronisation
-                _sf_decode_blocks(bt, st, files[0], p, a, z, False, what, then=index)
-                continue
-            # SF faults are raised by the group's decode; the RLE faults wait for the SF faults of the groups behind
-            rin = _sf_decode_blocks(bt, st, files[0], p, a, z, False, what)[0] if sf else _gather_payloads(bt, st, files[0], p, a, z)
-            index(*rin)
-            _, errs = bt.finish(st, bt.max_blocks, raise_on_error=False)
-            rle_errs += errs[:z - a]
-        b, e = _first_error(rle_errs)
-        if e:
-            raise ShafaError(e, f"{what}: block {b}")
-        if p.perr:
-            raise ShafaError(p.perr, f"{what}: block {p.fb}")
-        sizes, status, poff = _u64_host(d_size), d_status.cpu().tolist(), _u64_host(p.d_off)
-        blocks = [SeekBlock(sizes[i], nsym[i], poff[i], p.pn[i], first[i], status[i] != SEEK_UNINDEXED) for i in range(p.fb)]
+
+        def index(a, z, d_a, a_off, a_cap, d_a_n):
+            bt.seek_index_dev(st, d_a, a_off, a_cap, d_a_n, s.d_tab[a * tsz:z * tsz] if sf else None, span, flags,
+                              first[a:z], d_ckpt, d_status[a:z], d_size[a:z])
+        s.walk(index)
+        sizes, status, poff = _u64_host(d_size), d_status.cpu().tolist(), _u64_host(s.d_off)
+        blocks = [SeekBlock(sizes[i], nsym[i], poff[i], s.pn[i], first[i], status[i] != SEEK_UNINDEXED) for i in range(s.fb)]
         # int64, as the bounds searchsorted is given: another type would make it convert the slice for every range
         offsets = np.ascontiguousarray(d_ckpt.cpu().numpy()[1::2]) if is_rle else None
         return SeekIndex(d_ckpt, blocks, span, mode, lengths, offsets)
-    finally:
-        bt.close()
 
 
 def _seek_items(index, spans):
@@ -2434,28 +2429,20 @@ def _decompress_group(parsed, files, slots, dev, st, max_bytes, results):
             n_h = m[UNPACK_INFO_WORDS * len(order):UNPACK_INFO_WORDS * len(order) + ns]
             nsym_h = m[UNPACK_INFO_WORDS * len(order) + ns:]
             todo = []
-            for k, i in enumerate(order):                                # decompress_files' rules, file by file
+            for k, i in enumerate(order):                                # _parse_rules, file by file
                 sf, _, decode_rle = parsed[i]
-                info = m[UNPACK_INFO_WORDS * k:UNPACK_INFO_WORDS * (k + 1)]
-                if info[INFO_STATUS]:
-                    results[i] = ShafaError(FILE_STREAM_FAILED, "decompress_many: bad header")
+                s0, s1 = first[i], first[i] + slots[i]
+                try:
+                    mode, fb, perr = _parse_rules("decompress_many", m[UNPACK_INFO_WORDS * k:UNPACK_INFO_WORDS * (k + 1)],
+                                                  errs[s0:s1], n_h[s0:s1], nsym_h[s0:s1] if sf else None, sf,
+                                                  _accepted_modes(sf, decode_rle))
+                except ShafaError as e:
+                    results[i] = e
                     continue
-                mode = chr(info[INFO_MODE])
-                if not (mode == "R" or (sf and mode == "N" and not decode_rle)):
-                    results[i] = ShafaError(FILE_UNRECOGNIZABLE, f"decompress_many: mode {mode!r}")
-                    continue
-                s0, nidx = first[i], info[INFO_INDEXED]
-                e = errs[s0:s0 + nidx]
-                if sf:
-                    e = [x if x or nsym_h[s0 + b] <= 8 * n_h[s0 + b] else FILE_UNRECOGNIZABLE for b, x in enumerate(e)]
-                fb, perr = _first_error(e)
-                if not perr and info[INFO_COUNT] > nidx:
-                    perr = FILE_STREAM_FAILED
                 if fb == 0:
-                    results[i] = ShafaError(perr, "decompress_many: block 0") if perr else \
-                        torch.empty(0, dtype=torch.uint8, device=dev)
+                    results[i] = torch.empty(0, dtype=torch.uint8, device=dev)
                     continue
-                todo.append(_Many(i, sf, mode == "R" and decode_rle if sf else True, s0, fb, perr))
+                todo.append(_Many(i, sf, not _no_rle_stage(sf, mode, decode_rle), s0, fb, perr))
             part, acc = [], 0
             for f in todo:
                 if part and acc + f.fb > MANY_GROUP_BLOCKS:
@@ -2511,16 +2498,10 @@ def _decode_many(bt, st, dev, part, pbase, pend, d_off, d_n, d_nsym, d_tab, n_h,
         _, errs = bt.finish(st, nsfb, raise_on_error=False)             # synchronisation 2
         errs = errs[:nsfb]
         again = set()
+        args = (d_pay, poff, pn, d_pn, d_tb, d_ns, d_sfo, ooff, nsym)
+        faults = any(errs)                                              # none in the whole part: no file has to look
         for f in sfp:                                                   # the one slot for 33..64-bit codes was taken
-            b, e = _first_error(errs[f.c0:f.c0 + f.fb])
-            while e == LACK_OF_MEMORY and f.c0 + b not in again:
-                g = f.c0 + b
-                bt.sf_decode_dev(st, d_pay, poff[g:g + 1], pn[g:g + 1], d_pn[g:g + 1], d_tb[g * tsz:(g + 1) * tsz],
-                                 d_ns[g:g + 1], d_sfo, ooff[g:g + 1], nsym[g:g + 1])
-                _, one = bt.finish(st, 1, raise_on_error=False)
-                errs[g] = one[0]
-                again.add(g)
-                b, e = _first_error(errs[f.c0:f.c0 + f.fb])
+            b, e = _sf_decode_again(bt, st, args, errs, f.c0, f.c0 + f.fb, again, 1) if faults else (f.fb, SUCCESS)
             f.err = (b, e) if e else None
         redo = [k for k, f in enumerate(plain) if not f.err and any(g in again for g in range(f.c0, f.c0 + f.fb))]
         if redo:
