@@ -595,6 +595,45 @@ int shafa_hipd_merge_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_cap,
                                     const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
 
+/* ---- Byte planes of Lorenzo differences: the differences along up to three lags at once -----------------------------------
+ * Data that is smooth along SEVERAL axes — a 2-D or 3-D simulation field, a stack of images, [step, y, x] snapshots — keeps most
+ * of its redundancy when only one axis is differenced.  The integer Lorenzo predictor of the scientific-data codecs differences
+ * along every axis in turn, on the bit patterns.  Block b has nlags (1 .. SHAFA_PLANES_GRID_LAGS, one number for the call) slots
+ * h_lags[b * nlags + k]: the first is >= 1, every further slot is 0 (unused, and then so is every slot behind it) or greater
+ * than the slot in front of it, so one launch per element size serves any mix of 1-D, 2-D and 3-D tensors.  With M = 2^(8 elem),
+ * x the block's elements as unsigned little-endian integers, x[i] = 0 for i < 0, (S^L x)[i] = x[i - L] and L1 < L2 < L3 the
+ * used lags:
+ *   d = (1 - S^L1)(1 - S^L2)(1 - S^L3) x mod M,  i.e.  d[i] = sum over the subsets A of the used lags of (-1)^|A| x[i - sum A]
+ *   z[i] = the zigzag fold of d[i] (above),   plane j of the block = byte j of z[i]
+ * and back: d unfolded, then x[i] += x[i - L] in place once per lag, in any order (the passes commute).  It is a bijection on any
+ * input.  The difference does not start afresh at the end of a row or a slab — a row's first element is taken against the last
+ * one of the row in front — which is what makes the transform a product of flat lags.  A lag at or past h_cap[b] subtracts
+ * nothing.  It does not always pay: every further difference doubles the variance of whatever noise the data carries.
+ * shafa_hipd_split_planes_grid_dev writes the planes of z; shafa_hipd_merge_planes_grid_dev is its inverse.  With nlags = 1
+ * both write byte for byte what the _lag_dev entries write, with a block's lags (1, 0, 0) what the _diff_dev entries write.
+ * Everything said of the _lag_dev entries holds: the element side at multiples of elem, the plane side at multiples of 16, the
+ * capacities on the host and the sizes device resident, exactly the plain entries' bytes written and nothing outside them, the
+ * per-block code (d_n[b] > h_cap[b]: SHAFA_OUTSIDE_MODULE, no byte of the block read or written in any of the launches).
+ * Launches.  split is one launch: the _lag_dev split with one base unit per non-empty subset of the block's lags (up to seven),
+ * read at the summed distance and subtracted or added, one at a time: 2 bytes of HBM traffic per tensor byte while the taps
+ * hit L2.  merge is a chain on the stream in which no workgroup waits for another: a first pass from the planes to the elements
+ * at the block's smallest lag — the _diff_dev merge's three launches for the blocks where that lag is 1, the _lag_dev merge's up
+ * to three for the others, each family skipping the other's blocks — then, per further lag, the _lag_dev merge's launches with
+ * the elements themselves as their source, in place (no planes, no unfold; blocks without that lag are skipped).  3 bytes of
+ * traffic per tensor byte for the first pass and at most 3 for each further one.  The device workspace is the _lag_dev merge's
+ * with (44 + 8 elem) bytes per block, three lags where it has one: one region of sums, which the passes use in turn.  One that cannot be had is
+ * SHAFA_LACK_OF_MEMORY.  Enqueues only.
+ * Argument errors return with nothing enqueued (checked before HIP is touched): the _lag_dev entries' in their order; an nlags
+ * outside 1 .. SHAFA_PLANES_GRID_LAGS with elem; and where those entries check their lags, each SHAFA_OUTSIDE_MODULE: NULL
+ * h_lags, a first slot of 0, a slot not greater than a non-zero slot in front of it, a non-zero slot behind a 0. */
+#define SHAFA_PLANES_GRID_LAGS 3
+int shafa_hipd_split_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                     const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                                     const uint64_t *d_n, uint8_t *d_planes, const uint64_t *h_plane_off);
+int shafa_hipd_merge_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                     const uint64_t *h_lags, const uint8_t *d_planes, const uint64_t *h_plane_off,
+                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

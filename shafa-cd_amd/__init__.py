@@ -134,6 +134,8 @@ def lib():
     L.shafa_hipd_merge_planes_diff_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_lag_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_lag_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_split_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_merge_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -199,6 +201,7 @@ def lib():
                  "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev",
                  "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev",
                  "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
+                 "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev",
                  "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -290,6 +293,16 @@ def _u64arr(v):
 
 def _p64(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _grid_lags(what, lags, nblocks):
+    """the lags of a _grid launch, one tuple per block -> (nlags, the uint64 array [nblocks * nlags]), every tuple padded with 0
+    to the call's widest (what the entry makes of the values is the entry's to say)"""
+    rows = [tuple(int(g) for g in row) for row in lags]
+    if len(rows) != nblocks:
+        raise ValueError(f"{what}: one tuple of lags per block")
+    nl = max([len(r) for r in rows] + [1])
+    return nl, _u64arr([g for r in rows for g in r + (0,) * (nl - len(r))])
 
 
 def _i32arr(v):
@@ -547,6 +560,30 @@ class Batch:
             raise ValueError("merge_planes_lag_dev: one lag per block")
         _check(lib().shafa_hipd_merge_planes_lag_dev(self.h, self._st(stream), len(oo), elem, _p64(lg), _addr(d_planes), _p64(po),
                                                      _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)), "hipd_merge_planes_lag_dev")
+
+    def split_planes_grid_dev(self, stream, elem, lags, d_in, in_off, cap, d_n, d_planes, plane_off):
+        """split_planes_lag_dev with up to PLANES_GRID_LAGS lags a block: `lags` is a list with one tuple per block, the first
+        lag >= 1 and the others increasing (a trailing 0 is an unused slot; shorter tuples are padded with 0 to the call's
+        widest), and the planes are those of the zigzag fold of d = (1 - S^L1)(1 - S^L2)(1 - S^L3) x mod 2^(8 elem): the
+        differences along every lag in turn.  One lag a block is split_planes_lag_dev byte for byte.  Its arguments otherwise,
+        and exactly its bytes written.  Enqueues only, one launch (include/shafa_hip.h: "Byte planes of Lorenzo differences")."""
+        io, ic, po = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off)
+        nl, lg = _grid_lags("split_planes_grid_dev", lags, len(io))
+        _check(lib().shafa_hipd_split_planes_grid_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _addr(d_in), _p64(io),
+                                                      _p64(ic), d_n.data_ptr(), _addr(d_planes), _p64(po)),
+               "hipd_split_planes_grid_dev")
+
+    def merge_planes_grid_dev(self, stream, elem, lags, d_planes, plane_off, cap, d_n, d_out, out_off):
+        """split_planes_grid_dev's inverse: the differences unfolded from block b's planes, then x[i] += x[i - L] once per lag of
+        the block -> d_out + out_off[b], multiples of elem.  merge_planes_lag_dev's arguments otherwise, and exactly its bytes
+        written.  Enqueues only: the first pass is the difference merge's launches (a smallest lag of 1) or the lag merge's, each
+        further lag a pass in place over the elements; no workgroup waits for another (include/shafa_hip.h: "Byte planes of
+        Lorenzo differences")."""
+        oo, ic, po = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off)
+        nl, lg = _grid_lags("merge_planes_grid_dev", lags, len(oo))
+        _check(lib().shafa_hipd_merge_planes_grid_dev(self.h, self._st(stream), len(oo), elem, nl, _p64(lg), _addr(d_planes),
+                                                      _p64(po), _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)),
+               "hipd_merge_planes_grid_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -2752,6 +2789,7 @@ PLANES_NO_BASE = (1 << 64) - 1  # SHAFA_PLANES_NO_BASE: the base offset of a blo
 PLANES_LAG_STRIP = 256          # SHAFA_PLANES_LAG_STRIP, _ROWS, _ITEMS: the form merge_planes_lag_dev gives a block
 PLANES_LAG_ROWS = 32
 PLANES_LAG_ITEMS = 4096
+PLANES_GRID_LAGS = 3            # SHAFA_PLANES_GRID_LAGS: the lags a block of split_planes_grid_dev / merge_planes_grid_dev may have
 RECORDS_MAX_WIDTH = 64          # SHAFA_RECORDS_MAX_WIDTH: split_records_dev / merge_records_dev take records of 1 .. 64 bytes
 RECORDS_TILE = 8192             # SHAFA_RECORDS_TILE: the records of one tile of theirs
 
@@ -2832,7 +2870,7 @@ def _plane_stream(dev, stream):
 # The drivers below serve five variants of one chain.  A tensor is `units` = (count, width): its count of units of `width` bytes,
 # an element's 1, 2, 4 or 8 or a record's 1 .. RECORDS_MAX_WIDTH; column j of a unit is a plane.  The variant `kind` names the
 # pair of Batch methods, split_<kind>_dev / merge_<kind>_dev: "planes", "planes_xor" (with `bases`), "planes_diff", "planes_lag"
-# (`bases` holds the tensors' lags) or "records".
+# (`bases` holds the tensors' lags), "planes_grid" (`bases` holds the tensors' tuples of lags) or "records".
 def _by_width(units):
     """indices of the non-empty tensors, grouped by unit width -> [(width, [index, ...])]"""
     return [(w, [i for i, (n, x) in enumerate(units) if x == w and n]) for w in sorted({x for n, x in units if n})]
@@ -2859,8 +2897,10 @@ def _transpose(bt, way, kind, side):
 
 
 def _lag_side(kind, lags, idx):
-    """the lag argument of a split_planes_lag_dev / merge_planes_lag_dev launch over the tensors idx, behind the width: a tuple
-    to be spliced in, empty for every other variant"""
+    """the lag argument of a split_planes_lag_dev / merge_planes_lag_dev launch over the tensors idx, behind the width (the _grid
+    pair: the tuples of lags): a tuple to be spliced in, empty for every other variant"""
+    if kind == "planes_grid":
+        return ([tuple(lags[i]) for i in idx],)
     return ([int(lags[i]) for i in idx],) if kind == "planes_lag" else ()
 
 
@@ -2869,7 +2909,8 @@ def _split_into(bt, st, dev, ts, units, kind, bases=None):
     -> the planes buffer and each tensor's plane offsets in it, all multiples of 16.  "planes_xor" with `bases` (one entry per
     tensor: None or a tensor of the same dtype and numel): a width with a base among its tensors takes split_planes_xor_dev, the
     bases addressed from the lowest base address.  "planes_diff": one block a tensor, so the differences run over the
-    flattened tensor.  "planes_lag": the same at the distance bases[i], an int, for tensor i."""
+    flattened tensor.  "planes_lag": the same at the distance bases[i], an int, for tensor i.  "planes_grid": the same along every
+    lag of the tuple bases[i] in turn."""
     import torch
     poff, pos = [], 0
     for n, w in units:
@@ -3027,8 +3068,9 @@ def _back_to_back(buf, spans):
 
 def _plane_entries(what, ts, units, kind, bases, block_size, stream):
     """compress_tensors' chain over the checked tensors ts of `units`, and in its other variants compress_deltas' (with `bases`,
-    _split_into's), compress_sequences', compress_strided's (`bases` the lags) and compress_records': the split, the sizes, the
-    file sets of the planes that shrink -> per tensor its plane entries, and their bytes"""
+    _split_into's), compress_sequences', compress_strided's (`bases` the lags), compress_grids' (`bases` the tuples of lags) and
+    compress_records': the split, the sizes, the file sets of the planes that shrink -> per tensor its plane entries, and their
+    bytes"""
     import torch
     if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
         raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
@@ -3175,11 +3217,11 @@ def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=
 
 def _merge_items(what, items, kind, bases, check_base, stream):
     """decompress_tensors' checks and chain over the list `items`, and in its other variants decompress_deltas' (with `bases`,
-    one entry per item), decompress_sequences', decompress_strided's (`bases` the items' lags) and decompress_records' (whose
-    messages say "column" for a plane)"""
+    one entry per item), decompress_sequences', decompress_strided's (`bases` the items' lags), decompress_grids' (`bases` the
+    items' tuples of lags) and decompress_records' (whose messages say "column" for a plane)"""
     import torch
     noun, length = ("column", "record count") if kind == "records" else ("plane", "tensor's numel")
-    lags = bases if kind == "planes_lag" else None   # that variant's `bases` are ints, one per item
+    lags = bases if kind in ("planes_lag", "planes_grid") else None          # those variants' `bases` are lags, one entry per item
     if kind != "planes_xor":
         bases = None                                 # only this one has base tensors to check
     if bases is not None:
@@ -3248,7 +3290,7 @@ def _merge_items(what, items, kind, bases, check_base, stream):
         outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, lags if kind == "planes_lag" else bases)
+            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, lags if lags is not None else bases)
             bt.finish(st, len(items))
         finally:
             bt.close()
@@ -3329,3 +3371,8 @@ from .records import (CompressedRecords, compress_records, decompress_records, m
 # ------------------------------------------------------------------ differences along an axis, one file set per byte plane
 from . import strided  # noqa: E402
 from .strided import (CompressedStrided, compress_strided, decompress_strided, merge_strided, split_strided)  # noqa: E402,F401
+
+
+# ------------------------------------------------------------------ differences along up to three axes, one file set per byte plane
+from . import grids  # noqa: E402
+from .grids import (CompressedGrid, compress_grids, decompress_grids, merge_grid, split_grid)  # noqa: E402,F401

@@ -602,16 +602,19 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
 // the checks the plane and the record transposes share (include/shafa_hip.h), in one order, then the launch.  d_el is the element
 // or record side; `unit` the bytes of an element (1, 2, 4 or 8) or, TR_RECORDS, of a record (1 .. SHAFA_RECORDS_MAX_WIDTH);
 // TR_XOR: the _xor entries, with a base side; TR_DIFF: the _diff entries; TR_LAG: the _lag entries, with a lag a block (h_lag) and
-// the element side at multiples of the element
-enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_LAG, TR_RECORDS };
+// the element side at multiples of the element; TR_GRID: the _grid entries, the same with nlags (1 .. SHAFA_PLANES_GRID_LAGS)
+// lags a block in h_lag
+enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_LAG, TR_GRID, TR_RECORDS };
 static_assert(SHAFA_RECORDS_TILE == SHAFA_PLANES_TILE, "one tile for the plane and the record entries");
 
 static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
                          const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
-                         const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr)
+                         const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr,
+                         uint32_t nlags = 1)
 {
     const bool xr = tr == TR_XOR;
     if (!b || !d_el || !d_planes || !d_n || (xr && !d_base)) return SHAFA_OUTSIDE_MODULE;
+    if (tr == TR_GRID && (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS)) return SHAFA_OUTSIDE_MODULE;
     if (tr == TR_RECORDS ? unit < 1 || unit > SHAFA_RECORDS_MAX_WIDTH : unit != 1 && unit != 2 && unit != 4 && unit != 8)
         return SHAFA_OUTSIDE_MODULE;
     if (nblocks <= 0) return SHAFA_SUCCESS;
@@ -626,15 +629,22 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
     if (!h_off || !h_plane_off || (xr && !h_base_off) || ((uintptr_t)d_planes & 15)) return SHAFA_OUTSIDE_MODULE;
     for (size_t i = 0; i < (size_t)nblocks * unit; ++i)
         if (h_plane_off[i] & 15) return SHAFA_OUTSIDE_MODULE;
-    if (tr == TR_LAG) {
+    if (tr == TR_LAG || tr == TR_GRID) {
         if (!h_lag || (uintptr_t)d_el % unit) return SHAFA_OUTSIDE_MODULE;
-        for (int i = 0; i < nblocks; ++i)
-            if (!h_lag[i] || h_off[i] % unit) return SHAFA_OUTSIDE_MODULE;
+        for (int i = 0; i < nblocks; ++i) {
+            const u64 *g = h_lag + (size_t)i * nlags;
+            if (!g[0] || h_off[i] % unit) return SHAFA_OUTSIDE_MODULE;
+            for (uint32_t k = 1; k < nlags; ++k)     // 0: unused, and so is every slot behind it; else past the slot in front
+                if (g[k] ? g[k] <= g[k - 1] : k + 1 < nlags && g[k + 1]) return SHAFA_OUTSIDE_MODULE;
+        }
     }
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
     if (tr == TR_LAG)
         return planes_lag_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
                                      (u8 *)d_planes, h_plane_off, h_lag);
+    if (tr == TR_GRID)
+        return planes_grid_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
+                                      (u8 *)d_planes, h_plane_off, nlags, h_lag);
     if (tr == TR_RECORDS)
         return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
                                   h_plane_off);
@@ -703,6 +713,22 @@ int shafa_hipd_merge_planes_lag_dev(shafa_hipd_batch *b, void *stream, int nbloc
 {
     return transpose_dev(true, TR_LAG, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
                          h_plane_off, h_lag);
+}
+
+int shafa_hipd_split_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                     const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                                     const uint64_t *d_n, uint8_t *d_planes, const uint64_t *h_plane_off)
+{
+    return transpose_dev(false, TR_GRID, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags);
+}
+
+int shafa_hipd_merge_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                     const uint64_t *h_lags, const uint8_t *d_planes, const uint64_t *h_plane_off,
+                                     const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off)
+{
+    return transpose_dev(true, TR_GRID, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags);
 }
 
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,

@@ -281,6 +281,14 @@ int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
 // workspace more per 8 elements of the capacities' tiles where a block has more than one chunk
 int planes_lag_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, const u64 *h_lag);
+// the same with block b's differences taken along up to SHAFA_PLANES_GRID_LAGS lags at once, h_lags[b * nlags + k] (the first
+// >= 1, the others 0 or increasing: checked by the caller) (planes_lag.hip): split is one launch; merge is a first pass from the
+// planes at the block's smallest lag — the merge of differences where that is 1 (planes_diff_merge_enqueue, planes.hip, on the
+// caller's set-up, leaving the blocks with d_skip[b] != 0 alone), else the lag merge — and one pass in place per further lag
+int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags);
+void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 *d_el, int nblocks, const u64 *d_n,
+                               const u8 *d_planes, int *err, const u64 *d_skip);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

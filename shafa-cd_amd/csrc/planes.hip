@@ -346,17 +346,19 @@ __global__ __launch_bounds__(TP_THREADS) void planes_merge(u8 *__restrict__ d_el
 // ---- merge of the differences: three launches, none of which waits for another workgroup
 // launch 1: sums[t] = the sum of the d's of global tile t (a tile at or behind its block's size is not read; what the words of
 // a block's last unit hold behind its size goes into the block's last sum, which nothing reads)
-template <int E>
+// SKIP (the grid merge's first pass, planes_lag.hip): a block with d_skip[b] != 0 is the lag family's and left alone
+template <int E, bool SKIP = false>
 __global__ __launch_bounds__(TP_THREADS) void planes_diff_sums(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                                const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                                const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
                                                                const u64 *__restrict__ d_poff, u32 n_tiles, u32 per_wg,
-                                                               u64 *__restrict__ sums)
+                                                               u64 *__restrict__ sums, const u64 *__restrict__ d_skip)
 {
     using T = typename DiffT<E>::T;
     __shared__ T wsum[TP_THREADS / 64];
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
+        if (SKIP && d_skip[wk.b]) continue;          // (uniform)
         const u64 *poff = d_poff + (u64)wk.b * E;
         T s = 0;
 #pragma unroll
@@ -420,19 +422,20 @@ __device__ __forceinline__ void merge_tile_diff(const TpWalk &wk, u32 sh, u32 r,
 }
 
 // launch 3: sums[t] is by now the sum of the d's of the block's tiles in front of tile t
-template <int E>
+template <int E, bool SKIP = false>
 __global__ __launch_bounds__(TP_THREADS) void planes_merge_diff(u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                                 const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
                                                                 int nblk, const u64 *__restrict__ d_n,
                                                                 const u8 *__restrict__ d_planes, const u64 *__restrict__ d_poff,
                                                                 int *__restrict__ err, u32 n_tiles, u32 per_wg,
-                                                                const u64 *__restrict__ sums)
+                                                                const u64 *__restrict__ sums, const u64 *__restrict__ d_skip)
 {
     using T = typename DiffT<E>::T;
     __shared__ T wt[2 * (TP_THREADS / 64)];
     u32 turn = 0;
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
+        if (SKIP && d_skip[wk.b]) continue;          // (uniform)
         const u64 *poff = d_poff + (u64)wk.b * E;
         const T carry = (T)sums[wk.t];
         const u32 sh = (u32)((uintptr_t)wk.in & 15u), m = (16u - sh) & 15u, r = m & 3u;
@@ -462,23 +465,32 @@ void planes_launch(bool merge, const TileSetup &a, hipStream_t st, u8 *d_el, int
                            (const u8 *)d_el, a.off, a.cap, a.tbase, nblk, d_n, d_planes, poff, err, a.nt, a.per_wg, d_base, boff);
 }
 
+// the three launches of the merge of differences; d_skip (the grid merge): the blocks it leaves alone
+template <int E, bool SKIP>
+void planes_diff_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, const u8 *d_planes, int *err,
+                              const u64 *d_skip)
+{
+    const u64 *poff = (const u64 *)a.extra[0];
+    u64 *sums = (u64 *)a.scratch;
+    if (a.nt)
+        hipLaunchKernelGGL((planes_diff_sums<E, SKIP>), dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase,
+                           nblk, d_n, d_planes, poff, a.nt, a.per_wg, sums, d_skip);
+    const u32 bw = (u32)nblk < TP_MAX_BLOCK_WGS ? (u32)nblk : TP_MAX_BLOCK_WGS;
+    hipLaunchKernelGGL(planes_diff_scan, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblk, d_n, sums);
+    hipLaunchKernelGGL((planes_merge_diff<E, SKIP>), dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       d_planes, poff, err, a.nt, a.per_wg, (const u64 *)sums, d_skip);
+}
+
 template <int E>
 void planes_diff_launch(bool merge, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err)
 {
     const u64 *poff = (const u64 *)a.extra[0];
-    u64 *sums = (u64 *)a.scratch;
     if (!merge) {
         hipLaunchKernelGGL(planes_split_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
                            d_n, d_planes, poff, err, a.nt, a.per_wg);
         return;
     }
-    if (a.nt)
-        hipLaunchKernelGGL(planes_diff_sums<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
-                           d_n, (const u8 *)d_planes, poff, a.nt, a.per_wg, sums);
-    const u32 bw = (u32)nblk < TP_MAX_BLOCK_WGS ? (u32)nblk : TP_MAX_BLOCK_WGS;
-    hipLaunchKernelGGL(planes_diff_scan, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblk, d_n, sums);
-    hipLaunchKernelGGL(planes_merge_diff<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
-                       (const u8 *)d_planes, poff, err, a.nt, a.per_wg, (const u64 *)sums);
+    planes_diff_merge_launch<E, false>(a, st, d_el, nblk, d_n, d_planes, err, nullptr);
 }
 
 }  // namespace
@@ -525,4 +537,17 @@ int planes_diff_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
+}
+
+// the merge of differences as the grid merge's first pass (planes_lag.hip) on that launcher's set-up: extra 0 the plane offsets,
+// 8 bytes of scratch or more per tile; the blocks with d_skip[b] != 0 are left to the lag family
+void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 *d_el, int nblocks, const u64 *d_n,
+                               const u8 *d_planes, int *err, const u64 *d_skip)
+{
+    switch (elem) {
+    case 1: planes_diff_merge_launch<1, true>(a, st, d_el, nblocks, d_n, d_planes, err, d_skip); break;
+    case 2: planes_diff_merge_launch<2, true>(a, st, d_el, nblocks, d_n, d_planes, err, d_skip); break;
+    case 4: planes_diff_merge_launch<4, true>(a, st, d_el, nblocks, d_n, d_planes, err, d_skip); break;
+    default: planes_diff_merge_launch<8, true>(a, st, d_el, nblocks, d_n, d_planes, err, d_skip); break;
+    }
 }

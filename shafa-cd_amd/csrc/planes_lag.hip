@@ -26,6 +26,12 @@
 // the tiles of the capacities (TpWalk) and deal a block's items (or column runs) to its tiles in equal runs, so the grid is the
 // plain entries' whatever the lags.  The planes are read twice: 3 bytes of traffic per tensor byte.  The sums of block b lie at
 // LAG_SUMS_TILE elements per tile of the capacities in front of it: NC L <= (cap / 16)(1 + 1 / 32) once there are two chunks.
+//
+// The GRID entries (shafa_hipd_split_planes_grid_dev, shafa_hipd_merge_planes_grid_dev) take up to three lags a block,
+// d = (1 - S^L0)(1 - S^L1)(1 - S^L2) x, the differences along every lag in turn.  split: this file's split with one base unit per
+// non-empty subset of the block's lags, subtracted or added (planes_grid_split).  merge: a first pass from the planes at the
+// block's smallest lag — planes.hip's merge of differences where that is 1, else the three launches above — then per further lag
+// the three launches above with the ELEMENTS as their source, in place (LagSrc).
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -79,6 +85,21 @@ __device__ __forceinline__ void sub_words(u32 (&w)[4 * E], const u32 (&b)[4 * E]
             }
         } else if (E == 4) w[i] -= b[i];
         else w[i] = pk_sub<E>(w[i], b[i]);
+    }
+}
+
+template <int E>
+__device__ __forceinline__ void add_words(u32 (&w)[4 * E], const u32 (&b)[4 * E])
+{
+#pragma unroll
+    for (int i = 0; i < 4 * E; ++i) {
+        if (E == 8) {
+            if (i & 1) {
+                const u64 v = ((u64)w[i] << 32 | w[i - 1]) + ((u64)b[i] << 32 | b[i - 1]);
+                w[i - 1] = (u32)v; w[i] = (u32)(v >> 32);
+            }
+        } else if (E == 4) w[i] += b[i];
+        else w[i] = pk_add<E>(w[i], b[i]);
     }
 }
 
@@ -160,7 +181,79 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_split(const u8 *__restr
     tp_size_errors(cap, d_n, nblk, err);
 }
 
+// ---- split of the grid differences: d = (1 - S^L0)(1 - S^L1)(1 - S^L2) x, one base unit per non-empty subset of
+// the block's used lags (lg[k] != 0), read by lag_base at the summed distance, subtracted for an odd subset and added for an
+// even one; one base is live at a time.  A subset with an unused lag, or whose distance is past the unit, is skipped.
+template <int E, int Q>
+__device__ __forceinline__ void split_tile_grid(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], u8 *d_planes,
+                                                const u64 *poff)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        zz_fold<E, 4 * E>(w);
+        split_store<E>(w, wk.n, e0, d_planes, poff);
+    }
+}
+
+// d_lag: SHAFA_PLANES_GRID_LAGS rows of nblk lags, clamped by the host: 0 where a slot is unused or at or past the capacity
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                                const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                                const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                                int *__restrict__ err, u32 n_tiles, u32 per_wg)
+{
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile_grid<E, 0>(wk, r, lg, d_planes, poff); break;
+        case 1: split_tile_grid<E, 1>(wk, r, lg, d_planes, poff); break;
+        case 2: split_tile_grid<E, 2>(wk, r, lg, d_planes, poff); break;
+        default: split_tile_grid<E, 3>(wk, r, lg, d_planes, poff); break;
+        }
+    }
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
 // ---- merge
+// The three launches are templated on their SOURCE: LAG_PLANES the _lag entries' (d[i] unfolded from the planes),
+// LAG_PLANES_SKIP the same where a block whose lag is 0 is another family's and skipped (the grid merge's first pass), LAG_ELEMS
+// the elements themselves, in place: x[i] += x[i - L] with no planes and no unfold (the grid merge's further passes; a lag of 0:
+// the block has no such pass).  A lane reads only the elements it writes, and the sums are taken in a launch of their own in
+// front, so in place is safe.
+enum LagSrc { LAG_PLANES = 0, LAG_PLANES_SKIP = 1, LAG_ELEMS = 2 };
+
 // d[i], unfolded from byte i of the E planes at pl[0 .. E - 1]
 template <int E>
 __device__ __forceinline__ typename ElT<E>::T lag_d(const u8 *const (&pl)[E], u64 i)
@@ -170,6 +263,14 @@ __device__ __forceinline__ typename ElT<E>::T lag_d(const u8 *const (&pl)[E], u6
 #pragma unroll
     for (int j = 0; j < E; ++j) z = (T)(z | (T)((T)gload<u8>(pl[j] + i) << (8 * j)));
     return (T)((T)(z >> 1) ^ (T)(0 - (z & 1)));
+}
+
+// d[i] of the source: unfolded from the planes, or element i of the region at el itself
+template <int E, int SRC>
+__device__ __forceinline__ typename ElT<E>::T lag_src(const u8 *const (&pl)[E], const u8 *el, u64 i)
+{
+    if (SRC == LAG_ELEMS) return gload<typename ElT<E>::T>(el + i * E);
+    return lag_d<E>(pl, i);
 }
 
 // The walk all three launches share: every tile of the capacities is entered (the skips are by item, not by tile), and tile k of
@@ -187,7 +288,7 @@ struct LagRun {
 };
 
 // launch 1: sums[chunk L + column] for every chunk with a chunk behind it in the block's d_n[b] elements (all its rows are whole)
-template <int E>
+template <int E, int SRC = LAG_PLANES>
 __global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                               const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
@@ -200,6 +301,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restri
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         wk.enter();
         if (!wk.n) continue;                         // (uniform) empty, or past its capacity
+        if (SRC != LAG_PLANES && !d_lag[wk.b]) continue;                       // (uniform) not this pass's block
         const LagGeom g(cap[wk.b], d_lag[wk.b]);
         if (g.NC < 2) continue;                      // (uniform)
         const u64 rows = (wk.n + g.L - 1) / g.L;
@@ -207,7 +309,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restri
         T *sums = (T *)sums_all + (u64)wk.tb * LAG_SUMS_TILE;
         const u8 *pl[E];
 #pragma unroll
-        for (int j = 0; j < E; ++j) pl[j] = d_planes + d_poff[(u64)wk.b * E + j];
+        for (int j = 0; j < E; ++j) pl[j] = SRC == LAG_ELEMS ? nullptr : d_planes + d_poff[(u64)wk.b * E + j];
         const u32 s = tid / g.W, c = tid - s * g.W;
         for (u64 w = run.lo; w < run.hi; ++w) {
             const u64 ch = w / g.NS, col = (w - ch * g.NS) * g.W + c, row0 = ch * g.G;
@@ -218,7 +320,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restri
                 for (u32 q = 0; q < g.m; ++q) {
                     u64 i = (row0 + (u64)q * LAG_ROWS * g.S + (u64)s * LAG_ROWS) * g.L + col;
 #pragma unroll 8
-                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) t = (T)(t + lag_d<E>(pl, i));
+                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) t = (T)(t + lag_src<E, SRC>(pl, wk.in, i));
                 }
             }
             if (g.S > 1) {                           // (uniform)
@@ -236,7 +338,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_sums(const u8 *__restri
 }
 
 // launch 2: down each column, the sums of the chunks in front of every chunk that holds a row of the block
-template <int E>
+template <int E, int SRC = LAG_PLANES>
 __global__ __launch_bounds__(TP_THREADS) void planes_lag_scan(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                               const u64 *__restrict__ d_n, const u64 *__restrict__ d_lag,
@@ -248,6 +350,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_scan(const u8 *__restri
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         wk.enter();
         if (!wk.n) continue;                         // (uniform)
+        if (SRC != LAG_PLANES && !d_lag[wk.b]) continue;                       // (uniform) not this pass's block
         const LagGeom g(cap[wk.b], d_lag[wk.b]);
         if (g.NC < 2) continue;                      // (uniform)
         const u64 rows = (wk.n + g.L - 1) / g.L, nc = (rows + g.G - 1) / g.G;      // the chunks that hold a row
@@ -337,8 +440,35 @@ __device__ __forceinline__ void lag_d4(const u8 *const (&pl)[E], u64 i, typename
     }
 }
 
+// d[i .. i + 3] of the source: lag_d4, or the four elements at el + i E themselves (a multiple of E, as lag_store4's)
+template <int E, int SRC>
+__device__ __forceinline__ void lag_src4(const u8 *const (&pl)[E], const u8 *el, u64 i, typename ElT<E>::T (&d)[LAG_VEC])
+{
+    using T = typename ElT<E>::T;
+    if (SRC != LAG_ELEMS) {
+        lag_d4<E>(pl, i, d);
+        return;
+    }
+    const unsigned long long a = (unsigned long long)(el + i * E);
+    if (E == 1) {
+        const u32 x = *(const GLOBAL_AS u32_any_t *)a;
+#pragma unroll
+        for (u32 c = 0; c < LAG_VEC; ++c) d[c] = (T)(x >> (8 * c));
+    } else if (E == 2) {
+        const u32x2_t x = *(const GLOBAL_AS u32x2_any_t *)a;
+        d[0] = (T)x.x; d[1] = (T)(x.x >> 16); d[2] = (T)x.y; d[3] = (T)(x.y >> 16);
+    } else if (E == 4) {
+        const u32x4_t x = *(const GLOBAL_AS u32x4_any_t *)a;
+        d[0] = (T)x.x; d[1] = (T)x.y; d[2] = (T)x.z; d[3] = (T)x.w;
+    } else {
+        const u32x4_t x = *(const GLOBAL_AS u32x4_any_t *)a, y = *(const GLOBAL_AS u32x4_any_t *)(a + 16);
+        d[0] = (T)((u64)x.y << 32 | x.x); d[1] = (T)((u64)x.w << 32 | x.z);
+        d[2] = (T)((u64)y.y << 32 | y.x); d[3] = (T)((u64)y.w << 32 | y.z);
+    }
+}
+
 // one chunk of a strip of 256 columns from row row0 on: every lane of the workgroup calls (the barriers); m, rows, n uniform
-template <int E>
+template <int E, int SRC>
 __device__ __forceinline__ void lag_merge_wide(const u8 *const (&pl)[E], u8 *dst, u64 n, u64 L, u64 rows, u64 row0, u32 m, u64 strip0,
                                                const typename ElT<E>::T *prefix, typename ElT<E>::T *seg)
 {
@@ -358,10 +488,10 @@ __device__ __forceinline__ void lag_merge_wide(const u8 *const (&pl)[E], u8 *dst
             u64 i = i0;
 #pragma unroll
             for (u32 k = 0; k < LAG_VROWS; ++k, i += L) {
-                if (whole && i + LAG_VEC <= n) lag_d4<E>(pl, i, d[k]);
+                if (whole && i + LAG_VEC <= n) lag_src4<E, SRC>(pl, dst, i, d[k]);
                 else {
 #pragma unroll
-                    for (u32 c = 0; c < LAG_VEC; ++c) d[k][c] = col0 + c < L && i + c < n ? lag_d<E>(pl, i + c) : (T)0;
+                    for (u32 c = 0; c < LAG_VEC; ++c) d[k][c] = col0 + c < L && i + c < n ? lag_src<E, SRC>(pl, dst, i + c) : (T)0;
                 }
             }
         }
@@ -404,7 +534,7 @@ __device__ __forceinline__ void lag_merge_wide(const u8 *const (&pl)[E], u8 *dst
 }
 
 // launch 3: sums[chunk L + column] is by now the sum of the column's d's in front of the chunk (have_sums: launches 1 and 2 ran)
-template <int E>
+template <int E, int SRC = LAG_PLANES>
 __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                                const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
                                                                const u64 *__restrict__ d_n, const u8 *__restrict__ d_planes,
@@ -419,6 +549,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ 
         wk.enter();
         const u64 n = wk.n;
         if (!n) continue;                            // (uniform) empty, or past its capacity: no byte of it is touched
+        if (SRC != LAG_PLANES && !d_lag[wk.b]) continue;                       // (uniform) not this pass's block
         const LagGeom g(cap[wk.b], d_lag[wk.b]);
         const u64 rows = (n + g.L - 1) / g.L;
         const bool chained = (rows + g.G - 1) / g.G > 1;                         // (uniform) planes_lag_scan's condition
@@ -427,13 +558,13 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ 
         u8 *dst = (u8 *)wk.in;
         const u8 *pl[E];
 #pragma unroll
-        for (int j = 0; j < E; ++j) pl[j] = d_planes + d_poff[(u64)wk.b * E + j];
+        for (int j = 0; j < E; ++j) pl[j] = SRC == LAG_ELEMS ? nullptr : d_planes + d_poff[(u64)wk.b * E + j];
         const u32 s = tid / g.W, c = tid - s * g.W;
         for (u64 w = run.lo; w < run.hi; ++w) {
             const u64 ch = w / g.NS, col = (w - ch * g.NS) * g.W + c, row0 = ch * g.G;
             if (row0 >= rows) break;                 // (uniform) behind the block's last row
             if (g.W == LAG_STRIP) {                  // (uniform) four columns a lane
-                lag_merge_wide<E>(pl, dst, n, g.L, rows, row0, g.m, (w - ch * g.NS) * g.W, chained ? sums + ch * g.L : nullptr, seg);
+                lag_merge_wide<E, SRC>(pl, dst, n, g.L, rows, row0, g.m, (w - ch * g.NS) * g.W, chained ? sums + ch * g.L : nullptr, seg);
                 continue;
             }
             const bool act = s < g.S && col < g.L;
@@ -446,7 +577,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ 
                 {
                     u64 i = i0;
 #pragma unroll
-                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) d[k] = act && i < n ? lag_d<E>(pl, i) : (T)0;
+                    for (u32 k = 0; k < LAG_ROWS; ++k, i += g.L) d[k] = act && i < n ? lag_src<E, SRC>(pl, dst, i) : (T)0;
                 }
 #pragma unroll
                 for (u32 k = 1; k < LAG_ROWS; ++k) d[k] = (T)(d[k] + d[k - 1]);
@@ -496,7 +627,97 @@ void planes_lag_launch(bool merge, bool sums, const TileSetup &a, hipStream_t st
                        (const u8 *)d_planes, poff, lag, err, a.nt, a.per_wg, (const u8 *)a.scratch);
 }
 
+// one pass of the lag family over the blocks whose lag in the row `lag` is not 0: the sums and their scan where a block of the
+// pass has more than one chunk, then the merge
+template <int E, int SRC>
+void planes_lag_pass(bool sums, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, const u8 *d_planes,
+                     const u64 *poff, const u64 *lag, int *err)
+{
+    if (sums) {
+        hipLaunchKernelGGL((planes_lag_sums<E, SRC>), dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase,
+                           nblk, d_n, d_planes, poff, lag, a.nt, a.per_wg, a.scratch);
+        hipLaunchKernelGGL((planes_lag_scan<E, SRC>), dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase,
+                           nblk, d_n, lag, a.nt, a.per_wg, a.scratch);
+    }
+    hipLaunchKernelGGL((planes_lag_merge<E, SRC>), dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       d_planes, poff, lag, err, a.nt, a.per_wg, (const u8 *)a.scratch);
+}
+
+// what the host knows of a grid merge's passes: which are made at all, and which of them have a block of more than one chunk
+struct GridPlan {
+    bool diff, first, first_sums, pass[SHAFA_PLANES_GRID_LAGS], pass_sums[SHAFA_PLANES_GRID_LAGS];
+};
+
+// the launches read tile_setup's workspace: extra 0 the plane offsets, extra 1 the rows of lags (planes_grid_launch_dev), the
+// scratch the sums of whichever pass is running
+template <int E>
+void planes_grid_launch(bool merge, const GridPlan &gp, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n,
+                        u8 *d_planes, int *err)
+{
+    const u64 *poff = (const u64 *)a.extra[0], *lag = (const u64 *)a.extra[1];
+    if (!merge) {
+        hipLaunchKernelGGL(planes_grid_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblk,
+                           d_n, d_planes, poff, lag, err, a.nt, a.per_wg);
+        return;
+    }
+    if (gp.diff) planes_diff_merge_enqueue(E, a, st, d_el, nblk, d_n, d_planes, err, lag);
+    if (gp.first) planes_lag_pass<E, LAG_PLANES_SKIP>(gp.first_sums, a, st, d_el, nblk, d_n, d_planes, poff, lag, err);
+    for (int k = 1; k < SHAFA_PLANES_GRID_LAGS; ++k)
+        if (gp.pass[k])
+            planes_lag_pass<E, LAG_ELEMS>(gp.pass_sums[k], a, st, d_el, nblk, d_n, nullptr, poff, lag + (size_t)k * nblk, err);
+}
+
 }  // namespace
+
+// the _grid entries.  h_lags: nlags slots a block, checked by the caller (the first >= 1, the others 0 or
+// increasing).  The device gets SHAFA_PLANES_GRID_LAGS rows of nblocks lags, a slot at or past the block's capacity (it subtracts
+// nothing) and an unused one as 0.  split: one launch.  merge: row 0 is the lag family's first pass, planes -> elements at the
+// block's smallest lag, clamped as the _lag entries clamp it, and 0 where that lag is 1: those blocks are the _diff merge's, which
+// skips the others; rows 1 and 2 are the passes in place over the elements.  All passes share one scratch, the stream their order.
+int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags)
+{
+    const size_t nb = (size_t)nblocks;
+    std::vector<u64> lag(nb * SHAFA_PLANES_GRID_LAGS, 0);
+    GridPlan gp = {};
+    for (size_t b = 0; b < nb; ++b) {
+        const u64 cap = h_cap[b];
+        for (u32 k = 0; k < nlags; ++k) {
+            const u64 g = h_lags[b * nlags + k];
+            lag[k * nb + b] = g < cap ? g : 0;
+        }
+        if (!merge) continue;
+        const u64 first = lag[b] ? lag[b] : cap ? cap : 1;
+        if (first == 1) {
+            gp.diff = true;
+            lag[b] = 0;
+        } else {
+            gp.first = true;
+            lag[b] = first;
+            if (cap && LagGeom(cap, first).NC > 1) gp.first_sums = true;
+        }
+        for (int k = 1; k < SHAFA_PLANES_GRID_LAGS; ++k)
+            if (lag[k * nb + b]) {
+                gp.pass[k] = true;
+                if (LagGeom(cap, lag[k * nb + b]).NC > 1) gp.pass_sums[k] = true;
+            }
+    }
+    const bool sums = gp.first_sums || gp.pass_sums[1] || gp.pass_sums[2];
+    static_assert(SHAFA_PLANES_GRID_LAGS == 3, "the passes named here");
+    const TileExtra x[2] = {{h_plane_off, nb * elem * 8}, {lag.data(), lag.size() * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, sums ? (size_t)LAG_SUMS_TILE * elem : gp.diff ? 8 : 0, 0, &a))
+        return rc;
+    if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
+    switch (elem) {
+    case 1: planes_grid_launch<1>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 2: planes_grid_launch<2>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    case 4: planes_grid_launch<4>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    default: planes_grid_launch<8>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
 
 // the _lag entries: split is one launch; merge is the column sums and their scan (where a block has more than one chunk) and the
 // merge itself.  The caller has checked the arguments (every h_lag[b] >= 1).

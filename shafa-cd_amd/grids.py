@@ -1,0 +1,144 @@
+"""Lorenzo differences — the differences along up to three axes at once — one file set per byte plane: split_grid / merge_grid and
+compress_grids / decompress_grids on top of Batch.split_planes_grid_dev / merge_planes_grid_dev (csrc/planes_lag.hip;
+include/shafa_hip.h: "Byte planes of Lorenzo differences").
+
+compress_strided takes the difference along ONE axis.  A 2-D or 3-D simulation field, a stack of images, [step, y, x] snapshots
+are smooth along several axes at once, and one axis alone leaves most of that in place: there the integer Lorenzo predictor of
+the scientific-data codecs pays, the differences along every axis in turn, on the bit patterns.
+
+The drivers live in this submodule; the package re-exports them.  What is the grid's own is here: how axes become a tuple of
+lags, and the item.  The chains are the package's, compress_tensors' and decompress_tensors' with "planes_grid" as the variant and
+the tuples of lags where "planes_lag" has its lags (_plane_entries, _merge_items, _split_one, _merge_one), reached through the
+package at the time of the call."""
+import sys
+
+_pkg = sys.modules[__package__]
+
+
+class CompressedGrid:
+    """A tensor compressed by byte plane as its differences along up to three lags (compress_grids), in memory: `dtype` and
+    `shape` of the original, `lags` — the tuple of distances in elements of the flattened tensor, increasing — `planes` — one
+    entry per byte of the element, plane 0 the least significant, of the zigzag-folded differences: the dict compress_many
+    returns for that plane's bytes, or the plane itself (a uint8 CUDA tensor) where coding it would not shrink it — and `nbytes`,
+    the sum of the file lengths and of the raw planes' lengths.  Not a CompressedTensor: decompress_grids alone gives the tensor
+    back."""
+    __slots__ = ("dtype", "shape", "lags", "planes", "nbytes")
+
+    def __init__(self, dtype, shape, lags, planes, nbytes):
+        self.dtype, self.shape, self.lags, self.planes, self.nbytes = dtype, tuple(shape), lags, list(planes), int(nbytes)
+
+    def __repr__(self):
+        kinds = ["raw" if not isinstance(p, dict) else "+".join(sorted(p)) for p in self.planes]
+        return f"CompressedGrid({self.dtype}, {self.shape}, lags={self.lags}, planes={kinds}, nbytes={self.nbytes})"
+
+
+def _lag_tuple(what, lags):
+    """a tuple of 1 .. PLANES_GRID_LAGS strictly increasing lags, checked"""
+    if not isinstance(lags, (list, tuple)) or not 1 <= len(lags) <= _pkg.PLANES_GRID_LAGS:
+        raise ValueError(f"{what}: lags are a tuple of 1 .. {_pkg.PLANES_GRID_LAGS} ints, not {lags!r}")
+    lags = tuple(_pkg.strided._lag(what, g) for g in lags)
+    if any(a >= b for a, b in zip(lags, lags[1:])):
+        raise ValueError(f"{what}: lags are strictly increasing, not {lags!r}")
+    return lags
+
+
+def _axes_lags(what, shape, axes):
+    """the lags of `axes` (a tuple of ints, or None: the last three axes, or all of fewer) of a tensor of `shape`: each axis's lag
+    (strided._axis_lag), duplicates — axes of dimension 1 make them — dropped, sorted; (1,) for a 0-dimensional or an empty one"""
+    shape = tuple(int(d) for d in shape)
+    if axes is None:
+        axes = tuple(range(max(0, len(shape) - _pkg.PLANES_GRID_LAGS), len(shape))) or (0,)
+    if not isinstance(axes, (list, tuple)) or not axes:
+        raise ValueError(f"{what}: axes are a tuple of ints, not {axes!r}")
+    lags = tuple(sorted({_pkg.strided._axis_lag(what, shape, a) for a in axes}))
+    if len(lags) > _pkg.PLANES_GRID_LAGS:
+        raise ValueError(f"{what}: axes {tuple(axes)} of a tensor of shape {shape} make {len(lags)} distinct lags, more than "
+                         f"{_pkg.PLANES_GRID_LAGS}")
+    return lags
+
+
+def _lags(what, ts, axes, lags):
+    """one tuple of lags per checked tensor, from `lags` (None, a tuple of ints or a list of tuples) or else from `axes` (None, a
+    tuple of ints or a list of tuples)"""
+    def per_tensor(v, name):
+        if isinstance(v, list):
+            if len(v) != len(ts) or any(isinstance(x, int) for x in v):
+                raise ValueError(f"{what}: {name} is a tuple of ints or a list with one tuple per tensor")
+            return list(v)
+        return [v] * len(ts)
+    if lags is not None:
+        return [_lag_tuple(what, g) for g in per_tensor(lags, "lags")]
+    return [_axes_lags(what, t.shape, a) for t, a in zip(ts, per_tensor(axes, "axes"))]
+
+
+def split_grid(t, lags, stream=None):
+    """The byte planes of the differences along `lags` (a tuple of 1 .. 3 strictly increasing ints >= 1, in elements of the
+    flattened tensor) of a contiguous CUDA tensor with elements of k = 1, 2, 4 or 8 bytes: a uint8 tensor [k, numel], row j byte
+    j of the zigzag fold of ((1 - S^L1)(1 - S^L2)(1 - S^L3) x) mod 2^(8 k), x the elements as unsigned integers and 0 in front of
+    the tensor, S^L the shift by L elements.  Rows start at multiples of 16 bytes, as split_planes'.  One split_planes_grid_dev
+    launch, one synchronisation."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("split_grid: a contiguous CUDA tensor")
+    t = _pkg._plane_tensors("split_grid", t)[0]
+    lags = _lag_tuple("split_grid", lags)
+    return _pkg._split_one("planes_grid", t, t.numel(), t.element_size(), stream, [lags])
+
+
+def merge_grid(planes, dtype, shape, lags, stream=None):
+    """split_grid's inverse for one tensor: `planes` as merge_planes takes them, a uint8 CUDA tensor [k, numel] -> a tensor of
+    `dtype` and `shape`: the unfolded differences summed up at every distance of `lags` in turn.  One merge_planes_grid_dev call,
+    one synchronisation."""
+    import torch
+    k, shape, n = _pkg._plane_dtype("merge_grid", dtype, shape)
+    lags = _lag_tuple("merge_grid", lags)
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
+            or (planes.shape[1] > 1 and planes.stride(1) != 1):
+        raise ValueError("merge_grid: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
+    if tuple(planes.shape) != (k, n):
+        raise ValueError(f"merge_grid: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
+    return _pkg._merge_one("planes_grid", planes, dtype, shape, stream, [lags])
+
+
+def compress_grids(tensors, axes=None, lags=None, block_size=8 << 20, stream=None):
+    """compress_tensors of every tensor's differences ALONG SEVERAL AXES at once, the integer Lorenzo predictor — a 2-D or 3-D
+    field, a stack of images, [step, y, x] snapshots.  `tensors` and `block_size` as compress_tensors takes them, and its argument
+    ValueErrors.  `axes` is a tuple of ints for all tensors or a list with one tuple per tensor, negative values counting from
+    the back; None: each tensor's last three axes, or all of them if it has fewer.  An axis becomes a lag as in compress_strided
+    (the product of the dimensions behind it); duplicate lags — axes of dimension 1 make them — are dropped, the lags sorted, and
+    more than three distinct ones are a ValueError.  A 0-dimensional or an empty tensor takes (1,).  `lags`, a tuple of 1 .. 3
+    strictly increasing ints of 1 .. 2^64 - 1 or a list with one such tuple per tensor, overrides `axes`: the distances
+    themselves, for flat buffers.  Returns one CompressedGrid per tensor, which decompress_grids gives back bit for bit, whatever
+    the dtype and the values.
+
+    The differences run over the FLATTENED tensor: d = (1 - S^L1)(1 - S^L2)(1 - S^L3) x, S^L the shift by L elements.  None starts
+    afresh at the end of a row or a slab: a row's first element is taken against the last one of the row in front.  With one
+    axis this is compress_strided's transform, with axes=(-1,) compress_sequences'.
+
+    It does not always pay.  Every further difference doubles the variance of the noise the data carries: a smooth field of
+    integers came out at a third of its best single axis, a noisy uint8 image larger with two axes than with one.
+    Which axes pay is the caller's to know: nothing is tried both ways.
+
+    Chain: compress_tensors', with one split_planes_grid_dev per element size in place of the plain split — one block a tensor
+    with lags of its own, so the number of launches does not depend on the shapes; no temporary of the differences exists ->
+    compressed_sizes -> compress_many, as there."""
+    ts = _pkg._plane_tensors("compress_grids", tensors)
+    lags = _lags("compress_grids", ts, axes, lags)
+    entries, nbytes = _pkg._plane_entries("compress_grids", ts, _pkg._elements(ts), "planes_grid", lags, block_size, stream)
+    return [CompressedGrid(t.dtype, t.shape, g, ps, nb) for t, g, ps, nb in zip(ts, lags, entries, nbytes)]
+
+
+def decompress_grids(items, stream=None):
+    """compress_grids' inverse: `items` is a CompressedGrid or a list of them (their planes on one device) -> the list of
+    tensors, each equal to the original bit for bit.
+
+    Chain: decompress_tensors', with one merge_planes_grid_dev per element size in place of the plain merge: decompress_many over
+    all coded planes -> the sums at every lag in turn straight into fresh tensors.  Anything that is not a CompressedGrid — a
+    CompressedTensor of any kind, a CompressedStrided, a CompressedRecords — is refused with a ValueError before any device
+    work, as is an item whose lags are no tuple of increasing ints >= 1.  decompress_tensors' errors otherwise."""
+    if isinstance(items, CompressedGrid):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedGrid) for it in items):
+        raise ValueError("decompress_grids: a CompressedGrid or a list of them (compress_grids' items)")
+    lags = [_lag_tuple("decompress_grids", it.lags) for it in items]
+    return _pkg._merge_items("decompress_grids", items, "planes_grid", lags, False, stream)
