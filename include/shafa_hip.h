@@ -634,6 +634,37 @@ int shafa_hipd_merge_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblo
                                      const uint64_t *h_lags, const uint8_t *d_planes, const uint64_t *h_plane_off,
                                      const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_out, const uint64_t *h_out_off);
 
+/* ---- Plane histograms of Lorenzo differences: which lags pay, without the planes ------------------------------------------
+ * Whether a tensor compresses best as plain planes, along one axis or along several is a property of its data.  Each candidate's
+ * size follows from the histograms of its planes (shafa_hipd_sf_build_codes, shafa_hipd_sf_encoded_size_dev), and the histograms
+ * need no planes: this entry reads the elements and leaves the counts.
+ *   d_freq[(b * elem + j) * 256 + s] = the number of elements i < d_n[b] of block b whose byte j of z[i] is s,
+ * z exactly what shafa_hipd_split_planes_grid_dev writes for the block's row of lags.  One addition to those entries' rule for a
+ * row: a row of all zeros is the PLAIN candidate, z = x, no difference and no fold — the counts of shafa_hipd_split_planes_dev's
+ * planes.  (A first slot of 0 with a non-zero slot behind it stays SHAFA_OUTSIDE_MODULE; a lag at or past h_cap[b] subtracts
+ * nothing, as there.)  Each plane's 256 counts sum to d_n[b].  The layout is shafa_hipd_hist256's with nblocks * elem
+ * histograms: shafa_hipd_sf_build_codes and shafa_hipd_sf_encoded_size_dev take it as it is.  The call zeroes its nblocks * elem *
+ * 256 counts itself and writes nothing else.
+ * Blocks are only read and MAY OVERLAP OR COINCIDE on the element side: one tensor, one block per candidate row of lags, is the
+ * use.  The element side lies at multiples of elem (1, 2, 4 or 8), as the _grid_dev entries'; there is no plane side.
+ * Per-block code through shafa_hipd_finish: d_n[b] > h_cap[b] is SHAFA_OUTSIDE_MODULE, no byte of the block is read and its
+ * counts are 0.
+ * Launches.  One memset and one launch, enqueued only; no workgroup waits for another.  A workgroup walks a run of
+ * SHAFA_PLANES_HIST_RUN consecutive tiles of SHAFA_PLANES_TILE elements (numbered from the capacities), counts into 16 or 32
+ * KiB of LDS — 32, 8, 8 or 4 replicas of the elem histograms, 32-bit bins, which a run cannot overflow — and adds its non-zero bins to the
+ * block's counts with 64-bit global atomics when the walk enters another block and at its end.  1 byte of HBM traffic per tensor
+ * byte and candidate at the most; candidates on one region that fits the cache read it from there.
+ * Argument errors return with nothing enqueued (checked before HIP is touched), in the _grid_dev split's order with d_freq in
+ * d_planes' place and no plane-side rule: NULL b, d_in, d_freq or d_n, an nlags outside 1 .. SHAFA_PLANES_GRID_LAGS, an elem
+ * other than 1, 2, 4, 8: SHAFA_OUTSIDE_MODULE; nblocks <= 0: SHAFA_SUCCESS; nblocks past the batch's: SHAFA_LACK_OF_MEMORY;
+ * NULL h_cap: SHAFA_OUTSIDE_MODULE; capacities whose bytes pass 64 bits or whose tiles number 2^31 or more:
+ * SHAFA_LACK_OF_MEMORY; NULL h_in_off or h_lags, d_in or an offset off a multiple of elem, a malformed row:
+ * SHAFA_OUTSIDE_MODULE. */
+#define SHAFA_PLANES_HIST_RUN 8 /* tiles a workgroup counts before it adds its bins to the block's counts */
+int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                    const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                                    const uint64_t *d_n, uint64_t *d_freq);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

@@ -136,6 +136,7 @@ def lib():
     L.shafa_hipd_merge_planes_lag_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_split_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
+    L.shafa_hipd_hist_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -201,7 +202,7 @@ def lib():
                  "shafa_hipd_split_planes_xor_dev", "shafa_hipd_merge_planes_xor_dev",
                  "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev",
                  "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
-                 "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev",
+                 "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev", "shafa_hipd_hist_planes_grid_dev",
                  "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -584,6 +585,18 @@ class Batch:
         _check(lib().shafa_hipd_merge_planes_grid_dev(self.h, self._st(stream), len(oo), elem, nl, _p64(lg), _addr(d_planes),
                                                       _p64(po), _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)),
                "hipd_merge_planes_grid_dev")
+
+    def hist_planes_grid_dev(self, stream, elem, lags, d_in, in_off, cap, d_n, d_freq):
+        """The histograms of the planes split_planes_grid_dev would write, without the planes: d_freq[(b * elem + j) * 256 + s]
+        (int64) = how many of block b's d_n[b] elements have byte j of z equal to s.  `lags` as split_planes_grid_dev takes them,
+        and () — a row of zeros — for plain planes: no difference, no fold, split_planes_dev's counts.  The blocks are only read
+        and may overlap or coincide: one tensor, one block per candidate.  The element side at multiples of elem.  d_freq is
+        hist256's layout with len(in_off) * elem histograms and is zeroed by the call; sf_build_codes and sf_encoded_size_dev
+        take it as it is.  Enqueues only, one launch (include/shafa_hip.h: "Plane histograms of Lorenzo differences")."""
+        io, ic = _u64arr(in_off), _u64arr(cap)
+        nl, lg = _grid_lags("hist_planes_grid_dev", lags, len(io))
+        _check(lib().shafa_hipd_hist_planes_grid_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _addr(d_in), _p64(io),
+                                                     _p64(ic), d_n.data_ptr(), d_freq.data_ptr()), "hipd_hist_planes_grid_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -2790,6 +2803,7 @@ PLANES_LAG_STRIP = 256          # SHAFA_PLANES_LAG_STRIP, _ROWS, _ITEMS: the for
 PLANES_LAG_ROWS = 32
 PLANES_LAG_ITEMS = 4096
 PLANES_GRID_LAGS = 3            # SHAFA_PLANES_GRID_LAGS: the lags a block of split_planes_grid_dev / merge_planes_grid_dev may have
+PLANES_HIST_RUN = 8             # SHAFA_PLANES_HIST_RUN: the tiles a workgroup of hist_planes_grid_dev counts between two flushes
 RECORDS_MAX_WIDTH = 64          # SHAFA_RECORDS_MAX_WIDTH: split_records_dev / merge_records_dev take records of 1 .. 64 bytes
 RECORDS_TILE = 8192             # SHAFA_RECORDS_TILE: the records of one tile of theirs
 
@@ -3375,4 +3389,5 @@ from .strided import (CompressedStrided, compress_strided, decompress_strided, m
 
 # ------------------------------------------------------------------ differences along up to three axes, one file set per byte plane
 from . import grids  # noqa: E402
-from .grids import (CompressedGrid, compress_grids, decompress_grids, merge_grid, split_grid)  # noqa: E402,F401
+from .grids import (CompressedGrid, choose_lags, compress_grids, decompress_grids, grid_histograms, grid_sizes,  # noqa: E402,F401
+                    merge_grid, split_grid)

@@ -731,6 +731,35 @@ int shafa_hipd_merge_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblo
                          h_plane_off, h_lags, nlags);
 }
 
+// beside transpose_dev: its TR_GRID checks in its order without a plane side, and with a row of zeros allowed (plain planes)
+int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                    const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                                    const uint64_t *d_n, uint64_t *d_freq)
+{
+    if (!b || !d_in || !d_freq || !d_n) return SHAFA_OUTSIDE_MODULE;
+    if (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS) return SHAFA_OUTSIDE_MODULE;
+    if (elem != 1 && elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_cap) return SHAFA_OUTSIDE_MODULE;
+    u64 bytes = 0;
+    for (int i = 0; i < nblocks; ++i) {
+        if (h_cap[i] > ~0ull / elem || bytes + h_cap[i] * elem < bytes) return SHAFA_LACK_OF_MEMORY;
+        bytes += h_cap[i] * elem;
+    }
+    if (tile_count(nblocks, h_cap, SHAFA_PLANES_TILE) < nblocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || !h_lags || (uintptr_t)d_in % elem) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i) {
+        const u64 *g = h_lags + (size_t)i * nlags;
+        if (h_in_off[i] % elem) return SHAFA_OUTSIDE_MODULE;
+        for (uint32_t k = 1; k < nlags; ++k)         // the _grid entries' rows, or all zeros: a 0 has only zeros behind it
+            if (g[k] && (!g[k - 1] || g[k] <= g[k - 1])) return SHAFA_OUTSIDE_MODULE;
+    }
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return planes_grid_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags, h_lags,
+                                       d_freq);
+}
+
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,
                                  const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                  const uint64_t *h_plane_off)

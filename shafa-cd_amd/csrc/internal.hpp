@@ -289,6 +289,11 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags);
 void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 *d_el, int nblocks, const u64 *d_n,
                                const u8 *d_planes, int *err, const u64 *d_skip);
+// the histograms of the planes the grid split would write for these blocks, which may overlap, without the planes: d_freq[(b *
+// elem + j) * 256 + s] counts byte s in plane j of block b (planes_lag.hip).  A row of h_lags that is all zeros: plain planes, no
+// difference and no fold.  d_freq is zeroed first; the rows have been checked by the caller
+int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off, const u64 *h_cap,
+                                const u64 *d_n, u32 nlags, const u64 *h_lags, u64 *d_freq);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

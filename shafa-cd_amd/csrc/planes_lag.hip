@@ -246,6 +246,130 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_split(const u8 *__rest
     tp_size_errors(cap, d_n, nblk, err);
 }
 
+// ---- the histograms of the grid split's planes without the planes (shafa_hipd_hist_planes_grid_dev): the walk and the
+// element path of split_tile_grid, and where split_store would write one word of each plane, the word's bytes are counted into a
+// replicated LDS histogram per plane (hist.hip's layout: bin s of replica r at s REP + r, a lane's replica from its number).  The
+// high planes of good differences are one byte nearly everywhere; the replicas alone carry that (folding a lane's 16 equal bytes
+// into one atomic measured 1 % SLOWER: DESIGN 7.29).  Only the c = min(16, n - e0) elements in front of the block's end are
+// counted: the unit's bytes behind them are whatever lies behind the region.  A workgroup walks a run of SHAFA_PLANES_HIST_RUN
+// consecutive tiles and adds its non-zero bins to the block's counts, with 64-bit global atomics, when the walk enters another
+// block and at its end (flush: rle_encode_hist.hip's).  A bin of a replica takes at most RUN x 8192 elements between two
+// flushes, so 32-bit LDS counters hold.
+constexpr u32 GH_RUN = SHAFA_PLANES_HIST_RUN;
+// replicas: hist.hip's 32 at E = 1; 8 at E = 2 and 4, the fastest measured (16 and 32 KiB of LDS: DESIGN 7.29); 4 at E = 8, where 8
+// would be 64 KiB and two workgroups a CU
+template <int E> constexpr u32 gh_rep() { return E == 1 ? 32u : E == 8 ? 4u : 8u; }
+static_assert((u64)GH_RUN * TP_TILE < (1ull << 32), "a run's elements fit one 32-bit bin");
+
+template <int E>
+__device__ __forceinline__ void hist_count(const u32 (&w)[4 * E], u32 c, u32 *h)
+{
+    constexpr u32 REP = gh_rep<E>();
+    const u32 rep = threadIdx.x & (REP - 1u);
+#pragma unroll
+    for (int j = 0; j < E; ++j) {
+        const u32 o[4] = {split_dword<E>(w, j, 0), split_dword<E>(w, j, 1), split_dword<E>(w, j, 2), split_dword<E>(w, j, 3)};
+        u32 *hj = h + (u32)j * 256u * REP + rep;
+        if (c == PL_UNIT) {
+#pragma unroll
+            for (int k = 0; k < PL_UNIT; ++k) atomicAdd(hj + ((o[k >> 2] >> (8 * (k & 3))) & 0xFFu) * REP, 1u);
+        } else {
+#pragma unroll
+            for (int k = 0; k < PL_UNIT; ++k)
+                if ((u32)k < c) atomicAdd(hj + ((o[k >> 2] >> (8 * (k & 3))) & 0xFFu) * REP, 1u);
+        }
+    }
+}
+
+// split_tile_grid with the fold left out for a block of plain planes (fold, uniform) and hist_count for split_store
+template <int E, int Q>
+__device__ __forceinline__ void hist_tile_grid(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], bool fold, u32 *h)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        if (fold) zz_fold<E, 4 * E>(w);              // (uniform)
+        hist_count<E>(w, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), h);
+    }
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them a row of flags, 0 for a block of plain planes (a row of zeros
+// from the caller), else 1: the clamped lags alone do not tell the two apart
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_hist(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, const u64 *__restrict__ d_lag,
+                                                               int *__restrict__ err, u32 n_tiles, u64 *__restrict__ d_freq)
+{
+    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
+    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
+    const u32 tid = threadIdx.x;
+    // the workgroup's bins -> block b's counts; every thread sums and clears the replicas of bin tid of each plane (rotated)
+    auto flush = [&](int b) {
+        lds_barrier();
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            u32 c = 0;
+#pragma unroll
+            for (u32 q = 0; q < REP; ++q) {
+                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
+                c += *p;
+                *p = 0;
+            }
+            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
+        }
+        lds_barrier();
+    };
+    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
+    lds_barrier();
+    int cur_b = -1;                                  // the block whose counts the bins hold
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        if (wk.b != cur_b) {                         // (uniform)
+            if (cur_b >= 0) flush(cur_b);
+            cur_b = wk.b;
+        }
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const bool fold = d_lag[(u64)SHAFA_PLANES_GRID_LAGS * nblk + wk.b] != 0;
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: hist_tile_grid<E, 0>(wk, r, lg, fold, h); break;
+        case 1: hist_tile_grid<E, 1>(wk, r, lg, fold, h); break;
+        case 2: hist_tile_grid<E, 2>(wk, r, lg, fold, h); break;
+        default: hist_tile_grid<E, 3>(wk, r, lg, fold, h); break;
+        }
+    }
+    if (cur_b >= 0) flush(cur_b);
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
 // ---- merge
 // The three launches are templated on their SOURCE: LAG_PLANES the _lag entries' (d[i] unfolded from the planes),
 // LAG_PLANES_SKIP the same where a block whose lag is 0 is another family's and skipped (the grid merge's first pass), LAG_ELEMS
@@ -715,6 +839,32 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     case 4: planes_grid_launch<4>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     default: planes_grid_launch<8>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
+// shafa_hipd_hist_planes_grid_dev.  h_lags as the _grid entries', or a row of zeros: plain planes.  The device gets
+// the grid split's rows of clamped lags and a fourth row, 1 where the block's row is not all zeros.  The grid is this launcher's
+// own: a workgroup a run of SHAFA_PLANES_HIST_RUN consecutive tiles.  One memset, one launch.
+int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off, const u64 *h_cap,
+                                const u64 *d_n, u32 nlags, const u64 *h_lags, u64 *d_freq)
+{
+    const size_t nb = (size_t)nblocks;
+    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 1), 0);
+    for (size_t b = 0; b < nb; ++b)
+        for (u32 k = 0; k < nlags; ++k) {
+            const u64 g = h_lags[b * nlags + k];
+            lag[k * nb + b] = g < h_cap[b] ? g : 0;
+            if (g) lag[SHAFA_PLANES_GRID_LAGS * nb + b] = 1;
+        }
+    const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
+    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
+    const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
+    auto kernel = elem == 1 ? planes_grid_hist<1> : elem == 2 ? planes_grid_hist<2> : elem == 4 ? planes_grid_hist<4> : planes_grid_hist<8>;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
+                       bt->d_err, a.nt, d_freq);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

@@ -9,7 +9,12 @@ the scientific-data codecs pays, the differences along every axis in turn, on th
 The drivers live in this submodule; the package re-exports them.  What is the grid's own is here: how axes become a tuple of
 lags, and the item.  The chains are the package's, compress_tensors' and decompress_tensors' with "planes_grid" as the variant and
 the tuples of lags where "planes_lag" has its lags (_plane_entries, _merge_items, _split_one, _merge_one), reached through the
-package at the time of the call."""
+package at the time of the call.
+
+Which lags pay is the data's to say: grid_histograms / grid_sizes / choose_lags on top of Batch.hist_planes_grid_dev count the
+candidates' planes without making them and rank the candidates by an order-0 model of their size."""
+import ctypes as C
+import itertools
 import sys
 
 _pkg = sys.modules[__package__]
@@ -117,7 +122,8 @@ def compress_grids(tensors, axes=None, lags=None, block_size=8 << 20, stream=Non
 
     It does not always pay.  Every further difference doubles the variance of the noise the data carries: a smooth field of
     integers came out at a third of its best single axis, a noisy uint8 image larger with two axes than with one.
-    Which axes pay is the caller's to know: nothing is tried both ways.
+    Which axes pay is the caller's to know: nothing is tried both ways here.  choose_lags ranks the candidates from their planes'
+    histograms, without the planes, and its pick goes into `lags`.
 
     Chain: compress_tensors', with one split_planes_grid_dev per element size in place of the plain split — one block a tensor
     with lags of its own, so the number of launches does not depend on the shapes; no temporary of the differences exists ->
@@ -126,6 +132,137 @@ def compress_grids(tensors, axes=None, lags=None, block_size=8 << 20, stream=Non
     lags = _lags("compress_grids", ts, axes, lags)
     entries, nbytes = _pkg._plane_entries("compress_grids", ts, _pkg._elements(ts), "planes_grid", lags, block_size, stream)
     return [CompressedGrid(t.dtype, t.shape, g, ps, nb) for t, g, ps, nb in zip(ts, lags, entries, nbytes)]
+
+
+# ---- which lags pay: the planes' histograms without the planes (Batch.hist_planes_grid_dev)
+HIST_GROUP = 4096               # grid_histograms: candidates per device batch and launch
+
+
+def _candidate(what, c):
+    """a candidate: () — plain planes — or a tuple that _lag_tuple takes"""
+    if not isinstance(c, tuple):
+        raise ValueError(f"{what}: a candidate is a tuple of lags, () for plain planes, not {c!r}")
+    return c if c == () else _lag_tuple(what, c)
+
+
+def _candidate_list(what, cs):
+    if not isinstance(cs, list) or not cs:
+        raise ValueError(f"{what}: candidates are a non-empty list of tuples of lags, not {cs!r}")
+    return [_candidate(what, c) for c in cs]
+
+
+def _subsets(lags):
+    """() and every non-empty subset of a tuple of lags, fewer lags first: at most eight"""
+    return [s for r in range(len(lags) + 1) for s in itertools.combinations(lags, r)]
+
+
+def _default_candidates(what, shape, axes):
+    """the candidates of a tensor of `shape` from its axis lags"""
+    return _subsets(_axes_lags(what, shape, axes))
+
+
+def _candidates(what, ts, axes, candidates):
+    """one list of candidates per checked tensor: from `candidates` (a list of tuples for all tensors, or a list with one such
+    list per tensor) or else () and the subsets of each tensor's axis lags (`axes` as compress_grids takes them)"""
+    if candidates is None:
+        return [_subsets(g) for g in _lags(what, ts, axes, None)]
+    if isinstance(candidates, list) and any(isinstance(c, list) for c in candidates):
+        if len(candidates) != len(ts):
+            raise ValueError(f"{what}: candidates is a list of tuples or a list with one such list per tensor")
+        return [_candidate_list(what, cs) for cs in candidates]
+    return [_candidate_list(what, candidates)] * len(ts)
+
+
+def grid_histograms(t, lag_sets, stream=None):
+    """The byte histograms of the planes split_grid(t, lags) would give for every `lags` of the list `lag_sets`, without the
+    planes: `t` a contiguous CUDA tensor with elements of k = 1, 2, 4 or 8 bytes, every entry of `lag_sets` a tuple split_grid
+    takes or () for plain planes (split_planes').  Returns an int64 CUDA tensor [len(lag_sets), k, 256]; every row sums to
+    t.numel().  One hist_planes_grid_dev launch per HIST_GROUP candidates (the batch's max_blocks), one block per candidate on
+    the same region, one synchronisation."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("grid_histograms: a contiguous CUDA tensor")
+    t = _pkg._plane_tensors("grid_histograms", t)[0]
+    if not isinstance(lag_sets, (list, tuple)):
+        raise ValueError(f"grid_histograms: lag_sets is a list of tuples of lags, not {lag_sets!r}")
+    sets = [_candidate("grid_histograms", c) for c in lag_sets]
+    dev, k, n = t.device, t.element_size(), t.numel()
+    st = _pkg._plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
+        if sets and n:
+            bt = _pkg.Batch(min(len(sets), HIST_GROUP), 1 << 20)
+            try:
+                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
+                for lo in range(0, len(sets), bt.max_blocks):
+                    part = sets[lo:lo + bt.max_blocks]
+                    bt.hist_planes_grid_dev(st, k, part, t, [0] * len(part), [n] * len(part), d_n, freq[lo:lo + len(part)])
+                bt.finish(st, bt.max_blocks)
+            finally:
+                bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return freq
+
+
+def grid_sizes(tensors, axes=None, candidates=None, stream=None):
+    """How large would each candidate's planes be?  Per tensor a list of (lags, nbytes), sorted by (nbytes, len(lags), lags):
+    the first entry is the candidate to take, among equals the one with the fewest lags.  `tensors` as compress_grids takes
+    them.  `candidates` is a list of tuples for all tensors or a list with one such list per tensor, each tuple () — plain
+    planes, compress_tensors — or a tuple of lags as compress_grids' `lags`; None: () and every non-empty subset of the
+    tensor's axis lags (`axes` as compress_grids takes them: the last three axes by default), at most eight.  An empty or
+    0-dimensional tensor gives [((), 0)] whatever the candidates.
+
+    nbytes is a MODEL of the planes, of order 0: the sum over the candidate's byte planes of min(numel, the Shannon-Fano bytes
+    of the whole plane under the table of its own histogram) — a plane that would not shrink counts raw, as compress_tensors
+    keeps it.  It is not the size compress_grids reports: it knows nothing of RLE, of the split into blocks of block_size with
+    a table each, or of the files' tables and headers (DESIGN 7.29 has both side by side).
+
+    Chain: per element size one hist_planes_grid_dev over all tensors' candidates, one block per candidate on its tensor's
+    region — the planes never exist, and no histogram comes to the host -> sf_build_codes -> sf_encoded_size_dev -> one finish,
+    one read-back of the sizes."""
+    import torch
+    what = "grid_sizes"
+    ts = _pkg._plane_tensors(what, tensors)
+    cands = _candidates(what, ts, axes, candidates)
+    out = [[((), 0)] if not t.numel() or not t.dim() else None for t in ts]
+    blocks = [(i, c) for i, t in enumerate(ts) if out[i] is None for c in cands[i]]        # grouped by width below
+    if not blocks:
+        return out
+    dev = ts[0].device
+    st = _pkg._plane_stream(dev, stream)
+    widths = sorted({ts[i].element_size() for i, _ in blocks})
+    groups = [(w, [(i, c) for i, c in blocks if ts[i].element_size() == w]) for w in widths]
+    with torch.cuda.stream(st):
+        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
+        try:
+            sizes = []
+            for w, g in groups:
+                base = min(ts[i].data_ptr() for i, _ in g)
+                numel = [ts[i].numel() for i, _ in g]
+                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
+                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
+                bt.hist_planes_grid_dev(st, w, [c for _, c in g], base, [ts[i].data_ptr() - base for i, _ in g], numel, d_n, d_freq)
+                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
+                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
+                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
+                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
+                sizes.append(torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1))
+            bt.finish(st, bt.max_blocks)
+            host = torch.cat(sizes).cpu().tolist()
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    found = [[] for _ in ts]
+    for (i, c), nb in zip([x for _, g in groups for x in g], host):
+        found[i].append((c, int(nb)))
+    return [o if o is not None else sorted(f, key=lambda e: (e[1], len(e[0]), e[0])) for o, f in zip(out, found)]
+
+
+def choose_lags(tensors, axes=None, candidates=None, stream=None):
+    """Which lags to compress each tensor with: grid_sizes' first entry per tensor, the candidate whose planes the order-0 model
+    makes smallest, among equals the one with the fewest lags.  () says that plain planes win: compress_tensors.  Anything else
+    goes to compress_grids(tensor, lags=[...]).  grid_sizes' arguments, chain and caveats."""
+    return [sizes[0][0] for sizes in grid_sizes(tensors, axes, candidates, stream)]
 
 
 def decompress_grids(items, stream=None):
