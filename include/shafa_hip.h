@@ -665,6 +665,57 @@ int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
                                     const uint64_t *d_n, uint64_t *d_freq);
 
+/* ---- Error-bounded fields: quantise inside the Lorenzo split, restore behind the merge -------------------------------------
+ * The fields the _grid_dev entries are for are nearly always float or double, and the Lorenzo differences of raw float bit
+ * patterns leave every mantissa byte raw.  The codecs the predictor was taken from (SZ, cuSZ) quantise each value under an error
+ * bound first and difference the integers exactly.  These entries are the _grid_dev pair with that quantiser in the split and the
+ * restorer behind the merge; no temporary of codes exists.  T is float at elem 4 and double at elem 8 (any other elem:
+ * SHAFA_OUTSIDE_MODULE).  Block b has two host doubles, h_step[b] and h_bound[b], both exactly representable in T, finite, normal
+ * and > 0; inv = T(1.0 / step), the double division rounded to T once, is finite and not 0.  Every operation below is ONE IEEE
+ * operation in T, rounded to nearest even, none contracted into an FMA:
+ *   t    = x * inv
+ *   in   = |t| < 2^(8 elem - 2)                       (false for a NaN)
+ *   code = (signed integer of 8 elem bits) (in ? rint(t) : 0)
+ *   x'   = T(code) * step                             (from the INTEGER: a rint of -0.0 restores as +0.0)
+ *   good = in and (elem 4: |double(x) - double(x')| <= double(bound), the subtraction in double;
+ *                  elem 8: |x - x'| <= bound, the rounded subtraction)
+ * The planes are those shafa_hipd_split_planes_grid_dev writes for the block's lags over the array of codes taken as unsigned
+ * integers, byte for byte; a position in front of the block is the bit pattern 0, whose code is 0.  An element that is not good
+ * is an OUTLIER — a NaN, an infinity, a value past the code range or one whose restored value misses the bound: its code still
+ * goes into the planes, and it is recorded as well.  The merge restores every element as x' and then stores the outliers' own
+ * bits on top: an outlier comes back bit for bit, every other element within h_bound[b] (-0.0 may come back as +0.0).  The
+ * guarantee is checked per element on the device, against the very x' the merge will make.  step and bound are apart on
+ * purpose: with step = 2 bound the rounding of x' throws elements near a tie over the bound; a step a little below 2 bound keeps
+ * them inside.
+ * Outlier records.  A record is 16 bytes, {u64 position in the block, u64 the element's bits in the low 8 elem bits}.  Block b's
+ * records start at record h_outl_off[b] of d_outl and number at most h_outl_cap[b] (0 is legal).  The split zeroes
+ * d_outl_n[0 .. nblocks) itself; a lane with an outlier takes a slot with a 64-bit atomic add on d_outl_n[b] and writes the record
+ * only where slot < capacity.  After shafa_hipd_finish d_outl_n[b] is the number of outliers FOUND: a count above the capacity is
+ * the signal, not an error; the planes are complete either way and nothing is written past a block's capacity.  The order of the
+ * records within a block is not defined.
+ * Everything the _grid_dev pair says of the blocks, the lags, both sides' alignment, the capacities and d_n holds here, what is
+ * written and the per-block code for d_n[b] > h_cap[b] included.
+ * Launches.  split: a memset of d_outl_n and ONE launch, the grid split's with every loaded unit of 16 elements — the lane's own
+ * and every tap's — quantised in registers before it is subtracted or added.  merge: the _grid_dev merge's chain as it is, then
+ * a restore pass in place over the elements (code -> T(code) * step) and a patch pass, one thread per record of h_outl_n[b],
+ * which stores the record's bits at its position; a position >= d_n[b] gives the block SHAFA_OUTSIDE_MODULE and nothing is
+ * written for that record.  The patch pass is not enqueued where the call has no records.  No workgroup waits for another.
+ * Enqueues only.
+ * Argument errors return with nothing enqueued (checked before HIP is touched): the _grid_dev entries' in their order, and where
+ * those check their lags, each SHAFA_OUTSIDE_MODULE: NULL h_step or h_bound; a step or bound that is not finite, not normal, not
+ * > 0 or not exactly representable in T, or an inv that is 0 or not finite; NULL d_outl_n, h_outl_off or h_outl_cap (h_outl_n);
+ * NULL d_outl while any capacity (count) is not 0. */
+int shafa_hipd_split_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const double *h_step, const double *h_bound,
+                                           const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                           uint8_t *d_planes, const uint64_t *h_plane_off, uint64_t *d_outl,
+                                           const uint64_t *h_outl_off, const uint64_t *h_outl_cap, uint64_t *d_outl_n);
+int shafa_hipd_merge_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const double *h_step, const uint8_t *d_planes,
+                                           const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                           const uint64_t *d_outl, const uint64_t *h_outl_off, const uint64_t *h_outl_n,
+                                           uint8_t *d_out, const uint64_t *h_out_off);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

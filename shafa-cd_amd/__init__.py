@@ -137,6 +137,11 @@ def lib():
     L.shafa_hipd_split_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_hist_planes_grid_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u8p, u64p, u64p, vp, vp]
+    f64p = C.POINTER(C.c_double)
+    L.shafa_hipd_split_planes_grid_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, f64p, f64p, u8p, u64p, u64p,
+                                                         vp, u8p, u64p, vp, u64p, u64p, vp]
+    L.shafa_hipd_merge_planes_grid_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, f64p, u8p, u64p, u64p, vp,
+                                                         vp, u64p, u64p, u8p, u64p]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -203,6 +208,7 @@ def lib():
                  "shafa_hipd_split_planes_diff_dev", "shafa_hipd_merge_planes_diff_dev",
                  "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
                  "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev", "shafa_hipd_hist_planes_grid_dev",
+                 "shafa_hipd_split_planes_grid_quant_dev", "shafa_hipd_merge_planes_grid_quant_dev",
                  "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -294,6 +300,14 @@ def _u64arr(v):
 
 def _p64(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _f64arr(v):
+    return np.ascontiguousarray(v, dtype=np.float64)
+
+
+def _pf64(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
 def _grid_lags(what, lags, nblocks):
@@ -585,6 +599,42 @@ class Batch:
         _check(lib().shafa_hipd_merge_planes_grid_dev(self.h, self._st(stream), len(oo), elem, nl, _p64(lg), _addr(d_planes),
                                                       _p64(po), _p64(ic), d_n.data_ptr(), _addr(d_out), _p64(oo)),
                "hipd_merge_planes_grid_dev")
+
+    def split_planes_grid_quant_dev(self, stream, elem, lags, step, bound, d_in, in_off, cap, d_n, d_planes, plane_off, d_outl,
+                                    outl_off, outl_cap, d_outl_n):
+        """split_planes_grid_dev over the CODES of float (elem 4) or double (elem 8) elements under an error bound: `step` and
+        `bound` are host floats, one per block, exactly representable in the element type; code = rint(x * T(1 / step)) as a
+        signed integer, and the planes are split_planes_grid_dev's over the codes, byte for byte.  An element whose restored
+        value T(code) * step misses `bound` — a NaN, an infinity and a value past the code range among them — is an outlier: its
+        {position, bits} is written as two int64 at d_outl[2 * (outl_off[b] + slot)] while slot < outl_cap[b], and d_outl_n[b]
+        (int64, zeroed by the call) counts the outliers FOUND, above the capacity too.  d_outl may be None where every capacity
+        is 0.  Enqueues only: a memset and one launch (include/shafa_hip.h: "Error-bounded fields")."""
+        io, ic, po, oo, oc = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off), _u64arr(outl_off), _u64arr(outl_cap)
+        nl, lg = _grid_lags("split_planes_grid_quant_dev", lags, len(io))
+        sp, bd = _f64arr(step), _f64arr(bound)
+        if not len(sp) == len(bd) == len(oo) == len(oc) == len(io):
+            raise ValueError("split_planes_grid_quant_dev: one step, bound, record offset and record capacity per block")
+        _check(lib().shafa_hipd_split_planes_grid_quant_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pf64(sp), _pf64(bd),
+                                                            _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), _addr(d_planes),
+                                                            _p64(po), None if d_outl is None else _addr(d_outl), _p64(oo), _p64(oc),
+                                                            d_outl_n.data_ptr()), "hipd_split_planes_grid_quant_dev")
+
+    def merge_planes_grid_quant_dev(self, stream, elem, lags, step, d_planes, plane_off, cap, d_n, d_outl, outl_off, outl_n, d_out,
+                                    out_off):
+        """split_planes_grid_quant_dev's inverse: merge_planes_grid_dev's chain gives the codes, a restore pass in place makes
+        T(code) * step of each, and a patch pass stores the bits of block b's outl_n[b] (host) records from d_outl[2 *
+        outl_off[b]] on at their positions.  A record whose position is at or past d_n[b] gives the block OUTSIDE_MODULE and is
+        not written.  d_outl may be None where no block has a record.  Enqueues only (include/shafa_hip.h: "Error-bounded
+        fields")."""
+        oo, ic, po, ro, rn = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off), _u64arr(outl_off), _u64arr(outl_n)
+        nl, lg = _grid_lags("merge_planes_grid_quant_dev", lags, len(oo))
+        sp = _f64arr(step)
+        if not len(sp) == len(ro) == len(rn) == len(oo):
+            raise ValueError("merge_planes_grid_quant_dev: one step, record offset and record count per block")
+        _check(lib().shafa_hipd_merge_planes_grid_quant_dev(self.h, self._st(stream), len(oo), elem, nl, _p64(lg), _pf64(sp),
+                                                            _addr(d_planes), _p64(po), _p64(ic), d_n.data_ptr(),
+                                                            None if d_outl is None else _addr(d_outl), _p64(ro), _p64(rn),
+                                                            _addr(d_out), _p64(oo)), "hipd_merge_planes_grid_quant_dev")
 
     def hist_planes_grid_dev(self, stream, elem, lags, d_in, in_off, cap, d_n, d_freq):
         """The histograms of the planes split_planes_grid_dev would write, without the planes: d_freq[(b * elem + j) * 256 + s]
@@ -3099,24 +3149,37 @@ def _plane_entries(what, ts, units, kind, bases, block_size, stream):
             bt.finish(st, len(ts))
         finally:
             bt.close()
-        entries = [[buf[o:o + n] for o in poff[i]] for i, (n, _) in enumerate(units)]
-        cand = [(i, j) for i, (n, w) in enumerate(units) if n >= 1024 for j in range(w)]
-        if cand:
-            spans = [(poff[i][j], units[i][0]) for i, j in cand]
-            d_in, sizes = _back_to_back(buf, spans)
-            sized = compressed_sizes(d_in, sizes, block_size=block_size, stream=st)
-            keep = [c for c, e in zip(cand, sized) if isinstance(e, dict) and sum(e.values()) < units[c[0]][0]]
-        else:
-            keep = []
-        if keep:
-            d_in, sizes = _back_to_back(buf, [(poff[i][j], units[i][0]) for i, j in keep])
-            for (i, j), e in zip(keep, compress_many(d_in, sizes, block_size=block_size, stream=st)):
-                if isinstance(e, ShafaError):
-                    raise e
-                entries[i][j] = e
+        entries = _coded_planes(buf, poff, units, block_size, st)
     torch.cuda.current_stream(dev).wait_stream(st)
-    return entries, [sum(sum(int(f.numel()) for f in p.values()) if isinstance(p, dict) else int(p.numel()) for p in ps)
-                     for ps in entries]
+    return entries, _entry_bytes(entries)
+
+
+def _coded_planes(buf, poff, units, block_size, st):
+    """_plane_entries' half behind the split's finish, on the stream st (current): the planes of `units` at the offsets `poff`
+    of the planes buffer `buf` -> per tensor its plane entries, the file set of every plane that shrinks (compressed_sizes ->
+    compress_many) and a view of buf for every other"""
+    entries = [[buf[o:o + n] for o in poff[i]] for i, (n, _) in enumerate(units)]
+    cand = [(i, j) for i, (n, w) in enumerate(units) if n >= 1024 for j in range(w)]
+    if cand:
+        spans = [(poff[i][j], units[i][0]) for i, j in cand]
+        d_in, sizes = _back_to_back(buf, spans)
+        sized = compressed_sizes(d_in, sizes, block_size=block_size, stream=st)
+        keep = [c for c, e in zip(cand, sized) if isinstance(e, dict) and sum(e.values()) < units[c[0]][0]]
+    else:
+        keep = []
+    if keep:
+        d_in, sizes = _back_to_back(buf, [(poff[i][j], units[i][0]) for i, j in keep])
+        for (i, j), e in zip(keep, compress_many(d_in, sizes, block_size=block_size, stream=st)):
+            if isinstance(e, ShafaError):
+                raise e
+            entries[i][j] = e
+    return entries
+
+
+def _entry_bytes(entries):
+    """per tensor the bytes of its plane entries: the file lengths and the raw planes' lengths"""
+    return [sum(sum(int(f.numel()) for f in p.values()) if isinstance(p, dict) else int(p.numel()) for p in ps)
+            for ps in entries]
 
 
 def compress_tensors(tensors, block_size=8 << 20, stream=None):
@@ -3229,10 +3292,11 @@ def compress_deltas(tensors, bases, block_size=8 << 20, check_base=True, stream=
             for t, b, ps, nb, c in zip(ts, bs, entries, nbytes, crcs)]
 
 
-def _merge_items(what, items, kind, bases, check_base, stream):
+def _merge_items(what, items, kind, bases, check_base, stream, merge_into=None):
     """decompress_tensors' checks and chain over the list `items`, and in its other variants decompress_deltas' (with `bases`,
     one entry per item), decompress_sequences', decompress_strided's (`bases` the items' lags), decompress_grids' (`bases` the
-    items' tuples of lags) and decompress_records' (whose messages say "column" for a plane)"""
+    items' tuples of lags) and decompress_records' (whose messages say "column" for a plane).  `merge_into`: a stand-in for
+    _merge_into with its arguments (decompress_fields', whose items take one of two merges)"""
     import torch
     noun, length = ("column", "record count") if kind == "records" else ("plane", "tensor's numel")
     lags = bases if kind in ("planes_lag", "planes_grid") else None          # those variants' `bases` are lags, one entry per item
@@ -3304,7 +3368,8 @@ def _merge_items(what, items, kind, bases, check_base, stream):
         outs = [torch.empty(shape, dtype=it.dtype, device=dev) for it, (shape, _, _) in zip(items, metas)]
         bt = Batch(len(items), 1 << 20)
         try:
-            _merge_into(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind, lags if lags is not None else bases)
+            (merge_into or _merge_into)(bt, st, dev, planes, outs, [(n, k) for _, n, k in metas], kind,
+                                        lags if lags is not None else bases)
             bt.finish(st, len(items))
         finally:
             bt.close()
@@ -3391,3 +3456,9 @@ from .strided import (CompressedStrided, compress_strided, decompress_strided, m
 from . import grids  # noqa: E402
 from .grids import (CompressedGrid, choose_lags, compress_grids, decompress_grids, grid_histograms, grid_sizes,  # noqa: E402,F401
                     merge_grid, split_grid)
+
+
+# ------------------------------------------------------------------ error-bounded float fields: quantised Lorenzo differences
+from . import fields  # noqa: E402
+from .fields import (FIELD_SLACK, CompressedField, compress_fields, decompress_fields, quantize_field,  # noqa: E402,F401
+                     restore_field)

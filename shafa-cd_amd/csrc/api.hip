@@ -4,6 +4,7 @@
 #include "common.hpp"
 #include "internal.hpp"
 
+#include <cmath>
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -607,16 +608,28 @@ int shafa_hipd_find_dev(shafa_hipd_batch *b, void *stream, int nblocks, const ui
 enum Transpose { TR_PLANES, TR_XOR, TR_DIFF, TR_LAG, TR_GRID, TR_RECORDS };
 static_assert(SHAFA_RECORDS_TILE == SHAFA_PLANES_TILE, "one tile for the plane and the record entries");
 
+// a step or a bound of the _grid_quant entries: finite, normal, > 0 and exactly a T (float at elem 4); a step's inverse as T is
+// finite and not 0 as well
+static bool field_param_ok(uint32_t elem, double v, bool step)
+{
+    if (!std::isnormal(v) || v <= 0) return false;
+    if (elem == 4 && (!std::isnormal((float)v) || (double)(float)v != v)) return false;
+    if (!step) return true;
+    const double inv = field_inverse(elem, v);
+    return std::isfinite(inv) && inv != 0;
+}
+
 static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
                          const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
                          const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr,
-                         uint32_t nlags = 1)
+                         uint32_t nlags = 1, const FieldQuant *fq = nullptr)
 {
     const bool xr = tr == TR_XOR;
     if (!b || !d_el || !d_planes || !d_n || (xr && !d_base)) return SHAFA_OUTSIDE_MODULE;
     if (tr == TR_GRID && (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS)) return SHAFA_OUTSIDE_MODULE;
     if (tr == TR_RECORDS ? unit < 1 || unit > SHAFA_RECORDS_MAX_WIDTH : unit != 1 && unit != 2 && unit != 4 && unit != 8)
         return SHAFA_OUTSIDE_MODULE;
+    if (fq && unit != 4 && unit != 8) return SHAFA_OUTSIDE_MODULE;             // floats and doubles
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_cap) return SHAFA_OUTSIDE_MODULE;
@@ -638,13 +651,22 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
                 if (g[k] ? g[k] <= g[k - 1] : k + 1 < nlags && g[k + 1]) return SHAFA_OUTSIDE_MODULE;
         }
     }
+    if (fq) {                                        // the _grid_quant entries' own, where the lags are checked
+        if (!fq->h_step || (!merge && !fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
+        for (int i = 0; i < nblocks; ++i)
+            if (!field_param_ok(unit, fq->h_step[i], true) || (!merge && !field_param_ok(unit, fq->h_bound[i], false)))
+                return SHAFA_OUTSIDE_MODULE;
+        if ((!merge && !fq->d_outl_n) || !fq->h_outl_off || !fq->h_outl_count) return SHAFA_OUTSIDE_MODULE;
+        for (int i = 0; !fq->d_outl && i < nblocks; ++i)
+            if (fq->h_outl_count[i]) return SHAFA_OUTSIDE_MODULE;
+    }
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
     if (tr == TR_LAG)
         return planes_lag_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
                                      (u8 *)d_planes, h_plane_off, h_lag);
     if (tr == TR_GRID)
         return planes_grid_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n,
-                                      (u8 *)d_planes, h_plane_off, nlags, h_lag);
+                                      (u8 *)d_planes, h_plane_off, nlags, h_lag, fq);
     if (tr == TR_RECORDS)
         return records_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, unit, merge, (u8 *)d_el, h_off, h_cap, d_n, (u8 *)d_planes,
                                   h_plane_off);
@@ -729,6 +751,29 @@ int shafa_hipd_merge_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblo
 {
     return transpose_dev(true, TR_GRID, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
                          h_plane_off, h_lags, nlags);
+}
+
+// the error-bounded fields: the _grid entries with a quantiser in the split and a restorer behind the merge
+int shafa_hipd_split_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
+                                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                           const uint64_t *h_plane_off, uint64_t *d_outl, const uint64_t *h_outl_off,
+                                           const uint64_t *h_outl_cap, uint64_t *d_outl_n)
+{
+    const FieldQuant fq = {h_step, h_bound, d_outl, h_outl_off, h_outl_cap, d_outl_n};
+    return transpose_dev(false, TR_GRID, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags, &fq);
+}
+
+int shafa_hipd_merge_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const double *h_step, const uint8_t *d_planes,
+                                           const uint64_t *h_plane_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                           const uint64_t *d_outl, const uint64_t *h_outl_off, const uint64_t *h_outl_n,
+                                           uint8_t *d_out, const uint64_t *h_out_off)
+{
+    const FieldQuant fq = {h_step, nullptr, (u64 *)d_outl, h_outl_off, h_outl_n, nullptr};
+    return transpose_dev(true, TR_GRID, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags, &fq);
 }
 
 // beside transpose_dev: its TR_GRID checks in its order without a plane side, and with a row of zeros allowed (plain planes)

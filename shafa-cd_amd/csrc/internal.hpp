@@ -285,8 +285,21 @@ int planes_lag_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool
 // >= 1, the others 0 or increasing: checked by the caller) (planes_lag.hip): split is one launch; merge is a first pass from the
 // planes at the block's smallest lag — the merge of differences where that is 1 (planes_diff_merge_enqueue, planes.hip, on the
 // caller's set-up, leaving the blocks with d_skip[b] != 0 alone), else the lag merge — and one pass in place per further lag
+// fq (the _grid_quant entries, elem 4 or 8; checked by the caller): the elements are floats or doubles and the planes
+// those of their codes.  split: the quantising split in the grid split's place, d_outl_n zeroed in front of it; merge: the chain
+// as it is, then the restore in place and, where the call has a record, the patch
+struct FieldQuant {
+    const double *h_step, *h_bound;    // per block; the bound is the split's alone
+    u64 *d_outl;                       // records of {position, bits}
+    const u64 *h_outl_off;             // block b's first record
+    const u64 *h_outl_count;           // split: its capacity in records; merge: its records
+    u64 *d_outl_n;                     // split: the outliers found per block
+};
 int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
-                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags);
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags,
+                           const FieldQuant *fq = nullptr);
+// T(1 / step) as a double: the double division, rounded once to float at elem 4
+double field_inverse(u32 elem, double step);
 void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 *d_el, int nblocks, const u64 *d_n,
                                const u8 *d_planes, int *err, const u64 *d_skip);
 // the histograms of the planes the grid split would write for these blocks, which may overlap, without the planes: d_freq[(b *

@@ -32,6 +32,12 @@
 // non-empty subset of the block's lags, subtracted or added (planes_grid_split).  merge: a first pass from the planes at the
 // block's smallest lag — planes.hip's merge of differences where that is 1, else the three launches above — then per further lag
 // the three launches above with the ELEMENTS as their source, in place (LagSrc).
+//
+// The GRID QUANT entries (shafa_hipd_split_planes_grid_quant_dev, shafa_hipd_merge_planes_grid_quant_dev) are the grid
+// entries for float and double elements under an error bound.  split: the grid split with every loaded unit, the lane's own and
+// every base, quantised to integer codes in registers first, and the elements whose restored value misses the bound recorded
+// (planes_grid_quant_split).  merge: the grid merge's chain, then the codes -> values in place (planes_field_restore) and the
+// recorded elements' own bits on top (planes_field_patch).
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -241,6 +247,185 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_split(const u8 *__rest
         case 1: split_tile_grid<E, 1>(wk, r, lg, d_planes, poff); break;
         case 2: split_tile_grid<E, 2>(wk, r, lg, d_planes, poff); break;
         default: split_tile_grid<E, 3>(wk, r, lg, d_planes, poff); break;
+        }
+    }
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// ---- error-bounded fields (shafa_hipd_split_planes_grid_quant_dev, shafa_hipd_merge_planes_grid_quant_dev): the grid
+// split over the CODES of float or double elements, code = rint(x (x) inv) as a signed integer of the element's width, taken
+// unit by unit in registers as the units are loaded, the lane's own and every tap's alike: a code is a function of the element's
+// own bits, so a tap's unit quantises to what the lane that owns it stores, and the bit pattern 0 in front of the block to the
+// code 0.  Every operation is ONE IEEE operation in T, none contracted, the decoder's T(code) (x) step among them: the encoder
+// judges the very value the decoder will make.
+template <int E> struct FieldT { using F = float; using I = int; using U = u32; };
+template <> struct FieldT<8> { using F = double; using I = long long; using U = u64; };
+
+// a block's step, 1 / step and bound as T (uniform)
+template <int E> struct FieldQ {
+    typename FieldT<E>::F step, inv, bound;
+};
+
+template <int E>
+__device__ __forceinline__ typename FieldT<E>::F field_bits(u64 v)
+{
+    using U = typename FieldT<E>::U;
+    return __builtin_bit_cast(typename FieldT<E>::F, (U)v);
+}
+
+// element i of the unit in w
+template <int E>
+__device__ __forceinline__ typename FieldT<E>::U unit_elem(const u32 (&w)[4 * E], int i)
+{
+    if (E == 8) return (typename FieldT<E>::U)((u64)w[2 * i + 1] << 32 | w[2 * i]);
+    return (typename FieldT<E>::U)w[i];
+}
+
+__device__ __forceinline__ float field_abs(float t) { return __builtin_fabsf(t); }
+__device__ __forceinline__ double field_abs(double t) { return __builtin_fabs(t); }
+__device__ __forceinline__ float field_rint(float t) { return __builtin_rintf(t); }
+__device__ __forceinline__ double field_rint(double t) { return __builtin_rint(t); }
+
+// the code of the element with the bits xb; `in`: the scaled value lies inside the code range (false for a NaN)
+template <int E>
+__device__ __forceinline__ typename FieldT<E>::I field_code(typename FieldT<E>::U xb, typename FieldT<E>::F inv, bool &in)
+{
+#pragma clang fp contract(off)
+    using F = typename FieldT<E>::F;
+    using I = typename FieldT<E>::I;
+    const F t = __builtin_bit_cast(F, xb) * inv;
+    in = field_abs(t) < (F)(E == 8 ? 0x1p62 : 0x1p30);
+    return (I)(in ? field_rint(t) : (F)0);
+}
+
+// the value the decoder makes of a code
+template <int E>
+__device__ __forceinline__ typename FieldT<E>::F field_value(typename FieldT<E>::I code, typename FieldT<E>::F step)
+{
+#pragma clang fp contract(off)
+    return (typename FieldT<E>::F)code * step;
+}
+
+// is x' = T(code) (x) step within the bound of x?  At 4 bytes the subtraction is in double, which holds it exactly; at 8 it is
+// the rounded one
+template <int E>
+__device__ __forceinline__ bool field_good(typename FieldT<E>::U xb, typename FieldT<E>::I code, const FieldQ<E> &q)
+{
+#pragma clang fp contract(off)
+    using F = typename FieldT<E>::F;
+    const F x = __builtin_bit_cast(F, xb), xr = field_value<E>(code, q.step);
+    if (E == 8) return __builtin_fabs((double)(x - xr)) <= (double)q.bound;
+    return __builtin_fabs((double)x - (double)xr) <= (double)q.bound;
+}
+
+// the 16 elements of w -> their codes as unsigned integers, in place
+template <int E>
+__device__ __forceinline__ void quant_words(u32 (&w)[4 * E], const FieldQ<E> &q)
+{
+#pragma unroll
+    for (int i = 0; i < PL_UNIT; ++i) {
+        bool in;
+        const typename FieldT<E>::U c = (typename FieldT<E>::U)field_code<E>(unit_elem<E>(w, i), q.inv, in);
+        if (E == 8) { w[2 * i] = (u32)c; w[2 * i + 1] = (u32)((u64)c >> 32); }
+        else w[i] = (u32)c;
+    }
+}
+
+// where a block's outliers go: records of {position, bits}, `cap` of them at the most, *count the outliers found
+struct FieldOutl {
+    u64 *rec, cap;
+    unsigned long long *count;
+};
+
+// quant_words for the lane's OWN unit from element e0: the first c = min(16, n - e0) elements are judged as well, and one that
+// is not good is recorded in a slot of the block's, taken with an atomic of the lane's own (outliers are rare) and written only
+// where it lies inside the block's capacity
+template <int E>
+__device__ __forceinline__ void quant_words_judged(u32 (&w)[4 * E], const FieldQ<E> &q, u64 e0, u32 c, const FieldOutl &o)
+{
+#pragma unroll
+    for (int i = 0; i < PL_UNIT; ++i) {
+        using U = typename FieldT<E>::U;
+        bool in;
+        const U xb = unit_elem<E>(w, i);
+        const typename FieldT<E>::I code = field_code<E>(xb, q.inv, in);
+        if ((u32)i < c && !(in && field_good<E>(xb, code, q))) {
+            const u64 slot = atomicAdd(o.count, 1ull);
+            if (slot < o.cap) {
+                gstore<u64>(o.rec + 2 * slot, e0 + (u64)i);
+                gstore<u64>(o.rec + 2 * slot + 1, (u64)xb);
+            }
+        }
+        if (E == 8) { w[2 * i] = (u32)(U)code; w[2 * i + 1] = (u32)((u64)(U)code >> 32); }
+        else w[i] = (u32)(U)code;
+    }
+}
+
+// split_tile_grid with every loaded unit quantised before it is subtracted or added
+template <int E, int Q>
+__device__ __forceinline__ void split_tile_grid_quant(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
+                                                      const FieldQ<E> &q, const FieldOutl &o, u8 *d_planes, const u64 *poff)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+        quant_words_judged<E>(w, q, e0, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), o);
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                quant_words<E>(wb, q);               // the zeros in front of the block stay zeros
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        zz_fold<E, 4 * E>(w);
+        split_store<E>(w, wk.n, e0, d_planes, poff);
+    }
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them five rows of nblk: the bits of step, 1 / step and bound as T,
+// the block's first record in d_outl and its capacity in records.  d_outl_n has been zeroed on the stream.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                      const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                      int nblk, const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                                      const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                                      int *__restrict__ err, u32 n_tiles, u32 per_wg,
+                                                                      u64 *__restrict__ d_outl, u64 *__restrict__ d_outl_n)
+{
+    const u64 *qp = d_lag + (u64)SHAFA_PLANES_GRID_LAGS * nblk;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const FieldQ<E> q = {field_bits<E>(qp[wk.b]), field_bits<E>(qp[(u64)nblk + wk.b]), field_bits<E>(qp[2ull * nblk + wk.b])};
+        const FieldOutl o = {d_outl + 2 * qp[3ull * nblk + wk.b], qp[4ull * nblk + wk.b], (unsigned long long *)d_outl_n + wk.b};
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile_grid_quant<E, 0>(wk, r, lg, q, o, d_planes, poff); break;
+        case 1: split_tile_grid_quant<E, 1>(wk, r, lg, q, o, d_planes, poff); break;
+        case 2: split_tile_grid_quant<E, 2>(wk, r, lg, q, o, d_planes, poff); break;
+        default: split_tile_grid_quant<E, 3>(wk, r, lg, q, o, d_planes, poff); break;
         }
     }
     tp_size_errors(cap, d_n, nblk, err);
@@ -730,6 +915,77 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ 
     tp_size_errors(cap, d_n, nblk, err);
 }
 
+// ---- behind the grid merge of an error-bounded field: the codes, in place, -> T(code) (x) step, then the outliers'
+// own bits on top.
+// the restore: a tile's elements lie in whole 16-byte words of the address space but for the word the tile starts in and the one
+// it ends in (the element side is at multiples of E, so an element never straddles two words): a lane takes every 256th word, one
+// 16-byte load and store, and the elements of a cut word one by one.  d_step: the bits of the blocks' steps as T.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_field_restore(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                   const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                                   const u64 *__restrict__ d_n, const u64 *__restrict__ d_step,
+                                                                   u32 n_tiles, u32 per_wg)
+{
+    using U = typename FieldT<E>::U;
+    using I = typename FieldT<E>::I;
+    constexpr u32 PER = 16 / E;                      // elements of a word
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const typename FieldT<E>::F step = field_bits<E>(d_step[wk.b]);
+        const u64 end = wk.pos0 + TP_TILE < wk.n ? wk.pos0 + TP_TILE : wk.n;
+        const u64 lo = (u64)(uintptr_t)wk.in + wk.pos0 * E, hi = (u64)(uintptr_t)wk.in + end * E;      // the tile's bytes
+        for (u64 a = (lo & ~(u64)15) + 16ull * threadIdx.x; a < hi; a += 16ull * TP_THREADS) {
+            u8 *p = (u8 *)(uintptr_t)a;
+            if (a >= lo && a + 16 <= hi) {
+                const uint4 v = gload<uint4>(p);
+                u32 x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (u32 i = 0; i < PER; ++i) {
+                    const I code = E == 8 ? (I)((u64)x[(2 * i + 1) & 3] << 32 | x[(2 * i) & 3]) : (I)x[i];
+                    const u64 y = (u64)__builtin_bit_cast(U, field_value<E>(code, step));
+                    if (E == 8) { x[(2 * i) & 3] = (u32)y; x[(2 * i + 1) & 3] = (u32)(y >> 32); }
+                    else x[i] = (u32)y;
+                }
+                gstore<uint4>(p, make_uint4(x[0], x[1], x[2], x[3]));
+            } else {
+#pragma unroll
+                for (u32 i = 0; i < PER; ++i) {
+                    const u64 at = a + (u64)i * E;
+                    if (at >= lo && at < hi)
+                        gstore<U>(p + i * E, __builtin_bit_cast(U, field_value<E>((I)gload<U>(p + i * E), step)));
+                }
+            }
+        }
+    }
+}
+
+// the patch: one thread a record.  first[b]: the number of block b's first record among the call's (first[nblk]: their count);
+// rec_off[b]: its first record in d_outl.  A position at or past the block's size (a block past its capacity has none) is the
+// block's SHAFA_OUTSIDE_MODULE and nothing is written for it.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_field_patch(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                 const u64 *__restrict__ cap, int nblk, const u64 *__restrict__ d_n,
+                                                                 const u64 *__restrict__ rec_off, const u64 *__restrict__ first,
+                                                                 const u64 *__restrict__ d_outl, int *__restrict__ err)
+{
+    const u64 total = first[nblk];
+    for (u64 i = (u64)blockIdx.x * TP_THREADS + threadIdx.x; i < total; i += (u64)gridDim.x * TP_THREADS) {
+        int lo = 0, hi = nblk;                       // first[lo] <= i, the record's block in [lo, hi)
+        while (hi - lo > 1) {
+            const int mid = lo + (hi - lo) / 2;
+            if (first[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        const u64 *rec = d_outl + 2 * (rec_off[lo] + (i - first[lo]));
+        const u64 pos = gload<u64>(rec), n = d_n[lo] > cap[lo] ? 0 : d_n[lo];
+        if (pos >= n) {
+            set_error(err + lo, SHAFA_OUTSIDE_MODULE);
+            continue;
+        }
+        gstore<typename FieldT<E>::U>(d_el + off[lo] + pos * E, (typename FieldT<E>::U)gload<u64>(rec + 1));
+    }
+}
+
 // the launches read tile_setup's workspace: extra 0 the plane offsets, extra 1 the clamped lags, the scratch the column sums
 template <int E>
 void planes_lag_launch(bool merge, bool sums, const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes,
@@ -791,19 +1047,73 @@ void planes_grid_launch(bool merge, const GridPlan &gp, const TileSetup &a, hipS
             planes_lag_pass<E, LAG_ELEMS>(gp.pass_sums[k], a, st, d_el, nblk, d_n, nullptr, poff, lag + (size_t)k * nblk, err);
 }
 
+// the error-bounded entries' launches on planes_grid_launch_dev's set-up: extra 1 holds, behind the rows of lags, the rows that
+// function lays out for them
+template <int E>
+void field_split_launch(const TileSetup &a, hipStream_t st, const u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err,
+                        u64 *d_outl, u64 *d_outl_n)
+{
+    hipLaunchKernelGGL(planes_grid_quant_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       d_planes, (const u64 *)a.extra[0], (const u64 *)a.extra[1], err, a.nt, a.per_wg, d_outl, d_outl_n);
+}
+
+template <int E>
+void field_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u64 records, const u64 *d_outl,
+                        int *err)
+{
+    const u64 *q = (const u64 *)a.extra[1] + (size_t)nblk * SHAFA_PLANES_GRID_LAGS;     // steps, record places, running counts
+    hipLaunchKernelGGL(planes_field_restore<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n, q, a.nt,
+                       a.per_wg);
+    if (!records) return;
+    const u64 wgs = (records + TP_THREADS - 1) / TP_THREADS;
+    hipLaunchKernelGGL(planes_field_patch<E>, dim3((u32)(wgs < TP_MAX_WGS ? wgs : TP_MAX_WGS)), dim3(TP_THREADS), 0, st, d_el, a.off,
+                       a.cap, nblk, d_n, q + nblk, q + 2 * (size_t)nblk, d_outl, err);
+}
+
+// a double that is exactly a T -> T's bits; T(1 / step), the double division rounded to T once
+u64 field_bits_of(u32 elem, double v)
+{
+    if (elem == 8) return __builtin_bit_cast(u64, v);
+    return __builtin_bit_cast(u32, (float)v);
+}
+
 }  // namespace
+
+double field_inverse(u32 elem, double step) { return elem == 8 ? 1.0 / step : (double)(float)(1.0 / step); }
 
 // the _grid entries.  h_lags: nlags slots a block, checked by the caller (the first >= 1, the others 0 or
 // increasing).  The device gets SHAFA_PLANES_GRID_LAGS rows of nblocks lags, a slot at or past the block's capacity (it subtracts
 // nothing) and an unused one as 0.  split: one launch.  merge: row 0 is the lag family's first pass, planes -> elements at the
 // block's smallest lag, clamped as the _lag entries clamp it, and 0 where that lag is 1: those blocks are the _diff merge's, which
 // skips the others; rows 1 and 2 are the passes in place over the elements.  All passes share one scratch, the stream their order.
+// fq (the _grid_quant entries): the same upload carries, behind the rows of lags, the quantiser's rows — split: the bits of step,
+// 1 / step and bound as T, the first record and the capacity of every block; merge: the steps' bits, the first records and the
+// nblocks + 1 running counts of the records.
 int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
-                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags)
+                           const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags,
+                           const FieldQuant *fq)
 {
     const size_t nb = (size_t)nblocks;
-    std::vector<u64> lag(nb * SHAFA_PLANES_GRID_LAGS, 0);
+    std::vector<u64> lag(nb * SHAFA_PLANES_GRID_LAGS + (fq ? nb * 5 + 1 : 0), 0);
     GridPlan gp = {};
+    u64 records = 0;
+    if (fq) {                                        // the rows behind the lags: planes_grid_quant_split's, or the merge's
+        u64 *q = lag.data() + nb * SHAFA_PLANES_GRID_LAGS;
+        for (size_t b = 0; b < nb; ++b) {
+            q[b] = field_bits_of(elem, fq->h_step[b]);
+            if (!merge) {
+                q[nb + b] = field_bits_of(elem, field_inverse(elem, fq->h_step[b]));
+                q[2 * nb + b] = field_bits_of(elem, fq->h_bound[b]);
+                q[3 * nb + b] = fq->h_outl_off[b];
+                q[4 * nb + b] = fq->h_outl_count[b];
+            } else {                                 // the records' places, then the nb + 1 running counts of them
+                q[nb + b] = fq->h_outl_off[b];
+                q[2 * nb + b] = records;
+                records += fq->h_outl_count[b];
+            }
+        }
+        if (merge) q[3 * nb] = records;
+    }
     for (size_t b = 0; b < nb; ++b) {
         const u64 cap = h_cap[b];
         for (u32 k = 0; k < nlags; ++k) {
@@ -833,11 +1143,22 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, sums ? (size_t)LAG_SUMS_TILE * elem : gp.diff ? 8 : 0, 0, &a))
         return rc;
     if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
+    if (fq && !merge) {
+        HIP_TRY(hipMemsetAsync(fq->d_outl_n, 0, nb * sizeof(u64), st));
+        if (elem == 4) field_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+        else field_split_launch<8>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+        HIP_TRY(hipGetLastError());
+        return SHAFA_SUCCESS;
+    }
     switch (elem) {
     case 1: planes_grid_launch<1>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     case 2: planes_grid_launch<2>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     case 4: planes_grid_launch<4>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     default: planes_grid_launch<8>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
+    }
+    if (fq) {                                        // the codes -> the values, then the outliers on top
+        if (elem == 4) field_merge_launch<4>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
+        else field_merge_launch<8>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;

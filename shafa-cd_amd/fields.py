@@ -1,0 +1,380 @@
+"""Error-bounded float fields — the quantiser in front of the Lorenzo differences and the restorer behind them: quantize_field /
+restore_field and compress_fields / decompress_fields on top of Batch.split_planes_grid_quant_dev / merge_planes_grid_quant_dev
+(csrc/planes_lag.hip; include/shafa_hip.h: "Error-bounded fields").
+
+compress_grids takes a field bit for bit, and the Lorenzo differences of raw float bit patterns leave every mantissa byte raw.
+Under an absolute error bound chosen by the caller each value becomes the integer rint(x / step) first, as in the scientific-
+data codecs the predictor was taken from, and those integers are differenced exactly: that is where their factors come from.
+The quantiser runs inside the grid split, so no temporary of codes exists, and the bound is CHECKED per element on the device
+against the very value the decoder will make: an element that misses it — a NaN, an infinity, a value past the code range, a
+tie the rounding threw over — is an outlier, kept with its own bits and given back bit for bit.
+
+The drivers live in this submodule; the package re-exports them.  The coder's half of the chain (_coded_planes) and the decode
+chain (_merge_items) are the package's, reached through it at the time of the call."""
+import fractions
+import math
+import sys
+
+import numpy as np
+
+_pkg = sys.modules[__package__]
+
+FIELD_SLACK = 2.0 ** -7         # step = 2 abs_error (1 - FIELD_SLACK): keeps the ties of the restored value inside the bound
+
+
+class CompressedField:
+    """A float32 or float64 tensor compressed under an absolute error bound (compress_fields), in memory: `dtype` and `shape` of
+    the original, `lags` as CompressedGrid's, `abs_error` as the caller gave it, `step` and `bound` — the quantiser's step and
+    the bound every restored element was checked against, both exactly representable in the dtype — `planes` as CompressedGrid's,
+    of the zigzag-folded differences of the codes, `outlier_pos` (int64, sorted) and `outlier_bits` (int64, the element's bits in
+    the low bits) — the elements given back bit for bit — and `nbytes`, the planes' bytes plus (8 + element size) per outlier.
+    A `step` of 0.0 marks a tensor kept LOSSLESS: its planes are compress_grids', it has no outliers.  decompress_fields alone
+    gives the tensor back."""
+    __slots__ = ("dtype", "shape", "lags", "abs_error", "step", "bound", "planes", "outlier_pos", "outlier_bits", "nbytes")
+
+    def __init__(self, dtype, shape, lags, abs_error, step, bound, planes, outlier_pos, outlier_bits, nbytes):
+        self.dtype, self.shape, self.lags, self.abs_error = dtype, tuple(shape), lags, float(abs_error)
+        self.step, self.bound, self.planes = float(step), float(bound), list(planes)
+        self.outlier_pos, self.outlier_bits, self.nbytes = outlier_pos, outlier_bits, int(nbytes)
+
+    def __repr__(self):
+        kinds = ["raw" if not isinstance(p, dict) else "+".join(sorted(p)) for p in self.planes]
+        return (f"CompressedField({self.dtype}, {self.shape}, lags={self.lags}, abs_error={self.abs_error}, step={self.step}, "
+                f"planes={kinds}, outliers={int(self.outlier_pos.numel())}, nbytes={self.nbytes})")
+
+
+# ---- the step and the bound of an abs_error
+def _down(v, k):
+    """the largest float of k bytes that is <= the positive Fraction v, as a Python float"""
+    f = float(v)                                     # the nearest double
+    if fractions.Fraction(f) > v:
+        f = math.nextafter(f, 0.0)
+    if k == 4:
+        with np.errstate(over="ignore"):
+            g = np.float32(f)
+        if float(g) > f:
+            g = np.nextafter(g, np.float32(0))
+        f = float(g)
+    return f
+
+
+def _legal(v, k):
+    """a step or a bound the entries take: finite, normal in the element type and > 0"""
+    tiny = float(np.finfo(np.float32 if k == 4 else np.float64).tiny)
+    return math.isfinite(v) and v >= tiny
+
+
+def _inverse(step, k):
+    """T(1 / step): the double division, rounded once to float32 at 4 bytes"""
+    with np.errstate(over="ignore"):
+        return float(np.float32(1.0 / step)) if k == 4 else 1.0 / step
+
+
+def _params(what, abs_error, k):
+    """(step, bound) for an abs_error and an element size: step = 2 abs_error (1 - FIELD_SLACK) and bound = abs_error, each
+    rounded DOWN into the element type; a ValueError where the entries would refuse them"""
+    if isinstance(abs_error, bool) or not isinstance(abs_error, (int, float)) or not math.isfinite(abs_error) or not abs_error > 0:
+        raise ValueError(f"{what}: abs_error is a finite float > 0, not {abs_error!r}")
+    e = fractions.Fraction(abs_error)
+    step, bound = _down(2 * e * (1 - fractions.Fraction(FIELD_SLACK)), k), _down(e, k)
+    if not _legal(step, k) or not _legal(bound, k):
+        raise ValueError(f"{what}: an abs_error of {abs_error!r} is below what elements of {k} bytes resolve")
+    inv = _inverse(step, k)
+    if not math.isfinite(inv) or inv == 0:
+        raise ValueError(f"{what}: an abs_error of {abs_error!r} has no inverse step in elements of {k} bytes")
+    return step, bound
+
+
+def _field_tensors(what, tensors):
+    import torch
+    ts = _pkg._plane_tensors(what, tensors)
+    for t in ts:
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: float32 and float64 tensors, not {t.dtype}")
+    return ts
+
+
+def _abs_errors(what, ts, abs_error):
+    """one (step, bound) per checked tensor from `abs_error`, a float for all tensors or a list with one per tensor"""
+    if isinstance(abs_error, (list, tuple)):
+        if len(abs_error) != len(ts):
+            raise ValueError(f"{what}: abs_error is a float or a list with one float per tensor")
+        errs = list(abs_error)
+    else:
+        errs = [abs_error] * len(ts)
+    return errs, [_params(what, e, t.element_size()) for e, t in zip(errs, ts)]
+
+
+def outlier_capacity(numel):
+    """the records compress_fields gives a tensor: one that finds more is kept lossless"""
+    return 16 + numel // 64
+
+
+# ---- the launches
+def _layout(units):
+    """_split_into's planes buffer: each tensor's plane offsets, multiples of 16, and the buffer's bytes"""
+    poff, pos = [], 0
+    for n, w in units:
+        step = _pkg._al16(n)
+        poff.append([pos + j * step for j in range(w)])
+        pos += w * step
+    return poff, pos + 16
+
+
+def _split_fields(bt, st, dev, ts, units, lags, params, caps, buf, poff):
+    """one quantising split per element size over ts into buf -> (the records buffer [sum caps, 2], each tensor's first record,
+    the counts of outliers found, one per tensor of the launches in their order, and that order)"""
+    import torch
+    first, pos = [], 0
+    for c in caps:
+        first.append(pos)
+        pos += c
+    d_outl = torch.empty((pos, 2), dtype=torch.int64, device=dev)
+    groups = _pkg._by_width(units)
+    order = [i for _, idx in groups for i in idx]
+    d_n = torch.tensor([units[i][0] for i in order], dtype=torch.int64, device=dev)
+    d_found = torch.zeros(len(order), dtype=torch.int64, device=dev)
+    at = 0
+    for w, idx in groups:
+        base = min(ts[i].data_ptr() for i in idx)
+        bt.split_planes_grid_quant_dev(st, w, [tuple(lags[i]) for i in idx], [params[i][0] for i in idx],
+                                       [params[i][1] for i in idx], base, [ts[i].data_ptr() - base for i in idx],
+                                       [units[i][0] for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]],
+                                       d_outl if pos else None, [first[i] for i in idx], [caps[i] for i in idx],
+                                       d_found[at:at + len(idx)])
+        at += len(idx)
+    return d_outl, first, d_found, order
+
+
+def _sorted_records(rec):
+    """the records [count, 2] -> (positions, bits), sorted by position"""
+    import torch
+    pos, by = torch.sort(rec[:, 0])
+    return pos, rec[:, 1][by].clone()
+
+
+def _merge_fields(items, steps):
+    """_merge_into's stand-in for decompress_fields: the lossless items (a step of 0) through _merge_into as decompress_grids'
+    go, the others through one merge_planes_grid_quant_dev per element size"""
+    def merge_into(bt, st, dev, planes, outs, units, kind, lags):
+        import torch
+        plain = [i for i in range(len(items)) if not steps[i]]
+        if plain:
+            _pkg._merge_into(bt, st, dev, [planes[i] for i in plain], [outs[i] for i in plain], [units[i] for i in plain], kind,
+                             [lags[i] for i in plain])
+        quant = [(n, w) if steps[i] else (0, w) for i, (n, w) in enumerate(units)]
+        groups = _pkg._by_width(quant)
+        if not groups:
+            return
+        planes = [[p if p.data_ptr() % 16 == 0 else p.clone() for p in ps] for ps in planes]
+        order = [i for _, idx in groups for i in idx]
+        d_n = torch.tensor([units[i][0] for i in order], dtype=torch.int64, device=dev)
+        counts = [int(it.outlier_pos.numel()) for it in items]
+        first, pos = {}, 0
+        for i in order:
+            first[i] = pos
+            pos += counts[i]
+        d_outl = torch.stack([torch.cat([items[i].outlier_pos for i in order if counts[i]]),
+                              torch.cat([items[i].outlier_bits for i in order if counts[i]])], 1).contiguous() if pos else None
+        at = 0
+        for w, idx in groups:
+            pbase = min(p.data_ptr() for i in idx for p in planes[i])
+            obase = min(outs[i].data_ptr() for i in idx)
+            bt.merge_planes_grid_quant_dev(st, w, [tuple(lags[i]) for i in idx], [steps[i] for i in idx], pbase,
+                                           [p.data_ptr() - pbase for i in idx for p in planes[i]], [units[i][0] for i in idx],
+                                           d_n[at:at + len(idx)], d_outl, [first[i] for i in idx], [counts[i] for i in idx], obase,
+                                           [outs[i].data_ptr() - obase for i in idx])
+            at += len(idx)
+    return merge_into
+
+
+# ---- one tensor, no coder
+def quantize_field(t, abs_error, lags):
+    """The byte planes of the Lorenzo differences of a float32 or float64 CUDA tensor's CODES under the absolute error bound
+    `abs_error`, and its outliers: (planes, positions, bits).  `planes` is split_grid's [k, numel] uint8 tensor over the codes
+    rint(x * T(1 / step)) as integers of the element's width, step = 2 abs_error (1 - FIELD_SLACK) rounded down into the dtype;
+    `positions` (int64, sorted) and `bits` (int64) are the elements whose restored value code * step misses abs_error (rounded
+    down into the dtype) or that have no code: restore_field gives those back bit for bit and every other within the bound.
+    `lags` as split_grid takes them.  One split_planes_grid_quant_dev launch, a second one with room for every outlier found
+    where outlier_capacity's records were too few; one synchronisation each."""
+    import torch
+    what = "quantize_field"
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a contiguous CUDA tensor")
+    t = _field_tensors(what, t)[0]
+    lags = _pkg.grids._lag_tuple(what, lags)
+    k, n = t.element_size(), t.numel()
+    params = [_params(what, abs_error, k)]
+    dev = t.device
+    st = _pkg._plane_stream(dev, stream=None)
+    poff, nbytes = _layout([(n, k)])
+    with torch.cuda.stream(st):
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        bt = _pkg.Batch(1, 1 << 20)
+        try:
+            cap, found, d_outl = outlier_capacity(n), 0, None
+            while n:
+                d_outl, _, d_found, _ = _split_fields(bt, st, dev, [t], [(n, k)], [lags], params, [cap], buf, poff)
+                bt.finish(st, 1)
+                found = int(d_found.cpu()[0])
+                if found <= cap:
+                    break
+                cap = found
+        finally:
+            bt.close()
+        pos, bits = _sorted_records(d_outl[:found]) if found else (torch.empty(0, dtype=torch.int64, device=dev),) * 2
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return buf[:k * _pkg._al16(n)].view(k, _pkg._al16(n))[:, :n], pos, bits
+
+
+def _records(what, positions, bits, dev):
+    import torch
+    for r in (positions, bits):
+        if not isinstance(r, torch.Tensor) or r.dtype != torch.int64 or r.dim() != 1 or not r.is_contiguous():
+            raise ValueError(f"{what}: the outliers' positions and bits are contiguous 1-D int64 tensors")
+    if positions.numel() != bits.numel():
+        raise ValueError(f"{what}: one position and one bit pattern per outlier")
+    for r in (positions, bits):
+        if r.numel() and (not r.is_cuda or (dev is not None and r.device != dev)):
+            raise ValueError(f"{what}: the outliers are CUDA tensors on the planes' device")
+
+
+def _step(what, step, k):
+    if isinstance(step, bool) or not isinstance(step, (int, float)) or not _legal(float(step), k) \
+            or (k == 4 and float(np.float32(step)) != step) or not math.isfinite(_inverse(float(step), k)):
+        raise ValueError(f"{what}: step is a quantiser's step, a normal float of the dtype > 0, not {step!r}")
+    return float(step)
+
+
+def restore_field(planes, dtype, shape, lags, step, positions, bits, stream=None):
+    """quantize_field's inverse for one tensor: `planes` as merge_grid takes them -> a tensor of `dtype` (float32 or float64) and
+    `shape`, every element T(code) * step but the outliers, whose `bits` are stored at their `positions`.  One
+    merge_planes_grid_quant_dev call, one synchronisation."""
+    import torch
+    what = "restore_field"
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"{what}: float32 and float64 tensors, not {dtype!r}")
+    k, shape, n = _pkg._plane_dtype(what, dtype, shape)
+    lags = _pkg.grids._lag_tuple(what, lags)
+    step = _step(what, step, k)
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
+            or (planes.shape[1] > 1 and planes.stride(1) != 1):
+        raise ValueError(f"{what}: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
+    if tuple(planes.shape) != (k, n):
+        raise ValueError(f"{what}: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
+    _records(what, positions, bits, planes.device)
+    dev = planes.device
+    item = CompressedField(dtype, shape, lags, step, step, step, [], positions, bits, 0)
+    st = _pkg._plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        bt = _pkg.Batch(1, 1 << 20)
+        try:
+            _merge_fields([item], [step])(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out], [(n, k)], "planes_grid",
+                                          [lags])
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return out
+
+
+# ---- the drivers
+def compress_fields(tensors, abs_error, axes=None, lags=None, block_size=8 << 20, stream=None):
+    """compress_grids for float32 and float64 fields UNDER AN ABSOLUTE ERROR BOUND: every element comes back within `abs_error`
+    of the original, or bit for bit.  `tensors`, `axes`, `lags` and `block_size` as compress_grids takes them, and its argument
+    ValueErrors; any dtype but float32 and float64 is a ValueError.  `abs_error` is a float for all tensors or a list with one
+    per tensor, finite and > 0 and not below what the dtype resolves: a ValueError otherwise, before any device work.  Returns
+    one CompressedField per tensor, which decompress_fields gives back.
+
+    The transform: code = rint(x * T(1 / step)) as an integer of the element's width, step = 2 abs_error (1 - FIELD_SLACK)
+    rounded down into the dtype, and the planes are compress_grids' over the codes.  The decoder makes x' = T(code) * step; the
+    split makes the same x' and checks |x - x'| <= bound (abs_error rounded down into the dtype) for every element.  One that
+    fails — a NaN, an infinity, a value past the code range of 2^30 (2^62) steps, a tie the rounding of x' threw over the bound
+    — is an OUTLIER, kept as {position, bits} and given back bit for bit.  -0.0 may come back as +0.0.  The slack keeps ties
+    inside the bound while |x| stays below about 2^16 abs_error at float32.
+
+    A tensor that finds more outliers than outlier_capacity(numel) = 16 + numel // 64 is kept LOSSLESS, compress_grids' planes
+    and a `step` of 0.0: the bound sits at the data's own precision there, or the tensor is noise.
+
+    Chain: one split_planes_grid_quant_dev per element size over all tensors — no temporary of codes exists — one finish and
+    one read-back of the outlier counts (the tensors kept lossless then take one split_planes_grid_dev per element size and a
+    finish) -> compressed_sizes -> compress_many, as compress_tensors; a tensor's records are sorted by position, so an item
+    is reproducible."""
+    import torch
+    what = "compress_fields"
+    ts = _field_tensors(what, tensors)
+    lags = _pkg.grids._lags(what, ts, axes, lags)
+    errs, params = _abs_errors(what, ts, abs_error)
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
+        raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
+    if not ts:
+        return []
+    dev = ts[0].device
+    units = _pkg._elements(ts)
+    caps = [outlier_capacity(n) if n else 0 for n, _ in units]
+    poff, nbytes = _layout(units)
+    st = _pkg._plane_stream(dev, stream)
+    found = [0] * len(ts)
+    with torch.cuda.stream(st):
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        bt = _pkg.Batch(len(ts), 1 << 20)
+        try:
+            if any(n for n, _ in units):
+                d_outl, first, d_found, order = _split_fields(bt, st, dev, ts, units, lags, params, caps, buf, poff)
+                bt.finish(st, len(ts))
+                for i, c in zip(order, d_found.cpu().tolist()):
+                    found[i] = c
+            lossless = [i for i in range(len(ts)) if found[i] > caps[i]]
+            if lossless:                             # compress_grids' planes in the same places
+                groups = [(w, [lossless[j] for j in idx]) for w, idx in _pkg._by_width([units[i] for i in lossless])]
+                d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+                at = 0
+                for w, idx in groups:
+                    base = min(ts[i].data_ptr() for i in idx)
+                    bt.split_planes_grid_dev(st, w, [tuple(lags[i]) for i in idx], base, [ts[i].data_ptr() - base for i in idx],
+                                             [units[i][0] for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+                    at += len(idx)
+                bt.finish(st, len(ts))
+        finally:
+            bt.close()
+        entries = _pkg._coded_planes(buf, poff, units, block_size, st)
+        none = torch.empty(0, dtype=torch.int64, device=dev)
+        items = []
+        for i, (t, ps, nb) in enumerate(zip(ts, entries, _pkg._entry_bytes(entries))):
+            keep = found[i] and i not in lossless
+            pos, bits = _sorted_records(d_outl[first[i]:first[i] + found[i]]) if keep else (none, none)
+            step, bound = (0.0, 0.0) if i in lossless else params[i]
+            items.append(CompressedField(t.dtype, t.shape, lags[i], errs[i], step, bound, ps, pos, bits,
+                                         nb + (8 + t.element_size()) * int(pos.numel())))
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return items
+
+
+def decompress_fields(items, stream=None):
+    """compress_fields' inverse: `items` is a CompressedField or a list of them (their planes on one device) -> the list of
+    tensors, each element within its item's `bound` of the original, or bit for bit: the outliers, and every element of an item
+    kept lossless (a `step` of 0.0).
+
+    Chain: decompress_grids', decompress_many over all coded planes, then one merge_planes_grid_quant_dev per element size over
+    the quantised items — the sums at every lag in turn, the codes restored in place, the outliers' bits on top — and one
+    merge_planes_grid_dev per element size over the lossless ones.  Anything that is not a CompressedField is refused with a
+    ValueError before any device work, as is an item whose lags, step or outliers are malformed.  decompress_tensors' errors
+    otherwise."""
+    import torch
+    what = "decompress_fields"
+    if isinstance(items, CompressedField):
+        items = [items]
+    if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedField) for it in items):
+        raise ValueError(f"{what}: a CompressedField or a list of them (compress_fields' items)")
+    lags = [_pkg.grids._lag_tuple(what, it.lags) for it in items]
+    steps = []
+    for it in items:
+        if it.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"{what}: float32 and float64 tensors, not {it.dtype!r}")
+        _records(what, it.outlier_pos, it.outlier_bits, None)
+        lossless = isinstance(it.step, float) and it.step == 0.0
+        if lossless and it.outlier_pos.numel():
+            raise ValueError(f"{what}: an item kept lossless has no outliers")
+        steps.append(0.0 if lossless else _step(what, it.step, 4 if it.dtype == torch.float32 else 8))
+    return _pkg._merge_items(what, items, "planes_grid", lags, False, stream, _merge_fields(list(items), steps))

@@ -125,6 +125,10 @@ def compress_grids(tensors, axes=None, lags=None, block_size=8 << 20, stream=Non
     Which axes pay is the caller's to know: nothing is tried both ways here.  choose_lags ranks the candidates from their planes'
     histograms, without the planes, and its pick goes into `lags`.
 
+    Float fields are taken BIT FOR BIT here, mantissa bytes and all.  Under an absolute error bound compress_fields (fields.py)
+    quantises inside the same split and differences the integer codes exactly: a smooth float32 field comes out several times
+    smaller.
+
     Chain: compress_tensors', with one split_planes_grid_dev per element size in place of the plain split — one block a tensor
     with lags of its own, so the number of launches does not depend on the shapes; no temporary of the differences exists ->
     compressed_sizes -> compress_many, as there."""
