@@ -716,6 +716,40 @@ int shafa_hipd_merge_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, in
                                            const uint64_t *d_outl, const uint64_t *h_outl_off, const uint64_t *h_outl_n,
                                            uint8_t *d_out, const uint64_t *h_out_off);
 
+/* ---- Field sizes under an error bound: the quantising split's plane histograms, without the planes -------------------------
+ * Which lags to take under a bound, how large a field comes out at a given bound, which bound fits a budget: each follows from
+ * the histograms of the planes shafa_hipd_split_planes_grid_quant_dev would write and from the number of its outliers, and
+ * neither needs a plane or a record.  This entry is shafa_hipd_hist_planes_grid_dev over the CODES:
+ *   d_freq[(b * elem + j) * 256 + s] = the number of elements i < d_n[b] of block b whose byte j of z[i] is s,
+ * z exactly what shafa_hipd_split_planes_grid_quant_dev writes for the block's row of lags, h_step[b] and h_bound[b] — the codes
+ * of "Error-bounded fields" above, their Lorenzo differences, the zigzag fold.  The layout is shafa_hipd_hist256's with nblocks *
+ * elem histograms, which shafa_hipd_sf_build_codes and shafa_hipd_sf_encoded_size_dev take as it is; each plane's 256 counts sum
+ * to d_n[b].
+ *   d_outl_n[b] = the number of elements i < d_n[b] of block b that are not good by that section's rule,
+ * the number the split leaves in its own d_outl_n[b].  No record is written and there is no capacity.  The call zeroes its
+ * nblocks * elem * 256 counts and d_outl_n[0 .. nblocks) itself and writes nothing else.
+ * elem is 4 or 8 (T float or double).  A row of lags follows the _grid_quant_dev split's rule: the first slot >= 1, the others 0
+ * or increasing.  There is NO plain candidate here, a row of zeros is malformed: the split cannot make that item.  h_step and
+ * h_bound as the split takes them.
+ * Blocks are only read and MAY OVERLAP OR COINCIDE on the element side, which lies at multiples of elem: one tensor, one block
+ * per (row of lags, step), is the use.
+ * Per-block code through shafa_hipd_finish: d_n[b] > h_cap[b] is SHAFA_OUTSIDE_MODULE, no byte of the block is read and its
+ * counts are 0.
+ * Launches.  Two memsets and one launch, enqueued only; no workgroup waits for another.  The walk, the LDS bins and the 64-bit
+ * global atomics are shafa_hipd_hist_planes_grid_dev's.  A lane counts its outliers in a register; where a workgroup adds its
+ * bins to block b's counts, each of its waves that found an outlier adds its sum to d_outl_n[b] with one 64-bit atomic — a
+ * tensor in which every element is an outlier costs no more atomics than a clean one has non-zero bins.
+ * Argument errors return with nothing enqueued (checked before HIP is touched), in shafa_hipd_hist_planes_grid_dev's order: NULL
+ * b, d_in, d_freq or d_n, an nlags outside 1 .. SHAFA_PLANES_GRID_LAGS, an elem other than 4, 8: SHAFA_OUTSIDE_MODULE; nblocks
+ * <= 0: SHAFA_SUCCESS; nblocks past the batch's: SHAFA_LACK_OF_MEMORY; NULL h_cap: SHAFA_OUTSIDE_MODULE; capacities whose bytes
+ * pass 64 bits or whose tiles number 2^31 or more: SHAFA_LACK_OF_MEMORY; NULL h_in_off or h_lags, d_in or an offset off a
+ * multiple of elem, a malformed row; then NULL h_step or h_bound, a step, bound or inv the split refuses, NULL d_outl_n:
+ * SHAFA_OUTSIDE_MODULE. */
+int shafa_hipd_hist_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                          const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
+                                          const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
+                                          uint64_t *d_outl_n);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

@@ -142,6 +142,8 @@ def lib():
                                                          vp, u8p, u64p, vp, u64p, u64p, vp]
     L.shafa_hipd_merge_planes_grid_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, f64p, u8p, u64p, u64p, vp,
                                                          vp, u64p, u64p, u8p, u64p]
+    L.shafa_hipd_hist_planes_grid_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, f64p, f64p, u8p, u64p, u64p,
+                                                        vp, vp, vp]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -209,7 +211,7 @@ def lib():
                  "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
                  "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev", "shafa_hipd_hist_planes_grid_dev",
                  "shafa_hipd_split_planes_grid_quant_dev", "shafa_hipd_merge_planes_grid_quant_dev",
-                 "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
+                 "shafa_hipd_hist_planes_grid_quant_dev", "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -647,6 +649,22 @@ class Batch:
         nl, lg = _grid_lags("hist_planes_grid_dev", lags, len(io))
         _check(lib().shafa_hipd_hist_planes_grid_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _addr(d_in), _p64(io),
                                                      _p64(ic), d_n.data_ptr(), d_freq.data_ptr()), "hipd_hist_planes_grid_dev")
+
+    def hist_planes_grid_quant_dev(self, stream, elem, lags, step, bound, d_in, in_off, cap, d_n, d_freq, d_outl_n):
+        """hist_planes_grid_dev over the CODES of float (elem 4) or double (elem 8) elements under an error bound: d_freq (int64,
+        its layout) counts the planes split_planes_grid_quant_dev would write for the same `lags`, `step` and `bound`, and
+        d_outl_n[b] (int64) the elements it would record as outliers; neither a plane nor a record is written.  There is no
+        plain candidate: () is refused.  The blocks are only read and may coincide: one tensor, one block per (lags, step).
+        Both outputs are zeroed by the call.  Enqueues only, one launch (include/shafa_hip.h: "Field sizes under an error
+        bound")."""
+        io, ic = _u64arr(in_off), _u64arr(cap)
+        nl, lg = _grid_lags("hist_planes_grid_quant_dev", lags, len(io))
+        sp, bd = _f64arr(step), _f64arr(bound)
+        if not len(sp) == len(bd) == len(io):
+            raise ValueError("hist_planes_grid_quant_dev: one step and one bound per block")
+        _check(lib().shafa_hipd_hist_planes_grid_quant_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pf64(sp), _pf64(bd),
+                                                           _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), d_freq.data_ptr(),
+                                                           d_outl_n.data_ptr()), "hipd_hist_planes_grid_quant_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -3460,5 +3478,5 @@ from .grids import (CompressedGrid, choose_lags, compress_grids, decompress_grid
 
 # ------------------------------------------------------------------ error-bounded float fields: quantised Lorenzo differences
 from . import fields  # noqa: E402
-from .fields import (FIELD_SLACK, CompressedField, compress_fields, decompress_fields, quantize_field,  # noqa: E402,F401
-                     restore_field)
+from .fields import (FIELD_SLACK, CompressedField, choose_field_lags, compress_fields, decompress_fields,  # noqa: E402,F401
+                     field_histograms, field_rates, field_sizes, fit_abs_error, quantize_field, restore_field)

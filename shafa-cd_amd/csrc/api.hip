@@ -619,6 +619,14 @@ static bool field_param_ok(uint32_t elem, double v, bool step)
     return std::isfinite(inv) && inv != 0;
 }
 
+// the steps of a call's blocks and, where the entry takes them (h_bound non-NULL), the bounds
+static bool field_params_ok(uint32_t elem, int nblocks, const double *h_step, const double *h_bound)
+{
+    for (int i = 0; i < nblocks; ++i)
+        if (!field_param_ok(elem, h_step[i], true) || (h_bound && !field_param_ok(elem, h_bound[i], false))) return false;
+    return true;
+}
+
 static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
                          const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
                          const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr,
@@ -653,9 +661,7 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
     }
     if (fq) {                                        // the _grid_quant entries' own, where the lags are checked
         if (!fq->h_step || (!merge && !fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
-        for (int i = 0; i < nblocks; ++i)
-            if (!field_param_ok(unit, fq->h_step[i], true) || (!merge && !field_param_ok(unit, fq->h_bound[i], false)))
-                return SHAFA_OUTSIDE_MODULE;
+        if (!field_params_ok(unit, nblocks, fq->h_step, merge ? nullptr : fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
         if ((!merge && !fq->d_outl_n) || !fq->h_outl_off || !fq->h_outl_count) return SHAFA_OUTSIDE_MODULE;
         for (int i = 0; !fq->d_outl && i < nblocks; ++i)
             if (fq->h_outl_count[i]) return SHAFA_OUTSIDE_MODULE;
@@ -776,14 +782,16 @@ int shafa_hipd_merge_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, in
                          h_plane_off, h_lags, nlags, &fq);
 }
 
-// beside transpose_dev: its TR_GRID checks in its order without a plane side, and with a row of zeros allowed (plain planes)
-int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
-                                    const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
-                                    const uint64_t *d_n, uint64_t *d_freq)
+// beside transpose_dev: its TR_GRID checks in its order without a plane side.  quant false: shafa_hipd_hist_planes_grid_dev, any
+// elem and a row of zeros allowed (plain planes).  quant true: shafa_hipd_hist_planes_grid_quant_dev, elem 4 or 8, the _grid_quant
+// split's rows (none of zeros) and, where the lags are checked, its steps and bounds and d_outl_n
+static int grid_hist_dev(bool quant, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                         const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
+                         const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq, uint64_t *d_outl_n)
 {
     if (!b || !d_in || !d_freq || !d_n) return SHAFA_OUTSIDE_MODULE;
     if (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS) return SHAFA_OUTSIDE_MODULE;
-    if (elem != 1 && elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
+    if (quant ? elem != 4 && elem != 8 : elem != 1 && elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_cap) return SHAFA_OUTSIDE_MODULE;
@@ -796,13 +804,32 @@ int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nbloc
     if (!h_in_off || !h_lags || (uintptr_t)d_in % elem) return SHAFA_OUTSIDE_MODULE;
     for (int i = 0; i < nblocks; ++i) {
         const u64 *g = h_lags + (size_t)i * nlags;
-        if (h_in_off[i] % elem) return SHAFA_OUTSIDE_MODULE;
+        if (h_in_off[i] % elem || (quant && !g[0])) return SHAFA_OUTSIDE_MODULE;
         for (uint32_t k = 1; k < nlags; ++k)         // the _grid entries' rows, or all zeros: a 0 has only zeros behind it
             if (g[k] && (!g[k - 1] || g[k] <= g[k - 1])) return SHAFA_OUTSIDE_MODULE;
     }
+    if (quant && (!h_step || !h_bound || !field_params_ok(elem, nblocks, h_step, h_bound) || !d_outl_n)) return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    if (quant)
+        return planes_grid_quant_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags,
+                                                 h_lags, h_step, h_bound, d_freq, d_outl_n);
     return planes_grid_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags, h_lags,
                                        d_freq);
+}
+
+int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                    const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                                    const uint64_t *d_n, uint64_t *d_freq)
+{
+    return grid_hist_dev(false, b, stream, nblocks, elem, nlags, h_lags, nullptr, nullptr, d_in, h_in_off, h_cap, d_n, d_freq, nullptr);
+}
+
+int shafa_hipd_hist_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                          const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
+                                          const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
+                                          uint64_t *d_outl_n)
+{
+    return grid_hist_dev(true, b, stream, nblocks, elem, nlags, h_lags, h_step, h_bound, d_in, h_in_off, h_cap, d_n, d_freq, d_outl_n);
 }
 
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,

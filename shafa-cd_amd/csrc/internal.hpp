@@ -307,6 +307,11 @@ void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 
 // difference and no fold.  d_freq is zeroed first; the rows have been checked by the caller
 int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off, const u64 *h_cap,
                                 const u64 *d_n, u32 nlags, const u64 *h_lags, u64 *d_freq);
+// the same for the planes the quantising grid split would write (elem 4 or 8; rows, steps and bounds checked by the caller), and
+// d_outl_n[b] = the elements of block b that split would record, counted and not recorded; both are zeroed first
+int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
+                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const double *h_step,
+                                      const double *h_bound, u64 *d_freq, u64 *d_outl_n);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

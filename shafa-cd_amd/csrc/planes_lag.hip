@@ -38,6 +38,8 @@
 // every base, quantised to integer codes in registers first, and the elements whose restored value misses the bound recorded
 // (planes_grid_quant_split).  merge: the grid merge's chain, then the codes -> values in place (planes_field_restore) and the
 // recorded elements' own bits on top (planes_field_patch).
+// shafa_hipd_hist_planes_grid_quant_dev is to the quantising split what shafa_hipd_hist_planes_grid_dev is to the grid
+// split: the planes' histograms without the planes, and the outliers counted instead of recorded (planes_grid_quant_hist).
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -549,6 +551,120 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_hist(const u8 *__restr
         case 1: hist_tile_grid<E, 1>(wk, r, lg, fold, h); break;
         case 2: hist_tile_grid<E, 2>(wk, r, lg, fold, h); break;
         default: hist_tile_grid<E, 3>(wk, r, lg, fold, h); break;
+        }
+    }
+    if (cur_b >= 0) flush(cur_b);
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// ---- the histograms of the QUANTISING split's planes without the planes (shafa_hipd_hist_planes_grid_quant_dev):
+// planes_grid_hist over the codes.  The tile function is split_tile_grid_quant's element path — the lane's own unit quantised and
+// judged, every tap's unit quantised behind lag_base, the fold always — with hist_count for split_store and, for the records, a
+// COUNT: a lane adds its outliers to a register of its own (outl; a run is at most GH_RUN x 32 elements a lane), and flush adds
+// the waves' sums to the block's d_outl_n, one 64-bit atomic a wave that found any.  A tensor of noise at a tiny bound, where
+// every element is an outlier, costs 4 atomics a run so and not 65536.
+template <int E, int Q>
+__device__ __forceinline__ void hist_tile_grid_quant(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
+                                                     const FieldQ<E> &q, u32 *h, u32 &outl)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+        const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
+#pragma unroll
+        for (int i = 0; i < PL_UNIT; ++i) {          // quant_words_judged with a count for the record
+            using U = typename FieldT<E>::U;
+            bool in;
+            const U xb = unit_elem<E>(w, i);
+            const typename FieldT<E>::I code = field_code<E>(xb, q.inv, in);
+            if ((u32)i < c && !(in && field_good<E>(xb, code, q))) ++outl;
+            if (E == 8) { w[2 * i] = (u32)(U)code; w[2 * i + 1] = (u32)((u64)(U)code >> 32); }
+            else w[i] = (u32)(U)code;
+        }
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                quant_words<E>(wb, q);               // the zeros in front of the block stay zeros
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        zz_fold<E, 4 * E>(w);
+        hist_count<E>(w, c, h);
+    }
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them three rows of nblk: the bits of step, 1 / step and bound as T.
+// d_freq and d_outl_n have been zeroed on the stream.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_hist(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                     const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                     int nblk, const u64 *__restrict__ d_n,
+                                                                     const u64 *__restrict__ d_lag, int *__restrict__ err,
+                                                                     u32 n_tiles, u64 *__restrict__ d_freq,
+                                                                     u64 *__restrict__ d_outl_n)
+{
+    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
+    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
+    const u32 tid = threadIdx.x;
+    u32 outl = 0;                                    // the lane's outliers of block cur_b since the last flush
+    // planes_grid_hist's flush, and the waves' outliers -> block b's count; the lane's counter is cleared with the bins
+    auto flush = [&](int b) {
+        lds_barrier();
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            u32 c = 0;
+#pragma unroll
+            for (u32 q = 0; q < REP; ++q) {
+                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
+                c += *p;
+                *p = 0;
+            }
+            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
+        }
+        const u32 wsum = wave_reduce_add<u32>(outl);
+        if (wsum && lane_id() == 0) atomicAdd((unsigned long long *)d_outl_n + b, (unsigned long long)wsum);
+        outl = 0;
+        lds_barrier();
+    };
+    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
+    lds_barrier();
+    const u64 *qp = d_lag + (u64)SHAFA_PLANES_GRID_LAGS * nblk;
+    int cur_b = -1;                                  // the block whose counts the bins and the counters hold
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        if (wk.b != cur_b) {                         // (uniform)
+            if (cur_b >= 0) flush(cur_b);
+            cur_b = wk.b;
+        }
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const FieldQ<E> q = {field_bits<E>(qp[wk.b]), field_bits<E>(qp[(u64)nblk + wk.b]), field_bits<E>(qp[2ull * nblk + wk.b])};
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: hist_tile_grid_quant<E, 0>(wk, r, lg, q, h, outl); break;
+        case 1: hist_tile_grid_quant<E, 1>(wk, r, lg, q, h, outl); break;
+        case 2: hist_tile_grid_quant<E, 2>(wk, r, lg, q, h, outl); break;
+        default: hist_tile_grid_quant<E, 3>(wk, r, lg, q, h, outl); break;
         }
     }
     if (cur_b >= 0) flush(cur_b);
@@ -1186,6 +1302,38 @@ int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem
     auto kernel = elem == 1 ? planes_grid_hist<1> : elem == 2 ? planes_grid_hist<2> : elem == 4 ? planes_grid_hist<4> : planes_grid_hist<8>;
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
                        bt->d_err, a.nt, d_freq);
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
+// shafa_hipd_hist_planes_grid_quant_dev.  h_lags, h_step and h_bound as the _grid_quant split's, checked by the
+// caller.  The device gets the grid split's rows of clamped lags and behind them the bits of step, 1 / step and bound as T.  The
+// grid is planes_grid_hist_launch_dev's.  One pair of memsets, one launch.
+int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
+                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const double *h_step,
+                                      const double *h_bound, u64 *d_freq, u64 *d_outl_n)
+{
+    const size_t nb = (size_t)nblocks;
+    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 3), 0);
+    u64 *q = lag.data() + nb * SHAFA_PLANES_GRID_LAGS;
+    for (size_t b = 0; b < nb; ++b) {
+        for (u32 k = 0; k < nlags; ++k) {
+            const u64 g = h_lags[b * nlags + k];
+            lag[k * nb + b] = g < h_cap[b] ? g : 0;
+        }
+        q[b] = field_bits_of(elem, h_step[b]);
+        q[nb + b] = field_bits_of(elem, field_inverse(elem, h_step[b]));
+        q[2 * nb + b] = field_bits_of(elem, h_bound[b]);
+    }
+    const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
+    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_outl_n, 0, nb * sizeof(u64), st));
+    const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
+    auto kernel = elem == 4 ? planes_grid_quant_hist<4> : planes_grid_quant_hist<8>;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
+                       bt->d_err, a.nt, d_freq, d_outl_n);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }

@@ -9,6 +9,11 @@ The quantiser runs inside the grid split, so no temporary of codes exists, and t
 against the very value the decoder will make: an element that misses it — a NaN, an infinity, a value past the code range, a
 tie the rounding threw over — is an outlier, kept with its own bits and given back bit for bit.
 
+What a bound costs is the data's to say: field_histograms / field_sizes / choose_field_lags / field_rates / fit_abs_error on top
+of Batch.hist_planes_grid_quant_dev count the planes the quantising split would write, and its outliers, without making either,
+and give the size under an order-0 model: which lags to take under a bound, the size at each bound of a list, the smallest bound
+that fits a budget.
+
 The drivers live in this submodule; the package re-exports them.  The coder's half of the chain (_coded_planes) and the decode
 chain (_merge_items) are the package's, reached through it at the time of the call."""
 import fractions
@@ -297,6 +302,9 @@ def compress_fields(tensors, abs_error, axes=None, lags=None, block_size=8 << 20
     A tensor that finds more outliers than outlier_capacity(numel) = 16 + numel // 64 is kept LOSSLESS, compress_grids' planes
     and a `step` of 0.0: the bound sits at the data's own precision there, or the tensor is noise.
 
+    Which lags pay under the bound, and what a bound costs, can be asked first without compressing: choose_field_lags ranks the
+    candidates and its pick goes into `lags`; field_rates and fit_abs_error size a list of bounds.
+
     Chain: one split_planes_grid_quant_dev per element size over all tensors — no temporary of codes exists — one finish and
     one read-back of the outlier counts (the tensors kept lossless then take one split_planes_grid_dev per element size and a
     finish) -> compressed_sizes -> compress_many, as compress_tensors; a tensor's records are sorted by position, so an item
@@ -349,6 +357,192 @@ def compress_fields(tensors, abs_error, axes=None, lags=None, block_size=8 << 20
                                          nb + (8 + t.element_size()) * int(pos.numel())))
     torch.cuda.current_stream(dev).wait_stream(st)
     return items
+
+
+# ---- sizes under a bound: the quantising split's histograms without the planes (Batch.hist_planes_grid_quant_dev)
+def _lag_sets(what, cs):
+    """candidates that compress_fields can make: tuples of lags, and no () — it has no plain item"""
+    out = []
+    for c in cs:
+        if not isinstance(c, tuple) or c == ():
+            raise ValueError(f"{what}: a candidate is a non-empty tuple of lags, not {c!r}: compress_fields makes no plain planes")
+        out.append(_pkg.grids._lag_tuple(what, c))
+    return out
+
+
+def _field_candidates(what, ts, axes, candidates):
+    """one list of candidates per checked tensor: grid_sizes' `candidates` without (), or else the non-empty subsets of each
+    tensor's axis lags"""
+    if candidates is None:
+        return [_pkg.grids._subsets(g)[1:] for g in _pkg.grids._lags(what, ts, axes, None)]
+    return [_lag_sets(what, cs) for cs in _pkg.grids._candidates(what, ts, axes, candidates)]
+
+
+def _bounds(what, abs_errors, k):
+    """a non-empty list of bounds -> its (step, bound) pairs for elements of k bytes"""
+    if not isinstance(abs_errors, (list, tuple)) or not abs_errors:
+        raise ValueError(f"{what}: abs_errors is a non-empty list of floats, not {abs_errors!r}")
+    return [_params(what, e, k) for e in abs_errors]
+
+
+def _model_sizes(ts, blocks, stream):
+    """blocks: (index of a non-empty tensor of ts, lags, (step, bound)) -> [(nbytes, outliers)] in their order, nbytes the order-0
+    model of field_sizes.  Per element size one hist_planes_grid_quant_dev, Module T and the encoded sizes on the device; one
+    finish, one read-back"""
+    import ctypes as C
+    import torch
+    dev = ts[0].device
+    st = _pkg._plane_stream(dev, stream)
+    widths = sorted({ts[i].element_size() for i, _, _ in blocks})
+    groups = [(w, [j for j, (i, _, _) in enumerate(blocks) if ts[i].element_size() == w]) for w in widths]
+    with torch.cuda.stream(st):
+        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
+        try:
+            res = []
+            for w, g in groups:
+                idx = [blocks[j][0] for j in g]
+                base = min(ts[i].data_ptr() for i in idx)
+                numel = [ts[i].numel() for i in idx]
+                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
+                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
+                d_outl = torch.empty(len(g), dtype=torch.int64, device=dev)
+                bt.hist_planes_grid_quant_dev(st, w, [blocks[j][1] for j in g], [blocks[j][2][0] for j in g],
+                                              [blocks[j][2][1] for j in g], base, [ts[i].data_ptr() - base for i in idx], numel, d_n,
+                                              d_freq, d_outl)
+                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
+                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
+                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
+                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
+                planes = torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1)
+                res.append(torch.stack([planes + (8 + w) * d_outl, d_outl], 1))
+            bt.finish(st, bt.max_blocks)
+            host = torch.cat(res).cpu().tolist()
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    out = [None] * len(blocks)
+    for j, (nb, no) in zip([j for _, g in groups for j in g], host):
+        out[j] = (int(nb), int(no))
+    return out
+
+
+def field_histograms(t, abs_error, lag_sets, stream=None):
+    """The byte histograms of the planes quantize_field(t, abs_error, lags) would give for every `lags` of the list `lag_sets`,
+    and its count of outliers, without the planes and without the records: `t` a contiguous float32 or float64 CUDA tensor,
+    every entry of `lag_sets` a tuple quantize_field takes — () is a ValueError, there is no plain candidate under a bound —
+    and `abs_error` a float for all entries or a list with one per entry: the same lags may appear several times with
+    different bounds.  Returns (freq, outliers): int64 CUDA tensors [len(lag_sets), k, 256], every row summing to t.numel(), and
+    [len(lag_sets)].  Step and bound are compress_fields' (_params).  One hist_planes_grid_quant_dev launch per HIST_GROUP
+    candidates, one block per candidate on the same region, one synchronisation."""
+    import torch
+    what = "field_histograms"
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a contiguous CUDA tensor")
+    t = _field_tensors(what, t)[0]
+    if not isinstance(lag_sets, (list, tuple)):
+        raise ValueError(f"{what}: lag_sets is a list of tuples of lags, not {lag_sets!r}")
+    sets = _lag_sets(what, lag_sets)
+    dev, k, n = t.device, t.element_size(), t.numel()
+    if isinstance(abs_error, (list, tuple)):
+        if len(abs_error) != len(sets):
+            raise ValueError(f"{what}: abs_error is a float or a list with one float per entry of lag_sets")
+        params = [_params(what, e, k) for e in abs_error]
+    else:
+        params = [_params(what, abs_error, k)] * len(sets)
+    group = _pkg.grids.HIST_GROUP
+    st = _pkg._plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
+        outl = torch.zeros(len(sets), dtype=torch.int64, device=dev)
+        if sets and n:
+            bt = _pkg.Batch(min(len(sets), group), 1 << 20)
+            try:
+                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
+                for lo in range(0, len(sets), bt.max_blocks):
+                    part, pp = sets[lo:lo + bt.max_blocks], params[lo:lo + bt.max_blocks]
+                    bt.hist_planes_grid_quant_dev(st, k, part, [p[0] for p in pp], [p[1] for p in pp], t, [0] * len(part),
+                                                  [n] * len(part), d_n, freq[lo:lo + len(part)], outl[lo:lo + len(part)])
+                bt.finish(st, bt.max_blocks)
+            finally:
+                bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return freq, outl
+
+
+def field_sizes(tensors, abs_error, axes=None, candidates=None, stream=None):
+    """How large would compress_fields make each tensor with each candidate's lags, under its bound?  Per tensor a list of
+    (lags, nbytes, outliers), sorted by (outliers > outlier_capacity(numel), nbytes, len(lags), lags): the first entry is the
+    candidate to take.  `tensors`, `abs_error` and `axes` as compress_fields takes them, and its ValueErrors, before any device
+    work.  `candidates` as grid_sizes takes them, but a candidate of () is a ValueError: compress_fields makes no plain planes;
+    None: every non-empty subset of the tensor's axis lags, at most seven.  An empty or 0-dimensional tensor gives [((), 0, 0)]
+    whatever the candidates.
+
+    nbytes is CompressedField.nbytes' own formula over a MODEL of the planes, of order 0: the sum over the candidate's byte
+    planes of min(numel, the Shannon-Fano bytes of the whole plane under the table of its own histogram) — a plane that would
+    not shrink counts raw — plus (8 + element size) per outlier.  It is not the size compress_fields reports: it knows nothing
+    of RLE, of the split into blocks of block_size with a table each, or of the files' tables and headers (DESIGN 7.31 has both
+    side by side).  A candidate with more outliers than outlier_capacity(numel) sorts LAST: compress_fields would keep that
+    tensor lossless, its planes would be compress_grids' over the raw bits, and grid_sizes is the model for it then, not this
+    number.
+
+    Chain: per element size one hist_planes_grid_quant_dev over all tensors' candidates, one block per candidate on its
+    tensor's region — no plane and no record ever exists, and no histogram comes to the host -> sf_build_codes ->
+    sf_encoded_size_dev -> one finish, one read-back of the sizes and the counts."""
+    what = "field_sizes"
+    ts = _field_tensors(what, tensors)
+    cands = _field_candidates(what, ts, axes, candidates)
+    _, params = _abs_errors(what, ts, abs_error)
+    out = [[((), 0, 0)] if not t.numel() or not t.dim() else None for t in ts]
+    blocks = [(i, c, params[i]) for i in range(len(ts)) if out[i] is None for c in cands[i]]
+    if not blocks:
+        return out
+    found = [[] for _ in ts]
+    for (i, c, _), (nb, no) in zip(blocks, _model_sizes(ts, blocks, stream)):
+        found[i].append((c, nb, no))
+    key = lambda n: lambda e: (e[2] > outlier_capacity(n), e[1], len(e[0]), e[0])
+    return [o if o is not None else sorted(f, key=key(t.numel())) for o, f, t in zip(out, found, ts)]
+
+
+def choose_field_lags(tensors, abs_error, axes=None, candidates=None, stream=None):
+    """Which lags to compress each tensor with under its bound: field_sizes' first entry per tensor, ready for
+    compress_fields(tensors, abs_error, lags=[...]) — () for an empty or 0-dimensional tensor, which takes any lags.
+    field_sizes' arguments, chain and caveats."""
+    return [sizes[0][0] for sizes in field_sizes(tensors, abs_error, axes, candidates, stream)]
+
+
+def field_rates(t, abs_errors, lags=None, axes=None, stream=None):
+    """The rate of one tensor over a list of bounds: [(abs_error, nbytes, outliers)] in the order of `abs_errors`, a non-empty
+    list of floats as compress_fields takes one.  `lags` as compress_fields takes them for one tensor; None: the tensor's axis
+    lags (`axes`), as there.  nbytes and outliers are field_sizes' model, with its caveats; an entry with more outliers than
+    outlier_capacity(numel) is one compress_fields would keep lossless.  One block per bound on the same region, in ONE
+    hist_planes_grid_quant_dev launch, then field_sizes' chain.  An empty or 0-dimensional tensor gives 0 bytes at every bound."""
+    return _rates("field_rates", t, abs_errors, lags, axes, stream)
+
+
+def _rates(what, t, abs_errors, lags, axes, stream):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a contiguous CUDA tensor")
+    ts = _field_tensors(what, t)
+    g = _pkg.grids._lags(what, ts, axes, lags)[0]
+    params = _bounds(what, abs_errors, ts[0].element_size())
+    if not ts[0].numel() or not ts[0].dim():
+        return [(e, 0, 0) for e in abs_errors]
+    sizes = _model_sizes(ts, [(0, g, p) for p in params], stream)
+    return [(e, nb, no) for e, (nb, no) in zip(abs_errors, sizes)]
+
+
+def fit_abs_error(t, max_bytes, abs_errors, lags=None, axes=None, stream=None):
+    """The smallest bound of the list `abs_errors` at which the tensor fits `max_bytes` (an int >= 0): field_rates' nbytes <=
+    max_bytes, with no more outliers than outlier_capacity(numel) — past that compress_fields keeps the tensor lossless and the
+    model is not its size.  None where no bound of the list does.  field_rates' arguments, chain and caveats."""
+    what = "fit_abs_error"
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, int) or max_bytes < 0:
+        raise ValueError(f"{what}: max_bytes is an int >= 0, not {max_bytes!r}")
+    rates = _rates(what, t, abs_errors, lags, axes, stream)
+    n = t.numel()
+    fits = [e for e, nb, no in rates if nb <= max_bytes and no <= outlier_capacity(n)]
+    return min(fits) if fits else None
 
 
 def decompress_fields(items, stream=None):
