@@ -750,6 +750,58 @@ int shafa_hipd_hist_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int
                                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
                                           uint64_t *d_outl_n);
 
+/* ---- Point-wise relative bounds: mantissas rounded to the kept bits, in integer arithmetic --------------------------------
+ * One absolute bound serves a field whose values are all of one size.  A field that spans decades, and the bfloat16 and float16
+ * tensors torch users hold, want "keep k mantissa bits" instead: |x - x'| <= 2^-(keep + 1) |x| for every normal element.  These
+ * three entries are the _grid_quant_dev split and merge and the _grid_quant_dev histogram with that quantiser for rint(x / step):
+ * the mantissa rounded to `keep` bits, half to even, the carry free to enter the exponent ("bit rounding").  It is integer work
+ * on the element's own bits, so the rule is exact and needs no slack.  elem is 2, 4 or 8 (any other: SHAFA_OUTSIDE_MODULE).
+ * Block b has two host uint32_t, h_mant[b], the format's mantissa width — 7 (bfloat16) or 10 (float16) at elem 2, 23 at elem 4,
+ * 52 at elem 8; one call may mix the two 16-bit formats — and h_keep[b] <= h_mant[b], the mantissa bits kept.
+ * With W = 8 elem and d = mant - keep, in unsigned W-bit integer arithmetic on the element's bits x:
+ *   S    = x >> (W-1)                      M = x & (2^(W-1) - 1)
+ *   INF  = (2^(W-1-mant) - 1) << mant      MIN = 1 << mant
+ *   R    = M >= INF ? M >> d                                        (Inf / NaN: truncated, never carried)
+ *        : d == 0   ? M
+ *        :            (M + (2^(d-1) - 1) + ((M >> d) & 1)) >> d     (half to even; the carry may enter the exponent)
+ *   code = S ? -R : R                      as a signed W-bit integer
+ *   M'   = (|code| << d) mod 2^(W-1)       x' = (code < 0) << (W-1) | M'          (what the merge makes of ANY code)
+ *   good = (M < MIN or M >= INF) ? M' == M : M' < INF
+ * The planes are those shafa_hipd_split_planes_grid_dev writes for the block's lags over the array of codes taken as unsigned
+ * W-bit integers, byte for byte, tails included; a position in front of the block is the bit pattern 0, whose code is 0.  An
+ * element that is not good is an OUTLIER — a normal value that rounds up to Inf, a denormal with a dropped bit set, a NaN whose
+ * payload reaches into the dropped bits (one that would truncate to Inf among them): its code still goes into the planes, and it
+ * is recorded under the record contract of "Error-bounded fields" above, word for word (h_outl_off, h_outl_cap, d_outl, d_outl_n
+ * zeroed by the call, the slot taken with a 64-bit atomic, written only where slot < capacity, found > capacity the signal).
+ * Guarantee, exact: a good normal element comes back with |x - x'| <= 2^-(keep + 1) |x| in real numbers; +-Inf, a good NaN, a
+ * good denormal and +0.0 bit for bit; -0.0 as +0.0; an outlier bit for bit.  keep = mant changes nothing but -0.0.
+ * A row of lags follows the _grid_quant_dev split's rule.  "No differences" needs no rule of its own: a lag at or past the
+ * block's capacity subtracts nothing in split and merge alike.
+ * Launches.  split: a memset of d_outl_n and ONE launch, the grid split's with every loaded unit of 16 elements — the lane's own
+ * and every tap's — rounded in registers; at elem 2 each half of a word is rounded on its own, no carry passes between them.
+ * merge: the _grid_dev merge's chain as it is, a restore pass in place (code -> x') and the patch pass of "Error-bounded fields"
+ * where the call has a record.  hist: d_freq and d_outl_n as shafa_hipd_hist_planes_grid_quant_dev leaves them, over these codes:
+ * two memsets and one launch.  Blocks of the hist entry are only read and may overlap or coincide.  No workgroup waits for
+ * another.  Enqueues only.  Per-block codes through shafa_hipd_finish are the _quant_dev entries', the patch pass's position >=
+ * d_n[b] included.
+ * Argument errors return with nothing enqueued (checked before HIP is touched): the corresponding _quant_dev entry's in its
+ * order, with elem in {2, 4, 8} at the elem check; where that entry checks its steps and bounds, each SHAFA_OUTSIDE_MODULE: NULL
+ * h_mant or h_keep, a mant that is not the format's for elem, keep > mant; then the record arguments as there. */
+int shafa_hipd_split_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep,
+                                           const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n,
+                                           uint8_t *d_planes, const uint64_t *h_plane_off, uint64_t *d_outl,
+                                           const uint64_t *h_outl_off, const uint64_t *h_outl_cap, uint64_t *d_outl_n);
+int shafa_hipd_merge_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep,
+                                           const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_cap,
+                                           const uint64_t *d_n, const uint64_t *d_outl, const uint64_t *h_outl_off,
+                                           const uint64_t *h_outl_n, uint8_t *d_out, const uint64_t *h_out_off);
+int shafa_hipd_hist_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                          const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep, const uint8_t *d_in,
+                                          const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
+                                          uint64_t *d_outl_n);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

@@ -144,6 +144,13 @@ def lib():
                                                          vp, u64p, u64p, u8p, u64p]
     L.shafa_hipd_hist_planes_grid_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, f64p, f64p, u8p, u64p, u64p,
                                                         vp, vp, vp]
+    u32p = C.POINTER(C.c_uint32)
+    L.shafa_hipd_split_planes_grid_round_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u8p, u64p, u64p,
+                                                         vp, u8p, u64p, vp, u64p, u64p, vp]
+    L.shafa_hipd_merge_planes_grid_round_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u8p, u64p, u64p,
+                                                         vp, vp, u64p, u64p, u8p, u64p]
+    L.shafa_hipd_hist_planes_grid_round_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u8p, u64p, u64p,
+                                                        vp, vp, vp]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -211,7 +218,9 @@ def lib():
                  "shafa_hipd_split_planes_lag_dev", "shafa_hipd_merge_planes_lag_dev",
                  "shafa_hipd_split_planes_grid_dev", "shafa_hipd_merge_planes_grid_dev", "shafa_hipd_hist_planes_grid_dev",
                  "shafa_hipd_split_planes_grid_quant_dev", "shafa_hipd_merge_planes_grid_quant_dev",
-                 "shafa_hipd_hist_planes_grid_quant_dev", "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
+                 "shafa_hipd_hist_planes_grid_quant_dev", "shafa_hipd_split_planes_grid_round_dev",
+                 "shafa_hipd_merge_planes_grid_round_dev", "shafa_hipd_hist_planes_grid_round_dev",
+                 "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
     return L
@@ -310,6 +319,14 @@ def _f64arr(v):
 
 def _pf64(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _u32arr(v):
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
+def _pu32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 def _grid_lags(what, lags, nblocks):
@@ -665,6 +682,54 @@ class Batch:
         _check(lib().shafa_hipd_hist_planes_grid_quant_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pf64(sp), _pf64(bd),
                                                            _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), d_freq.data_ptr(),
                                                            d_outl_n.data_ptr()), "hipd_hist_planes_grid_quant_dev")
+
+    def split_planes_grid_round_dev(self, stream, elem, lags, mant, keep, d_in, in_off, cap, d_n, d_planes, plane_off, d_outl,
+                                    outl_off, outl_cap, d_outl_n):
+        """split_planes_grid_quant_dev with another quantiser: the mantissa of every element rounded to keep[b] of its mant[b]
+        bits, half to even, in integer arithmetic on the element's bits — elem 2 (mant 7: bfloat16, 10: float16; one call may mix
+        them), 4 (23) or 8 (52), 0 <= keep <= mant, host ints, one per block.  The planes are split_planes_grid_dev's over the
+        codes; a normal value that rounds up to Inf, a denormal or a NaN with a dropped bit set is an outlier, recorded as
+        split_planes_grid_quant_dev records its own.  Enqueues only: a memset and one launch (include/shafa_hip.h: "Point-wise
+        relative bounds")."""
+        io, ic, po, oo, oc = _u64arr(in_off), _u64arr(cap), _u64arr(plane_off), _u64arr(outl_off), _u64arr(outl_cap)
+        nl, lg = _grid_lags("split_planes_grid_round_dev", lags, len(io))
+        mt, kp = _u32arr(mant), _u32arr(keep)
+        if not len(mt) == len(kp) == len(oo) == len(oc) == len(io):
+            raise ValueError("split_planes_grid_round_dev: one mant, keep, record offset and record capacity per block")
+        _check(lib().shafa_hipd_split_planes_grid_round_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pu32(mt), _pu32(kp),
+                                                            _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), _addr(d_planes),
+                                                            _p64(po), None if d_outl is None else _addr(d_outl), _p64(oo), _p64(oc),
+                                                            d_outl_n.data_ptr()), "hipd_split_planes_grid_round_dev")
+
+    def merge_planes_grid_round_dev(self, stream, elem, lags, mant, keep, d_planes, plane_off, cap, d_n, d_outl, outl_off, outl_n,
+                                    d_out, out_off):
+        """split_planes_grid_round_dev's inverse: merge_planes_grid_dev's chain gives the codes, a restore pass in place makes the
+        rounded bits of each (sign, |code| << (mant - keep)), and merge_planes_grid_quant_dev's patch pass stores the records' bits
+        on top.  Its arguments with `mant` and `keep` for `step`.  Enqueues only (include/shafa_hip.h: "Point-wise relative
+        bounds")."""
+        oo, ic, po, ro, rn = _u64arr(out_off), _u64arr(cap), _u64arr(plane_off), _u64arr(outl_off), _u64arr(outl_n)
+        nl, lg = _grid_lags("merge_planes_grid_round_dev", lags, len(oo))
+        mt, kp = _u32arr(mant), _u32arr(keep)
+        if not len(mt) == len(kp) == len(ro) == len(rn) == len(oo):
+            raise ValueError("merge_planes_grid_round_dev: one mant, keep, record offset and record count per block")
+        _check(lib().shafa_hipd_merge_planes_grid_round_dev(self.h, self._st(stream), len(oo), elem, nl, _p64(lg), _pu32(mt), _pu32(kp),
+                                                            _addr(d_planes), _p64(po), _p64(ic), d_n.data_ptr(),
+                                                            None if d_outl is None else _addr(d_outl), _p64(ro), _p64(rn),
+                                                            _addr(d_out), _p64(oo)), "hipd_merge_planes_grid_round_dev")
+
+    def hist_planes_grid_round_dev(self, stream, elem, lags, mant, keep, d_in, in_off, cap, d_n, d_freq, d_outl_n):
+        """hist_planes_grid_quant_dev over split_planes_grid_round_dev's codes: d_freq counts the planes that split would write
+        for the same `lags`, `mant` and `keep`, d_outl_n[b] the elements it would record; neither a plane nor a record is
+        written.  The blocks are only read and may coincide: one tensor, one block per (lags, keep).  Both outputs are zeroed by
+        the call.  Enqueues only, one launch (include/shafa_hip.h: "Point-wise relative bounds")."""
+        io, ic = _u64arr(in_off), _u64arr(cap)
+        nl, lg = _grid_lags("hist_planes_grid_round_dev", lags, len(io))
+        mt, kp = _u32arr(mant), _u32arr(keep)
+        if not len(mt) == len(kp) == len(io):
+            raise ValueError("hist_planes_grid_round_dev: one mant and one keep per block")
+        _check(lib().shafa_hipd_hist_planes_grid_round_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pu32(mt), _pu32(kp),
+                                                           _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), d_freq.data_ptr(),
+                                                           d_outl_n.data_ptr()), "hipd_hist_planes_grid_round_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -3480,3 +3545,8 @@ from .grids import (CompressedGrid, choose_lags, compress_grids, decompress_grid
 from . import fields  # noqa: E402
 from .fields import (FIELD_SLACK, CompressedField, choose_field_lags, compress_fields, decompress_fields,  # noqa: E402,F401
                      field_histograms, field_rates, field_sizes, fit_abs_error, quantize_field, restore_field)
+
+# ------------------------------------------------------------------ point-wise relative bounds: mantissas rounded to the kept bits
+from . import rounding  # noqa: E402
+from .rounding import (MANTISSA_BITS, CompressedRounded, compress_rounded, decompress_rounded, fit_keep_bits,  # noqa: E402,F401
+                       restore_rounded, round_field, rounded_histograms, rounded_rates, rounded_sizes)

@@ -627,6 +627,18 @@ static bool field_params_ok(uint32_t elem, int nblocks, const double *h_step, co
     return true;
 }
 
+// the mantissa widths and the kept bits of the _grid_round entries' blocks: the format's mant for elem — 7 (bfloat16)
+// or 10 (float16) at 2, 23 at 4, 52 at 8 — and keep <= mant
+static bool round_params_ok(uint32_t elem, int nblocks, const uint32_t *h_mant, const uint32_t *h_keep)
+{
+    for (int i = 0; i < nblocks; ++i) {
+        const uint32_t m = h_mant[i];
+        if (elem == 2 ? m != 7 && m != 10 : m != (elem == 4 ? 23u : 52u)) return false;
+        if (h_keep[i] > m) return false;
+    }
+    return true;
+}
+
 static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t unit, const uint8_t *d_el,
                          const uint64_t *h_off, const uint8_t *d_base, const uint64_t *h_base_off, const uint64_t *h_cap,
                          const uint64_t *d_n, const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_lag = nullptr,
@@ -637,7 +649,7 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
     if (tr == TR_GRID && (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS)) return SHAFA_OUTSIDE_MODULE;
     if (tr == TR_RECORDS ? unit < 1 || unit > SHAFA_RECORDS_MAX_WIDTH : unit != 1 && unit != 2 && unit != 4 && unit != 8)
         return SHAFA_OUTSIDE_MODULE;
-    if (fq && unit != 4 && unit != 8) return SHAFA_OUTSIDE_MODULE;             // floats and doubles
+    if (fq && unit != 4 && unit != 8 && !(fq->round && unit == 2)) return SHAFA_OUTSIDE_MODULE;    // floats and doubles; rounding: 16 bits too
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_cap) return SHAFA_OUTSIDE_MODULE;
@@ -660,8 +672,12 @@ static int transpose_dev(bool merge, Transpose tr, shafa_hipd_batch *b, void *st
         }
     }
     if (fq) {                                        // the _grid_quant entries' own, where the lags are checked
-        if (!fq->h_step || (!merge && !fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
-        if (!field_params_ok(unit, nblocks, fq->h_step, merge ? nullptr : fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
+        if (fq->round) {                             // the _grid_round entries': widths and kept bits for steps and bounds
+            if (!fq->h_mant || !fq->h_keep || !round_params_ok(unit, nblocks, fq->h_mant, fq->h_keep)) return SHAFA_OUTSIDE_MODULE;
+        } else {
+            if (!fq->h_step || (!merge && !fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
+            if (!field_params_ok(unit, nblocks, fq->h_step, merge ? nullptr : fq->h_bound)) return SHAFA_OUTSIDE_MODULE;
+        }
         if ((!merge && !fq->d_outl_n) || !fq->h_outl_off || !fq->h_outl_count) return SHAFA_OUTSIDE_MODULE;
         for (int i = 0; !fq->d_outl && i < nblocks; ++i)
             if (fq->h_outl_count[i]) return SHAFA_OUTSIDE_MODULE;
@@ -782,16 +798,44 @@ int shafa_hipd_merge_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, in
                          h_plane_off, h_lags, nlags, &fq);
 }
 
-// beside transpose_dev: its TR_GRID checks in its order without a plane side.  quant false: shafa_hipd_hist_planes_grid_dev, any
-// elem and a row of zeros allowed (plain planes).  quant true: shafa_hipd_hist_planes_grid_quant_dev, elem 4 or 8, the _grid_quant
-// split's rows (none of zeros) and, where the lags are checked, its steps and bounds and d_outl_n
-static int grid_hist_dev(bool quant, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
-                         const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
-                         const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq, uint64_t *d_outl_n)
+// point-wise relative bounds: the _grid_quant entries with the rounding of the mantissa for the quantiser
+int shafa_hipd_split_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep, const uint8_t *d_in,
+                                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
+                                           const uint64_t *h_plane_off, uint64_t *d_outl, const uint64_t *h_outl_off,
+                                           const uint64_t *h_outl_cap, uint64_t *d_outl_n)
 {
+    const FieldQuant fq = {nullptr, nullptr, d_outl, h_outl_off, h_outl_cap, d_outl_n, true, h_mant, h_keep};
+    return transpose_dev(false, TR_GRID, b, stream, nblocks, elem, d_in, h_in_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags, &fq);
+}
+
+int shafa_hipd_merge_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                           const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep,
+                                           const uint8_t *d_planes, const uint64_t *h_plane_off, const uint64_t *h_cap,
+                                           const uint64_t *d_n, const uint64_t *d_outl, const uint64_t *h_outl_off,
+                                           const uint64_t *h_outl_n, uint8_t *d_out, const uint64_t *h_out_off)
+{
+    const FieldQuant fq = {nullptr, nullptr, (u64 *)d_outl, h_outl_off, h_outl_n, nullptr, true, h_mant, h_keep};
+    return transpose_dev(true, TR_GRID, b, stream, nblocks, elem, d_out, h_out_off, nullptr, nullptr, h_cap, d_n, d_planes,
+                         h_plane_off, h_lags, nlags, &fq);
+}
+
+// beside transpose_dev: its TR_GRID checks in its order without a plane side.  GH_PLAIN: shafa_hipd_hist_planes_grid_dev, any
+// elem and a row of zeros allowed (plain planes).  GH_QUANT: shafa_hipd_hist_planes_grid_quant_dev, elem 4 or 8, the _grid_quant
+// split's rows (none of zeros) and, where the lags are checked, its steps and bounds and d_outl_n.  GH_ROUND:
+// shafa_hipd_hist_planes_grid_round_dev, the same at elem 2, 4 or 8 with h_mant and h_keep for the steps and bounds
+enum GridHist { GH_PLAIN, GH_QUANT, GH_ROUND };
+static int grid_hist_dev(GridHist kind, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                         const uint64_t *h_lags, const double *h_step, const double *h_bound, const uint8_t *d_in,
+                         const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq, uint64_t *d_outl_n,
+                         const uint32_t *h_mant = nullptr, const uint32_t *h_keep = nullptr)
+{
+    const bool quant = kind != GH_PLAIN;
     if (!b || !d_in || !d_freq || !d_n) return SHAFA_OUTSIDE_MODULE;
     if (nlags < 1 || nlags > SHAFA_PLANES_GRID_LAGS) return SHAFA_OUTSIDE_MODULE;
-    if (quant ? elem != 4 && elem != 8 : elem != 1 && elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
+    const bool elem_ok = elem == 4 || elem == 8 || (elem == 2 && kind != GH_QUANT) || (elem == 1 && kind == GH_PLAIN);
+    if (!elem_ok) return SHAFA_OUTSIDE_MODULE;
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
     if (!h_cap) return SHAFA_OUTSIDE_MODULE;
@@ -808,8 +852,13 @@ static int grid_hist_dev(bool quant, shafa_hipd_batch *b, void *stream, int nblo
         for (uint32_t k = 1; k < nlags; ++k)         // the _grid entries' rows, or all zeros: a 0 has only zeros behind it
             if (g[k] && (!g[k - 1] || g[k] <= g[k - 1])) return SHAFA_OUTSIDE_MODULE;
     }
-    if (quant && (!h_step || !h_bound || !field_params_ok(elem, nblocks, h_step, h_bound) || !d_outl_n)) return SHAFA_OUTSIDE_MODULE;
+    if (kind == GH_QUANT && (!h_step || !h_bound || !field_params_ok(elem, nblocks, h_step, h_bound))) return SHAFA_OUTSIDE_MODULE;
+    if (kind == GH_ROUND && (!h_mant || !h_keep || !round_params_ok(elem, nblocks, h_mant, h_keep))) return SHAFA_OUTSIDE_MODULE;
+    if (quant && !d_outl_n) return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    if (kind == GH_ROUND)
+        return planes_grid_round_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags,
+                                                 h_lags, h_mant, h_keep, d_freq, d_outl_n);
     if (quant)
         return planes_grid_quant_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags,
                                                  h_lags, h_step, h_bound, d_freq, d_outl_n);
@@ -821,7 +870,7 @@ int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nbloc
                                     const uint64_t *h_lags, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
                                     const uint64_t *d_n, uint64_t *d_freq)
 {
-    return grid_hist_dev(false, b, stream, nblocks, elem, nlags, h_lags, nullptr, nullptr, d_in, h_in_off, h_cap, d_n, d_freq, nullptr);
+    return grid_hist_dev(GH_PLAIN, b, stream, nblocks, elem, nlags, h_lags, nullptr, nullptr, d_in, h_in_off, h_cap, d_n, d_freq, nullptr);
 }
 
 int shafa_hipd_hist_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
@@ -829,7 +878,16 @@ int shafa_hipd_hist_planes_grid_quant_dev(shafa_hipd_batch *b, void *stream, int
                                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
                                           uint64_t *d_outl_n)
 {
-    return grid_hist_dev(true, b, stream, nblocks, elem, nlags, h_lags, h_step, h_bound, d_in, h_in_off, h_cap, d_n, d_freq, d_outl_n);
+    return grid_hist_dev(GH_QUANT, b, stream, nblocks, elem, nlags, h_lags, h_step, h_bound, d_in, h_in_off, h_cap, d_n, d_freq, d_outl_n);
+}
+
+int shafa_hipd_hist_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,
+                                          const uint64_t *h_lags, const uint32_t *h_mant, const uint32_t *h_keep, const uint8_t *d_in,
+                                          const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
+                                          uint64_t *d_outl_n)
+{
+    return grid_hist_dev(GH_ROUND, b, stream, nblocks, elem, nlags, h_lags, nullptr, nullptr, d_in, h_in_off, h_cap, d_n, d_freq, d_outl_n,
+                         h_mant, h_keep);
 }
 
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,

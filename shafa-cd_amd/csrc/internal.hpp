@@ -294,6 +294,10 @@ struct FieldQuant {
     const u64 *h_outl_off;             // block b's first record
     const u64 *h_outl_count;           // split: its capacity in records; merge: its records
     u64 *d_outl_n;                     // split: the outliers found per block
+    // the _grid_round entries (elem 2, 4 or 8): the quantiser is the rounding of the mantissa to h_keep[b] of its
+    // h_mant[b] bits, h_step and h_bound are not looked at, and the kernels are the rounding ones
+    bool round = false;
+    const u32 *h_mant = nullptr, *h_keep = nullptr;
 };
 int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags,
@@ -312,6 +316,11 @@ int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem
 int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
                                       const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const double *h_step,
                                       const double *h_bound, u64 *d_freq, u64 *d_outl_n);
+// the same for the planes the rounding grid split would write (elem 2, 4 or 8; rows, h_mant and h_keep checked by the caller)
+// 
+int planes_grid_round_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
+                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const u32 *h_mant,
+                                      const u32 *h_keep, u64 *d_freq, u64 *d_outl_n);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

@@ -40,6 +40,10 @@
 // recorded elements' own bits on top (planes_field_patch).
 // shafa_hipd_hist_planes_grid_quant_dev is to the quantising split what shafa_hipd_hist_planes_grid_dev is to the grid
 // split: the planes' histograms without the planes, and the outliers counted instead of recorded (planes_grid_quant_hist).
+// The GRID ROUND entries (shafa_hipd_split_planes_grid_round_dev, shafa_hipd_merge_planes_grid_round_dev,
+// shafa_hipd_hist_planes_grid_round_dev) are the three above with another quantiser: the element's mantissa rounded to
+// `keep` bits, half to even, in integer arithmetic on its own bits, for elements of 2, 4 and 8 bytes (planes_grid_round_split,
+// planes_round_restore, planes_grid_round_hist); the records, the patch pass and the histogram's composition are those entries'.
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -262,6 +266,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_split(const u8 *__rest
 // judges the very value the decoder will make.
 template <int E> struct FieldT { using F = float; using I = int; using U = u32; };
 template <> struct FieldT<8> { using F = double; using I = long long; using U = u64; };
+template <> struct FieldT<2> { using F = float; using I = short; using U = u16; };     // the patch pass alone: a record's 16 bits
 
 // a block's step, 1 / step and bound as T (uniform)
 template <int E> struct FieldQ {
@@ -428,6 +433,170 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_split(const u8 *
         case 1: split_tile_grid_quant<E, 1>(wk, r, lg, q, o, d_planes, poff); break;
         case 2: split_tile_grid_quant<E, 2>(wk, r, lg, q, o, d_planes, poff); break;
         default: split_tile_grid_quant<E, 3>(wk, r, lg, q, o, d_planes, poff); break;
+        }
+    }
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// ---- point-wise relative bounds (shafa_hipd_split_planes_grid_round_dev and its two companions): the grid split over
+// the CODES of bfloat16, float16, float or double elements whose mantissa is rounded to `keep` of its `mant` bits, half to even,
+// the carry free to enter the exponent.  All of it is unsigned integer arithmetic of the element's width W = 8 E on the element's
+// own bits (include/shafa_hip.h: "Point-wise relative bounds"), so a tap's unit rounds to what the lane that owns it stores and the
+// bit pattern 0 in front of the block to the code 0.  At E = 2 an element is taken out of its word, rounded in 32 bits and put
+// back masked to 16: no carry passes from one half of a word into the other.
+template <int E> struct RoundT { using U = u32; };
+template <> struct RoundT<8> { using U = u64; };
+
+// a block's rounding (uniform): d = mant - keep dropped bits; half = 2^(d - 1) - 1 and tie = 1, both 0 at d = 0; inf the bits of
+// +Inf, min those of the smallest normal
+template <int E> struct RoundQ {
+    typename RoundT<E>::U half, tie, inf, min;
+    u32 d;
+    __device__ __forceinline__ RoundQ(u64 row)       // the block's row: d in the low byte, mant in the next
+    {
+        using U = typename RoundT<E>::U;
+        const u32 mant = (u32)(row >> 8) & 0xFFu;
+        d = (u32)row & 0xFFu;
+        half = d ? (U)(((U)1 << (d - 1)) - 1) : (U)0;
+        tie = d ? 1 : 0;
+        inf = (U)((((U)1 << (8 * E - 1 - mant)) - 1) << mant);
+        min = (U)1 << mant;
+    }
+};
+
+// the code of the element with the bits x (E = 2: in the low 16 bits, and so is the code), and whether it is good
+template <int E>
+__device__ __forceinline__ typename RoundT<E>::U round_code(typename RoundT<E>::U x, const RoundQ<E> &q, bool &good)
+{
+    using U = typename RoundT<E>::U;
+    constexpr u32 W = 8 * E;
+    constexpr U MAG = (U)(((U)1 << (W - 1)) - 1);
+    const U m = x & MAG;
+    const bool special = m >= q.inf;                 // Inf and NaN: truncated, never carried
+    const U r = special ? (U)(m >> q.d) : (U)((U)(m + q.half + ((m >> q.d) & q.tie)) >> q.d);
+    const U back = (U)(r << q.d) & MAG;              // what the merge makes of the code
+    good = (special || m < q.min) ? back == m : back < q.inf;
+    const U code = (x >> (W - 1)) & 1 ? (U)(0 - r) : r;
+    return E == 2 ? (U)(code & 0xFFFFu) : code;
+}
+
+// the bits the merge makes of ANY code
+template <int E>
+__device__ __forceinline__ typename RoundT<E>::U round_value(typename RoundT<E>::U code, u32 d)
+{
+    using U = typename RoundT<E>::U;
+    constexpr u32 W = 8 * E;
+    constexpr U MAG = (U)(((U)1 << (W - 1)) - 1);
+    const U neg = (code >> (W - 1)) & 1;
+    const U a = neg ? (U)(0 - code) : code;
+    return (U)(neg << (W - 1)) | ((U)(a << d) & MAG);
+}
+
+// the 16 elements of w -> their codes as unsigned integers, in place; bad(i, bits) for each of the first c that is not good
+template <int E, class F>
+__device__ __forceinline__ void round_unit(u32 (&w)[4 * E], const RoundQ<E> &q, u32 c, F &&bad)
+{
+#pragma unroll
+    for (int i = 0; i < PL_UNIT; ++i) {
+        using U = typename RoundT<E>::U;
+        const U xb = E == 8 ? (U)((u64)w[(2 * i + 1) % (4 * E)] << 32 | w[(2 * i) % (4 * E)])
+                   : E == 4 ? (U)w[i % (4 * E)] : (U)((w[(i >> 1) % (4 * E)] >> (16 * (i & 1))) & 0xFFFFu);
+        bool good;
+        const U code = round_code<E>(xb, q, good);
+        if ((u32)i < c && !good) bad(i, (u64)xb);
+        if (E == 8) { w[(2 * i) % (4 * E)] = (u32)code; w[(2 * i + 1) % (4 * E)] = (u32)((u64)code >> 32); }
+        else if (E == 4) w[i % (4 * E)] = (u32)code;
+        else w[(i >> 1) % (4 * E)] = (i & 1) ? (w[(i >> 1) % (4 * E)] & 0xFFFFu) | (u32)code << 16
+                                             : (w[(i >> 1) % (4 * E)] & 0xFFFF0000u) | (u32)code;
+    }
+}
+
+template <int E>
+__device__ __forceinline__ void round_words(u32 (&w)[4 * E], const RoundQ<E> &q)
+{
+    round_unit<E>(w, q, 0u, [](int, u64) {});
+}
+
+// round_words for the lane's OWN unit from element e0: the first c = min(16, n - e0) elements are judged as well and one that is
+// not good is recorded, quant_words_judged's way
+template <int E>
+__device__ __forceinline__ void round_words_judged(u32 (&w)[4 * E], const RoundQ<E> &q, u64 e0, u32 c, const FieldOutl &o)
+{
+    round_unit<E>(w, q, c, [&](int i, u64 xb) {
+        const u64 slot = atomicAdd(o.count, 1ull);
+        if (slot < o.cap) {
+            gstore<u64>(o.rec + 2 * slot, e0 + (u64)i);
+            gstore<u64>(o.rec + 2 * slot + 1, xb);
+        }
+    });
+}
+
+// split_tile_grid_quant with the rounding for the quantiser
+template <int E, int Q>
+__device__ __forceinline__ void split_tile_grid_round(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
+                                                      const RoundQ<E> &q, const FieldOutl &o, u8 *d_planes, const u64 *poff)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+        round_words_judged<E>(w, q, e0, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), o);
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                round_words<E>(wb, q);               // the zeros in front of the block stay zeros
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        zz_fold<E, 4 * E>(w);
+        split_store<E>(w, wk.n, e0, d_planes, poff);
+    }
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them planes_grid_quant_split's five rows of nblk, the first d | mant
+// << 8 and the next two unused: then the block's first record in d_outl and its capacity in records.  d_outl_n has been zeroed on
+// the stream.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_round_split(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                      const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                      int nblk, const u64 *__restrict__ d_n, u8 *__restrict__ d_planes,
+                                                                      const u64 *__restrict__ d_poff, const u64 *__restrict__ d_lag,
+                                                                      int *__restrict__ err, u32 n_tiles, u32 per_wg,
+                                                                      u64 *__restrict__ d_outl, u64 *__restrict__ d_outl_n)
+{
+    const u64 *qp = d_lag + (u64)SHAFA_PLANES_GRID_LAGS * nblk;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u64 *poff = d_poff + (u64)wk.b * E;
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const RoundQ<E> q(qp[wk.b]);
+        const FieldOutl o = {d_outl + 2 * qp[3ull * nblk + wk.b], qp[4ull * nblk + wk.b], (unsigned long long *)d_outl_n + wk.b};
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: split_tile_grid_round<E, 0>(wk, r, lg, q, o, d_planes, poff); break;
+        case 1: split_tile_grid_round<E, 1>(wk, r, lg, q, o, d_planes, poff); break;
+        case 2: split_tile_grid_round<E, 2>(wk, r, lg, q, o, d_planes, poff); break;
+        default: split_tile_grid_round<E, 3>(wk, r, lg, q, o, d_planes, poff); break;
         }
     }
     tp_size_errors(cap, d_n, nblk, err);
@@ -665,6 +834,108 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_hist(const u8 *_
         case 1: hist_tile_grid_quant<E, 1>(wk, r, lg, q, h, outl); break;
         case 2: hist_tile_grid_quant<E, 2>(wk, r, lg, q, h, outl); break;
         default: hist_tile_grid_quant<E, 3>(wk, r, lg, q, h, outl); break;
+        }
+    }
+    if (cur_b >= 0) flush(cur_b);
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// ---- the histograms of the ROUNDING split's planes without the planes (shafa_hipd_hist_planes_grid_round_dev):
+// planes_grid_quant_hist with split_tile_grid_round's element path: the bins, the runs, the flush and the outlier count in a
+// register are that kernel's.
+template <int E, int Q>
+__device__ __forceinline__ void hist_tile_grid_round(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
+                                                     const RoundQ<E> &q, u32 *h, u32 &outl)
+{
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
+        if (e0 >= wk.n) continue;
+        u32 w[4 * E];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, w);
+        }
+        const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
+        round_unit<E>(w, q, c, [&](int, u64) { ++outl; });                      // round_words_judged with a count for the record
+#pragma nounroll
+        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
+            u64 dist = 0;
+            bool used = true;
+#pragma unroll
+            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
+                if (sub >> k & 1u) {
+                    used = used && lg[k] != 0;
+                    dist += lg[k];
+                }
+            if (!used) continue;                     // (uniform)
+            if (e0 + PL_UNIT > dist) {
+                u32 wb[4 * E];
+                lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                round_words<E>(wb, q);               // the zeros in front of the block stay zeros
+                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
+                else add_words<E>(w, wb);
+            }
+        }
+        zz_fold<E, 4 * E>(w);
+        hist_count<E>(w, c, h);
+    }
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them one row of nblk: d | mant << 8.  d_freq and d_outl_n have been
+// zeroed on the stream.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_round_hist(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                     const u64 *__restrict__ cap, const u32 *__restrict__ tbase,
+                                                                     int nblk, const u64 *__restrict__ d_n,
+                                                                     const u64 *__restrict__ d_lag, int *__restrict__ err,
+                                                                     u32 n_tiles, u64 *__restrict__ d_freq,
+                                                                     u64 *__restrict__ d_outl_n)
+{
+    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
+    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
+    const u32 tid = threadIdx.x;
+    u32 outl = 0;                                    // the lane's outliers of block cur_b since the last flush
+    // planes_grid_quant_hist's flush
+    auto flush = [&](int b) {
+        lds_barrier();
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            u32 c = 0;
+#pragma unroll
+            for (u32 q = 0; q < REP; ++q) {
+                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
+                c += *p;
+                *p = 0;
+            }
+            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
+        }
+        const u32 wsum = wave_reduce_add<u32>(outl);
+        if (wsum && lane_id() == 0) atomicAdd((unsigned long long *)d_outl_n + b, (unsigned long long)wsum);
+        outl = 0;
+        lds_barrier();
+    };
+    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
+    lds_barrier();
+    const u64 *qp = d_lag + (u64)SHAFA_PLANES_GRID_LAGS * nblk;
+    int cur_b = -1;                                  // the block whose counts the bins and the counters hold
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        if (wk.b != cur_b) {                         // (uniform)
+            if (cur_b >= 0) flush(cur_b);
+            cur_b = wk.b;
+        }
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const RoundQ<E> q(qp[wk.b]);
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: hist_tile_grid_round<E, 0>(wk, r, lg, q, h, outl); break;
+        case 1: hist_tile_grid_round<E, 1>(wk, r, lg, q, h, outl); break;
+        case 2: hist_tile_grid_round<E, 2>(wk, r, lg, q, h, outl); break;
+        default: hist_tile_grid_round<E, 3>(wk, r, lg, q, h, outl); break;
         }
     }
     if (cur_b >= 0) flush(cur_b);
@@ -1075,6 +1346,49 @@ __global__ __launch_bounds__(TP_THREADS) void planes_field_restore(u8 *__restric
     }
 }
 
+// ---- behind the grid merge of a rounded field: planes_field_restore's walk with round_value for the restorer, eight
+// elements a 16-byte word at E = 2.  d_q: the blocks' d | mant << 8.
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_round_restore(u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                   const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                                   const u64 *__restrict__ d_n, const u64 *__restrict__ d_q,
+                                                                   u32 n_tiles, u32 per_wg)
+{
+    using U = typename RoundT<E>::U;
+    using S = typename ElT<E>::T;                    // an element as it is stored
+    constexpr u32 PER = 16 / E;                      // elements of a word
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const u32 d = (u32)d_q[wk.b] & 0xFFu;
+        const u64 end = wk.pos0 + TP_TILE < wk.n ? wk.pos0 + TP_TILE : wk.n;
+        const u64 lo = (u64)(uintptr_t)wk.in + wk.pos0 * E, hi = (u64)(uintptr_t)wk.in + end * E;      // the tile's bytes
+        for (u64 a = (lo & ~(u64)15) + 16ull * threadIdx.x; a < hi; a += 16ull * TP_THREADS) {
+            u8 *p = (u8 *)(uintptr_t)a;
+            if (a >= lo && a + 16 <= hi) {
+                const uint4 v = gload<uint4>(p);
+                u32 x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (u32 i = 0; i < 4; ++i) {
+                    if (E == 8) {
+                        if (i & 1) {
+                            const u64 y = (u64)round_value<E>((U)((u64)x[i] << 32 | x[i - 1]), d);
+                            x[i - 1] = (u32)y; x[i] = (u32)(y >> 32);
+                        }
+                    } else if (E == 4) x[i] = (u32)round_value<E>((U)x[i], d);
+                    else x[i] = (u32)round_value<E>((U)(x[i] & 0xFFFFu), d) | (u32)round_value<E>((U)(x[i] >> 16), d) << 16;
+                }
+                gstore<uint4>(p, make_uint4(x[0], x[1], x[2], x[3]));
+            } else {
+#pragma unroll
+                for (u32 i = 0; i < PER; ++i) {
+                    const u64 at = a + (u64)i * E;
+                    if (at >= lo && at < hi) gstore<S>(p + i * E, (S)round_value<E>((U)gload<S>(p + i * E), d));
+                }
+            }
+        }
+    }
+}
+
 // the patch: one thread a record.  first[b]: the number of block b's first record among the call's (first[nblk]: their count);
 // rec_off[b]: its first record in d_outl.  A position at or past the block's size (a block past its capacity has none) is the
 // block's SHAFA_OUTSIDE_MODULE and nothing is written for it.
@@ -1186,6 +1500,28 @@ void field_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, 
                        a.cap, nblk, d_n, q + nblk, q + 2 * (size_t)nblk, d_outl, err);
 }
 
+// the rounding entries' launches on the same set-up and the same rows, the first of them d | mant << 8
+template <int E>
+void round_split_launch(const TileSetup &a, hipStream_t st, const u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err,
+                        u64 *d_outl, u64 *d_outl_n)
+{
+    hipLaunchKernelGGL(planes_grid_round_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
+                       d_planes, (const u64 *)a.extra[0], (const u64 *)a.extra[1], err, a.nt, a.per_wg, d_outl, d_outl_n);
+}
+
+template <int E>
+void round_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u64 records, const u64 *d_outl,
+                        int *err)
+{
+    const u64 *q = (const u64 *)a.extra[1] + (size_t)nblk * SHAFA_PLANES_GRID_LAGS;     // d | mant << 8, record places, running counts
+    hipLaunchKernelGGL(planes_round_restore<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n, q, a.nt,
+                       a.per_wg);
+    if (!records) return;
+    const u64 wgs = (records + TP_THREADS - 1) / TP_THREADS;
+    hipLaunchKernelGGL(planes_field_patch<E>, dim3((u32)(wgs < TP_MAX_WGS ? wgs : TP_MAX_WGS)), dim3(TP_THREADS), 0, st, d_el, a.off,
+                       a.cap, nblk, d_n, q + nblk, q + 2 * (size_t)nblk, d_outl, err);
+}
+
 // a double that is exactly a T -> T's bits; T(1 / step), the double division rounded to T once
 u64 field_bits_of(u32 elem, double v)
 {
@@ -1202,6 +1538,8 @@ double field_inverse(u32 elem, double step) { return elem == 8 ? 1.0 / step : (d
 // nothing) and an unused one as 0.  split: one launch.  merge: row 0 is the lag family's first pass, planes -> elements at the
 // block's smallest lag, clamped as the _lag entries clamp it, and 0 where that lag is 1: those blocks are the _diff merge's, which
 // skips the others; rows 1 and 2 are the passes in place over the elements.  All passes share one scratch, the stream their order.
+// fq->round (the _grid_round entries): the same rows with d | mant << 8 for the step's bits, the inverse's and the
+// bound's rows unused, and the rounding kernels for the quantising ones.
 // fq (the _grid_quant entries): the same upload carries, behind the rows of lags, the quantiser's rows — split: the bits of step,
 // 1 / step and bound as T, the first record and the capacity of every block; merge: the steps' bits, the first records and the
 // nblocks + 1 running counts of the records.
@@ -1216,10 +1554,12 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     if (fq) {                                        // the rows behind the lags: planes_grid_quant_split's, or the merge's
         u64 *q = lag.data() + nb * SHAFA_PLANES_GRID_LAGS;
         for (size_t b = 0; b < nb; ++b) {
-            q[b] = field_bits_of(elem, fq->h_step[b]);
+            q[b] = fq->round ? (u64)(fq->h_mant[b] - fq->h_keep[b]) | (u64)fq->h_mant[b] << 8 : field_bits_of(elem, fq->h_step[b]);
             if (!merge) {
-                q[nb + b] = field_bits_of(elem, field_inverse(elem, fq->h_step[b]));
-                q[2 * nb + b] = field_bits_of(elem, fq->h_bound[b]);
+                if (!fq->round) {
+                    q[nb + b] = field_bits_of(elem, field_inverse(elem, fq->h_step[b]));
+                    q[2 * nb + b] = field_bits_of(elem, fq->h_bound[b]);
+                }
                 q[3 * nb + b] = fq->h_outl_off[b];
                 q[4 * nb + b] = fq->h_outl_count[b];
             } else {                                 // the records' places, then the nb + 1 running counts of them
@@ -1261,7 +1601,11 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
     if (fq && !merge) {
         HIP_TRY(hipMemsetAsync(fq->d_outl_n, 0, nb * sizeof(u64), st));
-        if (elem == 4) field_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+        if (fq->round) {
+            if (elem == 2) round_split_launch<2>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+            else if (elem == 4) round_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+            else round_split_launch<8>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+        } else if (elem == 4) field_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
         else field_split_launch<8>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
         HIP_TRY(hipGetLastError());
         return SHAFA_SUCCESS;
@@ -1272,7 +1616,11 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     case 4: planes_grid_launch<4>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     default: planes_grid_launch<8>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     }
-    if (fq) {                                        // the codes -> the values, then the outliers on top
+    if (fq && fq->round) {                           // the codes -> the rounded bits, then the outliers on top
+        if (elem == 2) round_merge_launch<2>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
+        else if (elem == 4) round_merge_launch<4>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
+        else round_merge_launch<8>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
+    } else if (fq) {                                 // the codes -> the values, then the outliers on top
         if (elem == 4) field_merge_launch<4>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
         else field_merge_launch<8>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
     }
@@ -1332,6 +1680,35 @@ int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u3
     HIP_TRY(hipMemsetAsync(d_outl_n, 0, nb * sizeof(u64), st));
     const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
     auto kernel = elem == 4 ? planes_grid_quant_hist<4> : planes_grid_quant_hist<8>;
+    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
+                       bt->d_err, a.nt, d_freq, d_outl_n);
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
+// shafa_hipd_hist_planes_grid_round_dev.  h_lags, h_mant and h_keep as the _grid_round split's, checked by the
+// caller.  The device gets the grid split's rows of clamped lags and behind them a row of d | mant << 8.  The grid is
+// planes_grid_hist_launch_dev's.  One pair of memsets, one launch.
+int planes_grid_round_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
+                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const u32 *h_mant,
+                                      const u32 *h_keep, u64 *d_freq, u64 *d_outl_n)
+{
+    const size_t nb = (size_t)nblocks;
+    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 1), 0);
+    for (size_t b = 0; b < nb; ++b) {
+        for (u32 k = 0; k < nlags; ++k) {
+            const u64 g = h_lags[b * nlags + k];
+            lag[k * nb + b] = g < h_cap[b] ? g : 0;
+        }
+        lag[nb * SHAFA_PLANES_GRID_LAGS + b] = (u64)(h_mant[b] - h_keep[b]) | (u64)h_mant[b] << 8;
+    }
+    const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
+    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
+    HIP_TRY(hipMemsetAsync(d_outl_n, 0, nb * sizeof(u64), st));
+    const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
+    auto kernel = elem == 2 ? planes_grid_round_hist<2> : elem == 4 ? planes_grid_round_hist<4> : planes_grid_round_hist<8>;
     hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
                        bt->d_err, a.nt, d_freq, d_outl_n);
     HIP_TRY(hipGetLastError());
