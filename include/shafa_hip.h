@@ -802,6 +802,61 @@ int shafa_hipd_hist_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int
                                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_freq,
                                           uint64_t *d_outl_n);
 
+/* ---- Error statistics: what a bound costs --------------------------------------------------------------------------------
+ * The entries above give the rate half of a rate-distortion curve; these three give the distortion half, in one read of the
+ * tensor and without a temporary.  All three write one record of SHAFA_ERR_WORDS uint64_t per block, at d_stat + 12 b.  In block
+ * b, for element i < d_n[b]: x is the original element, y the element it comes back as, D(.) the conversion to double (exact for
+ * bfloat16, float16 and float), the element is FINITE when x and y both are, and e = |D(x) - D(y)| is one double subtraction
+ * (exact at elem 2 and 4, the rounded one at elem 8).  Every product and sum is one IEEE double operation, none contracted;
+ * overflow to Inf is carried as IEEE carries it.
+ *   word 0       n, the d_n[b] the kernel compared
+ *   word 1       the finite elements
+ *   word 2       the others (x or y is NaN or +-Inf)
+ *   word 3       of word 2, those where the bits of y differ from the bits of x
+ *   word 4       the outliers: the elements that are not good by the entry's rule; 0 from shafa_hipd_error_dev
+ *   word 5       the finite elements with e > h_abs[b] + h_rel[b] |D(x)| (one multiplication, one addition, one comparison);
+ *                0 from the other two entries
+ *   word 6       the sum of e e over the finite elements, the bits of a double
+ *   word 7       the sum of D(x) D(x) over the finite elements, the bits of a double
+ *   word 8       the largest e of the finite elements, the bits of a double; 0.0 where there is none
+ *   word 9       the smallest i among the finite elements whose e is word 8; 2^64 - 1 where there is none
+ *   word 10, 11  the smallest and the largest D(x) of the finite elements, the bits of doubles, a zero extreme as +0.0; +Inf and
+ *                -Inf where there is none
+ * shafa_hipd_error_dev: y is the element of d_a — a decoder's or a merge's output region: d_a and every h_a_off[b] are multiples
+ * of 16, as shafa_hipd_compare_dev has them — and x the element of d_ref at d_ref + h_ref_off[b], any multiple of elem: the
+ * original is read where it lies.  elem is 2, 4 or 8; h_cap[b] is block b's capacity in ELEMENTS; h_mant[b] is the format's mantissa
+ * width as the _round_dev entries take it (it tells bfloat16 from float16; one call may mix them); h_abs[b] is a double >= 0 or
+ * +Inf, h_rel[b] a finite double >= 0.
+ * shafa_hipd_error_quant_dev (elem 4 or 8): y is what shafa_hipd_merge_planes_grid_quant_dev gives back for h_step[b] and
+ * h_bound[b]: x' where the element is good, x bit for bit where it is an outlier.  There are no lags: a code depends on the
+ * element's own bits alone.  shafa_hipd_error_round_dev (elem 2, 4 or 8): the same under the rounding rule of "Point-wise relative
+ * bounds" for h_mant[b] and h_keep[b].  The blocks of all three are only read; those of the last two may overlap or coincide: one
+ * tensor, one block per bound or per keep, is the use.
+ * The sums are taken in a fixed order — a lane's elements by index, a fixed tree across the wave, the waves in order, one partial
+ * per tile of SHAFA_PLANES_TILE elements; then a block's partials in ascending order by the same tree — and there are no
+ * floating-point atomics: a block's record is a function of its elements, its count and its parameters alone, not of its
+ * alignment, of the other blocks of the call or of scheduling.  Two launches (tiles, then one workgroup a block), enqueues only,
+ * no workgroup waits for another.  d_n[b] > h_cap[b] is the block's SHAFA_OUTSIDE_MODULE through shafa_hipd_finish: no byte of
+ * the block is read and its record is twelve zeros.
+ * Argument errors return with nothing enqueued (checked before HIP is touched).  _quant_dev and _round_dev: the corresponding
+ * hist entry's checks in its order for the arguments they share (NULL b, d_in or d_n; elem; nblocks <= 0: SHAFA_SUCCESS; nblocks
+ * past the batch's; NULL h_cap; capacities past 2^64 bytes or 2^31 tiles: SHAFA_LACK_OF_MEMORY; NULL h_in_off, d_in or an offset
+ * that is no multiple of elem; the steps and bounds, or the widths and kept bits), then NULL d_stat.  shafa_hipd_error_dev: NULL
+ * d_a or d_ref or a d_a that is no multiple of 16, and elem; then shafa_hipd_compare_dev's checks of side a in its order (NULL b
+ * or d_n; nblocks; NULL h_a_off or h_cap; an h_a_off[b] that is no multiple of 16); the capacities as above; NULL h_ref_off, d_ref
+ * or an h_ref_off[b] that is no multiple of elem; then, each SHAFA_OUTSIDE_MODULE: NULL h_mant or a width that is not the
+ * format's, NULL d_stat, NULL h_abs or h_rel, an h_abs[b] that is NaN or < 0, an h_rel[b] that is NaN, < 0 or Inf. */
+#define SHAFA_ERR_WORDS 12
+int shafa_hipd_error_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint32_t *h_mant, const double *h_abs,
+                         const double *h_rel, const uint8_t *d_a, const uint64_t *h_a_off, const uint64_t *h_cap,
+                         const uint64_t *d_n, const uint8_t *d_ref, const uint64_t *h_ref_off, uint64_t *d_stat);
+int shafa_hipd_error_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const double *h_step,
+                               const double *h_bound, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                               const uint64_t *d_n, uint64_t *d_stat);
+int shafa_hipd_error_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint32_t *h_mant,
+                               const uint32_t *h_keep, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                               const uint64_t *d_n, uint64_t *d_stat);
+
 /* ---- Byte columns of fixed-width records: the plain transposes for any width 1 .. 64 ------------------------------------
  * An RGB image is 3-byte records, an xyz point cloud 12-byte records, a binary log whatever its struct is: column j of such
  * data — byte j of every record — has a histogram of its own, which the planes of a 1-, 2-, 4- or 8-byte element mix.  Block

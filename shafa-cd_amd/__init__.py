@@ -151,6 +151,9 @@ def lib():
                                                          vp, vp, u64p, u64p, u8p, u64p]
     L.shafa_hipd_hist_planes_grid_round_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, C.c_uint32, u64p, u32p, u32p, u8p, u64p, u64p,
                                                         vp, vp, vp]
+    L.shafa_hipd_error_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u32p, f64p, f64p, u8p, u64p, u64p, vp, u8p, u64p, vp]
+    L.shafa_hipd_error_quant_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, f64p, f64p, u8p, u64p, u64p, vp, vp]
+    L.shafa_hipd_error_round_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u32p, u32p, u8p, u64p, u64p, vp, vp]
     L.shafa_hipd_split_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_merge_planes_xor_dev.argtypes = [vp, vp, C.c_int, C.c_uint32, u8p, u64p, u8p, u64p, u64p, vp, u8p, u64p]
     L.shafa_hipd_seek_index_dev.argtypes =[vp, vp, C.c_int, u8p, u64p, u64p, vp, vp, C.c_uint32, C.c_int, u64p, vp, vp, vp]
@@ -220,6 +223,7 @@ def lib():
                  "shafa_hipd_split_planes_grid_quant_dev", "shafa_hipd_merge_planes_grid_quant_dev",
                  "shafa_hipd_hist_planes_grid_quant_dev", "shafa_hipd_split_planes_grid_round_dev",
                  "shafa_hipd_merge_planes_grid_round_dev", "shafa_hipd_hist_planes_grid_round_dev",
+                 "shafa_hipd_error_dev", "shafa_hipd_error_quant_dev", "shafa_hipd_error_round_dev",
                  "shafa_hipd_split_records_dev", "shafa_hipd_merge_records_dev"):
         getattr(L, name).restype = C.c_int
     _lib = L
@@ -730,6 +734,42 @@ class Batch:
         _check(lib().shafa_hipd_hist_planes_grid_round_dev(self.h, self._st(stream), len(io), elem, nl, _p64(lg), _pu32(mt), _pu32(kp),
                                                            _addr(d_in), _p64(io), _p64(ic), d_n.data_ptr(), d_freq.data_ptr(),
                                                            d_outl_n.data_ptr()), "hipd_hist_planes_grid_round_dev")
+
+    def error_dev(self, stream, elem, mant, abs_bound, rel_bound, d_a, a_off, cap, d_n, d_ref, ref_off, d_stat):
+        """The error statistics of what came back against the original: block b's d_n[b] <= cap[b] elements of `elem` = 2, 4 or 8
+        bytes at d_a + a_off[b] (a decoder's or a merge's output: multiples of 16) against the elements at d_ref + ref_off[b]
+        (any multiple of elem, read where they lie) -> the record of ERR_WORDS int64 at d_stat[12 b:]: counts, the two sums of
+        squares, the largest error and its position, the originals' extremes, and how many finite elements err by more than
+        abs_bound[b] + rel_bound[b] |x| (host floats, one per block; abs_bound may be inf).  mant[b]: the format's mantissa width
+        (7: bfloat16, 10: float16).  Enqueues only, two launches (include/shafa_hip.h: "Error statistics")."""
+        ao, ic, ro = _u64arr(a_off), _u64arr(cap), _u64arr(ref_off)
+        mt, ab, rl = _u32arr(mant), _f64arr(abs_bound), _f64arr(rel_bound)
+        if not len(mt) == len(ab) == len(rl) == len(ro) == len(ic) == len(ao):
+            raise ValueError("error_dev: one mant, abs_bound, rel_bound, offset and capacity per block")
+        _check(lib().shafa_hipd_error_dev(self.h, self._st(stream), len(ao), elem, _pu32(mt), _pf64(ab), _pf64(rl), _addr(d_a), _p64(ao),
+                                          _p64(ic), d_n.data_ptr(), _addr(d_ref), _p64(ro), d_stat.data_ptr()), "hipd_error_dev")
+
+    def error_quant_dev(self, stream, elem, step, bound, d_in, in_off, cap, d_n, d_stat):
+        """error_dev's record of the blocks at d_in + in_off[b] (elem 4 or 8) against what merge_planes_grid_quant_dev would give
+        back for step[b] and bound[b], made in registers: no planes, no records, no second tensor; word 4 counts the outliers,
+        which come back bit for bit.  The blocks are only read and may coincide: one tensor, one block per bound.  Enqueues
+        only, two launches (include/shafa_hip.h: "Error statistics")."""
+        io, ic = _u64arr(in_off), _u64arr(cap)
+        sp, bd = _f64arr(step), _f64arr(bound)
+        if not len(sp) == len(bd) == len(ic) == len(io):
+            raise ValueError("error_quant_dev: one step, bound, offset and capacity per block")
+        _check(lib().shafa_hipd_error_quant_dev(self.h, self._st(stream), len(io), elem, _pf64(sp), _pf64(bd), _addr(d_in), _p64(io),
+                                                _p64(ic), d_n.data_ptr(), d_stat.data_ptr()), "hipd_error_quant_dev")
+
+    def error_round_dev(self, stream, elem, mant, keep, d_in, in_off, cap, d_n, d_stat):
+        """error_quant_dev under the rounding rule: elem 2, 4 or 8, keep[b] of the format's mant[b] mantissa bits kept, as
+        hist_planes_grid_round_dev takes them.  Enqueues only, two launches (include/shafa_hip.h: "Error statistics")."""
+        io, ic = _u64arr(in_off), _u64arr(cap)
+        mt, kp = _u32arr(mant), _u32arr(keep)
+        if not len(mt) == len(kp) == len(ic) == len(io):
+            raise ValueError("error_round_dev: one mant, keep, offset and capacity per block")
+        _check(lib().shafa_hipd_error_round_dev(self.h, self._st(stream), len(io), elem, _pu32(mt), _pu32(kp), _addr(d_in), _p64(io),
+                                                _p64(ic), d_n.data_ptr(), d_stat.data_ptr()), "hipd_error_round_dev")
 
     def split_planes_xor_dev(self, stream, elem, d_in, in_off, d_base, base_off, cap, d_n, d_planes, plane_off):
         """split_planes_dev of (element XOR base element): block b's base is its elem * d_n[b] bytes at d_base + base_off[b],
@@ -3550,3 +3590,8 @@ from .fields import (FIELD_SLACK, CompressedField, choose_field_lags, compress_f
 from . import rounding  # noqa: E402
 from .rounding import (MANTISSA_BITS, CompressedRounded, compress_rounded, decompress_rounded, fit_keep_bits,  # noqa: E402,F401
                        restore_rounded, round_field, rounded_histograms, rounded_rates, rounded_sizes)
+
+# ------------------------------------------------------------------ error statistics: what a bound costs
+from . import quality  # noqa: E402
+from .quality import (ERR_WORDS, ErrorStats, field_curve, field_errors, fit_keep_bits_snr, fit_psnr,  # noqa: E402,F401
+                      rounded_curve, rounded_errors, tensor_errors, verify_fields, verify_rounded)

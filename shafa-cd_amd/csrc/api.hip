@@ -890,6 +890,74 @@ int shafa_hipd_hist_planes_grid_round_dev(shafa_hipd_batch *b, void *stream, int
                          h_mant, h_keep);
 }
 
+// error statistics.  The capacities of a call's blocks in elements: their bytes fit 64 bits and their tiles 31
+static bool error_caps_ok(uint32_t elem, int nblocks, const uint64_t *h_cap)
+{
+    u64 bytes = 0;
+    for (int i = 0; i < nblocks; ++i) {
+        if (h_cap[i] > ~0ull / elem || bytes + h_cap[i] * elem < bytes) return false;
+        bytes += h_cap[i] * elem;
+    }
+    return tile_count(nblocks, h_cap, SHAFA_PLANES_TILE) == nblocks;
+}
+
+// the fused entries: grid_hist_dev's checks in its order without the lags, the record for d_freq and d_outl_n
+static int error_fused_dev(ErrorArgs e, shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint8_t *d_in,
+                           const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint64_t *d_stat)
+{
+    if (!b || !d_in || !d_n) return SHAFA_OUTSIDE_MODULE;
+    if (elem != 4 && elem != 8 && !(elem == 2 && e.src == ERR_ROUND)) return SHAFA_OUTSIDE_MODULE;
+    if (nblocks <= 0) return SHAFA_SUCCESS;
+    if (nblocks > ((Batch *)b)->max_blocks) return SHAFA_LACK_OF_MEMORY;
+    if (!h_cap) return SHAFA_OUTSIDE_MODULE;
+    if (!error_caps_ok(elem, nblocks, h_cap)) return SHAFA_LACK_OF_MEMORY;
+    if (!h_in_off || (uintptr_t)d_in % elem) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_in_off[i] % elem) return SHAFA_OUTSIDE_MODULE;
+    if (e.src == ERR_QUANT && (!e.h_step || !e.h_bound || !field_params_ok(elem, nblocks, e.h_step, e.h_bound))) return SHAFA_OUTSIDE_MODULE;
+    if (e.src == ERR_ROUND && (!e.h_mant || !e.h_keep || !round_params_ok(elem, nblocks, e.h_mant, e.h_keep))) return SHAFA_OUTSIDE_MODULE;
+    if (!d_stat) return SHAFA_OUTSIDE_MODULE;
+    if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
+    return planes_error_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, e, d_in, h_in_off, h_cap, d_n, d_stat);
+}
+
+int shafa_hipd_error_quant_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const double *h_step,
+                               const double *h_bound, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                               const uint64_t *d_n, uint64_t *d_stat)
+{
+    const ErrorArgs e = {ERR_QUANT, nullptr, nullptr, h_step, h_bound, nullptr, nullptr, nullptr, nullptr};
+    return error_fused_dev(e, b, stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, d_stat);
+}
+
+int shafa_hipd_error_round_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint32_t *h_mant,
+                               const uint32_t *h_keep, const uint8_t *d_in, const uint64_t *h_in_off, const uint64_t *h_cap,
+                               const uint64_t *d_n, uint64_t *d_stat)
+{
+    const ErrorArgs e = {ERR_ROUND, h_mant, h_keep, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    return error_fused_dev(e, b, stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, d_stat);
+}
+
+int shafa_hipd_error_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, const uint32_t *h_mant, const double *h_abs,
+                         const double *h_rel, const uint8_t *d_a, const uint64_t *h_a_off, const uint64_t *h_cap,
+                         const uint64_t *d_n, const uint8_t *d_ref, const uint64_t *h_ref_off, uint64_t *d_stat)
+{
+    if (!d_a || !d_ref || ((uintptr_t)d_a & 15)) return SHAFA_OUTSIDE_MODULE;
+    if (elem != 2 && elem != 4 && elem != 8) return SHAFA_OUTSIDE_MODULE;
+    int rc;
+    if (!size_pass_check((Batch *)b, nblocks, h_a_off, h_cap, d_n, d_n, &rc)) return rc;    // compare_dev's side a; d_stat: below
+    if (!error_caps_ok(elem, nblocks, h_cap)) return SHAFA_LACK_OF_MEMORY;
+    if (!h_ref_off || (uintptr_t)d_ref % elem) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (h_ref_off[i] % elem) return SHAFA_OUTSIDE_MODULE;
+    if (!h_mant || !round_params_ok(elem, nblocks, h_mant, h_mant)) return SHAFA_OUTSIDE_MODULE;     // the widths alone: keep = mant
+    if (!d_stat || !h_abs || !h_rel) return SHAFA_OUTSIDE_MODULE;
+    for (int i = 0; i < nblocks; ++i)
+        if (!(h_abs[i] >= 0) || !(h_rel[i] >= 0) || std::isinf(h_rel[i])) return SHAFA_OUTSIDE_MODULE;
+    if ((rc = batch_enter((Batch *)b, (hipStream_t)stream))) return rc;
+    const ErrorArgs e = {ERR_PAIR, h_mant, nullptr, nullptr, nullptr, h_abs, h_rel, d_ref, h_ref_off};
+    return planes_error_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, e, d_a, h_a_off, h_cap, d_n, d_stat);
+}
+
 int shafa_hipd_split_records_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t width, const uint8_t *d_in,
                                  const uint64_t *h_in_off, const uint64_t *h_cap, const uint64_t *d_n, uint8_t *d_planes,
                                  const uint64_t *h_plane_off)

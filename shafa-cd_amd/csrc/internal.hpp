@@ -321,6 +321,20 @@ int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u3
 int planes_grid_round_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
                                       const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const u32 *h_mant,
                                       const u32 *h_keep, u64 *d_freq, u64 *d_outl_n);
+// the error statistics of the blocks at d_el + h_off[b] (elem 2, 4 or 8; everything checked by the caller), one record of
+// SHAFA_ERR_WORDS words a block at d_stat.  ERR_PAIR (shafa_hipd_error_dev): d_el is what came back, at multiples of
+// 16, the originals lie at d_ref + h_ref_off[b], and h_mant, h_abs and h_rel are the blocks'.  ERR_QUANT (elem 4 or 8) and
+// ERR_ROUND: d_el is the original and what comes back is made from it under h_step and h_bound, or h_mant and h_keep.
+enum ErrSrc { ERR_PAIR = 0, ERR_QUANT = 1, ERR_ROUND = 2 };
+struct ErrorArgs {
+    ErrSrc src;
+    const u32 *h_mant, *h_keep;
+    const double *h_step, *h_bound, *h_abs, *h_rel;
+    const u8 *d_ref;
+    const u64 *h_ref_off;
+};
+int planes_error_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const ErrorArgs &e, const u8 *d_el, const u64 *h_off,
+                            const u64 *h_cap, const u64 *d_n, u64 *d_stat);
 // block b's d_n[b] <= h_cap[b] records of `width` = 1 .. SHAFA_RECORDS_MAX_WIDTH bytes at d_rec + h_off[b] (any alignment) <-> their
 // byte columns, column j at d_planes + h_plane_off[b * width + j] (multiples of 16): split reads d_rec, merge writes it
 // (records.hip); the arguments have been checked and the capacities' tiles of SHAFA_RECORDS_TILE records number fewer than 2^31

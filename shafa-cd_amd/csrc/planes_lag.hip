@@ -942,6 +942,305 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_round_hist(const u8 *_
     tp_size_errors(cap, d_n, nblk, err);
 }
 
+// ---- error statistics (shafa_hipd_error_dev, shafa_hipd_error_quant_dev, shafa_hipd_error_round_dev): what a bound
+// costs.  x is the original element and y the element it comes back as: the element of a second tensor (ERR_PAIR), or what the
+// quantising (ERR_QUANT) or the rounding (ERR_ROUND) merge would give back, made in registers from x with the split's own
+// functions — x' where the element is good, x's own bits where it is an outlier.  The walk is hist_tile_grid_quant's without taps,
+// bins or LDS histograms: a lane loads its units of 16 elements and folds them, by index, into an ErrAgg.  Every sum, product and
+// comparison is one IEEE double operation, none contracted, and the order is fixed: the lane's elements by index, err_wave_reduce's
+// tree across the wave, the four waves in order, one partial of SHAFA_ERR_WORDS words a tile; planes_error_blocks folds a block's
+// partials in ascending tile order the same way.  No atomics: a block's record is a function of its elements, its count and its
+// parameters alone.
+constexpr u32 ERR_WORDS = SHAFA_ERR_WORDS;
+constexpr u64 ERR_NONE = ~0ull;
+
+// the statistics of a piece of a block: words 1 .. 11 of the record (include/shafa_hip.h: "Error statistics")
+struct ErrAgg {
+    u64 fin, oth, diff, outl, over;
+    double se2, sx2, emax;
+    u64 arg;
+    double xmin, xmax;
+};
+
+__device__ __forceinline__ ErrAgg err_identity()
+{
+    return {0, 0, 0, 0, 0, 0.0, 0.0, 0.0, ERR_NONE, __builtin_inf(), -__builtin_inf()};
+}
+
+// a's piece, then b's.  The largest error's position is the smallest one that holds it whatever the order of the pieces.
+__device__ __forceinline__ ErrAgg err_then(const ErrAgg &a, const ErrAgg &b)
+{
+#pragma clang fp contract(off)
+    ErrAgg r;
+    r.fin = a.fin + b.fin; r.oth = a.oth + b.oth; r.diff = a.diff + b.diff; r.outl = a.outl + b.outl; r.over = a.over + b.over;
+    r.se2 = a.se2 + b.se2;
+    r.sx2 = a.sx2 + b.sx2;
+    const bool tb = b.emax > a.emax || (b.emax == a.emax && b.arg < a.arg);
+    r.emax = tb ? b.emax : a.emax;
+    r.arg = tb ? b.arg : a.arg;
+    r.xmin = b.xmin < a.xmin ? b.xmin : a.xmin;
+    r.xmax = b.xmax > a.xmax ? b.xmax : a.xmax;
+    return r;
+}
+
+__device__ __forceinline__ ErrAgg err_from_lane(const ErrAgg &a, int d)
+{
+    ErrAgg o;
+    o.fin = __shfl_down((unsigned long long)a.fin, d, 64); o.oth = __shfl_down((unsigned long long)a.oth, d, 64);
+    o.diff = __shfl_down((unsigned long long)a.diff, d, 64); o.outl = __shfl_down((unsigned long long)a.outl, d, 64);
+    o.over = __shfl_down((unsigned long long)a.over, d, 64);
+    o.se2 = __shfl_down(a.se2, d, 64); o.sx2 = __shfl_down(a.sx2, d, 64); o.emax = __shfl_down(a.emax, d, 64);
+    o.arg = __shfl_down((unsigned long long)a.arg, d, 64);
+    o.xmin = __shfl_down(a.xmin, d, 64); o.xmax = __shfl_down(a.xmax, d, 64);
+    return o;
+}
+
+// tp_wave_reduce's tree: after the step of distance d lane l holds lanes [l, l + 2 d); lane 0 ends with the wave's
+__device__ __forceinline__ ErrAgg err_wave_reduce(ErrAgg a)
+{
+    const int lane = lane_id();
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const ErrAgg o = err_from_lane(a, d);
+        if (lane + d < 64) a = err_then(a, o);
+    }
+    return a;
+}
+
+// a piece's words 1 .. 11 at p (word 0 is the record's n, 0 in a partial)
+__device__ __forceinline__ void err_put(u64 *p, const ErrAgg &a)
+{
+    p[1] = a.fin; p[2] = a.oth; p[3] = a.diff; p[4] = a.outl; p[5] = a.over;
+    p[6] = __builtin_bit_cast(u64, a.se2); p[7] = __builtin_bit_cast(u64, a.sx2); p[8] = __builtin_bit_cast(u64, a.emax);
+    p[9] = a.arg;
+    p[10] = __builtin_bit_cast(u64, a.xmin); p[11] = __builtin_bit_cast(u64, a.xmax);
+}
+
+__device__ __forceinline__ ErrAgg err_get(const u64 *p)
+{
+    return {p[1], p[2], p[3], p[4], p[5], __builtin_bit_cast(double, p[6]), __builtin_bit_cast(double, p[7]),
+            __builtin_bit_cast(double, p[8]), p[9], __builtin_bit_cast(double, p[10]), __builtin_bit_cast(double, p[11])};
+}
+
+// the four waves' results in LDS, in order
+__device__ __forceinline__ ErrAgg err_waves(const u64 *slot)
+{
+    ErrAgg a = err_get(slot);
+#pragma unroll
+    for (int q = 1; q < TP_THREADS / 64; ++q) a = err_then(a, err_get(slot + (u32)q * ERR_WORDS));
+    return a;
+}
+
+// D(.): the element's value as a double, exact.  At 2 bytes it is taken from the bits: bfloat16 is the top half of a float,
+// float16 is put together from its fields (bf16: the block's format, uniform).
+template <int E>
+__device__ __forceinline__ double err_value(typename RoundT<E>::U bits, bool bf16)
+{
+#pragma clang fp contract(off)
+    if (E == 8) return __builtin_bit_cast(double, (u64)bits);
+    if (E == 4) return (double)__builtin_bit_cast(float, (u32)bits);
+    if (bf16) return (double)__builtin_bit_cast(float, (u32)bits << 16);
+    const u32 b = (u32)bits, ex = (b >> 10) & 31u, m = b & 0x3FFu;
+    const u64 s = (u64)((b >> 15) & 1u) << 63;
+    u64 d;
+    if (ex == 31u) d = 0x7FFull << 52 | (u64)m << 42;                          // Inf, NaN
+    else if (ex) d = (u64)(ex + 1008u) << 52 | (u64)m << 42;                   // normal: the exponent rebiased from 15 to 1023
+    else d = __builtin_bit_cast(u64, (double)(int)m * 0x1p-24);                // denormal or zero: m 2^-24
+    return __builtin_bit_cast(double, s | d);
+}
+
+// element i of the unit in w, E = 2 included (unit_elem there has the code's width)
+template <int E>
+__device__ __forceinline__ typename RoundT<E>::U err_elem(const u32 (&w)[4 * E], int i)
+{
+    if constexpr (E == 2) return (w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+    else return (typename RoundT<E>::U)unit_elem<E>(w, i);
+}
+
+// a block's parameters (uniform), from its three words of the launch's rows: ERR_PAIR mant, the bits of abs and of rel;
+// ERR_QUANT the bits of step, 1 / step and bound as T; ERR_ROUND d | mant << 8
+template <int E, int SRC> struct ErrQ;
+template <int E> struct ErrQ<E, ERR_PAIR> {
+    bool bf16;
+    double abs, rel;
+    __device__ __forceinline__ ErrQ(u64 q0, u64 q1, u64 q2)
+        : bf16(q0 == 7), abs(__builtin_bit_cast(double, q1)), rel(__builtin_bit_cast(double, q2)) {}
+};
+template <int E> struct ErrQ<E, ERR_QUANT> {
+    static constexpr bool bf16 = false;
+    FieldQ<E> q;
+    __device__ __forceinline__ ErrQ(u64 q0, u64 q1, u64 q2) : q{field_bits<E>(q0), field_bits<E>(q1), field_bits<E>(q2)} {}
+};
+template <int E> struct ErrQ<E, ERR_ROUND> {
+    bool bf16;
+    RoundQ<E> q;
+    __device__ __forceinline__ ErrQ(u64 q0, u64, u64) : bf16(((q0 >> 8) & 0xFFu) == 7), q(q0) {}
+};
+
+// the bits element xb comes back as under the block's rule, and whether it is good (an outlier comes back bit for bit)
+template <int E>
+__device__ __forceinline__ typename RoundT<E>::U err_back(typename RoundT<E>::U xb, const ErrQ<E, ERR_QUANT> &p, bool &good)
+{
+    using U = typename FieldT<E>::U;
+    bool in;
+    const typename FieldT<E>::I code = field_code<E>((U)xb, p.q.inv, in);
+    good = in && field_good<E>((U)xb, code, p.q);
+    return good ? (typename RoundT<E>::U)__builtin_bit_cast(U, field_value<E>(code, p.q.step)) : xb;
+}
+
+template <int E>
+__device__ __forceinline__ typename RoundT<E>::U err_back(typename RoundT<E>::U xb, const ErrQ<E, ERR_ROUND> &p, bool &good)
+{
+    const typename RoundT<E>::U code = round_code<E>(xb, p.q, good);
+    return good ? round_value<E>(code, p.q.d) : xb;
+}
+
+// one tile of one lane: its PL_UNITS units of 16 elements, by index.  x is read at xs (xs mod 16 = 4 Q + r, any multiple of E);
+// ERR_PAIR: y at wk.in, a multiple of 16.  wk.n elements in both.
+template <int E, int SRC, int Q>
+__device__ __forceinline__ ErrAgg err_tile(const TpWalk &wk, const u8 *xs, u32 r, const ErrQ<E, SRC> &p)
+{
+#pragma clang fp contract(off)
+    using U = typename RoundT<E>::U;
+    constexpr u32 NONE = ~0u;
+    const double inf = __builtin_inf();
+    u32 fin = 0, oth = 0, diff = 0, outl = 0, over = 0, arg = NONE;             // arg: the element's number within the tile
+    double se2 = 0.0, sx2 = 0.0, emax = 0.0, xmin = inf, xmax = -inf;
+#pragma nounroll
+    for (int u = 0; u < PL_UNITS; ++u) {
+        const u32 rel0 = (u32)u * PL_PASS + threadIdx.x * PL_UNIT;
+        const u64 e0 = wk.pos0 + rel0;
+        if (e0 >= wk.n) continue;
+        u32 wx[4 * E], wy[SRC == ERR_PAIR ? 4 * E : 1];
+        {
+            uint4 a[E + 1];
+            load_words<E, true>(xs, wk.n * E, e0 * E, 4u * Q + r, a);
+            shift_into<E, Q, false>(a, r, wx);
+        }
+        if constexpr (SRC == ERR_PAIR) {
+            uint4 a[E + 1];
+            load_words<E, true>(wk.in, wk.n * E, e0 * E, 0u, a);
+            shift_into<E, 0, false>(a, 0u, wy);
+        }
+        const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
+#pragma unroll
+        for (int i = 0; i < PL_UNIT; ++i) {
+            if ((u32)i >= c) continue;
+            const U xb = err_elem<E>(wx, i);
+            U yb;
+            if constexpr (SRC == ERR_PAIR) yb = err_elem<E>(wy, i);
+            else {
+                bool good;
+                yb = err_back<E>(xb, p, good);
+                if (!good) ++outl;
+            }
+            const double dx = err_value<E>(xb, p.bf16), dy = err_value<E>(yb, p.bf16);
+            if (__builtin_fabs(dx) < inf && __builtin_fabs(dy) < inf) {
+                const double e = __builtin_fabs(dx - dy);
+                ++fin;
+                se2 = se2 + e * e;
+                sx2 = sx2 + dx * dx;
+                if (e > emax || arg == NONE) { emax = e; arg = rel0 + (u32)i; }
+                xmin = dx < xmin ? dx : xmin;
+                xmax = dx > xmax ? dx : xmax;
+                if constexpr (SRC == ERR_PAIR)
+                    if (e > p.abs + p.rel * __builtin_fabs(dx)) ++over;
+            } else {
+                ++oth;
+                if (yb != xb) ++diff;
+            }
+        }
+    }
+    return {fin, oth, diff, outl, over, se2, sx2, emax, arg == NONE ? ERR_NONE : wk.pos0 + arg, xmin, xmax};
+}
+
+// q: three rows of nblk words, ErrQ's.  ERR_PAIR: d_el is side a (y) and block b's x lies at d_ref + ref_off[b]; else d_el is x.
+// part: ERR_WORDS words a tile of the capacities; the tiles below a block's d_n are written.
+template <int E, int SRC>
+__global__ __launch_bounds__(TP_THREADS) void planes_error_tiles(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                                 const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                                 const u64 *__restrict__ d_n, const u8 *__restrict__ d_ref,
+                                                                 const u64 *__restrict__ ref_off, const u64 *__restrict__ q,
+                                                                 u64 *__restrict__ part, u32 n_tiles, u32 per_wg)
+{
+    __shared__ u64 wres[2][TP_THREADS / 64][ERR_WORDS];     // the waves' results; the halves alternate: one barrier a tile
+    u32 turn = 0;
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        const ErrQ<E, SRC> p(q[wk.b], q[(u64)nblk + wk.b], q[2ull * nblk + wk.b]);
+        const u8 *xs = SRC == ERR_PAIR ? d_ref + ref_off[wk.b] : wk.in;
+        const u32 sh = (u32)((uintptr_t)xs & 15u), r = sh & 3u;
+        ErrAgg a;
+        switch (sh >> 2) {                           // uniform
+        case 0: a = err_tile<E, SRC, 0>(wk, xs, r, p); break;
+        case 1: a = err_tile<E, SRC, 1>(wk, xs, r, p); break;
+        case 2: a = err_tile<E, SRC, 2>(wk, xs, r, p); break;
+        default: a = err_tile<E, SRC, 3>(wk, xs, r, p); break;
+        }
+        a = err_wave_reduce(a);
+        u64 *slot = &wres[turn & 1u][0][0];
+        ++turn;
+        if (lane_id() == 0) err_put(slot + (u32)wave_id() * ERR_WORDS, a);
+        lds_barrier();
+        if (threadIdx.x == 0) {
+            u64 *dst = part + (u64)wk.t * ERR_WORDS;
+            const ErrAgg t = err_waves(slot);
+            u64 v[ERR_WORDS];
+            v[0] = 0;
+            err_put(v, t);
+#pragma unroll
+            for (u32 i = 0; i < ERR_WORDS; i += 2) gstore<uint4>(dst + i, make_uint4((u32)v[i], (u32)(v[i] >> 32), (u32)v[i + 1], (u32)(v[i + 1] >> 32)));
+        }
+    }
+}
+
+// one workgroup a block (grid-stride): a thread folds a run of consecutive partials in ascending tile order, then the same tree.
+// d_n[b] > cap[b]: SHAFA_OUTSIDE_MODULE and a record of zeros.
+__global__ __launch_bounds__(TP_THREADS) void planes_error_blocks(const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                                  const u64 *__restrict__ d_n, const u64 *__restrict__ part,
+                                                                  u64 *__restrict__ d_stat, int *__restrict__ err)
+{
+    __shared__ u64 wres[TP_THREADS / 64][ERR_WORDS];
+    const int tid = threadIdx.x;
+    for (int b = blockIdx.x; b < nblk; b += gridDim.x) {
+        const u64 n = d_n[b];
+        u64 *rec = d_stat + (u64)b * ERR_WORDS;
+        if (n > cap[b]) {                            // (uniform) past the block's region
+            if (tid < (int)ERR_WORDS) gstore<u64>(rec + tid, 0ull);
+            if (tid == 0) set_error(err + b, SHAFA_OUTSIDE_MODULE);
+            continue;
+        }
+        const u32 nt = (u32)((n + TP_TILE - 1) / TP_TILE);
+        const u64 *r = part + (u64)tbase[b] * ERR_WORDS;
+        const u32 per = (nt + TP_THREADS - 1) / TP_THREADS;
+        const u32 lo = (u32)tid * per < nt ? (u32)tid * per : nt, hi = lo + per < nt ? lo + per : nt;
+        ErrAgg a = err_identity();
+        for (u32 j = lo; j < hi; ++j) {
+            u64 v[ERR_WORDS];
+#pragma unroll
+            for (u32 i = 0; i < ERR_WORDS; i += 2) {
+                const uint4 x = gload<uint4>(r + (u64)j * ERR_WORDS + i);
+                v[i] = (u64)x.y << 32 | x.x; v[i + 1] = (u64)x.w << 32 | x.z;
+            }
+            a = err_then(a, err_get(v));
+        }
+        a = err_wave_reduce(a);
+        if (lane_id() == 0) err_put(&wres[wave_id()][0], a);
+        lds_barrier();
+        if (tid == 0) {
+            ErrAgg t = err_waves(&wres[0][0]);
+            if (t.xmin == 0.0) t.xmin = 0.0;         // a zero extreme is +0.0
+            if (t.xmax == 0.0) t.xmax = 0.0;
+            u64 v[ERR_WORDS];
+            v[0] = n;
+            err_put(v, t);
+#pragma unroll
+            for (u32 i = 0; i < ERR_WORDS; ++i) gstore<u64>(rec + i, v[i]);
+        }
+        lds_barrier();                               // the next block of this workgroup writes the wave results
+    }
+}
+
 // ---- merge
 // The three launches are templated on their SOURCE: LAG_PLANES the _lag entries' (d[i] unfolded from the planes),
 // LAG_PLANES_SKIP the same where a block whose lag is 0 is another family's and skipped (the grid merge's first pass), LAG_ELEMS
@@ -1736,6 +2035,45 @@ int planes_lag_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool
     case 4: planes_lag_launch<4>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     default: planes_lag_launch<8>(merge, sums, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     }
+    HIP_TRY(hipGetLastError());
+    return SHAFA_SUCCESS;
+}
+
+// the error entries.  The arguments have been checked by the caller.  The device gets three rows of nblocks words,
+// ErrQ's, and for shafa_hipd_error_dev the offsets of the originals; the scratch is one partial of SHAFA_ERR_WORDS words per tile
+// of the capacities.  Two launches: the tiles (where there is one), then one workgroup a block.
+int planes_error_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const ErrorArgs &e, const u8 *d_el, const u64 *h_off,
+                            const u64 *h_cap, const u64 *d_n, u64 *d_stat)
+{
+    const size_t nb = (size_t)nblocks;
+    std::vector<u64> q(nb * 3, 0);
+    for (size_t b = 0; b < nb; ++b) {
+        if (e.src == ERR_PAIR) {
+            q[b] = e.h_mant[b];
+            q[nb + b] = __builtin_bit_cast(u64, e.h_abs[b]);
+            q[2 * nb + b] = __builtin_bit_cast(u64, e.h_rel[b]);
+        } else if (e.src == ERR_QUANT) {
+            q[b] = field_bits_of(elem, e.h_step[b]);
+            q[nb + b] = field_bits_of(elem, field_inverse(elem, e.h_step[b]));
+            q[2 * nb + b] = field_bits_of(elem, e.h_bound[b]);
+        } else q[b] = (u64)(e.h_mant[b] - e.h_keep[b]) | (u64)e.h_mant[b] << 8;
+    }
+    const TileExtra x[2] = {{q.data(), q.size() * 8}, {e.h_ref_off, nb * 8}};
+    TileSetup a;
+    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, ERR_WORDS * sizeof(u64), 0, &a)) return rc;
+    using Tiles = void (*)(const u8 *, const u64 *, const u64 *, const u32 *, int, const u64 *, const u8 *, const u64 *, const u64 *,
+                           u64 *, u32, u32);
+    Tiles tiles;
+    if (e.src == ERR_PAIR)
+        tiles = elem == 2 ? planes_error_tiles<2, ERR_PAIR> : elem == 4 ? planes_error_tiles<4, ERR_PAIR> : planes_error_tiles<8, ERR_PAIR>;
+    else if (e.src == ERR_QUANT) tiles = elem == 4 ? planes_error_tiles<4, ERR_QUANT> : planes_error_tiles<8, ERR_QUANT>;
+    else tiles = elem == 2 ? planes_error_tiles<2, ERR_ROUND> : elem == 4 ? planes_error_tiles<4, ERR_ROUND> : planes_error_tiles<8, ERR_ROUND>;
+    if (a.nt)
+        hipLaunchKernelGGL(tiles, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, e.d_ref,
+                           (const u64 *)a.extra[1], (const u64 *)a.extra[0], (u64 *)a.scratch, a.nt, a.per_wg);
+    const u32 bw = (u32)nblocks < TP_MAX_BLOCK_WGS ? (u32)nblocks : TP_MAX_BLOCK_WGS;
+    hipLaunchKernelGGL(planes_error_blocks, dim3(bw), dim3(TP_THREADS), 0, st, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.scratch,
+                       d_stat, bt->d_err);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }
