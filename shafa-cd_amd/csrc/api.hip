@@ -856,14 +856,9 @@ static int grid_hist_dev(GridHist kind, shafa_hipd_batch *b, void *stream, int n
     if (kind == GH_ROUND && (!h_mant || !h_keep || !round_params_ok(elem, nblocks, h_mant, h_keep))) return SHAFA_OUTSIDE_MODULE;
     if (quant && !d_outl_n) return SHAFA_OUTSIDE_MODULE;
     if (int rc = batch_enter((Batch *)b, (hipStream_t)stream)) return rc;
-    if (kind == GH_ROUND)
-        return planes_grid_round_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags,
-                                                 h_lags, h_mant, h_keep, d_freq, d_outl_n);
-    if (quant)
-        return planes_grid_quant_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags,
-                                                 h_lags, h_step, h_bound, d_freq, d_outl_n);
+    const FieldQuant fq = {h_step, h_bound, nullptr, nullptr, nullptr, d_outl_n, kind == GH_ROUND, h_mant, h_keep};
     return planes_grid_hist_launch_dev((Batch *)b, (hipStream_t)stream, nblocks, elem, d_in, h_in_off, h_cap, d_n, nlags, h_lags,
-                                       d_freq);
+                                       quant ? &fq : nullptr, d_freq);
 }
 
 int shafa_hipd_hist_planes_grid_dev(shafa_hipd_batch *b, void *stream, int nblocks, uint32_t elem, uint32_t nlags,

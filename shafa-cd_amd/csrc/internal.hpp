@@ -308,19 +308,13 @@ void planes_diff_merge_enqueue(u32 elem, const TileSetup &a, hipStream_t st, u8 
                                const u8 *d_planes, int *err, const u64 *d_skip);
 // the histograms of the planes the grid split would write for these blocks, which may overlap, without the planes: d_freq[(b *
 // elem + j) * 256 + s] counts byte s in plane j of block b (planes_lag.hip).  A row of h_lags that is all zeros: plain planes, no
-// difference and no fold.  d_freq is zeroed first; the rows have been checked by the caller
+// difference and no fold.  d_freq is zeroed first; the rows have been checked by the caller.
+// fq: the same for the planes the quantising grid split would write (elem 4 or 8; rows, steps and bounds checked by the caller;
+// DESIGN 7.31) or, fq->round, the rounding one (elem 2, 4 or 8; rows, h_mant and h_keep checked by the caller), and
+// fq->d_outl_n[b] = the elements of block b that split would record, counted and not recorded; both are zeroed first.  The
+// records' fields of fq are not looked at
 int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off, const u64 *h_cap,
-                                const u64 *d_n, u32 nlags, const u64 *h_lags, u64 *d_freq);
-// the same for the planes the quantising grid split would write (elem 4 or 8; rows, steps and bounds checked by the caller), and
-// d_outl_n[b] = the elements of block b that split would record, counted and not recorded; both are zeroed first
-int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
-                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const double *h_step,
-                                      const double *h_bound, u64 *d_freq, u64 *d_outl_n);
-// the same for the planes the rounding grid split would write (elem 2, 4 or 8; rows, h_mant and h_keep checked by the caller)
-// 
-int planes_grid_round_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
-                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const u32 *h_mant,
-                                      const u32 *h_keep, u64 *d_freq, u64 *d_outl_n);
+                                const u64 *d_n, u32 nlags, const u64 *h_lags, const FieldQuant *fq, u64 *d_freq);
 // the error statistics of the blocks at d_el + h_off[b] (elem 2, 4 or 8; everything checked by the caller), one record of
 // SHAFA_ERR_WORDS words a block at d_stat.  ERR_PAIR (shafa_hipd_error_dev): d_el is what came back, at multiples of
 // 16, the originals lie at d_ref + h_ref_off[b], and h_mant, h_abs and h_rel are the blocks'.  ERR_QUANT (elem 4 or 8) and

@@ -1776,56 +1776,39 @@ void planes_grid_launch(bool merge, const GridPlan &gp, const TileSetup &a, hipS
             planes_lag_pass<E, LAG_ELEMS>(gp.pass_sums[k], a, st, d_el, nblk, d_n, nullptr, poff, lag + (size_t)k * nblk, err);
 }
 
-// the error-bounded entries' launches on planes_grid_launch_dev's set-up: extra 1 holds, behind the rows of lags, the rows that
-// function lays out for them
-template <int E>
-void field_split_launch(const TileSetup &a, hipStream_t st, const u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err,
-                        u64 *d_outl, u64 *d_outl_n)
-{
-    hipLaunchKernelGGL(planes_grid_quant_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
-                       d_planes, (const u64 *)a.extra[0], (const u64 *)a.extra[1], err, a.nt, a.per_wg, d_outl, d_outl_n);
-}
-
-template <int E>
-void field_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u64 records, const u64 *d_outl,
-                        int *err)
-{
-    const u64 *q = (const u64 *)a.extra[1] + (size_t)nblk * SHAFA_PLANES_GRID_LAGS;     // steps, record places, running counts
-    hipLaunchKernelGGL(planes_field_restore<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n, q, a.nt,
-                       a.per_wg);
-    if (!records) return;
-    const u64 wgs = (records + TP_THREADS - 1) / TP_THREADS;
-    hipLaunchKernelGGL(planes_field_patch<E>, dim3((u32)(wgs < TP_MAX_WGS ? wgs : TP_MAX_WGS)), dim3(TP_THREADS), 0, st, d_el, a.off,
-                       a.cap, nblk, d_n, q + nblk, q + 2 * (size_t)nblk, d_outl, err);
-}
-
-// the rounding entries' launches on the same set-up and the same rows, the first of them d | mant << 8
-template <int E>
-void round_split_launch(const TileSetup &a, hipStream_t st, const u8 *d_el, int nblk, const u64 *d_n, u8 *d_planes, int *err,
-                        u64 *d_outl, u64 *d_outl_n)
-{
-    hipLaunchKernelGGL(planes_grid_round_split<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n,
-                       d_planes, (const u64 *)a.extra[0], (const u64 *)a.extra[1], err, a.nt, a.per_wg, d_outl, d_outl_n);
-}
-
-template <int E>
-void round_merge_launch(const TileSetup &a, hipStream_t st, u8 *d_el, int nblk, const u64 *d_n, u64 records, const u64 *d_outl,
-                        int *err)
-{
-    const u64 *q = (const u64 *)a.extra[1] + (size_t)nblk * SHAFA_PLANES_GRID_LAGS;     // d | mant << 8, record places, running counts
-    hipLaunchKernelGGL(planes_round_restore<E>, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblk, d_n, q, a.nt,
-                       a.per_wg);
-    if (!records) return;
-    const u64 wgs = (records + TP_THREADS - 1) / TP_THREADS;
-    hipLaunchKernelGGL(planes_field_patch<E>, dim3((u32)(wgs < TP_MAX_WGS ? wgs : TP_MAX_WGS)), dim3(TP_THREADS), 0, st, d_el, a.off,
-                       a.cap, nblk, d_n, q + nblk, q + 2 * (size_t)nblk, d_outl, err);
-}
-
 // a double that is exactly a T -> T's bits; T(1 / step), the double division rounded to T once
 u64 field_bits_of(u32 elem, double v)
 {
     if (elem == 8) return __builtin_bit_cast(u64, v);
     return __builtin_bit_cast(u32, (float)v);
+}
+
+// the blocks' lags, nlags slots a block -> SHAFA_PLANES_GRID_LAGS rows of nb lags at `rows` (zeroed by the caller): a slot at or past
+// the block's capacity subtracts nothing and goes as 0, as an unused one does
+void grid_lag_rows(u64 *rows, size_t nb, const u64 *h_cap, u32 nlags, const u64 *h_lags)
+{
+    for (size_t b = 0; b < nb; ++b)
+        for (u32 k = 0; k < nlags; ++k) {
+            const u64 g = h_lags[b * nlags + k];
+            rows[k * nb + b] = g < h_cap[b] ? g : 0;
+        }
+}
+
+// a quantiser's device rows of nb words at q, as FieldQ, RoundQ and ErrQ read them.  h_mant non-NULL: the rounding's one row,
+// d | mant << 8.  Else the bits of the steps as T and, where the caller has bounds (the merge has none), two more rows: the bits
+// of 1 / step and of the bounds
+void quant_rows(u64 *q, size_t nb, u32 elem, const double *h_step, const double *h_bound, const u32 *h_mant, const u32 *h_keep)
+{
+    for (size_t b = 0; b < nb; ++b) {
+        if (h_mant) {
+            q[b] = (u64)(h_mant[b] - h_keep[b]) | (u64)h_mant[b] << 8;
+            continue;
+        }
+        q[b] = field_bits_of(elem, h_step[b]);
+        if (!h_bound) continue;
+        q[nb + b] = field_bits_of(elem, field_inverse(elem, h_step[b]));
+        q[2 * nb + b] = field_bits_of(elem, h_bound[b]);
+    }
 }
 
 }  // namespace
@@ -1839,9 +1822,9 @@ double field_inverse(u32 elem, double step) { return elem == 8 ? 1.0 / step : (d
 // skips the others; rows 1 and 2 are the passes in place over the elements.  All passes share one scratch, the stream their order.
 // fq->round (the _grid_round entries): the same rows with d | mant << 8 for the step's bits, the inverse's and the
 // bound's rows unused, and the rounding kernels for the quantising ones.
-// fq (the _grid_quant entries): the same upload carries, behind the rows of lags, the quantiser's rows — split: the bits of step,
-// 1 / step and bound as T, the first record and the capacity of every block; merge: the steps' bits, the first records and the
-// nblocks + 1 running counts of the records.
+// fq (the _grid_quant entries): the same upload carries, behind the rows of lags, the quantiser's rows (quant_rows) — split: the
+// bits of step, 1 / step and bound as T, the first record and the capacity of every block; merge: the steps' bits, the first
+// records and the nblocks + 1 running counts of the records.
 int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, bool merge, u8 *d_el, const u64 *h_off,
                            const u64 *h_cap, const u64 *d_n, u8 *d_planes, const u64 *h_plane_off, u32 nlags, const u64 *h_lags,
                            const FieldQuant *fq)
@@ -1852,13 +1835,9 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     u64 records = 0;
     if (fq) {                                        // the rows behind the lags: planes_grid_quant_split's, or the merge's
         u64 *q = lag.data() + nb * SHAFA_PLANES_GRID_LAGS;
+        quant_rows(q, nb, elem, fq->h_step, merge ? nullptr : fq->h_bound, fq->round ? fq->h_mant : nullptr, fq->h_keep);
         for (size_t b = 0; b < nb; ++b) {
-            q[b] = fq->round ? (u64)(fq->h_mant[b] - fq->h_keep[b]) | (u64)fq->h_mant[b] << 8 : field_bits_of(elem, fq->h_step[b]);
             if (!merge) {
-                if (!fq->round) {
-                    q[nb + b] = field_bits_of(elem, field_inverse(elem, fq->h_step[b]));
-                    q[2 * nb + b] = field_bits_of(elem, fq->h_bound[b]);
-                }
                 q[3 * nb + b] = fq->h_outl_off[b];
                 q[4 * nb + b] = fq->h_outl_count[b];
             } else {                                 // the records' places, then the nb + 1 running counts of them
@@ -1869,13 +1848,9 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
         }
         if (merge) q[3 * nb] = records;
     }
-    for (size_t b = 0; b < nb; ++b) {
+    grid_lag_rows(lag.data(), nb, h_cap, nlags, h_lags);
+    for (size_t b = 0; merge && b < nb; ++b) {
         const u64 cap = h_cap[b];
-        for (u32 k = 0; k < nlags; ++k) {
-            const u64 g = h_lags[b * nlags + k];
-            lag[k * nb + b] = g < cap ? g : 0;
-        }
-        if (!merge) continue;
         const u64 first = lag[b] ? lag[b] : cap ? cap : 1;
         if (first == 1) {
             gp.diff = true;
@@ -1898,14 +1873,17 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, sums ? (size_t)LAG_SUMS_TILE * elem : gp.diff ? 8 : 0, 0, &a))
         return rc;
     if (!a.wgs) a.wgs = 1;                           // without a tile one workgroup still looks for blocks past a capacity of 0
+    // the quantising kernels exist at 4 and 8 bytes, the rounding ones at 2 as well; both read their rows behind the rows of lags
     if (fq && !merge) {
+        using Split = void (*)(const u8 *, const u64 *, const u64 *, const u32 *, int, const u64 *, u8 *, const u64 *, const u64 *,
+                               int *, u32, u32, u64 *, u64 *);
+        Split split;
+        if (fq->round && elem == 2) split = planes_grid_round_split<2>;
+        else if (fq->round) split = elem == 4 ? planes_grid_round_split<4> : planes_grid_round_split<8>;
+        else split = elem == 4 ? planes_grid_quant_split<4> : planes_grid_quant_split<8>;
         HIP_TRY(hipMemsetAsync(fq->d_outl_n, 0, nb * sizeof(u64), st));
-        if (fq->round) {
-            if (elem == 2) round_split_launch<2>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
-            else if (elem == 4) round_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
-            else round_split_launch<8>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
-        } else if (elem == 4) field_split_launch<4>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
-        else field_split_launch<8>(a, st, d_el, nblocks, d_n, d_planes, bt->d_err, fq->d_outl, fq->d_outl_n);
+        hipLaunchKernelGGL(split, dim3(a.wgs), dim3(TP_THREADS), 0, st, (const u8 *)d_el, a.off, a.cap, a.tbase, nblocks, d_n, d_planes,
+                           (const u64 *)a.extra[0], (const u64 *)a.extra[1], bt->d_err, a.nt, a.per_wg, fq->d_outl, fq->d_outl_n);
         HIP_TRY(hipGetLastError());
         return SHAFA_SUCCESS;
     }
@@ -1915,101 +1893,60 @@ int planes_grid_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, boo
     case 4: planes_grid_launch<4>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     default: planes_grid_launch<8>(merge, gp, a, st, d_el, nblocks, d_n, d_planes, bt->d_err); break;
     }
-    if (fq && fq->round) {                           // the codes -> the rounded bits, then the outliers on top
-        if (elem == 2) round_merge_launch<2>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
-        else if (elem == 4) round_merge_launch<4>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
-        else round_merge_launch<8>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
-    } else if (fq) {                                 // the codes -> the values, then the outliers on top
-        if (elem == 4) field_merge_launch<4>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
-        else field_merge_launch<8>(a, st, d_el, nblocks, d_n, records, fq->d_outl, bt->d_err);
+    if (fq) {                                        // the codes -> the values or the rounded bits in place, then the outliers on top
+        using Restore = void (*)(u8 *, const u64 *, const u64 *, const u32 *, int, const u64 *, const u64 *, u32, u32);
+        using Patch = void (*)(u8 *, const u64 *, const u64 *, int, const u64 *, const u64 *, const u64 *, const u64 *, int *);
+        Restore restore;
+        Patch patch;
+        switch (elem) {
+        case 2: restore = planes_round_restore<2>, patch = planes_field_patch<2>; break;
+        case 4: restore = planes_round_restore<4>, patch = planes_field_patch<4>; break;
+        default: restore = planes_round_restore<8>, patch = planes_field_patch<8>; break;
+        }
+        if (!fq->round) restore = elem == 4 ? planes_field_restore<4> : planes_field_restore<8>;
+        const u64 *q = (const u64 *)a.extra[1] + nb * SHAFA_PLANES_GRID_LAGS;    // steps or d | mant << 8, record places, running counts
+        hipLaunchKernelGGL(restore, dim3(a.wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, q, a.nt, a.per_wg);
+        const u64 wgs = (records + TP_THREADS - 1) / TP_THREADS;
+        if (records)
+            hipLaunchKernelGGL(patch, dim3((u32)(wgs < TP_MAX_WGS ? wgs : TP_MAX_WGS)), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap,
+                               nblocks, d_n, q + nb, q + 2 * nb, fq->d_outl, bt->d_err);
     }
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }
 
-// shafa_hipd_hist_planes_grid_dev.  h_lags as the _grid entries', or a row of zeros: plain planes.  The device gets
-// the grid split's rows of clamped lags and a fourth row, 1 where the block's row is not all zeros.  The grid is this launcher's
-// own: a workgroup a run of SHAFA_PLANES_HIST_RUN consecutive tiles.  One memset, one launch.
+// the hist entries of the _grid family: shafa_hipd_hist_planes_grid_dev without fq, and with it
+// shafa_hipd_hist_planes_grid_quant_dev or, fq->round, shafa_hipd_hist_planes_grid_round_dev; of fq
+// the quantiser's parameters and d_outl_n are looked at.  h_lags as the _grid entries', checked by the caller; without fq a row
+// of zeros is allowed: plain planes.  The device gets the grid split's rows of clamped lags and behind them, without fq, a fourth
+// row, 1 where the block's row is not all zeros, else the quantiser's rows as the split gets them.  The grid is this launcher's
+// own: a workgroup a run of SHAFA_PLANES_HIST_RUN consecutive tiles.  One memset, with fq a second one of d_outl_n, one launch.
 int planes_grid_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off, const u64 *h_cap,
-                                const u64 *d_n, u32 nlags, const u64 *h_lags, u64 *d_freq)
+                                const u64 *d_n, u32 nlags, const u64 *h_lags, const FieldQuant *fq, u64 *d_freq)
 {
     const size_t nb = (size_t)nblocks;
-    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 1), 0);
-    for (size_t b = 0; b < nb; ++b)
-        for (u32 k = 0; k < nlags; ++k) {
-            const u64 g = h_lags[b * nlags + k];
-            lag[k * nb + b] = g < h_cap[b] ? g : 0;
-            if (g) lag[SHAFA_PLANES_GRID_LAGS * nb + b] = 1;
-        }
-    const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
-    TileSetup a;
-    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
-    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
-    const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
-    auto kernel = elem == 1 ? planes_grid_hist<1> : elem == 2 ? planes_grid_hist<2> : elem == 4 ? planes_grid_hist<4> : planes_grid_hist<8>;
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
-                       bt->d_err, a.nt, d_freq);
-    HIP_TRY(hipGetLastError());
-    return SHAFA_SUCCESS;
-}
-
-// shafa_hipd_hist_planes_grid_quant_dev.  h_lags, h_step and h_bound as the _grid_quant split's, checked by the
-// caller.  The device gets the grid split's rows of clamped lags and behind them the bits of step, 1 / step and bound as T.  The
-// grid is planes_grid_hist_launch_dev's.  One pair of memsets, one launch.
-int planes_grid_quant_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
-                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const double *h_step,
-                                      const double *h_bound, u64 *d_freq, u64 *d_outl_n)
-{
-    const size_t nb = (size_t)nblocks;
-    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 3), 0);
+    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + (fq && !fq->round ? 3 : 1)), 0);
     u64 *q = lag.data() + nb * SHAFA_PLANES_GRID_LAGS;
-    for (size_t b = 0; b < nb; ++b) {
-        for (u32 k = 0; k < nlags; ++k) {
-            const u64 g = h_lags[b * nlags + k];
-            lag[k * nb + b] = g < h_cap[b] ? g : 0;
-        }
-        q[b] = field_bits_of(elem, h_step[b]);
-        q[nb + b] = field_bits_of(elem, field_inverse(elem, h_step[b]));
-        q[2 * nb + b] = field_bits_of(elem, h_bound[b]);
-    }
+    grid_lag_rows(lag.data(), nb, h_cap, nlags, h_lags);
+    if (fq) quant_rows(q, nb, elem, fq->h_step, fq->h_bound, fq->round ? fq->h_mant : nullptr, fq->h_keep);
+    else
+        for (size_t b = 0; b < nb; ++b) q[b] = h_lags[b * nlags] != 0;    // a row that is not all zeros starts with a lag
     const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
     TileSetup a;
     if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
     HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
-    HIP_TRY(hipMemsetAsync(d_outl_n, 0, nb * sizeof(u64), st));
     const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
-    auto kernel = elem == 4 ? planes_grid_quant_hist<4> : planes_grid_quant_hist<8>;
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
-                       bt->d_err, a.nt, d_freq, d_outl_n);
-    HIP_TRY(hipGetLastError());
-    return SHAFA_SUCCESS;
-}
-
-// shafa_hipd_hist_planes_grid_round_dev.  h_lags, h_mant and h_keep as the _grid_round split's, checked by the
-// caller.  The device gets the grid split's rows of clamped lags and behind them a row of d | mant << 8.  The grid is
-// planes_grid_hist_launch_dev's.  One pair of memsets, one launch.
-int planes_grid_round_hist_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, const u8 *d_el, const u64 *h_off,
-                                      const u64 *h_cap, const u64 *d_n, u32 nlags, const u64 *h_lags, const u32 *h_mant,
-                                      const u32 *h_keep, u64 *d_freq, u64 *d_outl_n)
-{
-    const size_t nb = (size_t)nblocks;
-    std::vector<u64> lag(nb * (SHAFA_PLANES_GRID_LAGS + 1), 0);
-    for (size_t b = 0; b < nb; ++b) {
-        for (u32 k = 0; k < nlags; ++k) {
-            const u64 g = h_lags[b * nlags + k];
-            lag[k * nb + b] = g < h_cap[b] ? g : 0;
-        }
-        lag[nb * SHAFA_PLANES_GRID_LAGS + b] = (u64)(h_mant[b] - h_keep[b]) | (u64)h_mant[b] << 8;
+    if (!fq) {
+        auto kernel = elem == 1 ? planes_grid_hist<1> : elem == 2 ? planes_grid_hist<2> : elem == 4 ? planes_grid_hist<4> : planes_grid_hist<8>;
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n,
+                           (const u64 *)a.extra[0], bt->d_err, a.nt, d_freq);
+    } else {
+        HIP_TRY(hipMemsetAsync(fq->d_outl_n, 0, nb * sizeof(u64), st));
+        auto kernel = elem == 4 ? planes_grid_quant_hist<4> : planes_grid_quant_hist<8>;
+        if (fq->round) kernel = elem == 2 ? planes_grid_round_hist<2> : elem == 4 ? planes_grid_round_hist<4> : planes_grid_round_hist<8>;
+        hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n,
+                           (const u64 *)a.extra[0], bt->d_err, a.nt, d_freq, fq->d_outl_n);
     }
-    const TileExtra x[1] = {{lag.data(), lag.size() * 8}};
-    TileSetup a;
-    if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 1, 0, 0, &a)) return rc;
-    HIP_TRY(hipMemsetAsync(d_freq, 0, nb * elem * 256 * sizeof(u64), st));
-    HIP_TRY(hipMemsetAsync(d_outl_n, 0, nb * sizeof(u64), st));
-    const u32 wgs = a.nt ? (a.nt + GH_RUN - 1) / GH_RUN : 1;    // without a tile one workgroup still looks for blocks past a capacity of 0
-    auto kernel = elem == 2 ? planes_grid_round_hist<2> : elem == 4 ? planes_grid_round_hist<4> : planes_grid_round_hist<8>;
-    hipLaunchKernelGGL(kernel, dim3(wgs), dim3(TP_THREADS), 0, st, d_el, a.off, a.cap, a.tbase, nblocks, d_n, (const u64 *)a.extra[0],
-                       bt->d_err, a.nt, d_freq, d_outl_n);
     HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
 }
@@ -2047,17 +1984,13 @@ int planes_error_launch_dev(Batch *bt, hipStream_t st, int nblocks, u32 elem, co
 {
     const size_t nb = (size_t)nblocks;
     std::vector<u64> q(nb * 3, 0);
-    for (size_t b = 0; b < nb; ++b) {
-        if (e.src == ERR_PAIR) {
+    if (e.src != ERR_PAIR) quant_rows(q.data(), nb, elem, e.h_step, e.h_bound, e.src == ERR_ROUND ? e.h_mant : nullptr, e.h_keep);
+    else
+        for (size_t b = 0; b < nb; ++b) {
             q[b] = e.h_mant[b];
             q[nb + b] = __builtin_bit_cast(u64, e.h_abs[b]);
             q[2 * nb + b] = __builtin_bit_cast(u64, e.h_rel[b]);
-        } else if (e.src == ERR_QUANT) {
-            q[b] = field_bits_of(elem, e.h_step[b]);
-            q[nb + b] = field_bits_of(elem, field_inverse(elem, e.h_step[b]));
-            q[2 * nb + b] = field_bits_of(elem, e.h_bound[b]);
-        } else q[b] = (u64)(e.h_mant[b] - e.h_keep[b]) | (u64)e.h_mant[b] << 8;
-    }
+        }
     const TileExtra x[2] = {{q.data(), q.size() * 8}, {e.h_ref_off, nb * 8}};
     TileSetup a;
     if (int rc = tile_setup(bt, st, nblocks, h_off, h_cap, TP_TILE, x, 2, ERR_WORDS * sizeof(u64), 0, &a)) return rc;

@@ -14,8 +14,11 @@ of Batch.hist_planes_grid_quant_dev count the planes the quantising split would 
 and give the size under an order-0 model: which lags to take under a bound, the size at each bound of a list, the smallest bound
 that fits a budget.
 
-The drivers live in this submodule; the package re-exports them.  The coder's half of the chain (_coded_planes) and the decode
-chain (_merge_items) are the package's, reached through it at the time of the call."""
+The drivers live in this submodule; the package re-exports them.  Their chains are written for any Quantiser — this module's and
+rounding.py's, which keeps its checks, its item and its three entries and calls in here.  The histogram loop and the order-0 model
+are grids.py's, the coder's half of the chain (_coded_planes) and the decode chain (_merge_items) the package's, all reached
+through the package at the time of the call."""
+import collections
 import fractions
 import math
 import sys
@@ -115,7 +118,37 @@ def outlier_capacity(numel):
     return 16 + numel // 64
 
 
-# ---- the launches
+# ---- a quantiser, and the chains every quantiser shares
+# What differs between the quantising split and the rounding one (rounding.py) is data.  A tensor's parameters are its ROW, opaque
+# to the chains below: (step, bound) here, (mantissa width, kept bits) there; None marks a tensor that goes, or went, without the
+# quantiser — kept lossless.  `split`, `merge` and `hist` make the Batch call of one launch, f(bt, st, width, lags, rows, *rest):
+# they lay the launch's rows out as their entry takes them and hand the rest on as it is (`hist` is grids._histograms' and
+# grids._model_sizes').  `item(t, lags, row, lossless, planes, positions, bits, nbytes)` builds the driver's item for a tensor, and
+# with it the way the item says that it was kept lossless.
+Quantiser = collections.namedtuple("Quantiser", "split merge hist item")
+
+
+def _field_item(t, lags, row, lossless, planes, pos, bits, nbytes):
+    """compress_fields' rows carry the caller's abs_error behind step and bound; a step of 0.0 says lossless"""
+    step, bound = (0.0, 0.0) if lossless else row[:2]
+    return CompressedField(t.dtype, t.shape, lags, row[2], step, bound, planes, pos, bits, nbytes)
+
+
+_QUANT = Quantiser(
+    split=lambda bt, st, w, lags, rows, *rest: bt.split_planes_grid_quant_dev(st, w, lags, [r[0] for r in rows],
+                                                                              [r[1] for r in rows], *rest),
+    merge=lambda bt, st, w, lags, rows, *rest: bt.merge_planes_grid_quant_dev(st, w, lags, [r[0] for r in rows], *rest),
+    hist=lambda bt, st, w, lags, rows, *rest: bt.hist_planes_grid_quant_dev(st, w, lags, [r[0] for r in rows],
+                                                                            [r[1] for r in rows], *rest),
+    item=_field_item)
+
+
+def _device_lags(lags, numel):
+    """the row of lags the entries get: () — rounding.py's "no differences" — is a lag at the capacity, which subtracts nothing in
+    split and merge alike"""
+    return tuple(lags) if len(lags) else (max(int(numel), 1),)
+
+
 def _layout(units):
     """_split_into's planes buffer: each tensor's plane offsets, multiples of 16, and the buffer's bytes"""
     poff, pos = [], 0
@@ -126,9 +159,9 @@ def _layout(units):
     return poff, pos + 16
 
 
-def _split_fields(bt, st, dev, ts, units, lags, params, caps, buf, poff):
-    """one quantising split per element size over ts into buf -> (the records buffer [sum caps, 2], each tensor's first record,
-    the counts of outliers found, one per tensor of the launches in their order, and that order)"""
+def _split(q, bt, st, dev, ts, units, lags, rows, caps, buf, poff):
+    """one split of the quantiser q per element size over ts into buf -> (the records buffer [sum caps, 2], each tensor's first
+    record, the counts of outliers found, one per tensor of the launches in their order, and that order)"""
     import torch
     first, pos = [], 0
     for c in caps:
@@ -142,11 +175,10 @@ def _split_fields(bt, st, dev, ts, units, lags, params, caps, buf, poff):
     at = 0
     for w, idx in groups:
         base = min(ts[i].data_ptr() for i in idx)
-        bt.split_planes_grid_quant_dev(st, w, [tuple(lags[i]) for i in idx], [params[i][0] for i in idx],
-                                       [params[i][1] for i in idx], base, [ts[i].data_ptr() - base for i in idx],
-                                       [units[i][0] for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]],
-                                       d_outl if pos else None, [first[i] for i in idx], [caps[i] for i in idx],
-                                       d_found[at:at + len(idx)])
+        q.split(bt, st, w, [_device_lags(lags[i], units[i][0]) for i in idx], [rows[i] for i in idx], base,
+                [ts[i].data_ptr() - base for i in idx], [units[i][0] for i in idx], d_n[at:at + len(idx)], buf,
+                [o for i in idx for o in poff[i]], d_outl if pos else None, [first[i] for i in idx], [caps[i] for i in idx],
+                d_found[at:at + len(idx)])
         at += len(idx)
     return d_outl, first, d_found, order
 
@@ -158,58 +190,45 @@ def _sorted_records(rec):
     return pos, rec[:, 1][by].clone()
 
 
-def _merge_fields(items, steps):
-    """_merge_into's stand-in for decompress_fields: the lossless items (a step of 0) through _merge_into as decompress_grids'
-    go, the others through one merge_planes_grid_quant_dev per element size"""
+def _merge(q, records, rows):
+    """_merge_into's stand-in for the decode chain (_merge_items) over tensors with the outliers records[i] = (positions, bits):
+    those kept lossless (a row of None) through _merge_into as decompress_grids' go, the others through one merge of the
+    quantiser q per element size"""
     def merge_into(bt, st, dev, planes, outs, units, kind, lags):
         import torch
-        plain = [i for i in range(len(items)) if not steps[i]]
+        lags = [_device_lags(g, n) for g, (n, _) in zip(lags, units)]
+        plain = [i for i in range(len(rows)) if rows[i] is None]
         if plain:
             _pkg._merge_into(bt, st, dev, [planes[i] for i in plain], [outs[i] for i in plain], [units[i] for i in plain], kind,
                              [lags[i] for i in plain])
-        quant = [(n, w) if steps[i] else (0, w) for i, (n, w) in enumerate(units)]
-        groups = _pkg._by_width(quant)
+        groups = _pkg._by_width([(n, w) if rows[i] is not None else (0, w) for i, (n, w) in enumerate(units)])
         if not groups:
             return
         planes = [[p if p.data_ptr() % 16 == 0 else p.clone() for p in ps] for ps in planes]
         order = [i for _, idx in groups for i in idx]
         d_n = torch.tensor([units[i][0] for i in order], dtype=torch.int64, device=dev)
-        counts = [int(it.outlier_pos.numel()) for it in items]
+        counts = [int(pos.numel()) for pos, _ in records]
         first, pos = {}, 0
         for i in order:
             first[i] = pos
             pos += counts[i]
-        d_outl = torch.stack([torch.cat([items[i].outlier_pos for i in order if counts[i]]),
-                              torch.cat([items[i].outlier_bits for i in order if counts[i]])], 1).contiguous() if pos else None
+        d_outl = torch.stack([torch.cat([records[i][j] for i in order if counts[i]]) for j in (0, 1)], 1).contiguous() if pos else None
         at = 0
         for w, idx in groups:
             pbase = min(p.data_ptr() for i in idx for p in planes[i])
             obase = min(outs[i].data_ptr() for i in idx)
-            bt.merge_planes_grid_quant_dev(st, w, [tuple(lags[i]) for i in idx], [steps[i] for i in idx], pbase,
-                                           [p.data_ptr() - pbase for i in idx for p in planes[i]], [units[i][0] for i in idx],
-                                           d_n[at:at + len(idx)], d_outl, [first[i] for i in idx], [counts[i] for i in idx], obase,
-                                           [outs[i].data_ptr() - obase for i in idx])
+            q.merge(bt, st, w, [lags[i] for i in idx], [rows[i] for i in idx], pbase,
+                    [p.data_ptr() - pbase for i in idx for p in planes[i]], [units[i][0] for i in idx], d_n[at:at + len(idx)], d_outl,
+                    [first[i] for i in idx], [counts[i] for i in idx], obase, [outs[i].data_ptr() - obase for i in idx])
             at += len(idx)
     return merge_into
 
 
-# ---- one tensor, no coder
-def quantize_field(t, abs_error, lags):
-    """The byte planes of the Lorenzo differences of a float32 or float64 CUDA tensor's CODES under the absolute error bound
-    `abs_error`, and its outliers: (planes, positions, bits).  `planes` is split_grid's [k, numel] uint8 tensor over the codes
-    rint(x * T(1 / step)) as integers of the element's width, step = 2 abs_error (1 - FIELD_SLACK) rounded down into the dtype;
-    `positions` (int64, sorted) and `bits` (int64) are the elements whose restored value code * step misses abs_error (rounded
-    down into the dtype) or that have no code: restore_field gives those back bit for bit and every other within the bound.
-    `lags` as split_grid takes them.  One split_planes_grid_quant_dev launch, a second one with room for every outlier found
-    where outlier_capacity's records were too few; one synchronisation each."""
+def _quantise_one(q, t, lags, row):
+    """quantize_field's chain for a checked tensor and any quantiser: one split, a second one with room for every outlier found
+    where outlier_capacity's records were too few -> (planes, positions, bits)"""
     import torch
-    what = "quantize_field"
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{what}: a contiguous CUDA tensor")
-    t = _field_tensors(what, t)[0]
-    lags = _pkg.grids._lag_tuple(what, lags)
     k, n = t.element_size(), t.numel()
-    params = [_params(what, abs_error, k)]
     dev = t.device
     st = _pkg._plane_stream(dev, stream=None)
     poff, nbytes = _layout([(n, k)])
@@ -219,7 +238,7 @@ def quantize_field(t, abs_error, lags):
         try:
             cap, found, d_outl = outlier_capacity(n), 0, None
             while n:
-                d_outl, _, d_found, _ = _split_fields(bt, st, dev, [t], [(n, k)], [lags], params, [cap], buf, poff)
+                d_outl, _, d_found, _ = _split(q, bt, st, dev, [t], [(n, k)], [lags], [row], [cap], buf, poff)
                 bt.finish(st, 1)
                 found = int(d_found.cpu()[0])
                 if found <= cap:
@@ -244,6 +263,104 @@ def _records(what, positions, bits, dev):
             raise ValueError(f"{what}: the outliers are CUDA tensors on the planes' device")
 
 
+def _restore_one(q, what, planes, dtype, shape, k, n, lags, row, positions, bits, stream):
+    """restore_field's chain for any quantiser, behind the checks of dtype, shape, lags and row: the checks of the planes and the
+    records, then one merge"""
+    import torch
+    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
+            or (planes.shape[1] > 1 and planes.stride(1) != 1):
+        raise ValueError(f"{what}: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
+    if tuple(planes.shape) != (k, n):
+        raise ValueError(f"{what}: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
+    _records(what, positions, bits, planes.device)
+    dev = planes.device
+    st = _pkg._plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        out = torch.empty(shape, dtype=dtype, device=dev)
+        bt = _pkg.Batch(1, 1 << 20)
+        try:
+            _merge(q, [(positions, bits)], [row])(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out], [(n, k)],
+                                                  "planes_grid", [lags])
+            bt.finish(st, 1)
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return out
+
+
+def _compress(what, q, ts, lags, rows, block_size, stream):
+    """compress_fields' chain for checked tensors and any quantiser: one split per element size, one finish and one read-back of
+    the outlier counts; the tensors that found more than their capacity take compress_grids' split in the same places and are
+    kept lossless; then the coder, and one item per tensor with its records sorted by position"""
+    import torch
+    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
+        raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
+    if not ts:
+        return []
+    dev = ts[0].device
+    units = _pkg._elements(ts)
+    caps = [outlier_capacity(n) if n else 0 for n, _ in units]
+    poff, nbytes = _layout(units)
+    st = _pkg._plane_stream(dev, stream)
+    found = [0] * len(ts)
+    with torch.cuda.stream(st):
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        bt = _pkg.Batch(len(ts), 1 << 20)
+        try:
+            if any(n for n, _ in units):
+                d_outl, first, d_found, order = _split(q, bt, st, dev, ts, units, lags, rows, caps, buf, poff)
+                bt.finish(st, len(ts))
+                for i, c in zip(order, d_found.cpu().tolist()):
+                    found[i] = c
+            lossless = [i for i in range(len(ts)) if found[i] > caps[i]]
+            if lossless:                             # compress_grids' planes in the same places
+                groups = [(w, [lossless[j] for j in idx]) for w, idx in _pkg._by_width([units[i] for i in lossless])]
+                d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
+                at = 0
+                for w, idx in groups:
+                    base = min(ts[i].data_ptr() for i in idx)
+                    bt.split_planes_grid_dev(st, w, [_device_lags(lags[i], units[i][0]) for i in idx], base,
+                                             [ts[i].data_ptr() - base for i in idx], [units[i][0] for i in idx],
+                                             d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
+                    at += len(idx)
+                bt.finish(st, len(ts))
+        finally:
+            bt.close()
+        entries = _pkg._coded_planes(buf, poff, units, block_size, st)
+        none = torch.empty(0, dtype=torch.int64, device=dev)
+        items = []
+        for i, (t, ps, nb) in enumerate(zip(ts, entries, _pkg._entry_bytes(entries))):
+            keep = found[i] and i not in lossless
+            pos, bits = _sorted_records(d_outl[first[i]:first[i] + found[i]]) if keep else (none, none)
+            items.append(q.item(t, lags[i], rows[i], i in lossless, ps, pos, bits, nb + (8 + t.element_size()) * int(pos.numel())))
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return items
+
+
+def _decompress(what, q, items, lags, rows, stream):
+    """decompress_fields' chain for checked items and any quantiser: the decode chain with _merge for its merge"""
+    return _pkg._merge_items(what, items, "planes_grid", lags, False, stream,
+                             _merge(q, [(it.outlier_pos, it.outlier_bits) for it in items], rows))
+
+
+# ---- one tensor, no coder
+def quantize_field(t, abs_error, lags):
+    """The byte planes of the Lorenzo differences of a float32 or float64 CUDA tensor's CODES under the absolute error bound
+    `abs_error`, and its outliers: (planes, positions, bits).  `planes` is split_grid's [k, numel] uint8 tensor over the codes
+    rint(x * T(1 / step)) as integers of the element's width, step = 2 abs_error (1 - FIELD_SLACK) rounded down into the dtype;
+    `positions` (int64, sorted) and `bits` (int64) are the elements whose restored value code * step misses abs_error (rounded
+    down into the dtype) or that have no code: restore_field gives those back bit for bit and every other within the bound.
+    `lags` as split_grid takes them.  One split_planes_grid_quant_dev launch, a second one with room for every outlier found
+    where outlier_capacity's records were too few; one synchronisation each."""
+    import torch
+    what = "quantize_field"
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: a contiguous CUDA tensor")
+    t = _field_tensors(what, t)[0]
+    lags = _pkg.grids._lag_tuple(what, lags)
+    return _quantise_one(_QUANT, t, lags, _params(what, abs_error, t.element_size()))
+
+
 def _step(what, step, k):
     if isinstance(step, bool) or not isinstance(step, (int, float)) or not _legal(float(step), k) \
             or (k == 4 and float(np.float32(step)) != step) or not math.isfinite(_inverse(float(step), k)):
@@ -262,26 +379,7 @@ def restore_field(planes, dtype, shape, lags, step, positions, bits, stream=None
     k, shape, n = _pkg._plane_dtype(what, dtype, shape)
     lags = _pkg.grids._lag_tuple(what, lags)
     step = _step(what, step, k)
-    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
-            or (planes.shape[1] > 1 and planes.stride(1) != 1):
-        raise ValueError(f"{what}: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
-    if tuple(planes.shape) != (k, n):
-        raise ValueError(f"{what}: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
-    _records(what, positions, bits, planes.device)
-    dev = planes.device
-    item = CompressedField(dtype, shape, lags, step, step, step, [], positions, bits, 0)
-    st = _pkg._plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        out = torch.empty(shape, dtype=dtype, device=dev)
-        bt = _pkg.Batch(1, 1 << 20)
-        try:
-            _merge_fields([item], [step])(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out], [(n, k)], "planes_grid",
-                                          [lags])
-            bt.finish(st, 1)
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return out
+    return _restore_one(_QUANT, what, planes, dtype, shape, k, n, lags, (step,), positions, bits, stream)
 
 
 # ---- the drivers
@@ -309,54 +407,11 @@ def compress_fields(tensors, abs_error, axes=None, lags=None, block_size=8 << 20
     one read-back of the outlier counts (the tensors kept lossless then take one split_planes_grid_dev per element size and a
     finish) -> compressed_sizes -> compress_many, as compress_tensors; a tensor's records are sorted by position, so an item
     is reproducible."""
-    import torch
     what = "compress_fields"
     ts = _field_tensors(what, tensors)
     lags = _pkg.grids._lags(what, ts, axes, lags)
     errs, params = _abs_errors(what, ts, abs_error)
-    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
-        raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
-    if not ts:
-        return []
-    dev = ts[0].device
-    units = _pkg._elements(ts)
-    caps = [outlier_capacity(n) if n else 0 for n, _ in units]
-    poff, nbytes = _layout(units)
-    st = _pkg._plane_stream(dev, stream)
-    found = [0] * len(ts)
-    with torch.cuda.stream(st):
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        bt = _pkg.Batch(len(ts), 1 << 20)
-        try:
-            if any(n for n, _ in units):
-                d_outl, first, d_found, order = _split_fields(bt, st, dev, ts, units, lags, params, caps, buf, poff)
-                bt.finish(st, len(ts))
-                for i, c in zip(order, d_found.cpu().tolist()):
-                    found[i] = c
-            lossless = [i for i in range(len(ts)) if found[i] > caps[i]]
-            if lossless:                             # compress_grids' planes in the same places
-                groups = [(w, [lossless[j] for j in idx]) for w, idx in _pkg._by_width([units[i] for i in lossless])]
-                d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
-                at = 0
-                for w, idx in groups:
-                    base = min(ts[i].data_ptr() for i in idx)
-                    bt.split_planes_grid_dev(st, w, [tuple(lags[i]) for i in idx], base, [ts[i].data_ptr() - base for i in idx],
-                                             [units[i][0] for i in idx], d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
-                    at += len(idx)
-                bt.finish(st, len(ts))
-        finally:
-            bt.close()
-        entries = _pkg._coded_planes(buf, poff, units, block_size, st)
-        none = torch.empty(0, dtype=torch.int64, device=dev)
-        items = []
-        for i, (t, ps, nb) in enumerate(zip(ts, entries, _pkg._entry_bytes(entries))):
-            keep = found[i] and i not in lossless
-            pos, bits = _sorted_records(d_outl[first[i]:first[i] + found[i]]) if keep else (none, none)
-            step, bound = (0.0, 0.0) if i in lossless else params[i]
-            items.append(CompressedField(t.dtype, t.shape, lags[i], errs[i], step, bound, ps, pos, bits,
-                                         nb + (8 + t.element_size()) * int(pos.numel())))
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return items
+    return _compress(what, _QUANT, ts, lags, [p + (e,) for p, e in zip(params, errs)], block_size, stream)
 
 
 # ---- sizes under a bound: the quantising split's histograms without the planes (Batch.hist_planes_grid_quant_dev, DESIGN 7.31)
@@ -385,45 +440,27 @@ def _bounds(what, abs_errors, k):
     return [_params(what, e, k) for e in abs_errors]
 
 
-def _model_sizes(ts, blocks, stream):
-    """blocks: (index of a non-empty tensor of ts, lags, (step, bound)) -> [(nbytes, outliers)] in their order, nbytes the order-0
-    model of field_sizes.  Per element size one hist_planes_grid_quant_dev, Module T and the encoded sizes on the device; one
-    finish, one read-back"""
-    import ctypes as C
-    import torch
-    dev = ts[0].device
-    st = _pkg._plane_stream(dev, stream)
-    widths = sorted({ts[i].element_size() for i, _, _ in blocks})
-    groups = [(w, [j for j, (i, _, _) in enumerate(blocks) if ts[i].element_size() == w]) for w in widths]
-    with torch.cuda.stream(st):
-        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
-        try:
-            res = []
-            for w, g in groups:
-                idx = [blocks[j][0] for j in g]
-                base = min(ts[i].data_ptr() for i in idx)
-                numel = [ts[i].numel() for i in idx]
-                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
-                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
-                d_outl = torch.empty(len(g), dtype=torch.int64, device=dev)
-                bt.hist_planes_grid_quant_dev(st, w, [blocks[j][1] for j in g], [blocks[j][2][0] for j in g],
-                                              [blocks[j][2][1] for j in g], base, [ts[i].data_ptr() - base for i in idx], numel, d_n,
-                                              d_freq, d_outl)
-                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
-                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
-                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
-                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
-                planes = torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1)
-                res.append(torch.stack([planes + (8 + w) * d_outl, d_outl], 1))
-            bt.finish(st, bt.max_blocks)
-            host = torch.cat(res).cpu().tolist()
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    out = [None] * len(blocks)
-    for j, (nb, no) in zip([j for _, g in groups for j in g], host):
-        out[j] = (int(nb), int(no))
-    return out
+def _sizes(q, ts, cands, rows, stream):
+    """field_sizes' shape for checked tensors and any quantiser: per tensor its candidates as (lags, nbytes, outliers), sorted by
+    (outliers > outlier_capacity(numel), nbytes, len(lags), lags); [((), 0, 0)] for an empty or 0-dimensional one"""
+    out = [[((), 0, 0)] if not t.numel() or not t.dim() else None for t in ts]
+    blocks = [(i, c, rows[i]) for i in range(len(ts)) if out[i] is None for c in cands[i]]
+    if not blocks:
+        return out
+    found = [[] for _ in ts]
+    for (i, c, _), (nb, no) in zip(blocks, _pkg.grids._model_sizes(q.hist, ts, blocks, True, stream)):
+        found[i].append((c, nb, no))
+    key = lambda n: lambda e: (e[2] > outlier_capacity(n), e[1], len(e[0]), e[0])
+    return [o if o is not None else sorted(f, key=key(t.numel())) for o, f, t in zip(out, found, ts)]
+
+
+def _rate_list(q, t, lags, labels, rows, stream):
+    """field_rates' shape for a checked tensor and any quantiser: one block per row on the same region, in one launch ->
+    [(label, nbytes, outliers)]; 0 bytes at every row for an empty or 0-dimensional tensor"""
+    if not t.numel() or not t.dim():
+        return [(e, 0, 0) for e in labels]
+    sizes = _pkg.grids._model_sizes(q.hist, [t], [(0, lags, r) for r in rows], True, stream)
+    return [(e, nb, no) for e, (nb, no) in zip(labels, sizes)]
 
 
 def field_histograms(t, abs_error, lag_sets, stream=None):
@@ -442,31 +479,14 @@ def field_histograms(t, abs_error, lag_sets, stream=None):
     if not isinstance(lag_sets, (list, tuple)):
         raise ValueError(f"{what}: lag_sets is a list of tuples of lags, not {lag_sets!r}")
     sets = _lag_sets(what, lag_sets)
-    dev, k, n = t.device, t.element_size(), t.numel()
+    k = t.element_size()
     if isinstance(abs_error, (list, tuple)):
         if len(abs_error) != len(sets):
             raise ValueError(f"{what}: abs_error is a float or a list with one float per entry of lag_sets")
         params = [_params(what, e, k) for e in abs_error]
     else:
         params = [_params(what, abs_error, k)] * len(sets)
-    group = _pkg.grids.HIST_GROUP
-    st = _pkg._plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
-        outl = torch.zeros(len(sets), dtype=torch.int64, device=dev)
-        if sets and n:
-            bt = _pkg.Batch(min(len(sets), group), 1 << 20)
-            try:
-                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
-                for lo in range(0, len(sets), bt.max_blocks):
-                    part, pp = sets[lo:lo + bt.max_blocks], params[lo:lo + bt.max_blocks]
-                    bt.hist_planes_grid_quant_dev(st, k, part, [p[0] for p in pp], [p[1] for p in pp], t, [0] * len(part),
-                                                  [n] * len(part), d_n, freq[lo:lo + len(part)], outl[lo:lo + len(part)])
-                bt.finish(st, bt.max_blocks)
-            finally:
-                bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return freq, outl
+    return _pkg.grids._histograms(_QUANT.hist, t, sets, params, True, stream)
 
 
 def field_sizes(tensors, abs_error, axes=None, candidates=None, stream=None):
@@ -491,16 +511,7 @@ def field_sizes(tensors, abs_error, axes=None, candidates=None, stream=None):
     what = "field_sizes"
     ts = _field_tensors(what, tensors)
     cands = _field_candidates(what, ts, axes, candidates)
-    _, params = _abs_errors(what, ts, abs_error)
-    out = [[((), 0, 0)] if not t.numel() or not t.dim() else None for t in ts]
-    blocks = [(i, c, params[i]) for i in range(len(ts)) if out[i] is None for c in cands[i]]
-    if not blocks:
-        return out
-    found = [[] for _ in ts]
-    for (i, c, _), (nb, no) in zip(blocks, _model_sizes(ts, blocks, stream)):
-        found[i].append((c, nb, no))
-    key = lambda n: lambda e: (e[2] > outlier_capacity(n), e[1], len(e[0]), e[0])
-    return [o if o is not None else sorted(f, key=key(t.numel())) for o, f, t in zip(out, found, ts)]
+    return _sizes(_QUANT, ts, cands, _abs_errors(what, ts, abs_error)[1], stream)
 
 
 def choose_field_lags(tensors, abs_error, axes=None, candidates=None, stream=None):
@@ -526,10 +537,7 @@ def _rates(what, t, abs_errors, lags, axes, stream):
     ts = _field_tensors(what, t)
     g = _pkg.grids._lags(what, ts, axes, lags)[0]
     params = _bounds(what, abs_errors, ts[0].element_size())
-    if not ts[0].numel() or not ts[0].dim():
-        return [(e, 0, 0) for e in abs_errors]
-    sizes = _model_sizes(ts, [(0, g, p) for p in params], stream)
-    return [(e, nb, no) for e, (nb, no) in zip(abs_errors, sizes)]
+    return _rate_list(_QUANT, ts[0], g, abs_errors, params, stream)
 
 
 def fit_abs_error(t, max_bytes, abs_errors, lags=None, axes=None, stream=None):
@@ -562,7 +570,7 @@ def decompress_fields(items, stream=None):
     if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedField) for it in items):
         raise ValueError(f"{what}: a CompressedField or a list of them (compress_fields' items)")
     lags = [_pkg.grids._lag_tuple(what, it.lags) for it in items]
-    steps = []
+    rows = []
     for it in items:
         if it.dtype not in (torch.float32, torch.float64):
             raise ValueError(f"{what}: float32 and float64 tensors, not {it.dtype!r}")
@@ -570,5 +578,5 @@ def decompress_fields(items, stream=None):
         lossless = isinstance(it.step, float) and it.step == 0.0
         if lossless and it.outlier_pos.numel():
             raise ValueError(f"{what}: an item kept lossless has no outliers")
-        steps.append(0.0 if lossless else _step(what, it.step, 4 if it.dtype == torch.float32 else 8))
-    return _pkg._merge_items(what, items, "planes_grid", lags, False, stream, _merge_fields(list(items), steps))
+        rows.append(None if lossless else (_step(what, it.step, 4 if it.dtype == torch.float32 else 8),))
+    return _decompress(what, _QUANT, items, lags, rows, stream)

@@ -177,6 +177,78 @@ def _candidates(what, ts, axes, candidates):
     return [_candidate_list(what, candidates)] * len(ts)
 
 
+# The histogram loop and the model-size chain are written once, here, for every split that has them: `hist` makes the split's
+# hist Batch call for one launch, hist(bt, st, width, lags, rows, region, offsets, counts, d_n, d_freq, d_outl) with `rows` the
+# launch's entries of the caller's parameter rows, which the callable lays out as its entry takes them.  This module's own split has
+# no quantiser and no outliers: `outliers` False, no count is made, and d_outl is None.  fields.py and rounding.py pass their
+# Quantiser's `hist`.
+def _plain_hist(bt, st, width, lags, rows, *rest):
+    bt.hist_planes_grid_dev(st, width, lags, *rest[:-1])
+
+
+def _histograms(hist, t, sets, rows, outliers, stream):
+    """one block per entry of `sets` on the region of the checked tensor t, HIST_GROUP entries a launch -> (freq [len(sets), k,
+    256], the outliers' counts [len(sets)] or None).  One batch of a launch's blocks, one finish"""
+    import torch
+    dev, k, n = t.device, t.element_size(), t.numel()
+    st = _pkg._plane_stream(dev, stream)
+    with torch.cuda.stream(st):
+        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
+        outl = torch.zeros(len(sets), dtype=torch.int64, device=dev) if outliers else None
+        if sets and n:
+            bt = _pkg.Batch(min(len(sets), HIST_GROUP), 1 << 20)
+            try:
+                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
+                for lo in range(0, len(sets), bt.max_blocks):
+                    part = sets[lo:lo + bt.max_blocks]
+                    hist(bt, st, k, part, rows[lo:lo + len(part)], t, [0] * len(part), [n] * len(part), d_n, freq[lo:lo + len(part)],
+                         outl[lo:lo + len(part)] if outliers else None)
+                bt.finish(st, bt.max_blocks)
+            finally:
+                bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    return freq, outl
+
+
+def _model_sizes(hist, ts, blocks, outliers, stream):
+    """blocks: (index of a non-empty tensor of ts, lags, the block's parameter row) -> in their order the order-0 model of their
+    planes' bytes, or with `outliers` [nbytes, count]: (8 + element size) bytes per outlier on top, and their count.  Per element
+    size one hist launch over its blocks, Module T and the encoded sizes on the device; one finish, one read-back"""
+    import torch
+    dev = ts[0].device
+    st = _pkg._plane_stream(dev, stream)
+    widths = sorted({ts[i].element_size() for i, _, _ in blocks})
+    groups = [(w, [j for j, (i, _, _) in enumerate(blocks) if ts[i].element_size() == w]) for w in widths]
+    with torch.cuda.stream(st):
+        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
+        try:
+            res = []
+            for w, g in groups:
+                idx = [blocks[j][0] for j in g]
+                base = min(ts[i].data_ptr() for i in idx)
+                numel = [ts[i].numel() for i in idx]
+                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
+                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
+                d_outl = torch.empty(len(g), dtype=torch.int64, device=dev) if outliers else None
+                hist(bt, st, w, [blocks[j][1] for j in g], [blocks[j][2] for j in g], base, [ts[i].data_ptr() - base for i in idx],
+                     numel, d_n, d_freq, d_outl)
+                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
+                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
+                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
+                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
+                planes = torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1)
+                res.append(torch.stack([planes + (8 + w) * d_outl, d_outl], 1) if outliers else planes)
+            bt.finish(st, bt.max_blocks)
+            host = torch.cat(res).cpu().tolist()
+        finally:
+            bt.close()
+    torch.cuda.current_stream(dev).wait_stream(st)
+    out = [None] * len(blocks)
+    for j, size in zip([j for _, g in groups for j in g], host):
+        out[j] = size
+    return out
+
+
 def grid_histograms(t, lag_sets, stream=None):
     """The byte histograms of the planes split_grid(t, lags) would give for every `lags` of the list `lag_sets`, without the
     planes: `t` a contiguous CUDA tensor with elements of k = 1, 2, 4 or 8 bytes, every entry of `lag_sets` a tuple split_grid
@@ -190,22 +262,7 @@ def grid_histograms(t, lag_sets, stream=None):
     if not isinstance(lag_sets, (list, tuple)):
         raise ValueError(f"grid_histograms: lag_sets is a list of tuples of lags, not {lag_sets!r}")
     sets = [_candidate("grid_histograms", c) for c in lag_sets]
-    dev, k, n = t.device, t.element_size(), t.numel()
-    st = _pkg._plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
-        if sets and n:
-            bt = _pkg.Batch(min(len(sets), HIST_GROUP), 1 << 20)
-            try:
-                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
-                for lo in range(0, len(sets), bt.max_blocks):
-                    part = sets[lo:lo + bt.max_blocks]
-                    bt.hist_planes_grid_dev(st, k, part, t, [0] * len(part), [n] * len(part), d_n, freq[lo:lo + len(part)])
-                bt.finish(st, bt.max_blocks)
-            finally:
-                bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return freq
+    return _histograms(_plain_hist, t, sets, [None] * len(sets), False, stream)[0]
 
 
 def grid_sizes(tensors, axes=None, candidates=None, stream=None):
@@ -224,41 +281,16 @@ def grid_sizes(tensors, axes=None, candidates=None, stream=None):
     Chain: per element size one hist_planes_grid_dev over all tensors' candidates, one block per candidate on its tensor's
     region — the planes never exist, and no histogram comes to the host -> sf_build_codes -> sf_encoded_size_dev -> one finish,
     one read-back of the sizes."""
-    import torch
     what = "grid_sizes"
     ts = _pkg._plane_tensors(what, tensors)
     cands = _candidates(what, ts, axes, candidates)
     out = [[((), 0)] if not t.numel() or not t.dim() else None for t in ts]
-    blocks = [(i, c) for i, t in enumerate(ts) if out[i] is None for c in cands[i]]        # grouped by width below
+    blocks = [(i, c, None) for i, t in enumerate(ts) if out[i] is None for c in cands[i]]
     if not blocks:
         return out
-    dev = ts[0].device
-    st = _pkg._plane_stream(dev, stream)
-    widths = sorted({ts[i].element_size() for i, _ in blocks})
-    groups = [(w, [(i, c) for i, c in blocks if ts[i].element_size() == w]) for w in widths]
-    with torch.cuda.stream(st):
-        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
-        try:
-            sizes = []
-            for w, g in groups:
-                base = min(ts[i].data_ptr() for i, _ in g)
-                numel = [ts[i].numel() for i, _ in g]
-                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
-                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
-                bt.hist_planes_grid_dev(st, w, [c for _, c in g], base, [ts[i].data_ptr() - base for i, _ in g], numel, d_n, d_freq)
-                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
-                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
-                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
-                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
-                sizes.append(torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1))
-            bt.finish(st, bt.max_blocks)
-            host = torch.cat(sizes).cpu().tolist()
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
     found = [[] for _ in ts]
-    for (i, c), nb in zip([x for _, g in groups for x in g], host):
-        found[i].append((c, int(nb)))
+    for (i, c, _), nb in zip(blocks, _model_sizes(_plain_hist, ts, blocks, False, stream)):
+        found[i].append((c, nb))
     return [o if o is not None else sorted(f, key=lambda e: (e[1], len(e[0]), e[0])) for o, f in zip(out, found)]
 
 

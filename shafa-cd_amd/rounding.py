@@ -11,9 +11,10 @@ lose no set bit come back as they were (-0.0 as +0.0); the few elements the roun
 a denormal or a NaN with a dropped bit set — are outliers, kept with their own bits.  The rounding runs inside the Lorenzo split,
 so no temporary of codes exists; noise wants no differences at all, and lags=() gives that.
 
-The drivers live in this submodule; the package re-exports them.  The layout, the record handling and the order-0 model are
-fields.py's, the coder's half of the chain (_coded_planes) and the decode chain (_merge_items) the package's, reached through it
-at the time of the call."""
+The drivers live in this submodule; the package re-exports them.  What is the rounding's own is here: its argument checks, its
+item and its Quantiser, the three Batch entries with their rows of (mantissa width, kept bits).  The chains — split, merge,
+compress, decompress, sizes and rates — are fields.py's, written for any Quantiser, the histogram loop and the order-0 model
+grids.py's; all are reached through the package at the time of the call."""
 import collections.abc
 import sys
 
@@ -110,71 +111,29 @@ def _rounded_lags(what, ts, axes, lags):
     return [_lag_set(what, lags)] * len(ts)
 
 
-def _device_lags(lags, numel):
-    """the row of lags the entries get: () is a lag at the capacity, which subtracts nothing in split and merge alike"""
-    return tuple(lags) if len(lags) else (max(int(numel), 1),)
+def _rows(dtypes, keeps):
+    """the rounding quantiser's rows: (the dtype's mantissa width, the kept bits) per tensor or entry"""
+    return [(MANTISSA_BITS[d], k) for d, k in zip(dtypes, keeps)]
 
 
-# ---- the launches
-def _split_rounded(bt, st, dev, ts, units, lags, keeps, caps, buf, poff):
-    """fields._split_fields with the rounding split: one launch per element size over ts into buf -> (the records buffer, each
-    tensor's first record, the counts of outliers found in the launches' order, and that order)"""
-    import torch
-    first, pos = [], 0
-    for c in caps:
-        first.append(pos)
-        pos += c
-    d_outl = torch.empty((pos, 2), dtype=torch.int64, device=dev)
-    groups = _pkg._by_width(units)
-    order = [i for _, idx in groups for i in idx]
-    d_n = torch.tensor([units[i][0] for i in order], dtype=torch.int64, device=dev)
-    d_found = torch.zeros(len(order), dtype=torch.int64, device=dev)
-    at = 0
-    for w, idx in groups:
-        base = min(ts[i].data_ptr() for i in idx)
-        bt.split_planes_grid_round_dev(st, w, [_device_lags(lags[i], units[i][0]) for i in idx],
-                                       [MANTISSA_BITS[ts[i].dtype] for i in idx], [keeps[i] for i in idx], base,
-                                       [ts[i].data_ptr() - base for i in idx], [units[i][0] for i in idx], d_n[at:at + len(idx)], buf,
-                                       [o for i in idx for o in poff[i]], d_outl if pos else None, [first[i] for i in idx],
-                                       [caps[i] for i in idx], d_found[at:at + len(idx)])
-        at += len(idx)
-    return d_outl, first, d_found, order
+# ---- the quantiser: the chains are fields.py's, with these three entries and this item
+def _rounded_item(t, lags, row, lossless, planes, pos, bits, nbytes):
+    """a keep_bits of None says lossless"""
+    return CompressedRounded(t.dtype, t.shape, lags, None if lossless else row[1], planes, pos, bits, nbytes)
 
 
-def _merge_rounded(items, keeps):
-    """_merge_into's stand-in for decompress_rounded: the lossless items (a keep of None) through _merge_into as decompress_grids'
-    go, the others through one merge_planes_grid_round_dev per element size"""
-    def merge_into(bt, st, dev, planes, outs, units, kind, lags):
-        import torch
-        dlags = [_device_lags(g, n) for g, (n, _) in zip(lags, units)]
-        plain = [i for i in range(len(items)) if keeps[i] is None]
-        if plain:
-            _pkg._merge_into(bt, st, dev, [planes[i] for i in plain], [outs[i] for i in plain], [units[i] for i in plain], kind,
-                             [dlags[i] for i in plain])
-        rounded = [(n, w) if keeps[i] is not None else (0, w) for i, (n, w) in enumerate(units)]
-        groups = _pkg._by_width(rounded)
-        if not groups:
-            return
-        planes = [[p if p.data_ptr() % 16 == 0 else p.clone() for p in ps] for ps in planes]
-        order = [i for _, idx in groups for i in idx]
-        d_n = torch.tensor([units[i][0] for i in order], dtype=torch.int64, device=dev)
-        counts = [int(it.outlier_pos.numel()) for it in items]
-        first, pos = {}, 0
-        for i in order:
-            first[i] = pos
-            pos += counts[i]
-        d_outl = torch.stack([torch.cat([items[i].outlier_pos for i in order if counts[i]]),
-                              torch.cat([items[i].outlier_bits for i in order if counts[i]])], 1).contiguous() if pos else None
-        at = 0
-        for w, idx in groups:
-            pbase = min(p.data_ptr() for i in idx for p in planes[i])
-            obase = min(outs[i].data_ptr() for i in idx)
-            bt.merge_planes_grid_round_dev(st, w, [dlags[i] for i in idx], [MANTISSA_BITS[items[i].dtype] for i in idx],
-                                           [keeps[i] for i in idx], pbase, [p.data_ptr() - pbase for i in idx for p in planes[i]],
-                                           [units[i][0] for i in idx], d_n[at:at + len(idx)], d_outl, [first[i] for i in idx],
-                                           [counts[i] for i in idx], obase, [outs[i].data_ptr() - obase for i in idx])
-            at += len(idx)
-    return merge_into
+def _hist(bt, st, w, lags, rows, base, offs, numel, *out):
+    """() among a histogram's candidates is the split's: a lag at the capacity, not grid_histograms' plain planes"""
+    bt.hist_planes_grid_round_dev(st, w, [_pkg.fields._device_lags(g, n) for g, n in zip(lags, numel)], [r[0] for r in rows],
+                                  [r[1] for r in rows], base, offs, numel, *out)
+
+
+_ROUND = _pkg.fields.Quantiser(
+    split=lambda bt, st, w, lags, rows, *rest: bt.split_planes_grid_round_dev(st, w, lags, [r[0] for r in rows],
+                                                                              [r[1] for r in rows], *rest),
+    merge=lambda bt, st, w, lags, rows, *rest: bt.merge_planes_grid_round_dev(st, w, lags, [r[0] for r in rows],
+                                                                              [r[1] for r in rows], *rest),
+    hist=_hist, item=_rounded_item)
 
 
 # ---- one tensor, no coder
@@ -193,60 +152,21 @@ def round_field(t, keep_bits, lags):
     t = _rounded_tensors(what, t)[0]
     keep = _keep(what, keep_bits, t.dtype)
     lags = _lag_set(what, lags)
-    k, n = t.element_size(), t.numel()
-    dev = t.device
-    st = _pkg._plane_stream(dev, stream=None)
-    poff, nbytes = _pkg.fields._layout([(n, k)])
-    with torch.cuda.stream(st):
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        bt = _pkg.Batch(1, 1 << 20)
-        try:
-            cap, found, d_outl = _pkg.fields.outlier_capacity(n), 0, None
-            while n:
-                d_outl, _, d_found, _ = _split_rounded(bt, st, dev, [t], [(n, k)], [lags], [keep], [cap], buf, poff)
-                bt.finish(st, 1)
-                found = int(d_found.cpu()[0])
-                if found <= cap:
-                    break
-                cap = found
-        finally:
-            bt.close()
-        pos, bits = _pkg.fields._sorted_records(d_outl[:found]) if found else (torch.empty(0, dtype=torch.int64, device=dev),) * 2
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return buf[:k * _pkg._al16(n)].view(k, _pkg._al16(n))[:, :n], pos, bits
+    return _pkg.fields._quantise_one(_ROUND, t, lags, (MANTISSA_BITS[t.dtype], keep))
 
 
 def restore_rounded(planes, dtype, shape, lags, keep_bits, positions, bits, stream=None):
     """round_field's inverse for one tensor: `planes` as merge_grid takes them -> a tensor of `dtype` and `shape`, every element
     the rounded value of its code but the outliers, whose `bits` are stored at their `positions`.  One
     merge_planes_grid_round_dev call, one synchronisation."""
-    import torch
     what = "restore_rounded"
     if dtype not in MANTISSA_BITS:
         raise ValueError(f"{what}: float16, bfloat16, float32 and float64 tensors, not {dtype!r}")
     k, shape, n = _pkg._plane_dtype(what, dtype, shape)
     lags = _lag_set(what, lags)
     keep = _keep(what, keep_bits, dtype)
-    if not isinstance(planes, torch.Tensor) or planes.dtype != torch.uint8 or not planes.is_cuda or planes.dim() != 2 \
-            or (planes.shape[1] > 1 and planes.stride(1) != 1):
-        raise ValueError(f"{what}: planes is a uint8 CUDA tensor [k, numel] with contiguous rows")
-    if tuple(planes.shape) != (k, n):
-        raise ValueError(f"{what}: planes of shape {tuple(planes.shape)} for {k} x {n} bytes")
-    _pkg.fields._records(what, positions, bits, planes.device)
-    dev = planes.device
-    item = CompressedRounded(dtype, shape, lags, keep, [], positions, bits, 0)
-    st = _pkg._plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        out = torch.empty(shape, dtype=dtype, device=dev)
-        bt = _pkg.Batch(1, 1 << 20)
-        try:
-            _merge_rounded([item], [keep])(bt, st, dev, [[planes[j].contiguous() for j in range(k)]], [out], [(n, k)], "planes_grid",
-                                           [lags])
-            bt.finish(st, 1)
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return out
+    return _pkg.fields._restore_one(_ROUND, what, planes, dtype, shape, k, n, lags, (MANTISSA_BITS[dtype], keep), positions, bits,
+                                    stream)
 
 
 # ---- the drivers
@@ -273,55 +193,11 @@ def compress_rounded(tensors, keep_bits, axes=None, lags=None, block_size=8 << 2
     Chain: compress_fields' — one split_planes_grid_round_dev per element size over all tensors, one finish and one read-back of
     the outlier counts (the tensors kept lossless then take one split_planes_grid_dev per element size and a finish) ->
     compressed_sizes -> compress_many; a tensor's records are sorted by position."""
-    import torch
     what = "compress_rounded"
     ts = _rounded_tensors(what, tensors)
     lags = _rounded_lags(what, ts, axes, lags)
     keeps = _keeps(what, ts, keep_bits)
-    if isinstance(block_size, bool) or not isinstance(block_size, int) or not 0 <= block_size < 1 << 64:
-        raise ValueError(f"{what}: block_size is a size in bytes (shafa_block_count's uint64_t)")
-    if not ts:
-        return []
-    F = _pkg.fields
-    dev = ts[0].device
-    units = _pkg._elements(ts)
-    caps = [F.outlier_capacity(n) if n else 0 for n, _ in units]
-    poff, nbytes = F._layout(units)
-    st = _pkg._plane_stream(dev, stream)
-    found = [0] * len(ts)
-    with torch.cuda.stream(st):
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        bt = _pkg.Batch(len(ts), 1 << 20)
-        try:
-            if any(n for n, _ in units):
-                d_outl, first, d_found, order = _split_rounded(bt, st, dev, ts, units, lags, keeps, caps, buf, poff)
-                bt.finish(st, len(ts))
-                for i, c in zip(order, d_found.cpu().tolist()):
-                    found[i] = c
-            lossless = [i for i in range(len(ts)) if found[i] > caps[i]]
-            if lossless:                             # compress_grids' planes in the same places
-                groups = [(w, [lossless[j] for j in idx]) for w, idx in _pkg._by_width([units[i] for i in lossless])]
-                d_n = torch.tensor([units[i][0] for _, idx in groups for i in idx], dtype=torch.int64, device=dev)
-                at = 0
-                for w, idx in groups:
-                    base = min(ts[i].data_ptr() for i in idx)
-                    bt.split_planes_grid_dev(st, w, [_device_lags(lags[i], units[i][0]) for i in idx], base,
-                                             [ts[i].data_ptr() - base for i in idx], [units[i][0] for i in idx],
-                                             d_n[at:at + len(idx)], buf, [o for i in idx for o in poff[i]])
-                    at += len(idx)
-                bt.finish(st, len(ts))
-        finally:
-            bt.close()
-        entries = _pkg._coded_planes(buf, poff, units, block_size, st)
-        none = torch.empty(0, dtype=torch.int64, device=dev)
-        items = []
-        for i, (t, ps, nb) in enumerate(zip(ts, entries, _pkg._entry_bytes(entries))):
-            keep = found[i] and i not in lossless
-            pos, bits = F._sorted_records(d_outl[first[i]:first[i] + found[i]]) if keep else (none, none)
-            items.append(CompressedRounded(t.dtype, t.shape, lags[i], None if i in lossless else keeps[i], ps, pos, bits,
-                                           nb + (8 + t.element_size()) * int(pos.numel())))
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return items
+    return _pkg.fields._compress(what, _ROUND, ts, lags, _rows([t.dtype for t in ts], keeps), block_size, stream)
 
 
 def decompress_rounded(items, stream=None):
@@ -337,7 +213,7 @@ def decompress_rounded(items, stream=None):
         items = [items]
     if not isinstance(items, (list, tuple)) or any(not isinstance(it, CompressedRounded) for it in items):
         raise ValueError(f"{what}: a CompressedRounded or a list of them (compress_rounded's items)")
-    lags, keeps = [], []
+    lags, rows = [], []
     for it in items:
         if it.dtype not in MANTISSA_BITS:
             raise ValueError(f"{what}: float16, bfloat16, float32 and float64 tensors, not {it.dtype!r}")
@@ -345,52 +221,11 @@ def decompress_rounded(items, stream=None):
         _pkg.fields._records(what, it.outlier_pos, it.outlier_bits, None)
         if it.keep_bits is None and it.outlier_pos.numel():
             raise ValueError(f"{what}: an item kept lossless has no outliers")
-        keeps.append(None if it.keep_bits is None else _keep(what, it.keep_bits, it.dtype))
-    return _pkg._merge_items(what, items, "planes_grid", lags, False, stream, _merge_rounded(list(items), keeps))
+        rows.append(None if it.keep_bits is None else (MANTISSA_BITS[it.dtype], _keep(what, it.keep_bits, it.dtype)))
+    return _pkg.fields._decompress(what, _ROUND, items, lags, rows, stream)
 
 
 # ---- sizes at a number of kept bits: the rounding split's histograms without the planes (Batch.hist_planes_grid_round_dev)
-def _model_sizes(ts, blocks, stream):
-    """blocks: (index of a non-empty tensor of ts, lags, keep) -> [(nbytes, outliers)] in their order, nbytes field_sizes' order-0
-    model.  Per element size one hist_planes_grid_round_dev, Module T and the encoded sizes on the device; one finish, one
-    read-back"""
-    import ctypes as C
-    import torch
-    dev = ts[0].device
-    st = _pkg._plane_stream(dev, stream)
-    widths = sorted({ts[i].element_size() for i, _, _ in blocks})
-    groups = [(w, [j for j, (i, _, _) in enumerate(blocks) if ts[i].element_size() == w]) for w in widths]
-    with torch.cuda.stream(st):
-        bt = _pkg.Batch(max(len(g) * w for w, g in groups), 1 << 20)
-        try:
-            res = []
-            for w, g in groups:
-                idx = [blocks[j][0] for j in g]
-                base = min(ts[i].data_ptr() for i in idx)
-                numel = [ts[i].numel() for i in idx]
-                d_n = torch.tensor(numel, dtype=torch.int64, device=dev)
-                d_freq = torch.empty(len(g) * w * 256, dtype=torch.int64, device=dev)
-                d_outl = torch.empty(len(g), dtype=torch.int64, device=dev)
-                bt.hist_planes_grid_round_dev(st, w, [_device_lags(blocks[j][1], n) for j, n in zip(g, numel)],
-                                              [MANTISSA_BITS[ts[i].dtype] for i in idx], [blocks[j][2] for j in g], base,
-                                              [ts[i].data_ptr() - base for i in idx], numel, d_n, d_freq, d_outl)
-                d_tab = torch.empty(len(g) * w * C.sizeof(_pkg.CodeTable), dtype=torch.uint8, device=dev)
-                bt.sf_build_codes(st, len(g) * w, d_freq, d_tab)
-                d_enc = torch.zeros(len(g) * w, dtype=torch.int64, device=dev)
-                bt.sf_encoded_size_dev(st, len(g) * w, d_freq, d_tab, d_enc)
-                planes = torch.minimum(d_enc.view(len(g), w), d_n[:, None]).sum(1)
-                res.append(torch.stack([planes + (8 + w) * d_outl, d_outl], 1))
-            bt.finish(st, bt.max_blocks)
-            host = torch.cat(res).cpu().tolist()
-        finally:
-            bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    out = [None] * len(blocks)
-    for j, (nb, no) in zip([j for _, g in groups for j in g], host):
-        out[j] = (int(nb), int(no))
-    return out
-
-
 def rounded_histograms(t, keep_bits, lag_sets, stream=None):
     """The byte histograms of the planes round_field(t, keep_bits, lags) would give for every `lags` of the list `lag_sets`, and
     its count of outliers, without the planes and without the records: `t` a contiguous float CUDA tensor, every entry of
@@ -410,33 +245,13 @@ def rounded_histograms(t, keep_bits, lag_sets, stream=None):
         if not isinstance(c, tuple):
             raise ValueError(f"{what}: an entry of lag_sets is a tuple of lags, () for no differences, not {c!r}")
         sets.append(_lag_set(what, c))
-    dev, k, n = t.device, t.element_size(), t.numel()
     if isinstance(keep_bits, (list, tuple)):
         if len(keep_bits) != len(sets):
             raise ValueError(f"{what}: keep_bits is an int or a list with one int per entry of lag_sets")
         keeps = [_keep(what, e, t.dtype) for e in keep_bits]
     else:
         keeps = [_keep(what, keep_bits, t.dtype)] * len(sets)
-    mant = MANTISSA_BITS[t.dtype]
-    group = _pkg.grids.HIST_GROUP
-    st = _pkg._plane_stream(dev, stream)
-    with torch.cuda.stream(st):
-        freq = torch.zeros(len(sets), k, 256, dtype=torch.int64, device=dev)
-        outl = torch.zeros(len(sets), dtype=torch.int64, device=dev)
-        if sets and n:
-            bt = _pkg.Batch(min(len(sets), group), 1 << 20)
-            try:
-                d_n = torch.full((bt.max_blocks,), n, dtype=torch.int64, device=dev)
-                for lo in range(0, len(sets), bt.max_blocks):
-                    part, kp = sets[lo:lo + bt.max_blocks], keeps[lo:lo + bt.max_blocks]
-                    bt.hist_planes_grid_round_dev(st, k, [_device_lags(c, n) for c in part], [mant] * len(part), kp, t,
-                                                  [0] * len(part), [n] * len(part), d_n, freq[lo:lo + len(part)],
-                                                  outl[lo:lo + len(part)])
-                bt.finish(st, bt.max_blocks)
-            finally:
-                bt.close()
-    torch.cuda.current_stream(dev).wait_stream(st)
-    return freq, outl
+    return _pkg.grids._histograms(_ROUND.hist, t, sets, _rows([t.dtype] * len(sets), keeps), True, stream)
 
 
 def _rounded_candidates(what, ts, axes, candidates):
@@ -460,16 +275,7 @@ def rounded_sizes(tensors, keep_bits, axes=None, candidates=None, stream=None):
     ts = _rounded_tensors(what, tensors)
     cands = _rounded_candidates(what, ts, axes, candidates)
     keeps = _keeps(what, ts, keep_bits)
-    out = [[((), 0, 0)] if not t.numel() or not t.dim() else None for t in ts]
-    blocks = [(i, c, keeps[i]) for i in range(len(ts)) if out[i] is None for c in cands[i]]
-    if not blocks:
-        return out
-    found = [[] for _ in ts]
-    for (i, c, _), (nb, no) in zip(blocks, _model_sizes(ts, blocks, stream)):
-        found[i].append((c, nb, no))
-    cap = _pkg.fields.outlier_capacity
-    key = lambda n: lambda e: (e[2] > cap(n), e[1], len(e[0]), e[0])
-    return [o if o is not None else sorted(f, key=key(t.numel())) for o, f, t in zip(out, found, ts)]
+    return _pkg.fields._sizes(_ROUND, ts, cands, _rows([t.dtype for t in ts], keeps), stream)
 
 
 def _rates(what, t, keeps, lags, axes, stream):
@@ -483,10 +289,7 @@ def _rates(what, t, keeps, lags, axes, stream):
     if not isinstance(keeps, (list, tuple)) or not keeps:
         raise ValueError(f"{what}: keeps is a non-empty list of ints, not {keeps!r}")
     keeps = [_keep(what, k, ts[0].dtype) for k in keeps]
-    if not ts[0].numel() or not ts[0].dim():
-        return [(k, 0, 0) for k in keeps]
-    sizes = _model_sizes(ts, [(0, g, k) for k in keeps], stream)
-    return [(k, nb, no) for k, (nb, no) in zip(keeps, sizes)]
+    return _pkg.fields._rate_list(_ROUND, ts[0], g, keeps, _rows([ts[0].dtype] * len(keeps), keeps), stream)
 
 
 def rounded_rates(t, keeps, lags=None, axes=None, stream=None):

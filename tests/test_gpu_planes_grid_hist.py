@@ -325,6 +325,42 @@ def test_grid_sizes_on_eight_dtypes_in_one_call(shafa):
         assert g == want and p == want[0][0], d
 
 
+def test_histogram_drivers_past_one_launch(shafa, monkeypatch):
+    """HIST_GROUP candidates go into one launch, and no other test passes more than that: with a group of 3 seven entries take
+    launches of 3, 3 and 1 blocks on a batch of 3 — the slices of the lag sets, of the parameters, of freq and of the outliers'
+    counts, and d_n used again.  grid_histograms, field_histograms and rounded_histograms then give, bit for bit, what one launch
+    gives, which the tests of each tie to numpy.  Seven different lag sets, bounds and keeps on 8200 floats, just past two tiles,
+    with NaNs and with denormals of one low bit each at different places, so that every entry has its own counts and, under the
+    rounding, its own number of outliers: a slice handed to the wrong entry shows."""
+    torch = _torch()
+    grids = shafa.grids
+    rng = np.random.default_rng(4096)
+    a = np.cumsum(rng.normal(0, 1, 5 * 40 * 41)).astype(np.float32)
+    a[[7, 4095, 4096, 8199]] = np.nan
+    low = (0, 3, 7, 11, 15, 19, 22)                                        # a keep of 23 - d drops the bits below d
+    a.view(np.uint32)[[100 + 1000 * i for i in range(7)]] = [1 << p for p in low]
+    t = torch.from_numpy(a.reshape(5, 40, 41)).to(_dev())
+    sets = [(1, 1640), (1,), (41,), (1640,), (1, 41), (41, 1640), (1, 41, 1640)]
+    errs = [0.3, 0.1, 0.03, 0.01, 0.003, 0.001, 0.0003]
+    keeps = [23, 20, 16, 12, 8, 4, 1]
+
+    def run():
+        return (shafa.grid_histograms(t, [()] + sets[1:]), *shafa.field_histograms(t, errs, sets),
+                *shafa.rounded_histograms(t, keeps, [()] + sets[1:]))
+
+    assert grids.HIST_GROUP >= 7
+    one = run()
+    monkeypatch.setattr(grids, "HIST_GROUP", 3)
+    three = run()
+    assert [tuple(x.shape) for x in one] == [(7, 4, 256), (7, 4, 256), (7,), (7, 4, 256), (7,)]
+    for x, y in zip(one, three):
+        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y)
+    for freq in (one[0], one[1], one[3]):
+        assert len({freq[i].cpu().numpy().tobytes() for i in range(7)}) > 1
+    print(f"past one launch: outliers under the bounds {one[2].tolist()}, under the keeps {one[4].tolist()}")
+    assert len(set(one[4].tolist())) > 1
+
+
 # ---------------------------------------------------------------- 8. what the chooser is worth
 def test_it_pays(shafa):
     """DESIGN 7.28's field: the chooser's pick compresses below every single axis and below plain planes, the model's margins are
