@@ -44,6 +44,8 @@
 // shafa_hipd_hist_planes_grid_round_dev) are the three above with another quantiser: the element's mantissa rounded to
 // `keep` bits, half to even, in integer arithmetic on its own bits, for elements of 2, 4 and 8 bytes (planes_grid_round_split,
 // planes_round_restore, planes_grid_round_hist); the records, the patch pass and the histogram's composition are those entries'.
+// The three splits and the histograms of the grid family are one tile walk (grid_tile) with three callables, the plain and the
+// rounding histogram one kernel body (grid_hist), the two restore passes one walk (restore_tile).
 #include "common.hpp"
 #include "internal.hpp"
 #include "tile_pass.hpp"
@@ -193,12 +195,20 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_split(const u8 *__restr
     tp_size_errors(cap, d_n, nblk, err);
 }
 
-// ---- split of the grid differences: d = (1 - S^L0)(1 - S^L1)(1 - S^L2) x, one base unit per non-empty subset of
-// the block's used lags (lg[k] != 0), read by lag_base at the summed distance, subtracted for an odd subset and added for an
-// even one; one base is live at a time.  A subset with an unused lag, or whose distance is past the unit, is skipped.
-template <int E, int Q>
-__device__ __forceinline__ void split_tile_grid(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], u8 *d_planes,
-                                                const u64 *poff)
+// ---- the grid differences: d = (1 - S^L0)(1 - S^L1)(1 - S^L2) x, one base unit (a TAP) per non-empty subset of the
+// block's used lags (lg[k] != 0), read by lag_base at the summed distance, subtracted for an odd subset and added for an even
+// one; one base is live at a time.  A subset with an unused lag, or whose distance is past the unit, is skipped.
+// grid_tile is the one walk of a tile for the grid split, its quantising and rounding forms and the three histograms, which
+// differ in three callables only:
+//     own(w, e0, c)    the lane's own unit from element e0 as loaded, c = min(16, n - e0) of its elements in front of the block's
+//                      end: nothing, or the elements -> their codes with the first c judged
+//     tap(wb)          a tap's unit: nothing, or the elements -> their codes (the zeros in front of the block stay zeros)
+//     sink(w, e0, c)   the unit of differences: fold and store a word of each plane, or count the c elements' bytes
+// Each member's tile function makes its lambdas from plain arguments BEHIND its kernel's switch over Q: built in front of one
+// shared switch, the closures cost the splits their code (LABNOTES, "one grid tile walk").
+template <int E, int Q, class Own, class Tap, class Sink>
+__device__ __forceinline__ void grid_tile(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], Own &&own, Tap &&tap,
+                                          Sink &&sink)
 {
 #pragma nounroll
     for (int u = 0; u < PL_UNITS; ++u) {
@@ -210,6 +220,8 @@ __device__ __forceinline__ void split_tile_grid(const TpWalk &wk, u32 r, const u
             load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
             shift_into<E, Q, false>(a, r, w);
         }
+        const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
+        own(w, e0, c);
 #pragma nounroll
         for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
             u64 dist = 0;
@@ -224,13 +236,24 @@ __device__ __forceinline__ void split_tile_grid(const TpWalk &wk, u32 r, const u
             if (e0 + PL_UNIT > dist) {
                 u32 wb[4 * E];
                 lag_base<E>(wk.in, wk.n, dist, e0, wb);
+                tap(wb);
                 if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
                 else add_words<E>(w, wb);
             }
         }
+        sink(w, e0, c);
+    }
+}
+
+// the grid split's tile: nothing is done to a loaded unit, the finished one is folded and stored
+template <int E, int Q>
+__device__ __forceinline__ void split_tile_grid(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], u8 *d_planes,
+                                                const u64 *poff)
+{
+    grid_tile<E, Q>(wk, r, lg, [](u32 (&)[4 * E], u64, u32) {}, [](u32 (&)[4 * E]) {}, [&](u32 (&w)[4 * E], u64 e0, u32) {
         zz_fold<E, 4 * E>(w);
         split_store<E>(w, wk.n, e0, d_planes, poff);
-    }
+    });
 }
 
 // d_lag: SHAFA_PLANES_GRID_LAGS rows of nblk lags, clamped by the host: 0 where a slot is unused or at or past the capacity
@@ -325,17 +348,27 @@ __device__ __forceinline__ bool field_good(typename FieldT<E>::U xb, typename Fi
     return __builtin_fabs((double)x - (double)xr) <= (double)q.bound;
 }
 
-// the 16 elements of w -> their codes as unsigned integers, in place
-template <int E>
-__device__ __forceinline__ void quant_words(u32 (&w)[4 * E], const FieldQ<E> &q)
+// the 16 elements of w -> their codes as unsigned integers, in place; bad(i, bits) for each of the first c that is not good
+template <int E, class F>
+__device__ __forceinline__ void quant_unit(u32 (&w)[4 * E], const FieldQ<E> &q, u32 c, F &&bad)
 {
 #pragma unroll
     for (int i = 0; i < PL_UNIT; ++i) {
+        using U = typename FieldT<E>::U;
         bool in;
-        const typename FieldT<E>::U c = (typename FieldT<E>::U)field_code<E>(unit_elem<E>(w, i), q.inv, in);
-        if (E == 8) { w[2 * i] = (u32)c; w[2 * i + 1] = (u32)((u64)c >> 32); }
-        else w[i] = (u32)c;
+        const U xb = unit_elem<E>(w, i);
+        const typename FieldT<E>::I code = field_code<E>(xb, q.inv, in);
+        if ((u32)i < c && !(in && field_good<E>(xb, code, q))) bad(i, (u64)xb);
+        if (E == 8) { w[2 * i] = (u32)(U)code; w[2 * i + 1] = (u32)((u64)(U)code >> 32); }
+        else w[i] = (u32)(U)code;
     }
+}
+
+// a tap's unit: nothing is judged
+template <int E>
+__device__ __forceinline__ void quant_words(u32 (&w)[4 * E], const FieldQ<E> &q)
+{
+    quant_unit<E>(w, q, 0u, [](int, u64) {});
 }
 
 // where a block's outliers go: records of {position, bits}, `cap` of them at the most, *count the outliers found
@@ -344,68 +377,30 @@ struct FieldOutl {
     unsigned long long *count;
 };
 
-// quant_words for the lane's OWN unit from element e0: the first c = min(16, n - e0) elements are judged as well, and one that
-// is not good is recorded in a slot of the block's, taken with an atomic of the lane's own (outliers are rare) and written only
-// where it lies inside the block's capacity
-template <int E>
-__device__ __forceinline__ void quant_words_judged(u32 (&w)[4 * E], const FieldQ<E> &q, u64 e0, u32 c, const FieldOutl &o)
+// what the quantising and the rounding split do with an element of the lane's OWN unit that is not good: it is recorded in a slot
+// of the block's, taken with an atomic of the lane's own (outliers are rare) and written only where it lies inside the block's
+// capacity
+__device__ __forceinline__ void outl_record(const FieldOutl &o, u64 pos, u64 bits)
 {
-#pragma unroll
-    for (int i = 0; i < PL_UNIT; ++i) {
-        using U = typename FieldT<E>::U;
-        bool in;
-        const U xb = unit_elem<E>(w, i);
-        const typename FieldT<E>::I code = field_code<E>(xb, q.inv, in);
-        if ((u32)i < c && !(in && field_good<E>(xb, code, q))) {
-            const u64 slot = atomicAdd(o.count, 1ull);
-            if (slot < o.cap) {
-                gstore<u64>(o.rec + 2 * slot, e0 + (u64)i);
-                gstore<u64>(o.rec + 2 * slot + 1, (u64)xb);
-            }
-        }
-        if (E == 8) { w[2 * i] = (u32)(U)code; w[2 * i + 1] = (u32)((u64)(U)code >> 32); }
-        else w[i] = (u32)(U)code;
+    const u64 slot = atomicAdd(o.count, 1ull);
+    if (slot < o.cap) {
+        gstore<u64>(o.rec + 2 * slot, pos);
+        gstore<u64>(o.rec + 2 * slot + 1, bits);
     }
 }
 
-// split_tile_grid with every loaded unit quantised before it is subtracted or added
+// the quantising split's tile: the lane's own unit quantised and judged, a tap's unit quantised, then the grid split's sink
 template <int E, int Q>
 __device__ __forceinline__ void split_tile_grid_quant(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
                                                       const FieldQ<E> &q, const FieldOutl &o, u8 *d_planes, const u64 *poff)
 {
-#pragma nounroll
-    for (int u = 0; u < PL_UNITS; ++u) {
-        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 >= wk.n) continue;
-        u32 w[4 * E];
-        {
-            uint4 a[E + 1];
-            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
-            shift_into<E, Q, false>(a, r, w);
-        }
-        quant_words_judged<E>(w, q, e0, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), o);
-#pragma nounroll
-        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
-            u64 dist = 0;
-            bool used = true;
-#pragma unroll
-            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
-                if (sub >> k & 1u) {
-                    used = used && lg[k] != 0;
-                    dist += lg[k];
-                }
-            if (!used) continue;                     // (uniform)
-            if (e0 + PL_UNIT > dist) {
-                u32 wb[4 * E];
-                lag_base<E>(wk.in, wk.n, dist, e0, wb);
-                quant_words<E>(wb, q);               // the zeros in front of the block stay zeros
-                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
-                else add_words<E>(w, wb);
-            }
-        }
-        zz_fold<E, 4 * E>(w);
-        split_store<E>(w, wk.n, e0, d_planes, poff);
-    }
+    grid_tile<E, Q>(
+        wk, r, lg, [&](u32 (&w)[4 * E], u64 e0, u32 c) { quant_unit<E>(w, q, c, [&](int i, u64 xb) { outl_record(o, e0 + (u64)i, xb); }); },
+        [&](u32 (&wb)[4 * E]) { quant_words<E>(wb, q); },
+        [&](u32 (&w)[4 * E], u64 e0, u32) {
+            zz_fold<E, 4 * E>(w);
+            split_store<E>(w, wk.n, e0, d_planes, poff);
+        });
 }
 
 // d_lag: planes_grid_split's rows of clamped lags and behind them five rows of nblk: the bits of step, 1 / step and bound as T,
@@ -511,64 +506,25 @@ __device__ __forceinline__ void round_unit(u32 (&w)[4 * E], const RoundQ<E> &q, 
     }
 }
 
+// a tap's unit: nothing is judged
 template <int E>
 __device__ __forceinline__ void round_words(u32 (&w)[4 * E], const RoundQ<E> &q)
 {
     round_unit<E>(w, q, 0u, [](int, u64) {});
 }
 
-// round_words for the lane's OWN unit from element e0: the first c = min(16, n - e0) elements are judged as well and one that is
-// not good is recorded, quant_words_judged's way
-template <int E>
-__device__ __forceinline__ void round_words_judged(u32 (&w)[4 * E], const RoundQ<E> &q, u64 e0, u32 c, const FieldOutl &o)
-{
-    round_unit<E>(w, q, c, [&](int i, u64 xb) {
-        const u64 slot = atomicAdd(o.count, 1ull);
-        if (slot < o.cap) {
-            gstore<u64>(o.rec + 2 * slot, e0 + (u64)i);
-            gstore<u64>(o.rec + 2 * slot + 1, xb);
-        }
-    });
-}
-
-// split_tile_grid_quant with the rounding for the quantiser
+// the rounding split's tile: split_tile_grid_quant with the rounding for the quantiser
 template <int E, int Q>
 __device__ __forceinline__ void split_tile_grid_round(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
                                                       const RoundQ<E> &q, const FieldOutl &o, u8 *d_planes, const u64 *poff)
 {
-#pragma nounroll
-    for (int u = 0; u < PL_UNITS; ++u) {
-        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 >= wk.n) continue;
-        u32 w[4 * E];
-        {
-            uint4 a[E + 1];
-            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
-            shift_into<E, Q, false>(a, r, w);
-        }
-        round_words_judged<E>(w, q, e0, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), o);
-#pragma nounroll
-        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
-            u64 dist = 0;
-            bool used = true;
-#pragma unroll
-            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
-                if (sub >> k & 1u) {
-                    used = used && lg[k] != 0;
-                    dist += lg[k];
-                }
-            if (!used) continue;                     // (uniform)
-            if (e0 + PL_UNIT > dist) {
-                u32 wb[4 * E];
-                lag_base<E>(wk.in, wk.n, dist, e0, wb);
-                round_words<E>(wb, q);               // the zeros in front of the block stay zeros
-                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
-                else add_words<E>(w, wb);
-            }
-        }
-        zz_fold<E, 4 * E>(w);
-        split_store<E>(w, wk.n, e0, d_planes, poff);
-    }
+    grid_tile<E, Q>(
+        wk, r, lg, [&](u32 (&w)[4 * E], u64 e0, u32 c) { round_unit<E>(w, q, c, [&](int i, u64 xb) { outl_record(o, e0 + (u64)i, xb); }); },
+        [&](u32 (&wb)[4 * E]) { round_words<E>(wb, q); },
+        [&](u32 (&w)[4 * E], u64 e0, u32) {
+            zz_fold<E, 4 * E>(w);
+            split_store<E>(w, wk.n, e0, d_planes, poff);
+        });
 }
 
 // d_lag: planes_grid_split's rows of clamped lags and behind them planes_grid_quant_split's five rows of nblk, the first d | mant
@@ -602,8 +558,8 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_round_split(const u8 *
     tp_size_errors(cap, d_n, nblk, err);
 }
 
-// ---- the histograms of the grid split's planes without the planes (shafa_hipd_hist_planes_grid_dev): the walk and the
-// element path of split_tile_grid, and where split_store would write one word of each plane, the word's bytes are counted into a
+// ---- the histograms of the grid split's planes without the planes (shafa_hipd_hist_planes_grid_dev): the split's
+// grid_tile, and where split_store would write one word of each plane, the word's bytes are counted into a
 // replicated LDS histogram per plane (hist.hip's layout: bin s of replica r at s REP + r, a lane's replica from its number).  The
 // high planes of good differences are one byte nearly everywhere; the replicas alone carry that (folding a lane's 16 equal bytes
 // into one atomic measured 1 % SLOWER: DESIGN 7.29).  Only the c = min(16, n - e0) elements in front of the block's end are
@@ -637,101 +593,20 @@ __device__ __forceinline__ void hist_count(const u32 (&w)[4 * E], u32 c, u32 *h)
     }
 }
 
-// split_tile_grid with the fold left out for a block of plain planes (fold, uniform) and hist_count for split_store
+// the three histograms' tiles: the splits' with hist_count for split_store and, for the record, a count in the lane's outl; the
+// fold is left out for a block of plain planes (fold, uniform)
 template <int E, int Q>
 __device__ __forceinline__ void hist_tile_grid(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS], bool fold, u32 *h)
 {
-#pragma nounroll
-    for (int u = 0; u < PL_UNITS; ++u) {
-        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 >= wk.n) continue;
-        u32 w[4 * E];
-        {
-            uint4 a[E + 1];
-            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
-            shift_into<E, Q, false>(a, r, w);
-        }
-#pragma nounroll
-        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
-            u64 dist = 0;
-            bool used = true;
-#pragma unroll
-            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
-                if (sub >> k & 1u) {
-                    used = used && lg[k] != 0;
-                    dist += lg[k];
-                }
-            if (!used) continue;                     // (uniform)
-            if (e0 + PL_UNIT > dist) {
-                u32 wb[4 * E];
-                lag_base<E>(wk.in, wk.n, dist, e0, wb);
-                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
-                else add_words<E>(w, wb);
-            }
-        }
+    grid_tile<E, Q>(wk, r, lg, [](u32 (&)[4 * E], u64, u32) {}, [](u32 (&)[4 * E]) {}, [&](u32 (&w)[4 * E], u64, u32 c) {
         if (fold) zz_fold<E, 4 * E>(w);              // (uniform)
-        hist_count<E>(w, wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0), h);
-    }
+        hist_count<E>(w, c, h);
+    });
 }
 
-// d_lag: planes_grid_split's rows of clamped lags and behind them a row of flags, 0 for a block of plain planes (a row of zeros
-// from the caller), else 1: the clamped lags alone do not tell the two apart
-template <int E>
-__global__ __launch_bounds__(TP_THREADS) void planes_grid_hist(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
-                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
-                                                               const u64 *__restrict__ d_n, const u64 *__restrict__ d_lag,
-                                                               int *__restrict__ err, u32 n_tiles, u64 *__restrict__ d_freq)
-{
-    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
-    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
-    const u32 tid = threadIdx.x;
-    // the workgroup's bins -> block b's counts; every thread sums and clears the replicas of bin tid of each plane (rotated)
-    auto flush = [&](int b) {
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            u32 c = 0;
-#pragma unroll
-            for (u32 q = 0; q < REP; ++q) {
-                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
-                c += *p;
-                *p = 0;
-            }
-            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
-        }
-        lds_barrier();
-    };
-    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
-    lds_barrier();
-    int cur_b = -1;                                  // the block whose counts the bins hold
-    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
-        if (!wk.enter()) continue;
-        if (wk.b != cur_b) {                         // (uniform)
-            if (cur_b >= 0) flush(cur_b);
-            cur_b = wk.b;
-        }
-        u64 lg[SHAFA_PLANES_GRID_LAGS];
-#pragma unroll
-        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
-        const bool fold = d_lag[(u64)SHAFA_PLANES_GRID_LAGS * nblk + wk.b] != 0;
-        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
-        switch (sh >> 2) {                           // uniform
-        case 0: hist_tile_grid<E, 0>(wk, r, lg, fold, h); break;
-        case 1: hist_tile_grid<E, 1>(wk, r, lg, fold, h); break;
-        case 2: hist_tile_grid<E, 2>(wk, r, lg, fold, h); break;
-        default: hist_tile_grid<E, 3>(wk, r, lg, fold, h); break;
-        }
-    }
-    if (cur_b >= 0) flush(cur_b);
-    tp_size_errors(cap, d_n, nblk, err);
-}
-
-// ---- the histograms of the QUANTISING split's planes without the planes (shafa_hipd_hist_planes_grid_quant_dev, DESIGN 7.31):
-// planes_grid_hist over the codes.  The tile function is split_tile_grid_quant's element path — the lane's own unit quantised and
-// judged, every tap's unit quantised behind lag_base, the fold always — with hist_count for split_store and, for the records, a
-// COUNT: a lane adds its outliers to a register of its own (outl; a run is at most GH_RUN x 32 elements a lane), and flush adds
-// the waves' sums to the block's d_outl_n, one 64-bit atomic a wave that found any.  A tensor of noise at a tiny bound, where
-// every element is an outlier, costs 4 atomics a run so and not 65536.
+// planes_grid_quant_hist keeps a walk and a body of its own, the text they had before grid_tile and grid_hist: through the shared
+// ones its float32 (1, 4096) and float64 (1,) legs measured 0.1 to 0.6 % over the unchanged kernel's in two alternated runs
+// (LABNOTES, "one grid tile walk").  A change to grid_tile or to grid_hist has to be made here as well.
 template <int E, int Q>
 __device__ __forceinline__ void hist_tile_grid_quant(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
                                                      const FieldQ<E> &q, u32 *h, u32 &outl)
@@ -748,7 +623,7 @@ __device__ __forceinline__ void hist_tile_grid_quant(const TpWalk &wk, u32 r, co
         }
         const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
 #pragma unroll
-        for (int i = 0; i < PL_UNIT; ++i) {          // quant_words_judged with a count for the record
+        for (int i = 0; i < PL_UNIT; ++i) {          // quant_unit with a count for the record
             using U = typename FieldT<E>::U;
             bool in;
             const U xb = unit_elem<E>(w, i);
@@ -781,6 +656,95 @@ __device__ __forceinline__ void hist_tile_grid_quant(const TpWalk &wk, u32 r, co
     }
 }
 
+template <int E, int Q>
+__device__ __forceinline__ void hist_tile_grid_round(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
+                                                     const RoundQ<E> &q, u32 *h, u32 &outl)
+{
+    grid_tile<E, Q>(
+        wk, r, lg, [&](u32 (&w)[4 * E], u64, u32 c) { round_unit<E>(w, q, c, [&](int, u64) { ++outl; }); },
+        [&](u32 (&wb)[4 * E]) { round_words<E>(wb, q); },
+        [&](u32 (&w)[4 * E], u64, u32 c) {
+            zz_fold<E, 4 * E>(w);
+            hist_count<E>(w, c, h);
+        });
+}
+
+// the body of the histogram kernels (planes_grid_quant_hist keeps a copy of its own): the bins, the walk in runs of GH_RUN tiles and the flushes.  tile(wk, h, outl) makes
+// the block's parameters from its rows and walks the tile wk has entered, counting into h.  OUTL: the kernel counts outliers as
+// well.  A lane adds its own to the register outl (a run is at most GH_RUN x 32 elements a lane), and flush adds the waves' sums
+// to the block's d_outl_n, one 64-bit atomic a wave that found any: a tensor of noise at a tiny bound, where every element is an
+// outlier, costs 4 atomics a run so and not 65536.
+template <int E, bool OUTL, class Tile>
+__device__ __forceinline__ void grid_hist(const u8 *d_el, const u64 *off, const u64 *cap, const u32 *tbase, int nblk, const u64 *d_n,
+                                          int *err, u32 n_tiles, u64 *d_freq, u64 *d_outl_n, Tile &&tile)
+{
+    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
+    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
+    const u32 tid = threadIdx.x;
+    u32 outl = 0;                                    // the lane's outliers of block cur_b since the last flush
+    // the workgroup's bins -> block b's counts; every thread sums and clears the replicas of bin tid of each plane (rotated); the
+    // lane's counter is cleared with the bins
+    auto flush = [&](int b) {
+        lds_barrier();
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            u32 c = 0;
+#pragma unroll
+            for (u32 q = 0; q < REP; ++q) {
+                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
+                c += *p;
+                *p = 0;
+            }
+            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
+        }
+        if constexpr (OUTL) {
+            const u32 wsum = wave_reduce_add<u32>(outl);
+            if (wsum && lane_id() == 0) atomicAdd((unsigned long long *)d_outl_n + b, (unsigned long long)wsum);
+            outl = 0;
+        }
+        lds_barrier();
+    };
+    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
+    lds_barrier();
+    int cur_b = -1;                                  // the block whose counts the bins and the counter hold
+    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
+        if (!wk.enter()) continue;
+        if (wk.b != cur_b) {                         // (uniform)
+            if (cur_b >= 0) flush(cur_b);
+            cur_b = wk.b;
+        }
+        tile(wk, h, outl);
+    }
+    if (cur_b >= 0) flush(cur_b);
+    tp_size_errors(cap, d_n, nblk, err);
+}
+
+// d_lag: planes_grid_split's rows of clamped lags and behind them a row of flags, 0 for a block of plain planes (a row of zeros
+// from the caller), else 1: the clamped lags alone do not tell the two apart
+template <int E>
+__global__ __launch_bounds__(TP_THREADS) void planes_grid_hist(const u8 *__restrict__ d_el, const u64 *__restrict__ off,
+                                                               const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
+                                                               const u64 *__restrict__ d_n, const u64 *__restrict__ d_lag,
+                                                               int *__restrict__ err, u32 n_tiles, u64 *__restrict__ d_freq)
+{
+    grid_hist<E, false>(d_el, off, cap, tbase, nblk, d_n, err, n_tiles, d_freq, nullptr, [&](const TpWalk &wk, u32 *h, u32 &) {
+        u64 lg[SHAFA_PLANES_GRID_LAGS];
+#pragma unroll
+        for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
+        const bool fold = d_lag[(u64)SHAFA_PLANES_GRID_LAGS * nblk + wk.b] != 0;
+        const u32 sh = (u32)((uintptr_t)wk.in & 15u), r = sh & 3u;
+        switch (sh >> 2) {                           // uniform
+        case 0: hist_tile_grid<E, 0>(wk, r, lg, fold, h); break;
+        case 1: hist_tile_grid<E, 1>(wk, r, lg, fold, h); break;
+        case 2: hist_tile_grid<E, 2>(wk, r, lg, fold, h); break;
+        default: hist_tile_grid<E, 3>(wk, r, lg, fold, h); break;
+        }
+    });
+}
+
+// ---- the histograms of the QUANTISING split's planes without the planes (shafa_hipd_hist_planes_grid_quant_dev, DESIGN 7.31):
+// planes_grid_hist over the codes, with the quantising split's callables for the lane's own unit and a tap's, the fold always,
+// and the outliers COUNTED where the split records them (grid_hist's outl).
 // d_lag: planes_grid_split's rows of clamped lags and behind them three rows of nblk: the bits of step, 1 / step and bound as T.
 // d_freq and d_outl_n have been zeroed on the stream.
 template <int E>
@@ -795,7 +759,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_hist(const u8 *_
     __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
     const u32 tid = threadIdx.x;
     u32 outl = 0;                                    // the lane's outliers of block cur_b since the last flush
-    // planes_grid_hist's flush, and the waves' outliers -> block b's count; the lane's counter is cleared with the bins
+    // grid_hist's flush
     auto flush = [&](int b) {
         lds_barrier();
 #pragma unroll
@@ -841,48 +805,7 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_quant_hist(const u8 *_
 }
 
 // ---- the histograms of the ROUNDING split's planes without the planes (shafa_hipd_hist_planes_grid_round_dev):
-// planes_grid_quant_hist with split_tile_grid_round's element path: the bins, the runs, the flush and the outlier count in a
-// register are that kernel's.
-template <int E, int Q>
-__device__ __forceinline__ void hist_tile_grid_round(const TpWalk &wk, u32 r, const u64 (&lg)[SHAFA_PLANES_GRID_LAGS],
-                                                     const RoundQ<E> &q, u32 *h, u32 &outl)
-{
-#pragma nounroll
-    for (int u = 0; u < PL_UNITS; ++u) {
-        const u64 e0 = wk.pos0 + (u64)u * PL_PASS + (u64)threadIdx.x * PL_UNIT;
-        if (e0 >= wk.n) continue;
-        u32 w[4 * E];
-        {
-            uint4 a[E + 1];
-            load_words<E, true>(wk.in, wk.n * E, e0 * E, 4u * Q + r, a);
-            shift_into<E, Q, false>(a, r, w);
-        }
-        const u32 c = wk.n - e0 >= PL_UNIT ? (u32)PL_UNIT : (u32)(wk.n - e0);
-        round_unit<E>(w, q, c, [&](int, u64) { ++outl; });                      // round_words_judged with a count for the record
-#pragma nounroll
-        for (u32 sub = 1; sub < 1u << SHAFA_PLANES_GRID_LAGS; ++sub) {          // (uniform)
-            u64 dist = 0;
-            bool used = true;
-#pragma unroll
-            for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k)
-                if (sub >> k & 1u) {
-                    used = used && lg[k] != 0;
-                    dist += lg[k];
-                }
-            if (!used) continue;                     // (uniform)
-            if (e0 + PL_UNIT > dist) {
-                u32 wb[4 * E];
-                lag_base<E>(wk.in, wk.n, dist, e0, wb);
-                round_words<E>(wb, q);               // the zeros in front of the block stay zeros
-                if (__builtin_popcount(sub) & 1) sub_words<E>(w, wb);           // (uniform)
-                else add_words<E>(w, wb);
-            }
-        }
-        zz_fold<E, 4 * E>(w);
-        hist_count<E>(w, c, h);
-    }
-}
-
+// planes_grid_quant_hist with the rounding for the quantiser.
 // d_lag: planes_grid_split's rows of clamped lags and behind them one row of nblk: d | mant << 8.  d_freq and d_outl_n have been
 // zeroed on the stream.
 template <int E>
@@ -893,39 +816,8 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_round_hist(const u8 *_
                                                                      u32 n_tiles, u64 *__restrict__ d_freq,
                                                                      u64 *__restrict__ d_outl_n)
 {
-    constexpr u32 REP = gh_rep<E>(), GH_BINS = 256u * E * REP;
-    __shared__ u32 h[GH_BINS];                       // bin s of replica r of plane j at (j 256 + s) REP + r
-    const u32 tid = threadIdx.x;
-    u32 outl = 0;                                    // the lane's outliers of block cur_b since the last flush
-    // planes_grid_quant_hist's flush
-    auto flush = [&](int b) {
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < E; ++j) {
-            u32 c = 0;
-#pragma unroll
-            for (u32 q = 0; q < REP; ++q) {
-                u32 *p = &h[((u32)j * 256u + tid) * REP + ((q + tid) & (REP - 1u))];
-                c += *p;
-                *p = 0;
-            }
-            if (c) atomicAdd((unsigned long long *)(d_freq + ((size_t)b * E + j) * 256 + tid), (unsigned long long)c);
-        }
-        const u32 wsum = wave_reduce_add<u32>(outl);
-        if (wsum && lane_id() == 0) atomicAdd((unsigned long long *)d_outl_n + b, (unsigned long long)wsum);
-        outl = 0;
-        lds_barrier();
-    };
-    for (u32 i = tid; i < GH_BINS; i += TP_THREADS) h[i] = 0;
-    lds_barrier();
     const u64 *qp = d_lag + (u64)SHAFA_PLANES_GRID_LAGS * nblk;
-    int cur_b = -1;                                  // the block whose counts the bins and the counters hold
-    for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, GH_RUN); wk.more(); wk.step()) {
-        if (!wk.enter()) continue;
-        if (wk.b != cur_b) {                         // (uniform)
-            if (cur_b >= 0) flush(cur_b);
-            cur_b = wk.b;
-        }
+    grid_hist<E, true>(d_el, off, cap, tbase, nblk, d_n, err, n_tiles, d_freq, d_outl_n, [&](const TpWalk &wk, u32 *h, u32 &outl) {
         u64 lg[SHAFA_PLANES_GRID_LAGS];
 #pragma unroll
         for (int k = 0; k < SHAFA_PLANES_GRID_LAGS; ++k) lg[k] = d_lag[(u64)k * nblk + wk.b];
@@ -937,15 +829,13 @@ __global__ __launch_bounds__(TP_THREADS) void planes_grid_round_hist(const u8 *_
         case 2: hist_tile_grid_round<E, 2>(wk, r, lg, q, h, outl); break;
         default: hist_tile_grid_round<E, 3>(wk, r, lg, q, h, outl); break;
         }
-    }
-    if (cur_b >= 0) flush(cur_b);
-    tp_size_errors(cap, d_n, nblk, err);
+    });
 }
 
 // ---- error statistics (shafa_hipd_error_dev, shafa_hipd_error_quant_dev, shafa_hipd_error_round_dev): what a bound
 // costs.  x is the original element and y the element it comes back as: the element of a second tensor (ERR_PAIR), or what the
 // quantising (ERR_QUANT) or the rounding (ERR_ROUND) merge would give back, made in registers from x with the split's own
-// functions — x' where the element is good, x's own bits where it is an outlier.  The walk is hist_tile_grid_quant's without taps,
+// functions — x' where the element is good, x's own bits where it is an outlier.  The walk is grid_tile's without taps,
 // bins or LDS histograms: a lane loads its units of 16 elements and folds them, by index, into an ErrAgg.  Every sum, product and
 // comparison is one IEEE double operation, none contracted, and the order is fixed: the lane's elements by index, err_wave_reduce's
 // tree across the wave, the four waves in order, one partial of SHAFA_ERR_WORDS words a tile; planes_error_blocks folds a block's
@@ -1603,9 +1493,33 @@ __global__ __launch_bounds__(TP_THREADS) void planes_lag_merge(u8 *__restrict__ 
 
 // ---- behind the grid merge of an error-bounded field: the codes, in place, -> T(code) (x) step, then the outliers'
 // own bits on top.
-// the restore: a tile's elements lie in whole 16-byte words of the address space but for the word the tile starts in and the one
-// it ends in (the element side is at multiples of E, so an element never straddles two words): a lane takes every 256th word, one
-// 16-byte load and store, and the elements of a cut word one by one.  d_step: the bits of the blocks' steps as T.
+// the restore of the tile wk has entered, for the quantised and the rounded field: a tile's elements lie in whole 16-byte words
+// of the address space but for the word the tile starts in and the one it ends in (the element side is at multiples of E, so an
+// element never straddles two words): a lane takes every 256th word, one 16-byte load and store with word(x) on its four u32 in
+// between, and the elements of a cut word one by one, elem(p) on the element at p.
+template <int E, class Word, class Elem>
+__device__ __forceinline__ void restore_tile(const TpWalk &wk, Word word, Elem elem)
+{
+    const u64 end = wk.pos0 + TP_TILE < wk.n ? wk.pos0 + TP_TILE : wk.n;
+    const u64 lo = (u64)(uintptr_t)wk.in + wk.pos0 * E, hi = (u64)(uintptr_t)wk.in + end * E;          // the tile's bytes
+    for (u64 a = (lo & ~(u64)15) + 16ull * threadIdx.x; a < hi; a += 16ull * TP_THREADS) {
+        u8 *p = (u8 *)(uintptr_t)a;
+        if (a >= lo && a + 16 <= hi) {
+            const uint4 v = gload<uint4>(p);
+            u32 x[4] = {v.x, v.y, v.z, v.w};
+            word(x);
+            gstore<uint4>(p, make_uint4(x[0], x[1], x[2], x[3]));
+        } else {
+#pragma unroll
+            for (u32 i = 0; i < 16 / E; ++i) {
+                const u64 at = a + (u64)i * E;
+                if (at >= lo && at < hi) elem(p + i * E);
+            }
+        }
+    }
+}
+
+// d_step: the bits of the blocks' steps as T
 template <int E>
 __global__ __launch_bounds__(TP_THREADS) void planes_field_restore(u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                                    const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
@@ -1614,39 +1528,26 @@ __global__ __launch_bounds__(TP_THREADS) void planes_field_restore(u8 *__restric
 {
     using U = typename FieldT<E>::U;
     using I = typename FieldT<E>::I;
-    constexpr u32 PER = 16 / E;                      // elements of a word
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
         const typename FieldT<E>::F step = field_bits<E>(d_step[wk.b]);
-        const u64 end = wk.pos0 + TP_TILE < wk.n ? wk.pos0 + TP_TILE : wk.n;
-        const u64 lo = (u64)(uintptr_t)wk.in + wk.pos0 * E, hi = (u64)(uintptr_t)wk.in + end * E;      // the tile's bytes
-        for (u64 a = (lo & ~(u64)15) + 16ull * threadIdx.x; a < hi; a += 16ull * TP_THREADS) {
-            u8 *p = (u8 *)(uintptr_t)a;
-            if (a >= lo && a + 16 <= hi) {
-                const uint4 v = gload<uint4>(p);
-                u32 x[4] = {v.x, v.y, v.z, v.w};
+        restore_tile<E>(
+            wk,
+            [&](u32 (&x)[4]) {
 #pragma unroll
-                for (u32 i = 0; i < PER; ++i) {
+                for (u32 i = 0; i < 16 / E; ++i) {
                     const I code = E == 8 ? (I)((u64)x[(2 * i + 1) & 3] << 32 | x[(2 * i) & 3]) : (I)x[i];
                     const u64 y = (u64)__builtin_bit_cast(U, field_value<E>(code, step));
                     if (E == 8) { x[(2 * i) & 3] = (u32)y; x[(2 * i + 1) & 3] = (u32)(y >> 32); }
                     else x[i] = (u32)y;
                 }
-                gstore<uint4>(p, make_uint4(x[0], x[1], x[2], x[3]));
-            } else {
-#pragma unroll
-                for (u32 i = 0; i < PER; ++i) {
-                    const u64 at = a + (u64)i * E;
-                    if (at >= lo && at < hi)
-                        gstore<U>(p + i * E, __builtin_bit_cast(U, field_value<E>((I)gload<U>(p + i * E), step)));
-                }
-            }
-        }
+            },
+            [&](u8 *p) { gstore<U>(p, __builtin_bit_cast(U, field_value<E>((I)gload<U>(p), step))); });
     }
 }
 
-// ---- behind the grid merge of a rounded field: planes_field_restore's walk with round_value for the restorer, eight
-// elements a 16-byte word at E = 2.  d_q: the blocks' d | mant << 8.
+// ---- behind the grid merge of a rounded field: restore_tile with round_value for the restorer, eight elements a
+// 16-byte word at E = 2.  d_q: the blocks' d | mant << 8.
 template <int E>
 __global__ __launch_bounds__(TP_THREADS) void planes_round_restore(u8 *__restrict__ d_el, const u64 *__restrict__ off,
                                                                    const u64 *__restrict__ cap, const u32 *__restrict__ tbase, int nblk,
@@ -1655,17 +1556,12 @@ __global__ __launch_bounds__(TP_THREADS) void planes_round_restore(u8 *__restric
 {
     using U = typename RoundT<E>::U;
     using S = typename ElT<E>::T;                    // an element as it is stored
-    constexpr u32 PER = 16 / E;                      // elements of a word
     for (TpWalk wk(d_el, off, cap, tbase, nblk, d_n, n_tiles, per_wg); wk.more(); wk.step()) {
         if (!wk.enter()) continue;
         const u32 d = (u32)d_q[wk.b] & 0xFFu;
-        const u64 end = wk.pos0 + TP_TILE < wk.n ? wk.pos0 + TP_TILE : wk.n;
-        const u64 lo = (u64)(uintptr_t)wk.in + wk.pos0 * E, hi = (u64)(uintptr_t)wk.in + end * E;      // the tile's bytes
-        for (u64 a = (lo & ~(u64)15) + 16ull * threadIdx.x; a < hi; a += 16ull * TP_THREADS) {
-            u8 *p = (u8 *)(uintptr_t)a;
-            if (a >= lo && a + 16 <= hi) {
-                const uint4 v = gload<uint4>(p);
-                u32 x[4] = {v.x, v.y, v.z, v.w};
+        restore_tile<E>(
+            wk,
+            [&](u32 (&x)[4]) {
 #pragma unroll
                 for (u32 i = 0; i < 4; ++i) {
                     if (E == 8) {
@@ -1676,15 +1572,8 @@ __global__ __launch_bounds__(TP_THREADS) void planes_round_restore(u8 *__restric
                     } else if (E == 4) x[i] = (u32)round_value<E>((U)x[i], d);
                     else x[i] = (u32)round_value<E>((U)(x[i] & 0xFFFFu), d) | (u32)round_value<E>((U)(x[i] >> 16), d) << 16;
                 }
-                gstore<uint4>(p, make_uint4(x[0], x[1], x[2], x[3]));
-            } else {
-#pragma unroll
-                for (u32 i = 0; i < PER; ++i) {
-                    const u64 at = a + (u64)i * E;
-                    if (at >= lo && at < hi) gstore<S>(p + i * E, (S)round_value<E>((U)gload<S>(p + i * E), d));
-                }
-            }
-        }
+            },
+            [&](u8 *p) { gstore<S>(p, (S)round_value<E>((U)gload<S>(p), d)); });
     }
 }
 

@@ -258,6 +258,57 @@ def test_one_launch_each_against_the_model(shafa, k):
     _all_three(shafa, L, [n + 5 for n in L.n])
 
 
+@pytest.mark.parametrize("k", (2, 4, 8))
+def test_block_borders_inside_a_run(shafa, k):
+    """test_gpu_field_hist's test of the same name for the rounding histogram: sixty-four blocks of 100 .. 3000 elements, a tile
+    each and so eight to a run, alternately all outliers and clean, neighbours at different keeps: a count flushed to the wrong
+    block, or a counter not cleared at a border, shows in the neighbour.  An outlier here is a NaN whose lowest mantissa bit is
+    set, at a keep below the mantissa's width: the bit is dropped, so the element does not come back (include/shafa_hip.h)"""
+    rng = np.random.default_rng(900 + k)
+    ns = rng.integers(100, 3001, 64).tolist()
+    ns[0], ns[1], ns[-1] = 100, 3000, 3000
+    nb = len(ns)
+    rows = [(1,), (1, 7), (3,), (2, 3, 50)]
+    fmts = {2: ("bfloat16", "float16"), 4: ("float32",), 8: ("float64",)}[k]
+    blocks = [(n, rows[b % 4], (0, 1, 3)[b % 3], fmts[b // 2 % len(fmts)], 1 + b % 5) for b, n in enumerate(ns)]
+    assert all(p[4] != q[4] and p[4] < MANT[p[3]] for p, q in zip(blocks, blocks[1:] + blocks[:1]))
+
+    def nans(n, fmt):
+        W, mant = 8 * k, MANT[fmt]
+        inf = ((1 << (W - 1 - mant)) - 1) << mant
+        sign = (np.arange(n) % 3 == 1).astype(UINT[k]) << UINT[k](W - 1)
+        return sign | UINT[k](inf | 1) | ((np.arange(n) % 5).astype(UINT[k]) << UINT[k](mant - 1))        # quiet and signalling
+
+    def clean(n, fmt):
+        return _to_bits(np.arange(n) * 0.5 + 3 * np.sin(np.arange(n) / 5), fmt)
+
+    # both ways round, so that every block is once behind a block of outliers and once in front of one
+    for first in (0, 1):
+        L = _Layout(shafa, blocks, xs=[nans(n, b[3]) if i % 2 == first else clean(n, b[3]) for i, (n, b) in enumerate(zip(ns, blocks))])
+        found = [len(r) for r in L.rec]
+        assert found == [n if b % 2 == first else 0 for b, n in enumerate(ns)]
+        st = _stream()
+        bt = shafa.Batch(nb * k, 1 << 20)
+        try:
+            d_n, d_el = _sizes(ns), _to(L.el)
+            d_freq, d_hcnt = _fill64(nb * k * 256 + 2), _fill64(nb + 2)
+            bt.hist_planes_grid_round_dev(st, k, L.lags, L.mant, L.keep, d_el, L.off, ns, d_n, d_freq[1:-1], d_hcnt[1:nb + 1])
+            # device code against device code: the rounding split's planes through hist256, and the split's own counts
+            d_pl, d_freq2, d_cnt = _fill(L.pl.size), _fill64(nb * k * 256 + 4), _fill64(nb + 2)
+            bt.split_planes_grid_round_dev(st, k, L.lags, L.mant, L.keep, d_el, L.off, ns, d_n, d_pl, L.poff, None, [0] * nb, [0] * nb,
+                                           d_cnt[1:nb + 1])
+            bt.hist256(st, d_pl, L.poff, [n for n in ns for _ in range(k)], d_freq2[2:-2])
+            assert bt.finish(st, nb * k) == (0, [0] * nb * k)
+            assert d_hcnt.tolist() == [FILL64 - (1 << 64)] + found + [FILL64 - (1 << 64)] == d_cnt.tolist()
+            hf = _u64img(d_freq)
+            assert (hf[1:-1].reshape(nb, k, 256).sum(2) == np.array(ns, np.uint64)[:, None]).all()         # every plane's counts sum to n
+            assert hf.tobytes() == _u64img(d_freq2)[1:-1].tobytes()
+            assert hf[0] == FILL64 and hf[-1] == FILL64 and hf[1:-1].tobytes() == L.freq.tobytes()
+            assert _img(d_el) == L.el.tobytes()
+        finally:
+            bt.close()
+
+
 # ---------------------------------------------------------------- 2. exhaustive at 16 bits
 def test_every_16_bit_pattern_at_every_keep(shafa):
     """all 65 536 bit patterns of bfloat16 and of float16, one block each per keep: 8 + 11 blocks in one launch of each of split,
