@@ -100,6 +100,11 @@ const char *shafa_hip_last_error(void);      /* text of the last SHAFA_DEVICE_ER
  *       longest code, at most 12.  A tile that needs more is not placed: its block is flagged on the device and encoded
  *       again by the 256-lane form in the same call (what happens to 13..16-bit codes whose rare symbols fill a whole
  *       32 KiB tile); small values make ordinary data take that path.
+ *   "rle_grid_rows": what one launch of the RLE encoder's and decoder's kernels may put on its grid, as (rows of the
+ *       largest block) x (blocks): a call's blocks are launched in consecutive runs within it, a block above it alone (rows:
+ *       a decoder input's 8 KiB tiles, an encoder input's pairs of 4 KiB tiles).  0 (default) = 2^22, v >= 1 = v (at most
+ *       2^24 - 1), negative: SHAFA_OUTSIDE_MODULE.  Results do not depend on it; small values make small batches take
+ *       several runs.
  * shafa_hip_init() reads the environment variables SHAFA_SF_ENCODE_ONE_PASS_MIN_BLOCKS and SHAFA_SF_DECODE_SPECULATE
  * once for the first two knobs. */
 int shafa_hip_set_option(const char *name, long value);
@@ -166,7 +171,9 @@ int shafa_hipd_hist256(shafa_hipd_batch *b, void *stream, int nblocks, const uin
 int shafa_hipd_sf_build_codes(shafa_hipd_batch *b, void *stream, int nblocks, const uint64_t *d_freq,
                               shafa_code_table *d_tables);
 
-/* block_compression per block; d_out_n[b] = RLE size; d_freq (may be NULL) = histogram of the RLE bytes. */
+/* block_compression per block; d_out_n[b] = RLE size; d_freq (may be NULL) = histogram of the RLE bytes.  Any number of
+ * blocks of any sizes up to the batch's: the launches are cut to fit the grid ("rle_grid_rows").  A block of 2^24 pairs of
+ * 4 KiB tiles (128 GiB) or more: SHAFA_LACK_OF_MEMORY for the call, before any device work. */
 int shafa_hipd_rle_encode(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                           const uint64_t *h_in_off, const uint64_t *h_in_n, uint8_t *d_out,
                           const uint64_t *h_out_off, const uint64_t *h_out_cap,
@@ -198,7 +205,7 @@ int shafa_hipd_hist256_tiles(shafa_hipd_batch *b, void *stream, int nblocks, con
                              uint8_t *d_tile_hist, const uint64_t *h_tile_hist_off);
 
 /* block_compression + make_freq of the RLE bytes as shafa_hipd_rle_encode (d_freq required), plus the tile histograms of
- * the RLE bytes: block b's region must hold shafa_hip_tile_hist_bytes(h_out_cap[b]) bytes. */
+ * the RLE bytes: block b's region must hold shafa_hip_tile_hist_bytes(h_out_cap[b]) bytes.  SHAFA_LACK_OF_MEMORY as there. */
 int shafa_hipd_rle_encode_tiles(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                                 const uint64_t *h_in_off, const uint64_t *h_in_n, uint8_t *d_out,
                                 const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n,
@@ -234,7 +241,9 @@ int shafa_hipd_sf_decode(shafa_hipd_batch *b, void *stream, int nblocks, const u
                          const shafa_code_table *h_tables, const uint64_t *h_n_symbols,
                          uint8_t *d_out, const uint64_t *h_out_off);
 
-/* rle_block_decompressor per block; d_out_n[b] = decoded size. */
+/* rle_block_decompressor per block; d_out_n[b] = decoded size.  Any number of blocks of any sizes up to the batch's: the
+ * launches are cut to fit the grid ("rle_grid_rows").  A block of 2^24 tiles of 8 KiB (128 GiB) or more: SHAFA_LACK_OF_MEMORY
+ * for the call, before any device work. */
 int shafa_hipd_rle_decode(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                           const uint64_t *h_in_off, const uint64_t *h_in_n, uint8_t *d_out,
                           const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);
@@ -264,7 +273,8 @@ int shafa_hipd_sf_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, con
 /* shafa_hipd_rle_decode with the block sizes in DEVICE memory: block b decodes the d_in_n[b] (<= h_in_cap[b]) bytes at
  * d_in + h_in_off[b].  Results equal shafa_hipd_rle_decode with h_in_n = d_in_n; d_in_n[b] > h_in_cap[b] is
  * SHAFA_OUTSIDE_MODULE for block b (d_out_n[b] = 0).  Enqueues only, as shafa_hipd_sf_decode_dev: with it an RLE
- * session decodes host-free (sf_decode_dev's d_n_symbols is this call's d_in_n).  NULL b or d_in_n: SHAFA_OUTSIDE_MODULE. */
+ * session decodes host-free (sf_decode_dev's d_n_symbols is this call's d_in_n).  NULL b or d_in_n: SHAFA_OUTSIDE_MODULE;
+ * SHAFA_LACK_OF_MEMORY as for shafa_hipd_rle_decode, by h_in_cap. */
 int shafa_hipd_rle_decode_dev(shafa_hipd_batch *b, void *stream, int nblocks, const uint8_t *d_in,
                               const uint64_t *h_in_off, const uint64_t *h_in_cap, const uint64_t *d_in_n,
                               uint8_t *d_out, const uint64_t *h_out_off, const uint64_t *h_out_cap, uint64_t *d_out_n);

@@ -1224,9 +1224,7 @@ MANY_GROUP_BLOCKS = 16384      # compress_many: blocks per device batch (the F /
 def _many_files(name, d_in, sizes, block_size):
     """compress_many's arguments checked -> (d_in as one tensor, sizes, each file's start in d_in, {file: its block sizes} by
     the C host's split (shafa_block_count) for the files of 1 KiB or more, groups of those files): a group holds at most
-    MANY_GROUP_BLOCKS blocks, and (its largest block's 8 KiB tiles) x (its blocks) stays within RLE_GRID_TILES, which bounds
-    the grid of rle_encode_tiles' emit pass — (pairs of 4 KiB tiles of the largest block) x (blocks) workgroups of 256 lanes —
-    below 2^32 lanes however many small blocks join a large one.  A file alone is one group whatever its block count."""
+    MANY_GROUP_BLOCKS blocks.  A file alone is one group whatever its block count."""
     import torch
     if isinstance(d_in, (list, tuple)):
         if sizes is None:
@@ -1250,16 +1248,14 @@ def _many_files(name, d_in, sizes, block_size):
             bs, last = C.c_uint64(int(block_size)), C.c_uint64(0)
             nb = int(host().shafa_block_count(n, C.byref(bs), C.byref(last)))
             split[f] = [bs.value] * (nb - 1) + [last.value]
-    groups, group, acc, mt = [], [], 0, 0
+    groups, group, acc = [], [], 0
     for f in split:
-        t = max(1, -(-max(split[f]) // 8192))
         k = len(split[f])
-        if group and (acc + k > MANY_GROUP_BLOCKS or max(mt, t) * (acc + k) > RLE_GRID_TILES):
+        if group and acc + k > MANY_GROUP_BLOCKS:
             groups.append(group)
-            group, acc, mt = [], 0, 0
+            group, acc = [], 0
         group.append(f)
         acc += k
-        mt = max(mt, t)
     if group:
         groups.append(group)
     return d_in, sizes, start, split, groups
@@ -1296,7 +1292,7 @@ def compress_many(d_in, sizes=None, block_size=65536, force_rle=False, force_fre
     files mixed (inputs and RLE outputs addressed from one base, tile histograms in one arena) -> the segmented packs, one
     call per kind of file (the single-file packs for a batch of one file) -> one finish.  Two synchronisations per batch.  force_rle keeps the chain without a size pass:
     rle_encode_tiles over all blocks into worst-case regions (2 n + 3, f.c:244), one synchronisation per batch.  Files are
-    batched by MANY_GROUP_BLOCKS blocks and by the RLE encoder's grid (_many_files)."""
+    batched by MANY_GROUP_BLOCKS blocks (_many_files); the RLE encoder cuts its own grids."""
     return _per_group("compress_many", d_in, sizes, block_size, stream, lambda g: _compress_group(g, force_rle, force_freq))
 
 
@@ -1609,9 +1605,6 @@ def _first_error(errs):
     return next(((i, e) for i, e in enumerate(errs) if e), (len(errs), SUCCESS))
 
 
-RLE_GRID_TILES = 1 << 22        # rle_decode_dev workgroups per call (x 256 lanes: below 2^32)
-
-
 def _rle_measure(bt, st, d_in, in_off, in_n, d_in_n, n_err):
     """The size pass (rle_decoded_size_dev) over these RLE blocks and its synchronisation, which reads the sizes back
     -> (decoded sizes, per-block codes).  n_err: the error words shafa_hipd_finish reads."""
@@ -1622,26 +1615,22 @@ def _rle_measure(bt, st, d_in, in_off, in_n, d_in_n, n_err):
     return _u64_host(d_size)[:len(in_n)], errs[:len(in_n)]
 
 
-def _groups(cost, max_bytes, tiles=None):
-    """Consecutive blocks whose costs (bytes) fit max_bytes — a block above it is a group of its own — and, with `tiles`
-    (one count per block), whose (largest count) x (blocks) stays within RLE_GRID_TILES -> [(first, end)]"""
-    groups, g0, acc, mt = [], 0, 0, 0
+def _groups(cost, max_bytes):
+    """Consecutive blocks whose costs (bytes) fit max_bytes — a block above it is a group of its own -> [(first, end)]"""
+    groups, g0, acc = [], 0, 0
     for b, c in enumerate(cost):
-        t = tiles[b] if tiles else 0
-        if b > g0 and (acc + c > max_bytes or max(mt, t) * (b - g0 + 1) > RLE_GRID_TILES):
+        if b > g0 and acc + c > max_bytes:
             groups.append((g0, b))
-            g0, acc, mt = b, 0, 0
+            g0, acc = b, 0
         acc += c
-        mt = max(mt, t)
     groups.append((g0, len(cost)))
     return groups
 
 
-def _rle_groups(sizes, in_n, max_bytes):
-    """Consecutive blocks whose exact output regions (_al16(size)) fit max_bytes and whose rle_decode_dev grid — (its largest
-    input's 8 KiB tiles) x (its blocks) workgroups of 256 lanes — stays within RLE_GRID_TILES, so the grid's lanes stay below
-    2^32 however many small blocks join a large one -> [(first, end)]"""
-    return _groups([_al16(s) for s in sizes], max_bytes, [max(1, -(-n // 8192)) for n in in_n])
+def _rle_groups(sizes, max_bytes):
+    """Consecutive blocks whose exact output regions (_al16(size)) fit max_bytes -> [(first, end)]; rle_decode_dev cuts its
+    own grids, however many small blocks join a large one"""
+    return _groups([_al16(s) for s in sizes], max_bytes)
 
 
 def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes, groups=None):
@@ -1651,7 +1640,7 @@ def _rle_decode_groups(bt, st, d_in, in_off, in_n, d_in_n, sizes, max_bytes, gro
     overwrites it.  Groups that decode to nothing are left out.  Enqueues only."""
     import torch
     dev = d_in.device
-    groups = groups or _rle_groups(sizes, in_n, max_bytes)
+    groups = groups or _rle_groups(sizes, max_bytes)
     biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
     d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
     d_out_n = torch.zeros(len(sizes), dtype=torch.int64, device=dev)
@@ -1898,7 +1887,7 @@ class _ParsedSet:
         else:
             self.sizes, self.rin = self.measure()
             self.fault()
-            self.groups = _rle_groups(self.sizes, self.rin[2], self.max_bytes)
+            self.groups = _rle_groups(self.sizes, self.max_bytes)
         self.starts = list(itertools.accumulate(self.sizes, initial=0))
 
     def walk(self, reader, before_last=None):
@@ -2562,8 +2551,8 @@ def decompress_many(entries, stream=None, max_bytes=None):
     over the blocks of every .shaf file -> pack_payloads_files(RAW) for files without RLE decoding -> synchronisation 2 ->
     each block that lost sf_decode_dev's single 33..64-bit slot decoded again alone (one synchronisation each, one more to pack
     its file again) -> the size pass over every RLE block (rle_decoded_size_dev) and the synchronisation that reads the sizes
-    -> rle_decode_dev into regions of exactly those sizes, in groups bounded by max_bytes (default: a quarter of the free
-    device memory) that follow each other without a synchronisation, each followed by pack_payloads_files(RAW) into exact
+    -> rle_decode_dev into regions of exactly those sizes, in groups bounded by max_bytes alone (default: a quarter of the free
+    device memory; the launcher cuts its own grids) that follow each other without a synchronisation, each followed by pack_payloads_files(RAW) into exact
     per-file regions -> one last synchronisation.
     Synchronisations per group: 2 without RLE decoding; with it, 4 with .shaf files and 3 for .rle + .freq only, however
     many RLE groups there are.  Decoded blocks are taken MANY_GROUP_BLOCKS at a time (sf_decode_dev puts
@@ -2777,7 +2766,7 @@ def _rle_decode_many(bt, st, dev, rle_in, max_bytes, results):
         if len(sel) < nb:
             in_off, in_n, sizes, owner = ([v[b] for b in sel] for v in (in_off, in_n, sizes, owner))
             d_in_n = d_in_n.index_select(0, torch.tensor(sel, dtype=torch.int64, device=dev))
-        groups = _rle_groups(sizes, in_n, max_bytes)
+        groups = _rle_groups(sizes, max_bytes)
         biggest = max(_layout(sizes[a:z])[1] for a, z in groups)
         d_out = torch.empty(biggest + 16, dtype=torch.uint8, device=dev)
         d_out_n = torch.zeros(len(sel), dtype=torch.int64, device=dev)

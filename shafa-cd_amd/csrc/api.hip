@@ -14,6 +14,7 @@
 // error text (per calling thread: the reference's drivers call the per-block functions from one thread per block)
 // ------------------------------------------------------------------------------------------------
 static thread_local char g_last_error[512] = "";
+u64 g_rle_grid_rows = 0;                     // "rle_grid_rows" (internal.hpp, grid_slices)
 
 int shafa_set_hip_error(hipError_t e, const char *what)
 {
@@ -337,6 +338,11 @@ int shafa_hip_set_option(const char *name, long value)
     }
     if (name && !strcmp(name, "rle_encode_general")) {
         rleenc_configure(value != 0);
+        return SHAFA_SUCCESS;
+    }
+    if (name && !strcmp(name, "rle_grid_rows")) {
+        if (value < 0) return SHAFA_OUTSIDE_MODULE;
+        g_rle_grid_rows = (u64)value < RLE_GRID_ROWS_MAX ? (u64)value : RLE_GRID_ROWS_MAX;      // 0: RLE_GRID_ROWS
         return SHAFA_SUCCESS;
     }
     if (name && !strcmp(name, "rle_encode_one_pass"))       // the one-pass form is gone: 0 (the two-pass kernels) is all there is

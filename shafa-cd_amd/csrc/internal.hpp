@@ -141,6 +141,39 @@ int tile_setup(Batch *bt, hipStream_t st, int nblocks, const u64 *h_off, const u
 // where they stay below; *ntiles (where asked for) is then their number
 int tile_count(int nblocks, const u64 *h_cap, u64 unit, u64 *ntiles = nullptr);
 
+// ---- the grids of the two RLE launch chains (rle_decode.hip, rle_encode.hip) -------
+// Both put (rows of the largest block) x (blocks) workgroups of 256 lanes on the grid, which nothing else bounds: one large block
+// among many small ones passes 2^32 lanes.  grid_slices cuts the blocks, in order, into runs [b0, b1) of at most max_run blocks
+// with (largest rows in the run) x (blocks in the run) <= the limit, each with its own launches; a block above the limit is a
+// run by itself (its tiles chain by ticket and look-back: a block cannot be split).  rows(b): what the chain's widest kernel
+// puts on x for block b.  SHAFA_LACK_OF_MEMORY, before any device work, for a block whose rows x 256 lanes reach 2^32.
+constexpr u64 RLE_GRID_ROWS = 1ull << 22;
+constexpr u64 RLE_GRID_ROWS_MAX = (1ull << 24) - 1;
+extern u64 g_rle_grid_rows;                        // api.hip, "rle_grid_rows": 0 = RLE_GRID_ROWS, else the limit (tests)
+struct GridRun {
+    int b0, b1;
+    u32 rows;                                      // the largest of the run
+};
+template <typename Rows> inline int grid_slices(int nblocks, int max_run, Rows rows, std::vector<GridRun> &runs)
+{
+    const u64 limit = g_rle_grid_rows ? g_rle_grid_rows : RLE_GRID_ROWS;
+    for (int b = 0; b < nblocks; ++b) {
+        const u64 r = rows(b);
+        if (r > RLE_GRID_ROWS_MAX) return SHAFA_LACK_OF_MEMORY;
+        if (!runs.empty()) {
+            GridRun &g = runs.back();
+            const u64 top = r > g.rows ? r : g.rows;
+            if (b - g.b0 < max_run && top * (u64)(b - g.b0 + 1) <= limit) {
+                g.b1 = b + 1;
+                g.rows = (u32)top;
+                continue;
+            }
+        }
+        runs.push_back(GridRun{b, b + 1, (u32)r});
+    }
+    return SHAFA_SUCCESS;
+}
+
 // ---- per-op parameter records (device arrays) --------------------------------------------------
 struct EncBlk {
     const u8 *in;

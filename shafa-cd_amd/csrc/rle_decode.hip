@@ -441,110 +441,76 @@ __global__ void rld_sizes_dev(RldBlk *__restrict__ blks, int nblk, const u64 *__
 
 }  // namespace
 
-int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
-                  const u64 *h_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n)
+// The body of both launchers.  d_in_n == nullptr: h_n are the blocks' sizes.  Else h_n are their capacities, which the records and
+// the grid are laid out from, and rld_sizes_dev fills in the sizes (workgroups past a block's real tile count return before they
+// take a ticket).  The descriptors and tickets of all blocks are zeroed once; then one launch per run of grid_slices, which finds
+// its blocks' descriptors, tickets, sizes and error words through the records.
+static int rld_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_n, const u64 *d_in_n,
+                      u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n)
 {
+    static_assert(sizeof(RldBlk) % 16 == 0, "the capacities are uploaded behind the records");
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
     u64 ndesc = 0;
-    u32 max_tiles = 0;
     for (int b = 0; b < nblocks; ++b) {
         if ((h_in_off[b] & 15) || (h_out_off[b] & 15)) return SHAFA_OUTSIDE_MODULE;
-        const u64 t = ceil_div_u64(h_in_n[b], RLD_TILE);
-        ndesc += t;
-        if (t > max_tiles) max_tiles = (u32)t;
+        ndesc += ceil_div_u64(h_n[b], RLD_TILE);
     }
+    std::vector<GridRun> runs;
+    int rc = grid_slices(nblocks, nblocks, [&](int b) { return ceil_div_u64(h_n[b], RLD_TILE); }, runs);
+    if (rc) return rc;
+    const size_t rec_bytes = (size_t)nblocks * sizeof(RldBlk), up_bytes = rec_bytes + (d_in_n ? (size_t)nblocks * 8 : 0);
     size_t off = 0;
     const size_t o_state = off; off += ndesc * 8 * RLD_DSTRIDE;
     const size_t o_sum = off; off += ndesc * 8 * RLD_DSTRIDE;
     const size_t o_tick = off; off += (size_t)nblocks * 4 * RLD_TSTRIDE; off = (off + 15) & ~(size_t)15;
     const size_t o_zero_end = off;
-    const size_t o_blk = off; off += (size_t)nblocks * sizeof(RldBlk);
-    int rc = batch_reserve(bt, st, off);
-    if (rc) return rc;
+    const size_t o_blk = off; off += up_bytes;         // the records, then (d_in_n) the capacities
+    if ((rc = batch_reserve(bt, st, off))) return rc;
     u8 *ws = (u8 *)bt->d_ws;
-    RldBlk *hb = (RldBlk *)batch_stage(bt, st, (size_t)nblocks * sizeof(RldBlk));
-    if (!hb) return SHAFA_LACK_OF_MEMORY;
+    u8 *hs = (u8 *)batch_stage(bt, st, up_bytes);
+    if (!hs) return SHAFA_LACK_OF_MEMORY;
+    RldBlk *hb = (RldBlk *)hs, *blks = (RldBlk *)(ws + o_blk);
     u32 dbase = 0;
     for (int b = 0; b < nblocks; ++b) {
         RldBlk &e = hb[b];
+        const u32 tiles = (u32)ceil_div_u64(h_n[b], RLD_TILE);
         e.in = d_in + h_in_off[b];
         e.out = d_out + h_out_off[b];
-        e.n = h_in_n[b];
+        e.n = d_in_n ? 0 : h_n[b];                     // d_in_n: rld_sizes_dev
         e.out_cap = h_out_cap[b];
         e.out_n = d_out_n + b;
         e.err = bt->d_err + b;
         e.desc_base = dbase;
-        e.n_tiles = (u32)ceil_div_u64(h_in_n[b], RLD_TILE);
+        e.n_tiles = d_in_n ? 0 : tiles;
         e.ticket = (u32)b;
         e.pad = 0;
-        dbase += e.n_tiles;
+        dbase += tiles;
     }
+    if (d_in_n) memcpy(hs + rec_bytes, h_n, (size_t)nblocks * 8);
     HIP_TRY(hipMemsetAsync(ws, 0, o_zero_end, st));
     HIP_TRY(hipMemsetAsync(d_out_n, 0, (size_t)nblocks * 8, st));
-    if ((rc = batch_upload(bt, st, ws + o_blk, hb, (size_t)nblocks * sizeof(RldBlk)))) return rc;
-    if (max_tiles) {
-        hipLaunchKernelGGL(rle_decode_kernel, dim3(max_tiles * (u32)nblocks), dim3(RLD_THREADS), 0, st,
-                           (const RldBlk *)(ws + o_blk), nblocks, (u64 *)(ws + o_state), (u64 *)(ws + o_sum),
-                           (u32 *)(ws + o_tick));
-        HIP_TRY(hipGetLastError());
-    }
+    if ((rc = batch_upload(bt, st, blks, hs, up_bytes))) return rc;
+    if (d_in_n)
+        hipLaunchKernelGGL(rld_sizes_dev, dim3((u32)(nblocks + 255) / 256), dim3(256), 0, st, blks, nblocks, d_in_n,
+                           (const u64 *)(ws + o_blk + rec_bytes));
+    for (const GridRun &g : runs)
+        if (g.rows)
+            hipLaunchKernelGGL(rle_decode_kernel, dim3(g.rows * (u32)(g.b1 - g.b0)), dim3(RLD_THREADS), 0, st,
+                               (const RldBlk *)blks + g.b0, g.b1 - g.b0, (u64 *)(ws + o_state), (u64 *)(ws + o_sum),
+                               (u32 *)(ws + o_tick));
+    HIP_TRY(hipGetLastError());
     return SHAFA_SUCCESS;
+}
+
+int rledec_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off,
+                  const u64 *h_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n)
+{
+    return rld_launch(bt, st, nblocks, d_in, h_in_off, h_in_n, nullptr, d_out, h_out_off, h_out_cap, d_out_n);
 }
 
 int rledec_launch_dev(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const u64 *h_in_off, const u64 *h_in_cap,
                       const u64 *d_in_n, u8 *d_out, const u64 *h_out_off, const u64 *h_out_cap, u64 *d_out_n)
 {
-    if (nblocks <= 0) return SHAFA_SUCCESS;
-    if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
-    u64 ndesc = 0;
-    u32 max_tiles = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        if ((h_in_off[b] & 15) || (h_out_off[b] & 15)) return SHAFA_OUTSIDE_MODULE;
-        const u64 t = ceil_div_u64(h_in_cap[b], RLD_TILE);
-        ndesc += t;
-        if (t > max_tiles) max_tiles = (u32)t;
-    }
-    size_t off = 0;
-    const size_t o_state = off; off += ndesc * 8 * RLD_DSTRIDE;
-    const size_t o_sum = off; off += ndesc * 8 * RLD_DSTRIDE;
-    const size_t o_tick = off; off += (size_t)nblocks * 4 * RLD_TSTRIDE; off = (off + 15) & ~(size_t)15;
-    const size_t o_zero_end = off;
-    const size_t o_blk = off; off += (size_t)nblocks * sizeof(RldBlk); off = (off + 15) & ~(size_t)15;
-    const size_t o_cap = off; off += (size_t)nblocks * 8;
-    int rc = batch_reserve(bt, st, off);
-    if (rc) return rc;
-    u8 *ws = (u8 *)bt->d_ws;
-    const size_t rec_bytes = (size_t)nblocks * sizeof(RldBlk);
-    u8 *hs = (u8 *)batch_stage(bt, st, (o_cap - o_blk) + (size_t)nblocks * 8);
-    if (!hs) return SHAFA_LACK_OF_MEMORY;
-    RldBlk *hb = (RldBlk *)hs;
-    u32 dbase = 0;
-    for (int b = 0; b < nblocks; ++b) {
-        RldBlk &e = hb[b];
-        e.in = d_in + h_in_off[b];
-        e.out = d_out + h_out_off[b];
-        e.n = 0;                                   // rld_sizes_dev
-        e.out_cap = h_out_cap[b];
-        e.out_n = d_out_n + b;
-        e.err = bt->d_err + b;
-        e.desc_base = dbase;
-        e.n_tiles = 0;
-        e.ticket = (u32)b;
-        e.pad = 0;
-        dbase += (u32)ceil_div_u64(h_in_cap[b], RLD_TILE);
-    }
-    memset(hs + rec_bytes, 0, (o_cap - o_blk) - rec_bytes);
-    memcpy(hs + (o_cap - o_blk), h_in_cap, (size_t)nblocks * 8);
-    HIP_TRY(hipMemsetAsync(ws, 0, o_zero_end, st));
-    HIP_TRY(hipMemsetAsync(d_out_n, 0, (size_t)nblocks * 8, st));
-    if ((rc = batch_upload(bt, st, ws + o_blk, hs, (o_cap - o_blk) + (size_t)nblocks * 8))) return rc;
-    hipLaunchKernelGGL(rld_sizes_dev, dim3((u32)(nblocks + 255) / 256), dim3(256), 0, st, (RldBlk *)(ws + o_blk), nblocks,
-                       d_in_n, (const u64 *)(ws + o_cap));
-    if (max_tiles)       // workgroups past a block's real tile count return before they take a ticket
-        hipLaunchKernelGGL(rle_decode_kernel, dim3(max_tiles * (u32)nblocks), dim3(RLD_THREADS), 0, st,
-                           (const RldBlk *)(ws + o_blk), nblocks, (u64 *)(ws + o_state), (u64 *)(ws + o_sum),
-                           (u32 *)(ws + o_tick));
-    HIP_TRY(hipGetLastError());
-    return SHAFA_SUCCESS;
+    return rld_launch(bt, st, nblocks, d_in, h_in_off, h_in_cap, d_in_n, d_out, h_out_off, h_out_cap, d_out_n);
 }

@@ -1048,13 +1048,14 @@ int rleenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const 
     if (nblocks <= 0) return SHAFA_SUCCESS;
     if (nblocks > bt->max_blocks) return SHAFA_LACK_OF_MEMORY;
     u64 ndesc = 0;
-    u32 max_tiles = 0;
     for (int b = 0; b < nblocks; ++b) {
         if ((h_in_off[b] & 15) || (h_out_off[b] & 15)) return SHAFA_OUTSIDE_MODULE;
-        const u64 t = ceil_div_u64(h_in_n[b], RLE_TILE);
-        ndesc += t;
-        if (t > max_tiles) max_tiles = (u32)t;
+        ndesc += ceil_div_u64(h_in_n[b], RLE_TILE);
     }
+    // a run's rows are the pairs of tiles of its largest block, rle3_emit's x and the widest of the five grids; blocks go on y
+    std::vector<GridRun> runs;
+    int rc = grid_slices(nblocks, 65535, [&](int b) { return ceil_div_u64(h_in_n[b], 2 * RLE_TILE); }, runs);
+    if (rc) return rc;
     // workspace: [G: output offset per tile] [RleBlk] [tsum] [R] [T] [masks]
     size_t off = 0;
     const size_t o_sum = off; off += ndesc * 8; off = (off + 15) & ~(size_t)15;
@@ -1063,8 +1064,7 @@ int rleenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const 
     const size_t o_R = off; off += ndesc * 4; off = (off + 15) & ~(size_t)15;
     const size_t o_T = off; off += ndesc * 4; off = (off + 15) & ~(size_t)15;
     const size_t o_M = off; off += ndesc * (RLE_TILE / 32) * sizeof(uint2);      // {E, Z} per 32 bytes: n / 4
-    int rc = batch_reserve(bt, st, off);
-    if (rc) return rc;
+    if ((rc = batch_reserve(bt, st, off))) return rc;
     u8 *ws = (u8 *)bt->d_ws;
     RleBlk *hb = (RleBlk *)batch_stage(bt, st, (size_t)nblocks * sizeof(RleBlk));
     if (!hb) return SHAFA_LACK_OF_MEMORY;
@@ -1086,18 +1086,20 @@ int rleenc_launch(Batch *bt, hipStream_t st, int nblocks, const u8 *d_in, const 
     }
     HIP_TRY(hipMemsetAsync(d_out_n, 0, (size_t)nblocks * 8, st));      // empty blocks: size 0
     if ((rc = batch_upload(bt, st, ws + o_blk, hb, (size_t)nblocks * sizeof(RleBlk)))) return rc;
-    if (max_tiles) {
-        const RleBlk *dblk = (const RleBlk *)(ws + o_blk);
-        const dim3 grid_t((max_tiles + 1) / 2, (u32)nblocks), grid_b((u32)nblocks);     // two tiles per workgroup
-        u32 *tsum = (u32 *)(ws + o_tsum), *Rr = (u32 *)(ws + o_R), *Tt = (u32 *)(ws + o_T);
-        u64 *Gg = (u64 *)(ws + o_sum);
-        hipLaunchKernelGGL(rle3_first, dim3((max_tiles + 3) / 4, (u32)nblocks), dim3(RLE_THREADS), 0, st, dblk, tsum, Tt);
-        hipLaunchKernelGGL(rle3_carry, grid_b, dim3(SCAN_THREADS), 0, st, dblk, (const u32 *)tsum, Rr);
-        hipLaunchKernelGGL(rle3_fix, dim3((max_tiles + 63) / 64, (u32)nblocks), dim3(RLE_THREADS), 0, st, dblk, (const u32 *)Rr, Tt);
-        hipLaunchKernelGGL(rle3_offsets, grid_b, dim3(SCAN_THREADS), 0, st, dblk, (const u32 *)Tt, Gg);
-        hipLaunchKernelGGL(rle3_emit, grid_t, dim3(RLE_THREADS), 0, st, dblk, (const u32 *)Rr, Tt, (const u64 *)Gg);
-        HIP_TRY(hipGetLastError());
+    u32 *tsum = (u32 *)(ws + o_tsum), *Rr = (u32 *)(ws + o_R), *Tt = (u32 *)(ws + o_T);
+    u64 *Gg = (u64 *)(ws + o_sum);
+    for (const GridRun &g : runs) {     // the kernels reach every per-tile array through the records (desc_base, masks)
+        if (!g.rows) continue;
+        const RleBlk *dblk = (const RleBlk *)(ws + o_blk) + g.b0;
+        const u32 nb = (u32)(g.b1 - g.b0), pairs = g.rows;
+        const dim3 grid_b(nb), thr(RLE_THREADS), scan(SCAN_THREADS);
+        hipLaunchKernelGGL(rle3_first, dim3((pairs + 1) / 2, nb), thr, 0, st, dblk, tsum, Tt);      // two pairs per workgroup
+        hipLaunchKernelGGL(rle3_carry, grid_b, scan, 0, st, dblk, (const u32 *)tsum, Rr);
+        hipLaunchKernelGGL(rle3_fix, dim3((pairs + 31) / 32, nb), thr, 0, st, dblk, (const u32 *)Rr, Tt);   // 64 tiles per workgroup
+        hipLaunchKernelGGL(rle3_offsets, grid_b, scan, 0, st, dblk, (const u32 *)Tt, Gg);
+        hipLaunchKernelGGL(rle3_emit, dim3(pairs, nb), thr, 0, st, dblk, (const u32 *)Rr, Tt, (const u64 *)Gg);
     }
+    HIP_TRY(hipGetLastError());
     if (d_freq) {   // make_freq of the RLE bytes (f.c:310): sizes are on the device
         rc = hist_launch_dev(bt, st, nblocks, d_out, h_out_off, h_out_cap, d_out_n, d_freq, d_thist, h_thist_off);
         if (rc) return rc;
