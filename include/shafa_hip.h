@@ -143,6 +143,8 @@ int shafa_hip_rle_decode(const uint8_t *in, size_t in_n, uint8_t *out, size_t ou
  * A batch is nblocks independent blocks.  Block b's input is the h_in_n[b] bytes at
  * d_in + h_in_off[b]; its output region is the h_out_cap[b] bytes at d_out + h_out_off[b]
  * (all four are host arrays of nblocks entries; every offset must be a multiple of 16).
+ * The offsets are 64-bit in every entry of this layer, h_thist_off, h_plane_off, h_dst_off and the payload places in d_off
+ * included: a region may lie anywhere in a buffer of any size, past byte 2^32 too; only a block's own size is bounded.
  * Calls enqueue work on `stream` (a hipStream_t passed as void*; NULL = the null stream) and
  * return without synchronising; results in device memory are valid after the stream is synchronised.
  * shafa_hipd_finish() synchronises the stream and returns the batch's first error, filling the

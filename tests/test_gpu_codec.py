@@ -413,7 +413,7 @@ DEFAULT_OPTIONS = {"sf_encode_one_pass_min_blocks": 0, "sf_encode_lanes": 0, "sf
                    "sf_decode_speculate": 1, "sf_decode_path": 0, "rle_encode_general": 0, "rle_encode_one_pass": 0}
 
 
-@pytest.mark.parametrize("options", [
+OPTION_SETS = [
     {"sf_encode_one_pass_min_blocks": 1 << 30},                            # count / scan / pack kernels (sfe3_*) for every launch
     {"sf_encode_one_pass_min_blocks": 1},                                  # the one-pass kernel even for one block
     {"sf_encode_one_pass_min_blocks": 1, "sf_encode_lanes": 256},          # ... 256-lane workgroups, 8 KiB tiles
@@ -424,7 +424,14 @@ DEFAULT_OPTIONS = {"sf_encode_one_pass_min_blocks": 0, "sf_encode_lanes": 0, "sf
     {"sf_decode_path": 1},                                                 # tables treated as incomplete: the byte-map kernels
     {"sf_decode_path": 2},                                                 # generic byte-map kernels (sfd_sync / sfd_tiles)
     {"rle_encode_general": 1},                                             # per-element general RLE tile code for every tile
-], ids=lambda o: ",".join(f"{k}={v}" for k, v in o.items()))
+]
+
+
+def option_id(o):
+    return ",".join(f"{k}={v}" for k, v in o.items())
+
+
+@pytest.mark.parametrize("options", OPTION_SETS, ids=option_id)
 def test_alternative_kernel_paths_stay_bit_exact(oracle, shafa, options):
     """Every fall-back / alternative kernel path that the library can be told to take (shafa_hip_set_option) must produce
     the oracle's bytes on the same inputs as the default path."""
